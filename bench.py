@@ -25,7 +25,22 @@ shards of H, the QAP front end distributed, witness in 1/N slices.  Two hosts dr
   * `config.prove_ms_rank_per_gpu`: one process per GPU (every rank of the launcher), exchanges through RCCL
     (csrc/comm/rccl_comm.cpp, icicle-snark_amd/parallel.py) — the fallback for `value` if the in-process group fails.
 
-Prints ONE JSON line (rank 0): the driver's contract plus
+A plain run (`--gpus 1` without `--full`) does only what its headline figure needs: synthesis of the inputs, the cache load,
+eleven untimed proves (the timed steps always run on a process that has proved a dozen times), the W warm-up steps, the K
+timed steps, `--dump-outputs DIR` when given, and the result line.  `--full` adds every secondary
+measurement of the single-GPU run: the PMC child passes, the cold path, the host-buffer / resident / bit-heavy timings, two
+proves in flight, the micro-benchmarks behind `roofline`, the drop-in sequence and the CPU baseline.  Runs over several GPUs
+keep their secondary figures either way.
+
+`--dump-outputs DIR` (one GPU) writes, after the timed steps, what they computed as float64 arrays of 16-bit limbs (exact):
+  public.npy          (n_public, 16)   the public signals of the last timed step (public.json);
+  proof_pi_a.npy      (3, 16)          the proof of the same witness on the same cached key with the blinding fixed at
+  proof_pi_b.npy      (3, 2, 16)       (r, s) = DUMP_RS (groth16_prove_resident): the timed steps draw r, s at random, so
+  proof_pi_c.npy      (3, 16)          their own proof.json differs from call to call, this one only from build to build;
+  verified.npy        (2,)             1.0 / 0.0: the library's pairing check on the last timed step's proof and on that one.
+The inputs are synthesised from fixed seeds: the same arguments give the same inputs, so two builds compare output for output.
+
+Prints ONE JSON line (rank 0): the driver's contract plus (with `--full` on one GPU)
   roofline          the dominant kernel (G1 bucket accumulation of the H MSM): algorithmic bytes / HIP-event time, and
                     `traffic` = HBM bytes from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) collected IN THIS RUN by
                     re-running three proves under the profiler in a child process (gfx950 ×2 fetch correction applied);
@@ -83,19 +98,19 @@ def _to_mont(K):
     return to_mont
 
 
-def make_inputs(K, S, N):
-    """synthesise benchmark/<N> (zkey bytes, wtns bytes) with the HIP library doing the heavy lifting"""
+def make_inputs(K, S, N, return_vk=False):
+    """synthesise benchmark/<N> (zkey bytes, wtns bytes[, verification key]) with the HIP library doing the heavy lifting"""
     n = 1
     while n < N + 2:
         n <<= 1
     K.release_domain()
     K.initialize_domain(K.get_root_of_unity(n))
     t0 = time.time()
-    zkey, _ = S.setup_squaring_chain(N, GpuVec(K), lambda g, sc: K.generator_mul(g, sc), points_to_mont=_to_mont(K))
+    zkey, vk = S.setup_squaring_chain(N, GpuVec(K), lambda g, sc: K.generator_mul(g, sc), points_to_mont=_to_mont(K))
     wtns = S.write_wtns(S.squaring_chain_witness(N))
     K.release_domain()
     log(f"synthesised benchmark/{N}: zkey {len(zkey) / 1e6:.1f} MB, wtns {len(wtns) / 1e6:.1f} MB in {time.time() - t0:.1f} s")
-    return zkey, wtns
+    return (zkey, wtns, vk) if return_vk else (zkey, wtns)
 
 
 def make_standin_inputs(K, S, name, scale=1.0, seed=7):
@@ -117,15 +132,47 @@ def make_standin_inputs(K, S, name, scale=1.0, seed=7):
     return zkey, wtns, vk, nc
 
 
-def workload_inputs(K, S, workload):
-    """→ (zkey, wtns, n_constraints, description, is_standin)"""
+def workload_inputs(K, S, workload, return_vk=False):
+    """→ (zkey, wtns, n_constraints, description, is_standin[, verification key])"""
     if workload in S.STANDIN_SIZES:
-        zkey, wtns, _, nc = make_standin_inputs(K, S, workload)
+        zkey, wtns, vk, nc = make_standin_inputs(K, S, workload)
         cfgname = {"aadhaar_standin": "anon_aadhaar", "keyless_standin": "Aptos keyless"}[workload]
-        return zkey, wtns, nc, f"SYNTHETIC STAND-IN for the {cfgname} circuit (random sparse R1CS, {nc} constraints, >=70 % bit wires; the real circuit cannot be built offline)", True
-    N = int(workload[:-1]) * 1000 if workload.endswith("k") else int(workload)
-    zkey, wtns = make_inputs(K, S, N)
-    return zkey, wtns, N, f"benchmark/{N // 1000}k squaring chain (BN254, {N} constraints)", False
+        out = zkey, wtns, nc, f"SYNTHETIC STAND-IN for the {cfgname} circuit (random sparse R1CS, {nc} constraints, >=70 % bit wires; the real circuit cannot be built offline)", True
+    else:
+        N = int(workload[:-1]) * 1000 if workload.endswith("k") else int(workload)
+        zkey, wtns, vk = make_inputs(K, S, N, return_vk=True)
+        out = zkey, wtns, N, f"benchmark/{N // 1000}k squaring chain (BN254, {N} constraints)", False
+    return out + (vk,) if return_vk else out
+
+
+# fixed blinding scalars of the proof that --dump-outputs writes beside the timed steps' public signals
+DUMP_RS = (0x1D5F0C2A7B, 0x2E6A1B3C8D)
+
+
+def _limbs16(x):
+    return [(int(x) >> (16 * i)) & 0xFFFF for i in range(16)]
+
+
+def dump_outputs(outdir, K, S, cm, key, wtns, vk, proof, public):
+    """--dump-outputs: the outputs of the last timed step (public signals; its proof only as a pairing-check verdict, since its
+    blinding is random) and the proof of the same witness with the blinding fixed at DUMP_RS, as float64 arrays of 16-bit limbs"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    vkj = S.vk_to_json(vk)
+    fixed, fixed_public, _ = cm.prove_mem(key, wtns, *DUMP_RS)
+    if json.loads(fixed_public) != json.loads(public):
+        raise RuntimeError("the fixed-blinding prove returned other public signals than the last timed step")
+    fp = json.loads(fixed)
+    arrays = {
+        "public": [_limbs16(v) for v in json.loads(public)],
+        "proof_pi_a": [_limbs16(v) for v in fp["pi_a"]],
+        "proof_pi_b": [[_limbs16(v) for v in c] for c in fp["pi_b"]],
+        "proof_pi_c": [_limbs16(v) for v in fp["pi_c"]],
+        "verified": [float(K.groth16_verify_json(proof, public, vkj)), float(K.groth16_verify_json(fixed, fixed_public, vkj))],
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    log(f"outputs of the timed path written to {outdir}: " + ", ".join(f"{n}.npy" for n in arrays))
 
 
 def cpu_baseline(zkey, wtns, N, what):
@@ -798,12 +845,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None, help="1600k (default) | <N>k | <constraints> | aadhaar_standin | keyless_standin")
     ap.add_argument("--constraints", type=int, default=None, help="(compatibility) squaring chain of this many constraints")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC child passes (roofline.traffic = null)")
-    ap.add_argument("--no-dropin", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements of the one-GPU line (PMC passes, cold path, narrower timings, two in flight, "
+                         "roofline micro-benchmarks, drop-in sequence, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float64; one GPU only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="(with --full) skip the rocprofv3 PMC child passes (roofline.traffic = null)")
+    ap.add_argument("--no-dropin", action="store_true", help="(with --full) skip the drop-in sequence and the two-in-flight timing")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--group-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs is supported with one GPU only")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.group_child:
         return group_child()
     workload = args.workload or (str(args.constraints) if args.constraints else "1600k")
@@ -822,7 +878,7 @@ def main():
     # HBM traffic of the dominant kernels, measured in this run: rocprofv3 PMC passes over a child process, BEFORE this
     # process touches the GPU (the profiler child initialises it on its own)
     pmc, pmc_note = None, None
-    if world == 1 and not args.no_pmc:
+    if world == 1 and args.full and not args.no_pmc:
         t0 = time.time()
         try:
             pmc = pmc_traffic(workload)
@@ -887,7 +943,7 @@ def main():
     else:
         exch = P.LocalExchange()
 
-    zkey, wtns, N, what, standin = workload_inputs(K, S, workload)
+    zkey, wtns, N, what, standin, vk = workload_inputs(K, S, workload, return_vk=True)
     keyless_loop = workload == "keyless_standin"
     tmpdir = tempfile.mkdtemp(prefix="isnark_bench_")
     # N > 1, first host: the library's own multi-device entry, driven by rank 0 (see the module docstring)
@@ -906,7 +962,14 @@ def main():
     key = f"{zkey_path}_HIP" if world == 1 else f"bench{N}"
     cold = {}
     thr_start = cpu_throttle()
-    if world == 1:
+    if world == 1 and not args.full:
+        # plain run: the state the cold-path measurements below end in — the key loaded from the zkey bytes, its fixed-base
+        # tables built and adopted
+        t0 = time.perf_counter()
+        cm.load(key, zkey, device_id=local_rank, wait_tables=False)
+        cold_ms = (time.perf_counter() - t0) * 1e3
+        cm.tables_ready(key, wait=True)
+    elif world == 1:
         # ---- cold path (the reference's "without cache" figure): zkey FILE → proof.json with NOTHING cached —
         # container parse, 0.8 GB of sections over PCIe WHILE the first proof (classic bucket layout) is computed behind the stages of
         # that upload (csrc/prover/prover.cpp: cold_prove; ICICLE_SNARK_COLD_PIPELINE=0 loads first, proves then); the key's fixed-base
@@ -1079,8 +1142,15 @@ def main():
                 sync()
                 xs.append((time.perf_counter() - t1) * 1e3)
             return sorted(xs)[k // 2]
-        host_ms = med(lambda: cm.prove_mem(key, wtns))                       # host buffer in, JSON strings out
-        resident_ms = med(lambda: cm.prove_mem(key, wtns, resident=True))    # witness already in HBM
+        if args.full:
+            host_ms = med(lambda: cm.prove_mem(key, wtns))                       # host buffer in, JSON strings out
+            resident_ms = med(lambda: cm.prove_mem(key, wtns, resident=True))    # witness already in HBM
+        else:
+            # a plain run makes the same ten proves untimed: without them one of the first few file proves of a fresh key now and
+            # then takes ~10 ms more, which lands in the timed steps when W is small
+            for resident in (False,) * 5 + (True,) * 5:
+                cm.prove_mem(key, wtns, resident=resident)
+            sync()
     for _ in range(max(1, args.warmup)):
         step()
     sync(); barrier()
@@ -1099,10 +1169,12 @@ def main():
     assert json.loads(proof)["protocol"] == "groth16"
     if not standin:
         assert json.loads(public) == [str(pow(3, 1 << N, S.R_MOD))]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, K, S, cm, key, wtns, vk, proof, public)
 
     # (the narrower regions — host buffer in, witness resident — were timed before the warm-up steps, see above)
     skew_ms = dropin_ms = dropin_detail = None
-    if world == 1:
+    if world == 1 and args.full:
         if not standin:
             # witness-shape sensitivity on the benchmark key: 70 % of the wires in {0,1}, 10 % below 2^64 (timing only: that
             # vector does not satisfy the circuit; the prover does identical work for any scalars of this shape)
@@ -1125,22 +1197,24 @@ def main():
     # streams, witness / QAP buffers, bucket arrays and pinned partials are one set — and (b) two threads on two managers that each
     # hold the key: what a per-prove context beside one set of key data would give at best.  Never `value`.
     two_in_flight = None
-    if world == 1 and not standin and not args.no_dropin:
+    if world == 1 and args.full and not standin and not args.no_dropin:
         try:
             two_in_flight = two_in_flight_ms(K, cm, key, zkey, wtns)
             log("two proves in flight:", two_in_flight)
         except Exception as e:   # noqa: BLE001 — secondary measurement
             log(f"two-in-flight measurement failed: {e!r}")
-    hbm_copy_gbps, mad_tops = K.microbench() if rank == 0 else (None, None)
+    # the micro-benchmarks behind `roofline` (runs of their own): with --full, and always on a run over several GPUs
+    secondary = args.full or world > 1
+    hbm_copy_gbps, mad_tops = K.microbench() if rank == 0 and secondary else (None, None)
     # what kind of box this is: the boxes of one pool differ most in scattered accesses (round 5: digit sort and table build 2–3× slower
     # on some boxes at the same copy rate) — printed as config.box_access_gbps, not used in any figure
     box_access = None
-    if rank == 0:
+    if rank == 0 and secondary:
         try:
             box_access = K.access_probes()
         except Exception as e:   # noqa: BLE001 — informational only
             log(f"access probes failed: {e!r}")
-    if world == 1 and not args.no_dropin:
+    if world == 1 and args.full and not args.no_dropin:
         cm.evict(key)
         cm.close()
         cm = None
@@ -1159,8 +1233,8 @@ def main():
         if use_group:
             g, kern_ms = group["acc_geom"], group["acc_ms"]
             phases = dict(qap=group["qap_ms"] * args.steps, msm=group["msm_ms"] * args.steps)
-        roof = roofline_block(g, kern_ms, pmc, pmc_note, hbm_copy_gbps, mad_tops)
-        if sort_ms:
+        roof = roofline_block(g, kern_ms, pmc, pmc_note, hbm_copy_gbps, mad_tops) if hbm_copy_gbps else None
+        if roof and sort_ms:
             sg = dict(sort_geom[0])
             # the witness pass of a prove = the digit sort of the tail + (when the witness is split, prover.cpp) of the head
             s_ms = sum(sort_ms) / len(sort_ms)
@@ -1180,7 +1254,7 @@ def main():
                                "traffic_h_sort": pmc.get("sort_h") if pmc else None,
                                "algorithmic_bytes": s_bytes, "geometry": sg,
                                "frac_of_measured_copy": s_bytes / ((s_ms + h_ms) * 1e-3) / 1e9 / hbm_copy_gbps}
-        if pmc:
+        if roof and pmc:
             roof["pmc_detail"] = pmc.get("detail")
         out = {
             "metric": "groth16_prove_constraints_per_s", "value": N / (ms_per_step * 1e-3), "unit": "constraints/s",
@@ -1215,7 +1289,9 @@ def main():
                                           else ("whole witness on every rank over PCIe" if world > 1 else "whole witness over PCIe")),
                        "prove_ms_files": ms_per_step if world == 1 else None,
                        "prove_ms_host_witness": host_ms, "prove_ms_hbm_resident": resident_ms,
-                       "secondary_timings": "prove_ms_host_witness and prove_ms_hbm_resident are medians of five proves each, taken BEFORE the W warm-up steps and the K timed steps" if world == 1 else None,
+                       "full": args.full,
+                       "secondary_timings": ("prove_ms_host_witness and prove_ms_hbm_resident are medians of five proves each, taken BEFORE the W warm-up steps and the K timed steps" if args.full else
+                                             "not measured: a plain run times the headline only (bench.py --full adds the secondary measurements)") if world == 1 else None,
                        "value_hbm_resident": N / (resident_ms * 1e-3) if resident_ms else None,
                        "prove_ms_dropin_sequence": dropin_ms, "dropin_sequence_detail": dropin_detail,
                        # cold path, reported separately: zkey bytes in host memory → device-resident cache
@@ -1233,7 +1309,7 @@ def main():
                        "box_access_gbps": box_access},
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if cm is not None:
                 cm.evict(key)
             out["cpu_baseline"] = cpu_baseline(zkey, wtns, N, what)

@@ -1,6 +1,6 @@
-"""The CPU oracle against oracle/_ref — the reference's own sources compiled where they lie — on fresh
-random inputs.  Skipped where the reference tree (hence the build) is absent; the committed golden
-vectors (test_oracle_golden.py) carry the same pin everywhere else.  CPU only."""
+"""The CPU oracle against oracle/_ref — the reference's own sources compiled where they lie — on seeded
+random inputs.  Where the reference tree (hence the build) is absent, the `R` fixture answers from the
+recorded results of the same calls (tests/golden/ref_calls.json).  CPU only."""
 import random
 
 import numpy as np
