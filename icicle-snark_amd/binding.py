@@ -102,6 +102,7 @@ bn254_pairing_target_field_add bn254_pairing_target_field_sub bn254_pairing_targ
 bn254_pairing_target_field_pow bn254_pairing_target_field_from_u32 bn254_pairing_target_field_generate_scalars
 icicle_snark_last_error icicle_snark_g1_generator_mul icicle_snark_g2_generator_mul icicle_snark_last_msm_timings
 icicle_snark_msm_profile icicle_snark_microbench icicle_snark_pmc_probes icicle_snark_access_probes
+icicle_snark_pairing_batch
 """.split()
 
 _lib = None
@@ -695,7 +696,7 @@ groth16_prove_mem groth16_prove_resident groth16_cache_info groth16_last_error g
 groth16_dist_supported groth16_dist_stage1 groth16_dist_stage2 groth16_dist_exchange_done groth16_upload_witness_slice
 groth16_witness_ready groth16_cache_load_devices groth16_parse_device groth16_cache_set_budget groth16_cache_info_sized
 groth16_verify groth16_verify_json groth16_verify_last_error groth16_group_describe groth16_cache_tables_ready
-groth16_cache_manager_prewarm
+groth16_cache_manager_prewarm groth16_verify_batch groth16_verify_batch_last_timings
 """.split()
 
 
@@ -737,6 +738,52 @@ def groth16_verify_json(proof_json: str, public_json: str, vk_json: str) -> bool
         lib().groth16_verify_last_error.restype = C.c_char_p
         raise ProverError(f"groth16_verify: {lib().groth16_verify_last_error().decode()} (code {rc})")
     return rc == 1
+
+
+def pairing_batch(P: np.ndarray, Q: np.ndarray) -> np.ndarray:
+    """e(P[i], Q[i]) for n pairs on the current device (icicle_snark_pairing_batch): P (n,2,4) / Q (n,4,4) standard-form
+    affine u64, (0,0) = identity; returns (n,12,4) in bn254_pairing's basis and form."""
+    P = np.ascontiguousarray(P, dtype=np.uint64).reshape(-1, 2, 4)
+    Q = np.ascontiguousarray(Q, dtype=np.uint64).reshape(-1, 4, 4)
+    n = len(P)
+    if len(Q) != n:
+        raise ValueError("pairing_batch: P and Q differ in length")
+    out = np.zeros((n, 12, 4), dtype=np.uint64)
+    if n == 0:
+        return out
+    dp, dq, do = DeviceVec.from_host(P), DeviceVec.from_host(Q), DeviceVec(out.nbytes)
+    try:
+        check(lib().icicle_snark_pairing_batch(ptr_of(dp), ptr_of(dq), C.c_uint64(n), None, ptr_of(do)), "pairing_batch")
+        check(lib().icicle_device_synchronize(), "pairing_batch")
+        out = do.to_host(out.shape)
+    finally:
+        for d in (dp, dq, do):
+            d.free()
+    return out
+
+
+def groth16_verify_batch(proofs, publics, vk: str, device: str = "HIP") -> list:
+    """verify n proofs (JSON texts) against one verification key on one GPU (groth16_verify_batch): one verdict per item,
+    each what groth16_verify_json's C function returns for it — 1 accepted, 0 rejected, negative = that item's format
+    error.  Raises ProverError for a malformed vk, a bad device string or a device failure."""
+    n = len(proofs)
+    if len(publics) != n:
+        raise ValueError("groth16_verify_batch: proofs and publics differ in length")
+    pa = (C.c_char_p * max(n, 1))(*[p.encode() if isinstance(p, str) else p for p in proofs])
+    qa = (C.c_char_p * max(n, 1))(*[q.encode() if isinstance(q, str) else q for q in publics])
+    out = (C.c_int32 * max(n, 1))()
+    rc = lib().groth16_verify_batch(pa, qa, C.c_int(n), vk.encode(), device.encode(), out)
+    if rc != 0:
+        lib().groth16_verify_last_error.restype = C.c_char_p
+        raise ProverError(f"groth16_verify_batch: {lib().groth16_verify_last_error().decode()} (code {rc})")
+    return [int(out[i]) for i in range(n)]
+
+
+def groth16_verify_batch_last_timings():
+    """(host parse ms, device ms) of this thread's last groth16_verify_batch"""
+    a, b = C.c_double(), C.c_double()
+    lib().groth16_verify_batch_last_timings(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def groth16_verify(proof: str, public: str, vk: str):

@@ -2,15 +2,18 @@
 //   > prove --witness W --zkey Z --proof P --public Q --device HIP
 // prints COMMAND_COMPLETED after every command, COMMAND_EMPTY for blank lines, COMMAND_EXIT on "exit".
 //   > verify --proof P --public Q --vk verification_key.json
+//   > verify-batch --list L --vk verification_key.json [--device HIP]   (L: one "<proof.json> <public.json>" per line)
+#include <fstream>
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "groth16_prover.h"
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -88,6 +91,72 @@ int main()
       else {
         std::cerr << "verify failed (" << rc << "): " << groth16_verify_last_error() << std::endl;
         std::cout << "VERIFY_FAILED" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "verify-batch") {
+      // every "<proof.json> <public.json>" line of the list against one key, on one GPU: one line per item, then the counts
+      std::string list, vk = "verification_key.json", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--list") in >> list;
+        else if (a == "--vk") in >> vk;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      auto slurp = [](const std::string& path, std::string* out) {
+        std::ifstream f(path, std::ios::binary);
+        if (!f) return false;
+        std::ostringstream ss;
+        ss << f.rdbuf();
+        *out = ss.str();
+        return true;
+      };
+      std::string vk_text, list_text;
+      if (list.empty() || !slurp(list, &list_text) || !slurp(vk, &vk_text)) {
+        std::cerr << "verify-batch: cannot read " << (list.empty() ? std::string("--list (missing)") : list) << " or " << vk << std::endl;
+        std::cout << "COMMAND_COMPLETED" << std::endl;
+        continue;
+      }
+      std::vector<std::string> proofs, publics;
+      std::vector<int> readable; // 1: both files read; 0: reported as an error without being judged
+      std::istringstream ls(list_text);
+      std::string ln;
+      while (std::getline(ls, ln)) {
+        std::istringstream lf(ln);
+        std::string pp, qp, pt, qt;
+        if (!(lf >> pp)) continue; // blank line
+        const bool ok = (lf >> qp) && slurp(pp, &pt) && slurp(qp, &qt);
+        proofs.push_back(ok ? pt : std::string());
+        publics.push_back(ok ? qt : std::string());
+        readable.push_back(ok ? 1 : 0);
+      }
+      const int n = (int)proofs.size();
+      std::vector<const char*> pj(n), qj(n);
+      for (int i = 0; i < n; i++) {
+        pj[i] = proofs[i].c_str();
+        qj[i] = publics[i].c_str();
+      }
+      std::vector<int32_t> verdicts(n);
+      const int rc = groth16_verify_batch(pj.data(), qj.data(), n, vk_text.c_str(), device.c_str(), verdicts.data());
+      if (rc != 0) {
+        std::cerr << "verify-batch failed (" << rc << "): " << groth16_verify_last_error() << std::endl;
+      } else {
+        int acc = 0, rej = 0, err = 0;
+        for (int i = 0; i < n; i++) {
+          if (!readable[i]) {
+            std::cout << i << " error: cannot read input file" << std::endl;
+            err++;
+          } else if (verdicts[i] == 1) {
+            std::cout << i << " accepted" << std::endl;
+            acc++;
+          } else if (verdicts[i] == 0) {
+            std::cout << i << " rejected" << std::endl;
+            rej++;
+          } else {
+            std::cout << i << " error: malformed proof or public signals (code " << verdicts[i] << ")" << std::endl;
+            err++;
+          }
+        }
+        std::cout << "accepted " << acc << " rejected " << rej << " errors " << err << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

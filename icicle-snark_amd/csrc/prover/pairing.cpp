@@ -25,6 +25,7 @@
 #include "../../../include/groth16_prover.h"
 #include "../common.h"
 #include "../ec.h"
+#include "verify_batch.h"
 
 using namespace bn254;
 
@@ -445,11 +446,16 @@ bool g1_valid(const G1::A& a) // Montgomery form
   const fe rhs = Fq::add(Fq::mul(Fq::sqr(a.x), a.x), Fq::to_mont(three));
   return Fq::eq(Fq::sqr(a.y), rhs);
 }
-bool g2_valid(const G2::A& a) // Montgomery form: on the twist y² = x³ + 3/ξ and killed by r
+bool g2_on_twist(const G2::A& a) // Montgomery form: on the twist y² = x³ + 3/ξ
 {
   if (G2::aff_is_zero(a)) return true;
   const f2 rhs = F2::add(F2::mul(F2::sqr(a.x), a.x), K().b_twist);
-  if (!F2::eq(F2::sqr(a.y), rhs)) return false;
+  return F2::eq(F2::sqr(a.y), rhs);
+}
+bool g2_valid(const G2::A& a) // Montgomery form: on the twist and killed by r
+{
+  if (G2::aff_is_zero(a)) return true;
+  if (!g2_on_twist(a)) return false;
   const G2::A std_a = {Fq2Ops::from_mont(a.x), Fq2Ops::from_mont(a.y)};
   bn254_g2_projective_t P, Q;
   bn254_g2_from_affine((const bn254_g2_affine_t*)&std_a, &P);
@@ -469,7 +475,9 @@ bool read_g1(const JVal* v, G1::A* out) // deserialize_g1_affine — src/convers
   *out = {Fq::to_mont(x), Fq::to_mont(y)};
   return g1_valid(*out);
 }
-bool read_g2(const JVal* v, G2::A* out) // deserialize_g2_affine — src/conversions.rs:72-96
+// deserialize_g2_affine — src/conversions.rs:72-96; `subgroup` false leaves the order-r test to the caller (the batched
+// verifier runs it on the device)
+bool read_g2(const JVal* v, G2::A* out, bool subgroup = true)
 {
   if (!v || v->t != JVal::ARR || v->a.size() < 2 || v->a[0].a.size() < 2 || v->a[1].a.size() < 2) return false;
   for (const JVal& row : v->a) {
@@ -482,7 +490,7 @@ bool read_g2(const JVal* v, G2::A* out) // deserialize_g2_affine — src/convers
   for (const fe& ci : c)
     if (!Fq::is_canonical(ci)) return false;
   *out = {{Fq::to_mont(c[0]), Fq::to_mont(c[1])}, {Fq::to_mont(c[2]), Fq::to_mont(c[3])}};
-  return g2_valid(*out);
+  return subgroup ? g2_valid(*out) : g2_on_twist(*out);
 }
 bool read_file(const char* path, std::string* out)
 {
@@ -510,6 +518,75 @@ void bn254_base_field_generate_scalars_one(bn254_fq_t* out) // unseeded, like ut
 }
 
 } // namespace
+
+// ---- parsing for the batched verifier (prover/verify_batch.hip): the checks of groth16_verify_json, split into the key's
+// and each item's, with the same codes and messages.  Only the order-r test of pi_b is left out (done on the device).
+namespace isnark {
+namespace vb {
+int fail(int code, const char* msg) { return vfail(code, msg); }
+int parse_vk(const char* vk_json, VbKey* out)
+{
+  JParser pv{vk_json, vk_json + strlen(vk_json)};
+  JVal vk = pv.document();
+  if (!pv.ok || vk.t != JVal::OBJ) return vfail(-2, "malformed JSON");
+  (void)K();
+  G1::A alpha1;
+  G2::A beta2, gamma2, delta2;
+  if (!read_g1(vk.get("vk_alpha_1"), &alpha1) || !read_g2(vk.get("vk_beta_2"), &beta2) || !read_g2(vk.get("vk_gamma_2"), &gamma2) || !read_g2(vk.get("vk_delta_2"), &delta2))
+    return vfail(-2, "verification key: bad point");
+  const JVal* ic = vk.get("IC");
+  const JVal* np = vk.get("nPublic");
+  if (!ic || ic->t != JVal::ARR || !np) return vfail(-2, "verification key: IC / nPublic missing");
+  if ((np->t != JVal::NUM && np->t != JVal::STR) || np->s.empty() || np->s.size() > 9 || np->s.find_first_not_of("0123456789") != std::string::npos)
+    return vfail(-2, "verification key: nPublic is not a non-negative integer");
+  const size_t n_public = (size_t)strtoul(np->s.c_str(), nullptr, 10);
+  if (ic->a.size() < n_public + 1) return vfail(-2, "public inputs / IC length mismatch");
+  out->n_public = n_public;
+  out->ic.resize(2 * (n_public + 1));
+  for (size_t i = 0; i <= n_public; i++) {
+    G1::A a;
+    if (!read_g1(&ic->a[i], &a)) return vfail(-2, i == 0 ? "IC: bad point" : "IC / public: bad value");
+    out->ic[2 * i] = Fq::from_mont(a.x);
+    out->ic[2 * i + 1] = Fq::from_mont(a.y);
+  }
+  out->alpha[0] = Fq::from_mont(alpha1.x);
+  out->alpha[1] = Fq::from_mont(alpha1.y);
+  const G2::A* g2s[3] = {&beta2, &gamma2, &delta2};
+  fe2* dst[3] = {out->beta, out->gamma, out->delta};
+  for (int k = 0; k < 3; k++) {
+    dst[k][0] = Fq2Ops::from_mont(g2s[k]->x);
+    dst[k][1] = Fq2Ops::from_mont(g2s[k]->y);
+  }
+  return 0;
+}
+int parse_item(const char* proof_json, const char* public_json, size_t n_public, VbItem* item, fe* pub)
+{
+  if (!proof_json || !public_json) return vfail(-3, "null argument");
+  JParser pp{proof_json, proof_json + strlen(proof_json)}, pq{public_json, public_json + strlen(public_json)};
+  JVal proof = pp.document(), pubv = pq.document();
+  if (!pp.ok || !pq.ok || proof.t != JVal::OBJ || pubv.t != JVal::ARR) return vfail(-2, "malformed JSON");
+  G1::A pi_a, pi_c;
+  G2::A pi_b;
+  (void)K();
+  if (!read_g1(proof.get("pi_a"), &pi_a) || !read_g2(proof.get("pi_b"), &pi_b, false) || !read_g1(proof.get("pi_c"), &pi_c))
+    return vfail(-2, "proof: bad point (not canonical, not on the curve, or outside the r-torsion)");
+  if (pubv.a.size() < n_public) return vfail(-2, "public inputs / IC length mismatch");
+  for (size_t i = 0; i < n_public; i++)
+    if (pubv.a[i].t != JVal::STR) return vfail(-2, "public signals must be decimal strings");
+  for (size_t i = 0; i < n_public; i++) {
+    if (!dec_to_fe(pubv.a[i].s, &pub[i])) return vfail(-2, "IC / public: bad value");
+    if (!Fr::is_canonical(pub[i])) return vfail(-2, "public signal is not below the scalar field modulus");
+  }
+  item->a[0] = Fq::from_mont(pi_a.x);
+  item->a[1] = Fq::from_mont(pi_a.y);
+  item->b[0] = Fq2Ops::from_mont(pi_b.x);
+  item->b[1] = Fq2Ops::from_mont(pi_b.y);
+  item->c[0] = Fq::from_mont(pi_c.x);
+  item->c[1] = Fq::from_mont(pi_c.y);
+  return 0;
+}
+} // namespace vb
+} // namespace isnark
 
 extern "C" {
 

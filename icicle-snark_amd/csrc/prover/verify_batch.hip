@@ -1,0 +1,230 @@
+// verify_batch.hip — Groth16 verification of many proofs against one verification key on one GPU, and the batched pairing
+// primitive it is built from (pairing29.h: the host pairing's algorithm on the lazy radix-2^29 field).
+//
+//   icicle_snark_pairing_batch   out[i] = e(p[i], q[i]), one lane per pairing
+//   groth16_verify_batch         per proof, one lane: [r]·pi_b = O, cpub = IC₀ + Σ pubⱼ·ICⱼ₊₁, one multi-Miller loop over
+//                                (−A, B), (cpub, γ₂), (C, δ₂) with γ₂ / δ₂'s lines precomputed once per call on the host, the
+//                                final exponentiation, and a comparison with conj(e(α₁, β₂)) (also computed once per call)
+//
+// The JSON texts are parsed on the host (pairing.cpp: the same checks and codes as groth16_verify_json) by up to 16 pooled
+// workers; items that fail there keep their negative code and never reach the device.  The rest go to the device in chunks of
+// at most CHUNK proofs, so device memory stays bounded whatever n is.
+#include <chrono>
+#include <stdlib.h>
+#include <string.h>
+#include <string>
+#include <vector>
+
+#include "../../../include/groth16_prover.h"
+#include "../common.h"
+#include "../pairing29.h"
+#include "../workers.h"
+#include "verify_batch.h"
+
+using namespace bn254;
+
+namespace {
+
+constexpr uint32_t CHUNK = 1u << 16;
+constexpr int WG = 64;
+
+__global__ __launch_bounds__(WG) void pairing_batch_kernel(const fe* __restrict__ p, const fe2* __restrict__ q, uint64_t n, fe* __restrict__ out)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+  if (i >= n) return;
+  const fe* P = p + 2 * i;
+  const fe2* Q = q + 2 * i;
+  const fe px = P[0], py = P[1];
+  const fe2 qx = Q[0], qy = Q[1];
+  const bool pz = p29::std_is_zero(px) && p29::std_is_zero(py);
+  const bool qz = p29::std_is_zero(qx.c0) && p29::std_is_zero(qx.c1) && p29::std_is_zero(qy.c0) && p29::std_is_zero(qy.c1);
+  const p29::F12 e = (pz || qz) ? p29::f12_one() : p29::pairing(f29::from_std(px), f29::from_std(py), Fq2_29::load_std(qx), Fq2_29::load_std(qy));
+  p29::f12_store_std(e, out + 12 * i);
+}
+
+// items[i] / pub[j·m + i] (public signal j of item i) → verdict[i] ∈ {1, 0, −2}
+__global__ __launch_bounds__(WG) void verify_batch_kernel(const p29::VerifyKey29* __restrict__ vk, const G1L::A* __restrict__ ic,
+                                                          const uint8_t* __restrict__ ic_zero, const isnark::vb::VbItem* __restrict__ items,
+                                                          const fe* __restrict__ pub, uint32_t m, int32_t* __restrict__ verdict)
+{
+  const uint32_t i = blockIdx.x * WG + threadIdx.x;
+  if (i >= m) return;
+  const isnark::vb::VbItem it = items[i];
+  verdict[i] = p29::verify_proof(*vk, ic, ic_zero, it.a, it.b, it.c, pub + i, m);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+thread_local double g_last_parse_ms = 0, g_last_device_ms = 0;
+
+// "HIP", "CUDA" (device 0) or "HIP:k" / "CUDA:k"; −1 for anything else (a device list included)
+int parse_one_device(const char* s)
+{
+  const char* colon = strchr(s, ':');
+  const std::string type = colon ? std::string(s, colon) : std::string(s);
+  if (type != "HIP" && type != "CUDA") return -1;
+  if (!colon) return 0;
+  const char* d = colon + 1;
+  if (!*d || strlen(d) > 6 || strspn(d, "0123456789") != strlen(d)) return -1;
+  return atoi(d);
+}
+
+struct DevBuf { // device allocations of one call, freed on every exit path
+  std::vector<void*> ptrs;
+  ~DevBuf()
+  {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  template <class T>
+  T* alloc(size_t count)
+  {
+    void* p = nullptr;
+    if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
+    ptrs.push_back(p);
+    return (T*)p;
+  }
+};
+
+int device_fail(eIcicleError code, const char* what, hipError_t e)
+{
+  char msg[200];
+  snprintf(msg, sizeof msg, "device: %s: %s", what, hipGetErrorString(e));
+  return isnark::vb::fail((int)code, msg);
+}
+
+} // namespace
+
+ISNARK_API eIcicleError icicle_snark_pairing_batch(const bn254_affine_t* p, const bn254_g2_affine_t* q, uint64_t n, icicleStreamHandle stream,
+                                                   bn254_fq12_t* out)
+{
+  if (n == 0) return ICICLE_SUCCESS;
+  if (!p || !q || !out) return ICICLE_INVALID_POINTER;
+  const uint64_t blocks = (n + WG - 1) / WG;
+  hipLaunchKernelGGL(pairing_batch_kernel, dim3((uint32_t)blocks), dim3(WG), 0, (hipStream_t)stream, (const fe*)p, (const fe2*)q, n, (fe*)out);
+  return isnark::check_launch("pairing_batch_kernel");
+}
+
+ISNARK_API void groth16_verify_batch_last_timings(double* parse_ms, double* device_ms)
+{
+  if (parse_ms) *parse_ms = g_last_parse_ms;
+  if (device_ms) *device_ms = g_last_device_ms;
+}
+
+ISNARK_API int groth16_verify_batch(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json, const char* device,
+                                    int32_t* verdicts)
+{
+  using namespace isnark::vb;
+  g_last_parse_ms = g_last_device_ms = 0;
+  if (n < 0) return fail(-3, "negative batch size");
+  if (n == 0) return 0;
+  if (!proof_jsons || !public_jsons || !vk_json || !device || !verdicts) return fail(-3, "null argument");
+  const int dev = parse_one_device(device);
+  if (dev < 0) return fail((int)ICICLE_INVALID_DEVICE, "device must be HIP, CUDA or HIP:k (one device)");
+  const auto t0 = std::chrono::steady_clock::now();
+  VbKey key;
+  if (int rc = parse_vk(vk_json, &key)) return rc;
+  const size_t np = key.n_public;
+
+  // items on the pool (≤ 16 tasks of contiguous ranges), the key's device part on this thread meanwhile
+  std::vector<VbItem> items(n);
+  std::vector<fe> pub((size_t)n * np + 1);
+  const int tasks = std::max(1, std::min(16, n / 64));
+  std::vector<isnark::HostTask> ht(tasks);
+  for (int t = 0; t < tasks; t++) {
+    const int lo = (int)((int64_t)n * t / tasks), hi = (int)((int64_t)n * (t + 1) / tasks);
+    ht[t].fn = [&, lo, hi] {
+      for (int i = lo; i < hi; i++) verdicts[i] = parse_item(proof_jsons[i], public_jsons[i], np, &items[i], pub.data() + (size_t)i * np);
+    };
+    if (t > 0) isnark::WorkerPool::get().run_or_inline(&ht[t]);
+  }
+  std::vector<p29::VerifyKey29> vkh(1);
+  p29::make_verify_key(key.alpha, key.beta, key.gamma, key.delta, (int)np, vkh.data());
+  std::vector<G1L::A> ic(np + 1);
+  std::vector<uint8_t> icz(np + 1);
+  for (size_t j = 0; j <= np; j++) {
+    icz[j] = p29::std_is_zero(key.ic[2 * j]) && p29::std_is_zero(key.ic[2 * j + 1]);
+    ic[j] = {f29::from_std(key.ic[2 * j]), f29::from_std(key.ic[2 * j + 1])};
+  }
+  ht[0].fn();
+  for (int t = 1; t < tasks; t++)
+    if (ht[t].queued) isnark::WorkerPool::wait(&ht[t]);
+  std::vector<int> live;
+  live.reserve(n);
+  for (int i = 0; i < n; i++)
+    if (verdicts[i] == 0) live.push_back(i);
+  g_last_parse_ms = ms_since(t0);
+  if (live.empty()) return 0;
+
+  // device part
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  struct Restore {
+    int d;
+    ~Restore()
+    {
+      if (d >= 0) (void)hipSetDevice(d);
+    }
+  } restore{prev};
+  hipError_t e = hipSetDevice(dev);
+  if (e != hipSuccess) return device_fail(ICICLE_INVALID_DEVICE, "hipSetDevice", e);
+  hipStream_t st = nullptr;
+  if ((e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "hipStreamCreate", e);
+  struct StreamGuard {
+    hipStream_t s;
+    ~StreamGuard() { (void)hipStreamDestroy(s); }
+  } sg{st};
+  const uint32_t cap = (uint32_t)std::min<size_t>(CHUNK, live.size());
+  DevBuf db;
+  p29::VerifyKey29* d_vk = db.alloc<p29::VerifyKey29>(1);
+  G1L::A* d_ic = db.alloc<G1L::A>(np + 1);
+  uint8_t* d_icz = db.alloc<uint8_t>(np + 1);
+  VbItem* d_items = db.alloc<VbItem>(cap);
+  fe* d_pub = db.alloc<fe>((size_t)cap * np + 1);
+  int32_t* d_verdict = db.alloc<int32_t>(cap);
+  if (!d_vk || !d_ic || !d_icz || !d_items || !d_pub || !d_verdict) return device_fail(ICICLE_ALLOCATION_FAILED, "hipMalloc", hipErrorOutOfMemory);
+  hipEvent_t ev0, ev1;
+  (void)hipEventCreate(&ev0);
+  (void)hipEventCreate(&ev1);
+  struct EvGuard {
+    hipEvent_t a, b;
+    ~EvGuard()
+    {
+      (void)hipEventDestroy(a);
+      (void)hipEventDestroy(b);
+    }
+  } eg{ev0, ev1};
+  (void)hipEventRecord(ev0, st);
+  if ((e = hipMemcpyAsync(d_vk, vkh.data(), sizeof(p29::VerifyKey29), hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_ic, ic.data(), (np + 1) * sizeof(G1L::A), hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_icz, icz.data(), np + 1, hipMemcpyHostToDevice, st)) != hipSuccess)
+    return device_fail(ICICLE_COPY_FAILED, "upload", e);
+  std::vector<VbItem> hitems(cap);
+  std::vector<fe> hpub((size_t)cap * np + 1);
+  std::vector<int32_t> hv(cap);
+  for (size_t base = 0; base < live.size(); base += cap) {
+    const uint32_t m = (uint32_t)std::min<size_t>(cap, live.size() - base);
+    for (uint32_t k = 0; k < m; k++) {
+      const int i = live[base + k];
+      hitems[k] = items[i];
+      for (size_t j = 0; j < np; j++) hpub[j * m + k] = pub[(size_t)i * np + j];
+    }
+    if ((e = hipMemcpyAsync(d_items, hitems.data(), m * sizeof(VbItem), hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (np && (e = hipMemcpyAsync(d_pub, hpub.data(), (size_t)m * np * sizeof(fe), hipMemcpyHostToDevice, st)) != hipSuccess))
+      return device_fail(ICICLE_COPY_FAILED, "upload", e);
+    hipLaunchKernelGGL(verify_batch_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, st, d_vk, d_ic, d_icz, d_items, d_pub, m, d_verdict);
+    if ((e = hipGetLastError()) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "verify_batch_kernel launch", e);
+    if ((e = hipMemcpyAsync(hv.data(), d_verdict, m * sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return device_fail(ICICLE_COPY_FAILED, "download", e);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return device_fail(ICICLE_SYNCHRONIZATION_FAILED, "verify_batch_kernel", e);
+    for (uint32_t k = 0; k < m; k++) verdicts[live[base + k]] = hv[k];
+  }
+  (void)hipEventRecord(ev1, st);
+  if ((e = hipEventSynchronize(ev1)) != hipSuccess) return device_fail(ICICLE_SYNCHRONIZATION_FAILED, "event", e);
+  float dms = 0;
+  (void)hipEventElapsedTime(&dms, ev0, ev1);
+  g_last_device_ms = dms;
+  return 0;
+}

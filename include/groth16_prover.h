@@ -175,6 +175,18 @@ int groth16_verify(const char* proof_path, const char* public_path, const char* 
 int groth16_verify_json(const char* proof_json, const char* public_json, const char* vk_json);
 const char* groth16_verify_last_error(void);
 
+/* groth16_verify_batch — verify n proofs against ONE verification key on one GPU.
+ * verdicts[i] = exactly what groth16_verify_json(proof_jsons[i], public_jsons[i], vk_json) returns: 1 accepted,
+ * 0 rejected, negative = that item's format error (same codes).  device: "HIP", "CUDA" or "HIP:k" (one device; a list
+ * is an error).  Returns 0 when every item was judged, whatever the verdicts; < 0 for a malformed vk or a null argument
+ * (text in groth16_verify_last_error()); > 0 (eIcicleError) for a bad device string or a device failure.  n = 0
+ * succeeds and writes nothing.  The JSON texts are parsed on the host (≤ 16 threads); the pi_b subgroup test, the
+ * public-input sum, the multi-Miller loop and the final exponentiation run on the device, one lane per proof. */
+int groth16_verify_batch(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json,
+                         const char* device, int32_t* verdicts);
+/* host parse time (vk and items) and device time (HIP events, uploads to verdicts) of this thread's last batch, ms */
+void groth16_verify_batch_last_timings(double* parse_ms, double* device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,6 +255,10 @@ const char* icicle_snark_last_error(void);
  * fixed-base multiplication used by the zkey synthesiser. */
 eIcicleError icicle_snark_g1_generator_mul(const bn254_scalar_t* s, uint64_t n, icicleStreamHandle stream, bn254_affine_t* out);
 eIcicleError icicle_snark_g2_generator_mul(const bn254_scalar_t* s, uint64_t n, icicleStreamHandle stream, bn254_g2_affine_t* out);
+/* out[i] = e(p[i], q[i]) for n pairs.  Device pointers, standard-form affine in, 12 standard-form Fq coefficients out, in
+ * the same basis and canonical form as bn254_pairing.  An identity input (0,0) gives 1.  Enqueued on `stream`. */
+eIcicleError icicle_snark_pairing_batch(const bn254_affine_t* p, const bn254_g2_affine_t* q, uint64_t n, icicleStreamHandle stream,
+                                        bn254_fq12_t* out);
 /* per-phase device timings of the most recent MSM on this thread, milliseconds (HIP events):
  * [0] recode+sort, [1] bucket accumulation, [2] bucket reduction, [3] total.  Valid only when the
  * environment variable ICICLE_SNARK_PROFILE=1 is set (adds stream synchronisation). */
