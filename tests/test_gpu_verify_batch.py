@@ -1,5 +1,6 @@
 """Batched Groth16 verification on the GPU (groth16_verify_batch) and its pairing primitive (icicle_snark_pairing_batch):
-bit-for-bit against the host pairing, verdict for verdict against the host verifier groth16_verify_json."""
+bit-for-bit against the host pairing and against bilinearity, verdict for verdict against the host verifier groth16_verify_json
+and a discrete-log model of the verification equation (tests/groth16_dlog_model.py)."""
 import json
 import os
 import random
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden, unhex
+import groth16_dlog_model as M
 
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -65,30 +67,8 @@ def _rerandomise(K, proof, delta2, theta, rho):
 
 def _non_subgroup_twist_point():
     """a point ON the twist but outside the order-r subgroup (as tests/test_verify.py builds it)"""
-    def f2mul(a, b):
-        return ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
-
-    def f2sqrt(a):
-        n = (a[0] * a[0] + a[1] * a[1]) % Q
-        sn = pow(n, (Q + 1) // 4, Q)
-        if sn * sn % Q != n:
-            return None
-        for sgn in (1, -1):
-            t = (a[0] + sgn * sn) * pow(2, -1, Q) % Q
-            x0 = pow(t, (Q + 1) // 4, Q)
-            if x0 * x0 % Q == t and x0:
-                x1 = a[1] * pow(2 * x0, -1, Q) % Q
-                if f2mul((x0, x1), (x0, x1)) == (a[0] % Q, a[1] % Q):
-                    return (x0, x1)
-        return None
-    d = pow(82, -1, Q)
-    bt = f2mul((3, 0), (9 * d % Q, -d % Q))
-    for x0 in range(1, 50):
-        rhs = f2mul(f2mul((x0, 0), (x0, 0)), (x0, 0))
-        y = f2sqrt(((rhs[0] + bt[0]) % Q, (rhs[1] + bt[1]) % Q))
-        if y:
-            return [[str(x0), "0"], [str(y[0]), str(y[1])], ["1", "0"]]
-    raise AssertionError("no twist point found")
+    x0, x1, y0, y1 = M.twist_point_outside_subgroup()
+    return [[str(x0), str(x1)], [str(y0), str(y1)], ["1", "0"]]
 
 
 # ---- pairing primitive ----------------------------------------------------------------------------------------------------
@@ -255,3 +235,201 @@ def test_cli_verify_batch(gpu, golden, tmp_path):
     got = [ln.replace("> ", "") for ln in out.stdout.splitlines()]
     assert got[:6] == ["0 accepted", "1 accepted", "2 rejected", "3 error: cannot read input file",
                        "accepted 2 rejected 1 errors 1", "COMMAND_COMPLETED"], out.stdout
+
+
+# ---- the discrete-log case table (tests/groth16_dlog_model.py; tests/test_pairing29.py runs it through the checked header) --------
+@pytest.fixture(scope="module")
+def dlog(O):
+    table = M.case_table()
+    pts = M.Points(O)
+    pts.need_items([it for _, items in table for it in items])
+    pts.resolve()
+    texts = [(M.vk_json(pts, key), [(M.proof_json(pts, it.proof), M.public_json(it.signals)) for it in items]) for key, items in table]
+    return table, pts, texts
+
+
+def test_dlog_table_verdicts_equal_model_and_host(gpu, dlog):
+    """every item of the table: groth16_verify_batch = model = groth16_verify_json, in batches of 1, 63, 64, 65 and 300 of one key
+    whose items (edge cases, valid and rejected) are shuffled together"""
+    K = gpu
+    table, _, texts = dlog
+    sizes = (1, 63, 64, 65, 300)
+    rnd = random.Random(6365)
+    bad = []
+    for t, ((key, items), (vkj, pq)) in enumerate(zip(table, texts)):
+        for it, (pj, qj) in zip(items, pq):
+            if _host_verdict(K, pj, qj, vkj) != it.want:
+                bad.append(("host", it.label, it.want))
+        for size in (sizes[t % 5], sizes[(t + 2) % 5]):
+            idx = list(range(len(items))) + [rnd.randrange(len(items)) for _ in range(size - len(items))]
+            rnd.shuffle(idx)
+            for b in ([[k] for k in idx] if size == 1 else [idx]):
+                got = K.groth16_verify_batch([pq[k][0] for k in b], [pq[k][1] for k in b], vkj)
+                bad += [("gpu", size, items[k].label, g, items[k].want) for k, g in zip(b, got) if g != items[k].want]
+    assert not bad, bad[:20]
+    assert {it.want for _, items in table for it in items} == {1, 0, -2}
+
+
+def test_real_prover_key_with_five_signals(gpu, S, O):
+    """a prover key with nPublic = 5: its proofs are accepted, and each signal changed in turn is rejected, on the GPU and the host"""
+    K = gpu
+    r1, w = S.random_circuit(200, 5, 10, seed=55)
+    zkey, vk = S.setup(r1, lambda g, k: K.generator_mul(g, k), points_to_mont=lambda a: O.fq_convert_montgomery(a, True))
+    wtns = S.write_wtns(w)
+    cm = K.CacheManager()
+    try:
+        cm.load("vb5", zkey)
+        proofs = [cm.prove_mem("vb5", wtns, 7 + i, 11 + 3 * i)[:2] for i in range(4)]
+    finally:
+        cm.close()
+        K.release_domain()
+    vkj = S.vk_to_json(vk)
+    assert json.loads(vkj)["nPublic"] == 5
+    pub = json.loads(proofs[0][1])
+    assert len(pub) == 5
+    items = list(proofs)
+    for j in range(5):
+        changed = list(pub)
+        changed[j] = str((int(pub[j]) + 1 + j) % R_ORDER)
+        items.append((proofs[j % 4][0], json.dumps(changed)))
+    want = [1] * 4 + [0] * 5
+    assert K.groth16_verify_batch([p for p, _ in items], [q for _, q in items], vkj) == want
+    assert [_host_verdict(K, p, q, vkj) for p, q in items] == want
+
+
+# ---- the chunk boundary of groth16_verify_batch (CHUNK live proofs per launch, verify_batch.hip) ------------------------------
+CHUNK = 1 << 16
+
+
+@pytest.fixture(scope="module")
+def pool3(O):
+    """a key with nPublic = 3 and 251 proofs of it, each with its own random signals; every fourth is invalid (c off by one)"""
+    rnd = random.Random(3333)
+    key = M.random_key(rnd, 3, "n=3")
+    items = []
+    for k in range(251):
+        sig = [rnd.randrange(R_ORDER) for _ in range(3)]
+        items.append(M.Item(key, M.prove(key, sig, rnd.randrange(1, R_ORDER), rnd.randrange(1, R_ORDER), e=int(k % 4 == 3)), sig, f"pool {k}"))
+    pts = M.Points(O)
+    pts.need_items(items)
+    pts.resolve()
+    texts = [(M.proof_json(pts, it.proof), M.public_json(it.signals)) for it in items]
+    assert {it.want for it in items} == {0, 1}
+    return M.vk_json(pts, key), items, texts
+
+
+def _tiled_batch(pool3, n, errors):
+    """n items tiled from the pool; at the indices in `errors` a parse error (−2) of one of three kinds"""
+    vkj, items, texts = pool3
+    proofs = [texts[i % 251][0] for i in range(n)]
+    publics = [texts[i % 251][1] for i in range(n)]
+    want = [items[i % 251].want for i in range(n)]
+    for t, i in enumerate(errors):
+        p, q = json.loads(publics[i]), proofs[i]
+        if t % 3 == 0:
+            proofs[i] = q[:-2]                                                   # malformed JSON
+        elif t % 3 == 1:
+            publics[i] = json.dumps([p[0], str(int(p[1]) + R_ORDER), p[2]])      # a signal ≥ r at j = 1
+        else:
+            publics[i] = json.dumps(p[:2])                                       # too few signals
+        want[i] = -2
+    return proofs, publics, want
+
+
+def test_chunk_boundary_with_gaps_in_the_live_list(gpu, pool3):
+    """CHUNK + 4097 items with ~1 % parse errors before the boundary: the first launch takes the first CHUNK live items, the second
+    a short chunk (m < cap) of distinct signal vectors, so the per-chunk signal layout pub[j·m + k] is exercised with m ≠ cap"""
+    K = gpu
+    vkj, items, texts = pool3
+    n = CHUNK + 4097
+    errors = [i for i in range(0, CHUNK, 97)]
+    proofs, publics, want = _tiled_batch(pool3, n, errors)
+    live = [i for i in range(n) if want[i] != -2]
+    last1, first2 = live[CHUNK - 1], live[CHUNK]
+    assert last1 > CHUNK - 1 and len(live) - CHUNK < CHUNK
+    bad = next(k for k in range(251) if items[k].want == 0)
+    for i in (last1, first2):  # rejected proofs on both sides of the boundary
+        proofs[i], publics[i], want[i] = texts[bad][0], texts[bad][1], 0
+    assert len({publics[i] for i in live[CHUNK:CHUNK + 251]}) >= 250
+    got = K.groth16_verify_batch(proofs, publics, vkj)
+    wrong = [(i, got[i], want[i]) for i in range(n) if got[i] != want[i]]
+    assert not wrong, (len(wrong), wrong[:10], last1, first2)
+    assert got[last1] == got[first2] == 0 and got[last1 - 1] == want[last1 - 1]
+    sample = [0, errors[1], last1 - 1, last1, first2, first2 + 1, n - 1] + random.Random(7).sample(range(n), 57)
+    assert [_host_verdict(K, proofs[i], publics[i], vkj) for i in sample] == [want[i] for i in sample]
+
+
+def test_batch_of_exactly_one_chunk_of_live_items(gpu, pool3):
+    K = gpu
+    vkj, _, _ = pool3
+    errors = list(range(5, CHUNK, 1311))
+    proofs, publics, want = _tiled_batch(pool3, CHUNK + len(errors), errors)
+    assert sum(v != -2 for v in want) == CHUNK
+    got = K.groth16_verify_batch(proofs, publics, vkj)
+    assert got == want
+    sample = [0, len(want) - 1] + random.Random(8).sample(range(len(want)), 30)
+    assert [_host_verdict(K, proofs[i], publics[i], vkj) for i in sample] == [want[i] for i in sample]
+
+
+# ---- pairing_batch against bilinearity (no host pairing involved) ----------------------------------------------------------------
+def _conj(e):
+    """f^(p⁶) in bn254_pairing's basis: the six c1 coefficients negated mod q (= f⁻¹ for a pairing value)"""
+    out = np.array(e, copy=True)
+    c1 = _ints(e[6:12])
+    out[6:12] = _arr([(Q - v) % Q for v in c1])
+    return out
+
+
+def test_pairing_batch_is_bilinear(gpu, O):
+    K = gpu
+    rnd = random.Random(2025)
+    pts = M.Points(O)
+    ab = [(rnd.randrange(1, R_ORDER), rnd.randrange(1, R_ORDER)) for _ in range(21)]
+    pts.need("g1", [1] + [a for a, _ in ab] + [a * b for a, b in ab])
+    pts.need("g2", [1] + [b for _, b in ab] + [a * b for a, b in ab])
+    pts.resolve()
+    P = [pts.g1(a) for a, _ in ab] + [pts.g1(a * b) for a, b in ab] + [pts.g1(1)] * 21
+    Qs = [pts.g2(b) for _, b in ab] + [pts.g2(1)] * 21 + [pts.g2(a * b) for a, b in ab]
+    got = K.pairing_batch(_arr([v for p in P for v in p]), _arr([v for q in Qs for v in q]))  # 63 lanes
+    assert np.array_equal(got[:21], got[21:42]) and np.array_equal(got[:21], got[42:])
+    one = np.zeros((12, 4), dtype=np.uint64)
+    one[0, 0] = 1
+    assert len({got[i].tobytes() for i in range(21)} | {one.tobytes()}) == 22  # 21 distinct values, none of them 1
+    # e(−P, Q) = conj(e(P, Q))
+    negP = [(x, (Q - y) % Q) for x, y in P[:21]]
+    neg = K.pairing_batch(_arr([v for p in negP for v in p]), _arr([v for q in Qs[:21] for v in q]))
+    for i in range(21):
+        assert np.array_equal(neg[i], _conj(got[i])), i
+
+
+def test_pairing_batch_edge_coordinates(gpu, O):
+    """G₁ = (1, 2), −G₁ = (1, q − 2) and −k·G₁ (y = q − y(k·G₁)), each against e(G₁, ∓k·b·G₂), in batches of 1, 63 and 65"""
+    K = gpu
+    rnd = random.Random(1265)
+    ks = [1, 2, 3, 4, 5, 6, 7, 8, 1000, R_ORDER - 1, R_ORDER - 2]
+    pts = M.Points(O)
+    b = [rnd.randrange(1, R_ORDER) for _ in ks]
+    pts.need("g1", [1] + ks)
+    pts.need("g2", b + [k * bb for k, bb in zip(ks, b)] + [-k * bb for k, bb in zip(ks, b)])
+    pts.resolve()
+    assert pts.g1(1) == (1, 2) and pts.g1(-1) == (1, Q - 2)
+    pairs, rel = [], []  # rel: (i, j, conj): e_i = e_j, or e_i = conj(e_j)
+    for k, bb in zip(ks, b):
+        x, y = pts.g1(k)
+        base = len(pairs)
+        pairs += [((x, y), pts.g2(bb)), ((x, (Q - y) % Q), pts.g2(bb)), ((1, 2), pts.g2(k * bb)), ((1, 2), pts.g2(-k * bb))]
+        rel += [(base, base + 2, False), (base + 1, base + 3, False), (base + 1, base, True)]
+    P = _arr([v for p, _ in pairs for v in p])
+    Qa = _arr([v for _, q in pairs for v in q])
+    for size in (1, 63, 65):
+        if size == 1:
+            got = np.stack([K.pairing_batch(P[2 * i:2 * i + 2], Qa[4 * i:4 * i + 4])[0] for i in range(len(pairs))])
+        else:  # the pairs repeated to fill the batch; lanes past the first copy must agree with it
+            idx = [i % len(pairs) for i in range(size)]
+            full = K.pairing_batch(P.reshape(-1, 2, 4)[idx], Qa.reshape(-1, 4, 4)[idx])
+            for lane in range(len(pairs), size):
+                assert np.array_equal(full[lane], full[lane % len(pairs)]), (size, lane)
+            got = full[:len(pairs)]
+        for i, j, cj in rel:
+            assert np.array_equal(got[i], _conj(got[j]) if cj else got[j]), (size, i, j)
+        assert not np.array_equal(got[0], got[1])

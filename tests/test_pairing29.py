@@ -1,6 +1,7 @@
 """Checked host build of the radix-2^29 pairing (csrc/pairing29.h) that the batched GPU verifier runs: compiled here with
 g++ -DF29_CHECK, which turns every lazy bound of ff29.h / ec29.h / pairing29.h into a recorded failure, and compared with
-the library's host pairing (bn254_pairing) and host verifier (groth16_verify_json).  No GPU."""
+the library's host pairing (bn254_pairing), its host verifier (groth16_verify_json) and a discrete-log model of the
+verification equation that needs no pairing at all (tests/groth16_dlog_model.py).  No GPU."""
 import ctypes as C
 import json
 import os
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden, unhex
+import groth16_dlog_model as M
 
 Q = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -36,6 +38,10 @@ def _p(a):
 
 def _arr(ints):
     return np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in ints), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def _ints(a):
+    return [int.from_bytes(r.tobytes(), "little") for r in np.asarray(a).reshape(-1, 4)]
 
 
 def _pairing29(chk, P, Qs):
@@ -152,3 +158,71 @@ def test_g2_subgroup_check(chk, K):
     pt = _arr([x0, 0, y[0], y[1]])
     assert chk.p29_g2_in_subgroup(_p(pt)) == 0
     assert chk.p29_last_failure().decode() == ""
+
+
+# ---- the discrete-log case table (tests/groth16_dlog_model.py): verdicts from integers mod r, no pairing -------------------------
+# Keys with 0, 2, 3, 8 and 40 public signals, and keys that reach the verifier's rare branches: IC₂ = ±IC₁ with equal signals
+# (Straus doubles at the top set bit / cancels at every set bit), an identity ICⱼ (ic_zero), IC₀ = O, IC₀ = ±Σ sⱼ·ICⱼ₊₁ (the final
+# addition doubles / cpub = O), γ₂ = O and δ₂ = O (use_gamma / use_delta = 0), α₁ = O and β₂ = O (target 1).  Per key and signal
+# vector: a valid proof, c off by one, A = O, B = O, C = O, −A, a signal ±1, two signals swapped, pi_b outside the subgroup.
+
+
+@pytest.fixture(scope="module")
+def dlog(O):
+    table = M.case_table()
+    pts = M.Points(O)
+    pts.need_items([it for _, items in table for it in items])
+    pts.need("g1", [M.cpub_dlog(it.key, it.signals) for _, items in table for it in items])
+    pts.resolve()
+    return table, pts
+
+
+def _key_arrays(pts, key):
+    n = key.n_public
+    return (_arr(pts.g1(key.alpha)), _arr(pts.g2(key.beta)), _arr(pts.g2(key.gamma)), _arr(pts.g2(key.delta)),
+            _arr([v for k in key.ic[:n + 1] for v in pts.g1(k)]))
+
+
+def _strided(items, n):
+    """signal j of item k at [j·m + k], as verify_batch_kernel reads them"""
+    return _arr([it.signals[j] for j in range(n) for it in items]) if n else np.zeros((1, 4), dtype=np.uint64)
+
+
+def test_dlog_table_verdicts_equal_the_model(chk, dlog):
+    table, pts = dlog
+    bad, total = [], 0
+    for key, items in table:
+        items = [it for it in items if not it.json_only]  # a signal ≥ r never gets past the parser
+        assert {0, 1} <= {it.want for it in items}, key.name
+        m = len(items)
+        a = _arr([v for it in items for v in pts.g1(it.proof.a)])
+        b = _arr([v for it in items for v in (M.twist_point_outside_subgroup() if it.proof.b_outside else pts.g2(it.proof.b))])
+        c = _arr([v for it in items for v in pts.g1(it.proof.c)])
+        out = np.zeros(m, dtype=np.int32)
+        chk.p29_verify_batch(*[_p(x) for x in _key_arrays(pts, key)], key.n_public, m, _p(_strided(items, key.n_public)),
+                             _p(a), _p(b), _p(c), _p(out))
+        assert chk.p29_last_failure().decode() == "", key.name
+        bad += [(it.label, int(v), it.want) for it, v in zip(items, out) if v != it.want]
+        total += m
+    assert not bad, bad
+    assert total > 200
+
+
+def test_dlog_table_public_input_equals_the_model(chk, dlog):
+    """public_input's Straus sum point for point against cpub = (ic₀ + Σ sⱼ·icⱼ₊₁)·G₁, cpub = O reported as such.  Verdicts cannot
+    see that last flag: lines evaluated at (0, 0) are c·v·w, which the final exponentiation maps to 1."""
+    table, pts = dlog
+    for key, items in table:
+        items = [it for it in items if not it.json_only]
+        m = len(items)
+        found = np.zeros(m, dtype=np.int32)
+        xy = np.zeros((2 * m, 4), dtype=np.uint64)
+        chk.p29_public_input(_p(_key_arrays(pts, key)[4]), key.n_public, m, _p(_strided(items, key.n_public)), _p(found), _p(xy))
+        assert chk.p29_last_failure().decode() == "", key.name
+        for k, it in enumerate(items):
+            want = pts.g1(M.cpub_dlog(key, it.signals))
+            if not any(want):
+                assert found[k] == 0, it.label
+            else:
+                assert found[k] == 1 and _ints(xy[2 * k:2 * k + 2]) == list(want), it.label
+    assert any(not any(pts.g1(M.cpub_dlog(k, it.signals))) for k, items in table for it in items)  # cpub = O was reached
