@@ -6,6 +6,7 @@
 #include <mutex>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -14,6 +15,22 @@
 namespace isnark {
 
 void set_last_error(const char* fmt, ...);
+
+// ---- environment knobs.  A site that is `static const` reads its knob once per process; the others read
+// it at every call, because in-process callers (the tests) change it between calls.
+inline const char* env_str(const char* name) { return getenv(name); }
+inline bool env_set(const char* name) { return getenv(name) != nullptr; } // (X=0 counts as set)
+// atoi / atoll of the value when the variable is set (text that is no number: 0), else `dflt`
+inline int env_int(const char* name, int dflt)
+{
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+inline long long env_i64(const char* name, long long dflt)
+{
+  const char* v = getenv(name);
+  return v ? atoll(v) : dflt;
+}
 
 #define ISNARK_API extern "C" __attribute__((visibility("default")))
 

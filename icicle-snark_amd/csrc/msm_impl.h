@@ -721,7 +721,7 @@ eIcicleError build_table_sliced_run(const void* d_points, uint32_t n, int from_f
   }
   if (slice > n) slice = n;
   const uint64_t ms = (uint64_t)slice * g.W;
-  static const bool trace_tb = getenv("ICICLE_SNARK_TRACE_TABLES") != nullptr;
+  static const bool trace_tb = env_set("ICICLE_SNARK_TRACE_TABLES");
   const auto tb0 = std::chrono::steady_clock::now();
   auto tb_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count(); };
   P* rows = nullptr;
@@ -1122,7 +1122,7 @@ eIcicleError msm_impl(const bn254_scalar_t* scalars, const AT* bases, int msm_si
   const uint32_t batch = cfg->batch_size > 1 ? (uint32_t)cfg->batch_size : 1;
   const uint32_t stride = cfg->precompute_factor > 1 ? (uint32_t)cfg->precompute_factor : 1;
   const bool shared = cfg->are_points_shared_in_batch || batch == 1;
-  const bool profile = getenv("ICICLE_SNARK_PROFILE") != nullptr;
+  const bool profile = env_set("ICICLE_SNARK_PROFILE");
 
   Staged ss, sb;
   ICICLE_TRY(ss.in(scalars, (size_t)L * batch * sizeof(fe), cfg->are_scalars_on_device, s));

@@ -115,7 +115,7 @@ eIcicleError msm_g2_build_table(const void* d_points, uint32_t n, int from_form,
 // bases per slice of the sliced build (ICICLE_SNARK_TABLE_SLICE_LOG overrides the default of 2^18 for G2, twice that for G1)
 inline uint32_t table_slice_bases()
 {
-  static const int lg = getenv("ICICLE_SNARK_TABLE_SLICE_LOG") ? atoi(getenv("ICICLE_SNARK_TABLE_SLICE_LOG")) : 18;
+  static const int lg = env_int("ICICLE_SNARK_TABLE_SLICE_LOG", 18);
   return 1u << (lg < 12 ? 12 : lg > 22 ? 22 : lg);
 }
 eIcicleError msm_g1_build_table_sliced(const void* d_points, uint32_t n, int from_form, const MsmGeom& g, hipStream_t s, void** d_table, const std::atomic<bool>* cancel);

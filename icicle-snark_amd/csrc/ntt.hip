@@ -971,7 +971,7 @@ eIcicleError ntt_impl(const bn254_scalar_t* input, int size, NTTDir dir, const N
   else if (logn <= 2 * MAX_LOG_R) { np = 2; lr[0] = (logn + 1) / 2; lr[1] = logn / 2; }
   else { np = 3; lr[0] = MAX_LOG_R; lr[1] = (logn - MAX_LOG_R + 1) / 2; lr[2] = (logn - MAX_LOG_R) / 2; } // 9 bits = three radix-8 rounds
   // transforms whose passes can all work on full tiles of at most 8 bits run on the lazy radix-2^29 field (ntt_pass29_kernel)
-  static const bool allow29 = !(getenv("ICICLE_SNARK_NTT29") && atoi(getenv("ICICLE_SNARK_NTT29")) == 0);
+  static const bool allow29 = env_int("ICICLE_SNARK_NTT29", 1) != 0;
   int np29 = 0, lr29[3] = {0, 0, 0};
   const bool use29 = allow29 && dom.tw29 && plan29(logn, np29, lr29);
   if (use29) {

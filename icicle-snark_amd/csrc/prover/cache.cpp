@@ -139,7 +139,7 @@ MsmGeom witness_table_geometry(uint32_t len)
 namespace {
 void assign_stream_roles(ZKeyCache* z, bool allow_measure)
 {
-  static const bool off = getenv("ICICLE_SNARK_PIPE_ROLES") && atoi(getenv("ICICLE_SNARK_PIPE_ROLES")) == 0;
+  static const bool off = env_int("ICICLE_SNARK_PIPE_ROLES", 1) == 0;
   if (off) return;
   hipStream_t phys[6] = {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5};
   int cls[6];
@@ -170,7 +170,7 @@ void assign_stream_roles(ZKeyCache* z, bool allow_measure)
   z->s_g3 = phys[best[3]];
   z->s_g4 = phys[best[4]];
   z->s_g5 = phys[best[5]];
-  if (getenv("ICICLE_SNARK_TRACE_COLD") || getenv("ICICLE_SNARK_VERBOSE"))
+  if (env_set("ICICLE_SNARK_TRACE_COLD") || env_set("ICICLE_SNARK_VERBOSE"))
     fprintf(stderr, "[icicle-snark-hip] stream pipes %d %d %d %d %d %d -> roles (qap A B2 Hsort B1 C) take streams %d %d %d %d %d %d (cost %d)\n", cls[0], cls[1], cls[2], cls[3], cls[4], cls[5], best[0],
             best[1], best[2], best[3], best[4], best[5], best_cost);
 }
@@ -186,10 +186,10 @@ void table_build_thread(ZKeyCache* z)
   // the first one is the one a caller without a cache waits for.  A key nobody proves with gets its tables after the grace time.
   // (cold pipeline: not before the key's sections have landed — cold_prove clears `hold` behind the upload, or evicts the key)
   while (tb.hold.load(std::memory_order_acquire) && !tb.cancel.load()) std::this_thread::sleep_for(std::chrono::milliseconds(1));
-  const int grace_ms = getenv("ICICLE_SNARK_TABLE_GRACE_MS") ? atoi(getenv("ICICLE_SNARK_TABLE_GRACE_MS")) : TABLE_BUILD_GRACE_MS;
+  const int grace_ms = env_int("ICICLE_SNARK_TABLE_GRACE_MS", TABLE_BUILD_GRACE_MS);
   for (int waited = 0; !tb.witness_only && waited < grace_ms && !tb.go.load(std::memory_order_acquire) && !tb.cancel.load(); waited++) std::this_thread::sleep_for(std::chrono::milliseconds(1));
   const auto t0 = std::chrono::steady_clock::now();
-  static const bool trace_tb = getenv("ICICLE_SNARK_TRACE_TABLES") != nullptr;
+  static const bool trace_tb = env_set("ICICLE_SNARK_TRACE_TABLES");
   bool ok = hipSetDevice(z->device_id) == hipSuccess;
   if (trace_tb) fprintf(stderr, "[tables] thread: device set at %.1f ms\n", ms_since(t0));
   // The key's first prove (classic layout) has counted the non-zero digits of its witness: a witness of 0 / 1 wires and small values
@@ -253,7 +253,7 @@ void table_build_thread(ZKeyCache* z)
       if (e != ICICLE_SUCCESS) {
         (void)hipGetLastError();
         ok = false;
-        if (getenv("ICICLE_SNARK_VERBOSE") && !tb.cancel.load()) fprintf(stderr, "[icicle-snark-hip] deferred tables: build failed (%s)%s\n", icicle_snark_last_error(), narrowed && attempt == 0 ? "; retrying with the dense digit width" : "; the key keeps the classic layout");
+        if (env_set("ICICLE_SNARK_VERBOSE") && !tb.cancel.load()) fprintf(stderr, "[icicle-snark-hip] deferred tables: build failed (%s)%s\n", icicle_snark_last_error(), narrowed && attempt == 0 ? "; retrying with the dense digit width" : "; the key keeps the classic layout");
       }
     }
     if (ok || !narrowed || attempt == 1 || tb.cancel.load() || !s) break;
@@ -274,7 +274,7 @@ void table_build_thread(ZKeyCache* z)
       t = nullptr;
     }
   tb.build_ms = ms_since(t0);
-  if (getenv("ICICLE_SNARK_TRACE_COLD")) fprintf(stderr, "[cold] deferred tables %s after %.1f ms\n", ok ? "complete" : "abandoned", tb.build_ms);
+  if (env_set("ICICLE_SNARK_TRACE_COLD")) fprintf(stderr, "[cold] deferred tables %s after %.1f ms\n", ok ? "complete" : "abandoned", tb.build_ms);
   tb.state.store(ok ? 2 : 3, std::memory_order_release);
 }
 } // namespace
@@ -370,7 +370,7 @@ void cold_upload_task(ColdPlan* pl)
   ColdUpload* cu = pl->cu;
   ColdFeed& F = cu->feed;
   ZKeyCache* z = pl->z;
-  const bool trace = getenv("ICICLE_SNARK_TRACE_COLD") != nullptr;
+  const bool trace = env_set("ICICLE_SNARK_TRACE_COLD");
   const auto t0 = std::chrono::steady_clock::now();
   auto bail = [&](int code, const char* fmt, const char* detail) {
     char buf[256];
@@ -459,7 +459,7 @@ void cold_upload_wait(ColdUpload* cu)
 int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int count, std::unique_ptr<ZKeyCache>& out, bool defer_tables, ColdUpload* cold)
 {
   if (count < 1 || rank < 0 || rank >= count) return fail(ERR_ARG, "bad shard %d/%d", rank, count);
-  const bool trace = getenv("ICICLE_SNARK_TRACE_COLD") != nullptr;
+  const bool trace = env_set("ICICLE_SNARK_TRACE_COLD");
   auto t_prev = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!trace) return;
@@ -600,7 +600,7 @@ int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int co
   // (msm_plan.h; ICICLE_SNARK_TABLES=0 disables it): every base array becomes W rows 2^(c·w)·P so that all digits of a
   // scalar share one bucket set — 13 instead of 16 mixed additions per scalar at 1.6 M constraints for 13× the base memory.
   // (decided BEFORE the upload since round 5: the cold pipeline below only applies when no table has to be built in here)
-  const int tables_env = getenv("ICICLE_SNARK_TABLES") ? atoi(getenv("ICICLE_SNARK_TABLES")) : 1;
+  const int tables_env = env_int("ICICLE_SNARK_TABLES", 1);
   bool tables = tables_env != 0;
   // Above 2^22 points the 32-bit sort entry has no room for 20-bit digits beside the point index (msm_sort.hip: tab_low_bits):
   // the tables would fall back to c = 19 / 14 digits, and measured at 6.4 M constraints (domain 2^23) that is no faster than the
@@ -625,7 +625,7 @@ int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int co
       z->geom_h = msm_geometry(z->H.len(), 0, 0);
     }
   }
-  const bool defer_env = !(getenv("ICICLE_SNARK_DEFER_TABLES") && atoi(getenv("ICICLE_SNARK_DEFER_TABLES")) == 0);
+  const bool defer_env = env_int("ICICLE_SNARK_DEFER_TABLES", 1) != 0;
   const bool defer = tables && defer_tables && defer_env && count == 1;
   // cold pipeline: the caller's prove starts while the sections are still on their way (nothing in here needs their contents then)
   const bool pipeline = cold != nullptr && count == 1 && !h_strided && (defer || !tables);
@@ -762,7 +762,8 @@ int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int co
 // a tenth to a fifth of the non-zero digits of a dense witness, so the four witness MSMs (A, B1, B2, C) spend more in reducing
 // empty-ish buckets than in filling them — the G2 reduction heads the critical chain (HISTORY.md §9-2a).  After a prove the
 // entry count of the witness digit sort is known; if it calls for a narrower digit (target ≈ 32 entries per bucket; one bit is
-// enough from the dense width, two bits afterwards: prover.cpp, follow_witness), the four tables are rebuilt from their own row 0 with that width — once, ≈ 0.1–0.3 s, like a cache build — and the
+// enough from the dense width, two bits afterwards: follow_witness below), the four tables are rebuilt from their own row 0 with that
+// width — once, ≈ 0.1–0.3 s, like a cache build — and the
 // next proves sort with it and size the large-bucket threshold from the observed count.  Measured on the stand-in keys of
 // BASELINE configs 4 / 5: c = 20 → 18, prove 5.5 → 4.7 ms (1.0 M constraints) and 8.15 → 7.3 ms (1.4 M); c ≤ 16 is slower again
 // (one thread per bucket: chains of hundreds).  A later, denser witness moves the key back the same way.  H stays dense.
@@ -807,7 +808,7 @@ int rebuild_witness_tables(ZKeyCache* z, int c_new)
       for (void* t : fresh)
         if (t) (void)hipFree(t);
       // not an error of the prove: the key keeps its tables and its width (out of memory is the expected cause)
-      if (getenv("ICICLE_SNARK_VERBOSE")) fprintf(stderr, "[icicle-snark-hip] witness tables keep c = %d (rebuild for c = %d failed: %s)\n", z->geom_w.c, c_new, icicle_snark_last_error());
+      if (env_set("ICICLE_SNARK_VERBOSE")) fprintf(stderr, "[icicle-snark-hip] witness tables keep c = %d (rebuild for c = %d failed: %s)\n", z->geom_w.c, c_new, icicle_snark_last_error());
       return 0;
     }
   }
@@ -818,6 +819,27 @@ int rebuild_witness_tables(ZKeyCache* z, int c_new)
     z->device_bytes += (int64_t)j.sh->len() * ((int64_t)g.W - (int64_t)z->geom_w.W) * (j.g2 ? 128 : 64);
   }
   z->geom_w = g;
+  return 0;
+}
+
+// The key follows its witnesses: a digit width at least two bits off the one the last witness called for (one bit when the key
+// still has its dense width — below ≈ 28 entries per bucket it pays, witness_table_geometry —; every later move needs two bits
+// and eight proves: no flapping) → the four witness tables are re-built with that width.  `sync` = false: by a worker thread
+// BESIDE the proves of the key (round 5; rounds 3–4 re-built them inside a prove, 0.1–0.3 s), which go on with the tables they
+// have until the new ones are complete and adopt_tables swaps them in (all four and geom_w together); shard_commitments calls
+// this at the END of the prove that counted the digits.  `sync` = true (ICICLE_SNARK_SYNC_REBUILD=1): re-built here, at the
+// start of the next prove, as rounds 3–4 did.
+int follow_witness(ZKeyCache* z, bool sync)
+{
+  if (!(z->geom_w.tab && z->witness_entries && z->proves_since_rebuild >= 1 && z->tb.state.load(std::memory_order_acquire) == 0)) return 0;
+  const int c_t = witness_digit_target(z, z->witness_entries);
+  const bool from_default = z->geom_w.c == z->geom_w_default_c;
+  if (!(((from_default && c_t < z->geom_w.c) || c_t <= z->geom_w.c - 2 || c_t >= z->geom_w.c + 2) && (from_default || z->proves_since_rebuild >= 8))) return 0;
+  if (sync) {
+    if (int rc = rebuild_witness_tables(z, c_t)) return rc;
+  } else
+    start_witness_rebuild(z, c_t);
+  z->proves_since_rebuild = 0;
   return 0;
 }
 

@@ -65,7 +65,7 @@ int parse_device_string(const char* device, std::vector<int>& ids)
   const std::string type = colon ? std::string(device, colon) : std::string(device);
   if (type != "HIP" && type != "CUDA")
     return fail((int)ICICLE_INVALID_DEVICE, "device type '%.63s' is not registered (only HIP; this library has no CPU fallback)", type.c_str());
-  const char* list = colon ? colon + 1 : getenv("ICICLE_SNARK_DEVICES");
+  const char* list = colon ? colon + 1 : env_str("ICICLE_SNARK_DEVICES");
   if (!colon && (!list || !*list)) {
     ids.push_back(0); // Device::new(device, 0) — src/lib.rs:26
     return 0;
@@ -150,7 +150,7 @@ std::string group_describe(const DeviceGroup* g)
   // ranks of an RCCL communicator that take part in the exchanges: 0 unless the rccl transport was selected
   out += ", \"rccl_ranks\": " + std::to_string(g->mode == XCHG_RCCL ? g->comms.size() : (size_t)0);
   out += std::string(", \"distributed_front_end\": ") + (g->dist ? "true" : "false");
-  out += std::string(", \"transport_forced_by_env\": ") + (getenv("ICICLE_SNARK_EXCHANGE") && *getenv("ICICLE_SNARK_EXCHANGE") ? "true" : "false");
+  out += std::string(", \"transport_forced_by_env\": ") + (env_str("ICICLE_SNARK_EXCHANGE") && *env_str("ICICLE_SNARK_EXCHANGE") ? "true" : "false");
   out += "}";
   return out;
 }
@@ -395,7 +395,7 @@ static int setup_exchange(DeviceGroup* g)
     for (int j = 0; j < i; j++)
       if (g->devs[i] == g->devs[j]) distinct = false;
   std::vector<int> order;
-  const char* forced = getenv("ICICLE_SNARK_EXCHANGE");
+  const char* forced = env_str("ICICLE_SNARK_EXCHANGE");
   if (forced && *forced) {
     if (!strcmp(forced, "pull")) order = {XCHG_PULL};
     else if (!strcmp(forced, "memcpy")) order = {XCHG_MEMCPY};
@@ -427,7 +427,7 @@ static int setup_exchange(DeviceGroup* g)
       rc = exchange_self_test(g);
     }
     if (!rc) {
-      if (getenv("ICICLE_SNARK_VERBOSE")) fprintf(stderr, "[icicle-snark-hip] device group of %d: %s exchange\n", G, mode_name(m));
+      if (env_set("ICICLE_SNARK_VERBOSE")) fprintf(stderr, "[icicle-snark-hip] device group of %d: %s exchange\n", G, mode_name(m));
       return 0;
     }
     last_rc = rc;

@@ -140,7 +140,7 @@ extern "C" __attribute__((visibility("default"))) void groth16_cache_manager_pre
 __attribute__((visibility("default"))) Groth16CacheManager* groth16_cache_manager_new(void)
 {
   Groth16CacheManager* cm = new Groth16CacheManager();
-  if (const char* b = getenv("ICICLE_SNARK_CACHE_BUDGET_MB")) cm->budget_bytes = (uint64_t)atoll(b) << 20;
+  cm->budget_bytes = (uint64_t)env_i64("ICICLE_SNARK_CACHE_BUDGET_MB", 0) << 20;
   // a device is already chosen (icicle_set_device before the manager, like src/lib.rs:25-31 before :44): what the first cache
   // load needs of it — six streams with their DMA queues, the pinned staging pool — is created now, on a helper thread
   const int dev = default_device_or_none();
@@ -154,7 +154,7 @@ __attribute__((visibility("default"))) void groth16_cache_manager_prewarm(Groth1
   if (!cm || device_id < 0) return;
   std::lock_guard<std::mutex> lk(cm->mu);
   if (cm->warm.joinable()) return;
-  static const bool off = getenv("ICICLE_SNARK_PREWARM") && atoi(getenv("ICICLE_SNARK_PREWARM")) == 0;
+  static const bool off = env_int("ICICLE_SNARK_PREWARM", 1) == 0;
   if (off) return;
   try {
     // six streams for the first key, two lanes for its cold upload: a lane created on demand costs the first cold prove of a
@@ -377,63 +377,67 @@ __attribute__((visibility("default"))) int groth16_commitments(Groth16CacheManag
 
 namespace isnark {
 namespace prover {
-int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, size_t wtns_len, uint8_t* out_points, Groth16Timings* tm, EarlyTerms* et)
+namespace {
+// The process-static knobs of the prove path, read once, at the first prove of the process.
+struct ProveKnobs {
+  // print when the launching thread has enqueued each phase of a prove and when the host tails are done, in µs since the call
+  const bool trace_host = env_set("ICICLE_SNARK_TRACE_HOST");
+  // which MSMs (bit 0 … 4 = A, B1, B2, C, H) run their large-bucket kernels on a side stream beside the accumulation (default B2 + H)
+  const int large_side = env_int("ICICLE_SNARK_LARGE_SIDE", 0x14);
+  // the share of a witness, in percent, that is sorted and accumulated while the rest is still being uploaded (0 = off; −1: follows the upload)
+  const int head_pct = env_int("ICICLE_SNARK_HEAD_PCT", -1);
+  // smallest witness that is split (−1: 2^19 wires; the tests set 0 so that circuits the oracle proves in seconds take the path)
+  const long head_min = (long)env_i64("ICICLE_SNARK_HEAD_MIN", -1);
+  // groth16_prove does not print its `proof took: …` line
+  const bool quiet = env_int("ICICLE_SNARK_QUIET", 0) != 0;
+};
+const ProveKnobs& knobs()
 {
-  if (!wtns && !z->witness_resident) return fail(ERR_ARG, "no witness given and none resident on the device");
-  const auto t0 = std::chrono::steady_clock::now();
-  static const bool trace_host = getenv("ICICLE_SNARK_TRACE_HOST") != nullptr;
-  auto mark = [&](const char* what) {
-    if (trace_host) fprintf(stderr, "[host] %-12s %8.1f us\n", what, ms_since(t0) * 1e3);
-  };
-  if (int rc = set_active_device(z->device_id)) return rc;
-  if (int rc = ensure_domain(cm, z)) return rc;
-  mark("domain");
-  // deferred fixed-base tables (cache.cpp): complete → this prove is the first to use them; still building → classic layout
-  (void)adopt_tables(z, false);
-  // the key follows its witnesses: a digit width at least two bits off the one the last witness called for (one bit when the key still
-  // has its dense width) → the four witness
-  // tables are re-built with that width, at most once every eight proves — by a worker thread BESIDE the proves of the key (round 5;
-  // rounds 3–4 re-built them here, 0.1–0.3 s inside a prove), which go on with the tables they have until the new ones are complete
-  // and adopt_tables above swaps them in (all four and geom_w together).  The worker is started at the END of the prove that counted
-  // the digits (follow_witness below); ICICLE_SNARK_SYNC_REBUILD=1 re-builds here, inside the next prove, as rounds 3–4 did.
-  auto follow_witness = [&](bool sync) -> int {
-    if (!(z->geom_w.tab && z->witness_entries && z->proves_since_rebuild >= 1 && z->tb.state.load(std::memory_order_acquire) == 0)) return 0;
-    const int c_t = witness_digit_target(z, z->witness_entries);
-    // (from the dense width one bit narrower is taken at once — below ≈ 28 entries per bucket it pays, cache.cpp: witness_table_geometry —;
-    //  every later move needs two bits and eight proves: no flapping)
-    const bool from_default = z->geom_w.c == z->geom_w_default_c;
-    if (!(((from_default && c_t < z->geom_w.c) || c_t <= z->geom_w.c - 2 || c_t >= z->geom_w.c + 2) && (from_default || z->proves_since_rebuild >= 8))) return 0;
-    if (sync) {
-      if (int rc = rebuild_witness_tables(z, c_t)) return rc;
-    } else
-      start_witness_rebuild(z, c_t);
-    z->proves_since_rebuild = 0;
-    return 0;
-  };
-  const bool sync_rebuild = getenv("ICICLE_SNARK_SYNC_REBUILD") && atoi(getenv("ICICLE_SNARK_SYNC_REBUILD")) != 0;
-  if (sync_rebuild)
-    if (int rc = follow_witness(true)) return rc;
-  const uint32_t n = z->domain_size, nv = z->n_vars, npub = z->n_public;
-  hipStream_t g1 = z->s_g1, g2 = z->s_g2, g3 = z->s_g3, gq = z->s_qap;
-  double h2d_host_ms = 0;
+  static const ProveKnobs k;
+  return k;
+}
+
+typedef std::chrono::steady_clock::time_point TimePoint;
+void trace_mark(TimePoint t0, const char* what)
+{
+  if (knobs().trace_host) fprintf(stderr, "[host] %-12s %8.1f us\n", what, ms_since(t0) * 1e3);
+}
+
+constexpr uint32_t HEAD_UNIT = (uint32_t)(STAGED_CHUNK_BYTES / 32); // the head of a witness is a whole number of upload chunks
+constexpr int H_BEHIND = 1;                                         // the witness MSM whose stream carries H's chain (enqueue_h_msm): B1
+
+struct DrainOnError {
+  ZKeyCache* z;
+  bool armed = true;
+  ~DrainOnError()
+  {
+    if (!armed) return;
+    for (hipStream_t st : {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5})
+      if (st) (void)hipStreamSynchronize(st);
+  }
+};
+
+// What the stages of one prove share.  Lives on shard_commitments' stack and outlives every pooled host task that refers to it
+// (all of them are waited for on every path).
+struct ProveCtx {
+  Groth16CacheManager* const cm;
+  ZKeyCache* const z;
+  const TimePoint t0;
+  const bool new_witness; // the call brings a witness (else: the resident one)
+  const uint32_t n, nv, npub, wlo, wlen;
+  const uint32_t skip_below; // C ignores witness[0..=n_public]
+  const hipStream_t g1, g2, g3, gq;
+  const hipStream_t st4[4]; // A, B1, B2, C: separate streams, so that one MSM's latency-bound reduction overlaps another's accumulation
+  const Shard* const sh4[4];
   SortPlan plan_w, plan_head, plan_h; // witness (all of it, or its tail when the head is sorted apart), head of the witness, H scalars
   // bucket arrays of the four witness MSMs (A, B1, B2, C): owned here because a head and a tail accumulation share them
   WsScoped<uint8_t> bk[4];
-  // Declared after the plans, so it runs before their destructors, and before the first enqueue of this call: on an error
-  // return the kernels already enqueued may still read the plans' workspace (which ~SortPlan hands back to the arena) or
-  // the caller's pinned witness buffer — drain the six streams first.
-  struct DrainOnError {
-    ZKeyCache* z;
-    bool armed = true;
-    ~DrainOnError()
-    {
-      if (!armed) return;
-      for (hipStream_t st : {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5})
-        if (st) (void)hipStreamSynchronize(st);
-    }
-  } drain{z};
-  const uint32_t wlo = z->A.lo, wlen = z->A.len(), skip = npub + 1;
-  const uint32_t early_max = EARLY_MAX_DEFAULT;
+  // Declared after the plans and the bucket arrays, so it runs before their destructors, and constructed before the first enqueue
+  // of the call: on an error return the kernels already enqueued may still read the plans' workspace (which ~SortPlan hands back
+  // to the arena) or the caller's pinned witness buffer — drain the six streams first.
+  DrainOnError drain;
+  MsmProfile* prof[5]; // A, B1, B2, C, H — this entry's own slots (published to the device's ring at the end by the lead shard)
+  MsmProfile* psort;   // the witness sort is timed with the profile of the G2 MSM
   // Witness MSMs of small circuits (domain up to 2^19) leave the GPU far from full: they start right
   // after the witness sort instead of waiting for the QAP (200 k constraints: 3.71 → 3.51 ms, 400 k: 6.69 → 6.24 ms; the QAP
   // itself slows down — 1.1 → 3.9 ms at 400 k — which is why the large ones are held back: 800 k: 9.87 → 10.27 ms).
@@ -441,175 +445,222 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
   // sort behind its own PCIe upload and its accumulations behind that sort: the all-gather of the witness, the distributed front
   // end and its two all-to-alls — xGMI round trips during which the GPU would otherwise wait — then run beside them; only H needs
   // the front end.  (On ONE GPU with every shard aliased to it this is neutral: there is no exchange latency to hide.)
-  const bool own_slice_first = z->in_group && z->slice_aligned && z->own_slice_event_set && wtns == nullptr;
-  const bool early = wlen <= early_max && (n <= early_max || own_slice_first); // (rank-per-GPU shards keep the full-size inverse transform: neutral there)
-  MsmProfile* prof[5]; // A, B1, B2, C, H — this entry's own slots (published to the device's ring at the end by the lead shard)
-  for (int k = 0; k < 5; k++) {
-    prof[k] = &z->prof[k];
-    msm_profile_own_init(prof[k]);
-  }
-  msm_profile_own_init(&z->prof[5]); // digit sort of the witness head (roofline.scatter of bench.py adds it to the tail's)
-  z->prof[5].L = 0;
-  z->prof[5].valid = true; // (published either way so that the ring keeps its order; L = 0 says "no head in this prove")
-  // (tab > 1 = table mode with exactly this digit width: a key adapted to its witnesses, cache.cpp)
-  const bool adapted_w = z->geom_w.tab && z->geom_w.c != z->geom_w_default_c;
-  const uint32_t skip_below = skip > wlo ? skip - wlo : 0; // C ignores witness[0..=n_public]
-  const Shard* sh4[4] = {&z->A, &z->B1, &z->B2, &z->C};
-  hipStream_t st4[4] = {g1, z->s_g4, g2, z->s_g5}; // A, B1, B2, C: separate streams, so that one MSM's latency-bound reduction overlaps another's accumulation
-  // accumulation of witness[first … first + pl.L) into the bucket array of MSM k (0 A, 1 B1, 2 B2, 3 C) on stream st: the sort
-  // entries index scalars relative to `first`, so the table pointer moves with it (C's bases start at wire n_public + 1)
-  // The large-bucket kernels of an MSM on a SIDE stream beside its accumulation (msm_plan.h: LargeSide): B2's on the front end's
-  // stream and H's on the H-sort stream — both idle by then.  ICICLE_SNARK_LARGE_SIDE: bit k = MSM k (A, B1, B2, C, H); default B2 + H.
-  static const int large_side_mask = getenv("ICICLE_SNARK_LARGE_SIDE") ? atoi(getenv("ICICLE_SNARK_LARGE_SIDE")) : 0x14;
-  auto large_side = [&](int k, hipStream_t side_stream) {
-    LargeSide ls;
-    if ((large_side_mask >> k) & 1) {
-      ls.stream = side_stream;
-      ls.fork = z->ev_lfork[k];
-      ls.join = z->ev_ljoin[k];
-    }
-    return ls;
-  };
-  auto accumulate = [&](int k, const SortPlan& pl, uint32_t first, bool into, hipStream_t st, MsmProfile* p, bool resident = false, const LargeSide* side = nullptr) -> int {
-    const size_t esz = k == 2 ? 128 : 64;
-    uint32_t sb = 0;
-    size_t base_off = first;
-    if (k == 3) {
-      if (first >= skip_below) base_off = first - skip_below;
-      else {
-        base_off = 0;
-        sb = skip_below - first;
-      }
-    }
-    const void* pts = (const uint8_t*)sh4[k]->d_points + base_off * esz;
-    if (k == 2) P_ICICLE(msm_g2_accumulate(&pl, pts, 2, sb, st, bk[k].p, into, p, sh4[k]->len(), resident, side));
-    else P_ICICLE(msm_g1_accumulate(&pl, pts, 2, sb, st, bk[k].p, into, p, sh4[k]->len(), resident, side));
-    return 0;
-  };
+  const bool own_slice_first, early;
+  const bool adapted_w; // (tab > 1 = table mode with exactly this digit width: a key adapted to its witnesses, cache.cpp)
+  // set by the stages
+  uint32_t head = 0; // wires of the witness that are sorted and accumulated while the rest is still on its way (receive_witness)
+  bool head_forced = false, pinned_src = false;
+  hipStream_t gs = nullptr;       // stream of the witness sort (receive_witness)
+  bool h_chain = false;           // H runs behind B1 on B1's stream, gh (enqueue_h_msm)
+  hipStream_t gh = nullptr;
+  const fe* d_hscalars = nullptr; // the front end's result, this rank's range
+  double h2d_host_ms = 0;
 
-  // ---- the witness arrives.  HEAD / TAIL: over PCIe the witness takes 1.4 ms (host buffer) to 2.7 ms (file) at 1.6 M constraints
-  // and nothing of construct_r1cs can start before all of it is there (the spmv reads arbitrary wires) — but the witness MSMs are
-  // sums over wires: the first `head` wires are sorted and accumulated into the four bucket arrays while the rest is still on
-  // its way, and the tail's accumulation continues those buckets after the front end (msm_plan.h: `into`).  The GPU, idle during
-  // the upload before, takes 8–20 % of the witness accumulations (what the upload of the machine affords) off the critical path.
-  uint32_t head = 0;
-  const uint32_t head_unit = (uint32_t)(STAGED_CHUNK_BYTES / 32); // the head is a whole number of upload chunks
-  bool pinned_src = false, head_forced = false;
+  ProveCtx(Groth16CacheManager* cm_, ZKeyCache* z_, bool new_witness_, TimePoint t0_)
+      : cm(cm_), z(z_), t0(t0_), new_witness(new_witness_), n(z_->domain_size), nv(z_->n_vars), npub(z_->n_public), wlo(z_->A.lo), wlen(z_->A.len()),
+        skip_below(npub + 1 > wlo ? npub + 1 - wlo : 0), g1(z_->s_g1), g2(z_->s_g2), g3(z_->s_g3), gq(z_->s_qap), st4{z_->s_g1, z_->s_g4, z_->s_g2, z_->s_g5},
+        sh4{&z_->A, &z_->B1, &z_->B2, &z_->C}, drain{z_}, own_slice_first(z_->in_group && z_->slice_aligned && z_->own_slice_event_set && !new_witness_),
+        early(wlen <= EARLY_MAX_DEFAULT && (n <= EARLY_MAX_DEFAULT || own_slice_first)), // (rank-per-GPU shards keep the full-size inverse transform: neutral there)
+        adapted_w(z_->geom_w.tab && z_->geom_w.c != z_->geom_w_default_c)
+  {
+    for (int k = 0; k < 5; k++) {
+      prof[k] = &z->prof[k];
+      msm_profile_own_init(prof[k]);
+    }
+    psort = prof[2];
+    msm_profile_own_init(&z->prof[5]); // digit sort of the witness head (roofline.scatter of bench.py adds it to the tail's)
+    z->prof[5].L = 0;
+    z->prof[5].valid = true; // (published either way so that the ring keeps its order; L = 0 says "no head in this prove")
+  }
+  void mark(const char* what) const { trace_mark(t0, what); }
+};
+
+int check_witness(const ZKeyCache* z, const Wtns& w)
+{
+  // src/proof_helper.rs:253-262
+  if (!Fr::eq(z->r, w.q)) return fail(ERR_FORMAT, "Curve of the witness does not match the curve of the proving key");
+  if (w.n_witness != z->n_vars) return fail(ERR_FORMAT, "Invalid witness length. Circuit: %u, witness: %u", z->n_vars, w.n_witness);
+  return 0;
+}
+
+// The large-bucket kernels of MSM k on a SIDE stream beside its accumulation (msm_plan.h: LargeSide): B2's on the front end's
+// stream and H's on the H-sort stream — both idle by then.  ICICLE_SNARK_LARGE_SIDE: bit k = MSM k (A, B1, B2, C, H); default B2 + H.
+LargeSide large_side(const ProveCtx& c, int k, hipStream_t side_stream)
+{
+  LargeSide ls;
+  if ((knobs().large_side >> k) & 1) {
+    ls.stream = side_stream;
+    ls.fork = c.z->ev_lfork[k];
+    ls.join = c.z->ev_ljoin[k];
+  }
+  return ls;
+}
+
+// accumulation of witness[first … first + pl.L) into the bucket array of MSM k (0 A, 1 B1, 2 B2, 3 C) on stream st: the sort
+// entries index scalars relative to `first`, so the table pointer moves with it (C's bases start at wire n_public + 1)
+int accumulate(ProveCtx& c, int k, const SortPlan& pl, uint32_t first, bool into, hipStream_t st, MsmProfile* p, bool resident = false, const LargeSide* side = nullptr)
+{
+  const size_t esz = k == 2 ? 128 : 64;
+  uint32_t sb = 0;
+  size_t base_off = first;
+  if (k == 3) {
+    if (first >= c.skip_below) base_off = first - c.skip_below;
+    else {
+      base_off = 0;
+      sb = c.skip_below - first;
+    }
+  }
+  const void* pts = (const uint8_t*)c.sh4[k]->d_points + base_off * esz;
+  if (k == 2) P_ICICLE(msm_g2_accumulate(&pl, pts, 2, sb, st, c.bk[k].p, into, p, c.sh4[k]->len(), resident, side));
+  else P_ICICLE(msm_g1_accumulate(&pl, pts, 2, sb, st, c.bk[k].p, into, p, c.sh4[k]->len(), resident, side));
+  return 0;
+}
+
+void fill_profile(MsmProfile* p, const SortPlan& pl, int g2flag)
+{
+  p->L = pl.L; p->nbuckets = pl.nbuckets; p->c = pl.g.c; p->W = pl.g.W; p->is_g2 = g2flag;
+}
+
+// head: digit sort, then the four accumulations (zero-initialising their bucket arrays) — ONE chain on g2, each kernel
+// launched with no more workgroups than the GPU holds (`resident`).  Four concurrent accumulations with ordinary
+// grids were measured first: their queued workgroups kept the hardware pipes busy dispatching, the barrier packets
+// behind the staging DMAs (the events the upload workers wait for before they re-use a pinned buffer) were not
+// processed until the kernels ended, and the upload stalled for their whole length (70 % of the bytes in 1.8 ms, the
+// rest 1.1 ms late: profiles/r04_head_concurrent_timeline.txt).
+int enqueue_head(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t g2 = c.g2;
+  SortPlan& plan_head = c.plan_head;
+  (void)hipEventRecord(z->ev_t_head_start, g2); // (timing, with ev_t_head_end and ev_t_witness: steers head_frac)
+  MsmProfile* ph = &z->prof[5];
+  (void)hipEventRecord(ph->ev[0], g2);
+  P_ICICLE(msm_sort_run(z->d_witness, c.head, 0, 0, 0, g2, &plan_head, z->geom_w.c, 0, 1, c.adapted_w ? (uint64_t)((double)z->witness_entries * c.head / c.nv) + 1 : 0));
+  for (int e = 1; e < 5; e++) (void)hipEventRecord(ph->ev[e], g2);
+  ph->has_sort_end = ph->valid = true;
+  fill_profile(ph, plan_head, 0);
+  ph->L = c.head;
+  // entry count of the head's sort (offset + count of its last bucket) for the key's digit-width rule — on g2, in stream
+  // order behind the sort that writes them (round-4 advisor: on the tail's stream nothing ordered the copies behind it)
+  if (plan_head.nbuckets) {
+    P_HIP(hipMemcpyAsync(&z->h_stats[2], plan_head.offsets + plan_head.nbuckets - 1, 4, hipMemcpyDeviceToHost, g2));
+    P_HIP(hipMemcpyAsync(&z->h_stats[3], plan_head.counts + plan_head.nbuckets - 1, 4, hipMemcpyDeviceToHost, g2));
+  }
+  if (plan_head.g.tab != z->geom_w.tab || plan_head.g.c != z->geom_w.c || plan_head.nbuckets != z->geom_w.NB)
+    return fail((int)ICICLE_UNKNOWN_ERROR, "window geometry of the cached tables does not match the sort of the witness head");
+  for (int k = 0; k < 4; k++) P_HIP(c.bk[k].alloc(msm_bucket_bytes(&plan_head, k == 2), c.st4[k]));
+  for (int k : {2, 0, 1, 3})
+    if (int rc = accumulate(c, k, plan_head, 0, false, g2, nullptr, true)) return rc;
+  P_HIP(hipEventRecord(z->ev_head_done, g2));
+  (void)hipEventRecord(z->ev_t_head_end, g2); // (timing: where the head's chain ends relative to the upload)
+  return 0;
+}
+
+// the witness with a head: the upload (two DMAs from a pinned source, else the staged uploader on a pooled worker) and, as soon as
+// the head's bytes are in, the head's chain on g2
+int upload_with_head(ProveCtx& c, const Wtns& w)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t g2 = c.g2, g3 = c.g3, gq = c.gq;
+  const uint32_t head = c.head, nv = c.nv;
+  // the head's kernels go to g2; the staging lanes of the upload are three of the streams with nothing to do before the whole
+  // witness is there (QAP, H sort, C's own) — no extra stream, no extra hardware queue
+  const hipStream_t lanes[3] = {gq, g3, z->s_g5}; // (two to five lanes measure the same: profiles/r04_upload_lanes.txt)
+  StagedProgress prog;
+  prog.head_bytes = (size_t)head * 32;
+  int up_rc = 0, wait_rc = 0; // up_rc and up_err belong to the uploader task until it has been waited for
+  std::string up_err;
+  HostTask uploader; // (a pooled worker, workers.h; waited for on every path below)
+  bool uploader_started = false;
+  const void* hint_base;
+  size_t hint_len;
+  int hint_fd;
+  staged_copy_file_hint_get(&hint_base, &hint_len, &hint_fd);
+  if (c.pinned_src) {
+    // the caller's buffer is pinned: two DMAs straight from it on the QAP stream, an event between them
+    P_HIP(hipMemcpyAsync(z->d_witness, w.values, (size_t)head * 32, hipMemcpyHostToDevice, gq));
+    P_HIP(hipEventRecord(z->ev_head_in, gq));
+    P_HIP(hipMemcpyAsync(z->d_witness + head, (const uint8_t*)w.values + (size_t)head * 32, (size_t)(nv - head) * 32, hipMemcpyHostToDevice, gq));
+    P_HIP(hipStreamWaitEvent(g2, z->ev_head_in, 0));
+  } else {
+    uploader.fn = [&] {
+      staged_copy_file_hint(hint_base, hint_len, hint_fd);
+      up_rc = staged_upload(z->device_id, {{z->d_witness, (const uint8_t*)w.values, (size_t)nv * 32}}, lanes, 3, &prog);
+      if (up_rc) up_err = last_error_text(); // (the text lives in this worker's thread-local slot: hand it to the caller)
+      staged_copy_file_hint(nullptr, 0, -1);
+      prog.done.store(true, std::memory_order_release);
+      prog.notify();
+    };
+    // no worker to be had (thread limit of the container): the upload runs here, the head follows it instead of overlapping it
+    WorkerPool::get().run_or_inline(&uploader);
+    uploader_started = true;
+    prog.wait_head(); // blocks (condition variable) until every lane has recorded the event behind its last chunk of the head
+    c.mark("head in");
+    const int tot = prog.lanes_total.load(std::memory_order_acquire);
+    for (int t = 0; t < tot; t++)
+      if (prog.ev[t] && hipStreamWaitEvent(g2, prog.ev[t], 0) != hipSuccess) wait_rc = fail((int)ICICLE_UNKNOWN_ERROR, "hipStreamWaitEvent");
+  }
+  int hrc = 0;
+  if (!wait_rc) hrc = enqueue_head(c);
+  c.mark("head enq");
+  if (uploader_started && uploader.queued) WorkerPool::wait(&uploader);
+  c.mark("upload");
+  if (up_rc) return fail(up_rc, "%s", up_err.c_str());
+  if (wait_rc) return wait_rc;
+  if (hrc) return hrc;
+  if (c.pinned_src) P_HIP(hipEventRecord(z->ev_witness, gq));
+  return 0;
+}
+
+// ---- the witness arrives.  HEAD / TAIL: over PCIe the witness takes 1.4 ms (host buffer) to 2.7 ms (file) at 1.6 M constraints
+// and nothing of construct_r1cs can start before all of it is there (the spmv reads arbitrary wires) — but the witness MSMs are
+// sums over wires: the first `head` wires are sorted and accumulated into the four bucket arrays while the rest is still on
+// its way, and the tail's accumulation continues those buckets after the front end (msm_plan.h: `into`).  The GPU, idle during
+// the upload before, takes 8–20 % of the witness accumulations (what the upload of the machine affords) off the critical path.
+int receive_witness(ProveCtx& c, const void* wtns, size_t wtns_len)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t g2 = c.g2, g3 = c.g3, gq = c.gq;
+  const uint32_t nv = c.nv;
   if (wtns) {
     Wtns w;
     if (int rc = parse_wtns((const uint8_t*)wtns, wtns_len, w)) return rc;
-    // src/proof_helper.rs:253-262
-    if (!Fr::eq(z->r, w.q)) return fail(ERR_FORMAT, "Curve of the witness does not match the curve of the proving key");
-    if (w.n_witness != z->n_vars) return fail(ERR_FORMAT, "Invalid witness length. Circuit: %u, witness: %u", z->n_vars, w.n_witness);
+    if (int rc = check_witness(z, w)) return rc;
     // a new witness invalidates whatever the distributed stages left behind for the previous one
     z->witness_resident = false;
     z->dist_ready = z->dist_stage2_done = false;
     z->witness_event_set = false;
-    // (ICICLE_SNARK_HEAD_PCT: the head's share in percent, 0 = off; ICICLE_SNARK_HEAD_MIN: smallest witness that is split —
-    //  the tests set it to 0 so that circuits the oracle proves in seconds take the path)
-    static const int head_pct_env = getenv("ICICLE_SNARK_HEAD_PCT") ? atoi(getenv("ICICLE_SNARK_HEAD_PCT")) : -1;
-    static const long head_min_env = getenv("ICICLE_SNARK_HEAD_MIN") ? atol(getenv("ICICLE_SNARK_HEAD_MIN")) : -1;
+    const int head_pct = knobs().head_pct;
+    const long head_min_env = knobs().head_min;
     const uint32_t head_min = head_min_env >= 0 ? (uint32_t)head_min_env : (1u << 19);
-    head_forced = head_pct_env >= 0;
+    c.head_forced = head_pct >= 0;
     // Not for a key adapted to light witnesses (cache.cpp: mostly 0 / 1 wires, a fifth of the digits of a dense witness): its
     // accumulations are short and the second sort, the second round of large-bucket kernels and the transforms slowed by the
     // head's last workgroups cost more than the head takes off the MSM phase (stand-ins of BASELINE configs 4 / 5: 5.6 → 7.0 ms
     // and 8.6 → 9.3 ms with a head; benchmark/1600k: 16.8 → 16.3 ms, 3200k: 30.7 → 29.4 ms).
-    const bool head_ok = z->geom_w.tab && z->shard_count == 1 && wlo == 0 && wlen == nv && nv >= head_min;
-    if (head_ok && head_pct_env >= 0 && (!early || head_min_env >= 0)) {
-      head = (uint32_t)((double)nv * (head_pct_env / 100.0) / head_unit + 0.5) * head_unit; // forced share (tests, sweeps)
-    } else if (head_ok && !early && !adapted_w) {
-      if (z->head_units < 0) z->head_units = (int)((double)nv * 0.10 / head_unit + 0.5); // first prove of the key: a tenth
-      head = (uint32_t)z->head_units * head_unit;
+    const bool head_ok = z->geom_w.tab && z->shard_count == 1 && c.wlo == 0 && c.wlen == nv && nv >= head_min;
+    uint32_t head = 0;
+    if (head_ok && head_pct >= 0 && (!c.early || head_min_env >= 0)) {
+      head = (uint32_t)((double)nv * (head_pct / 100.0) / HEAD_UNIT + 0.5) * HEAD_UNIT; // forced share (tests, sweeps)
+    } else if (head_ok && !c.early && !c.adapted_w) {
+      if (z->head_units < 0) z->head_units = (int)((double)nv * 0.10 / HEAD_UNIT + 0.5); // first prove of the key: a tenth
+      head = (uint32_t)z->head_units * HEAD_UNIT;
     }
-    if (head < head_unit || head >= nv || nv - head < head_unit) head = 0;
+    if (head < HEAD_UNIT || head >= nv || nv - head < HEAD_UNIT) head = 0;
     if (z->feed) head = 0;
+    c.head = head;
     const auto tu = std::chrono::steady_clock::now();
-    pinned_src = !z->feed && is_pinned_host(w.values, z->device_id);
+    c.pinned_src = !z->feed && is_pinned_host(w.values, z->device_id);
     P_HIP(hipEventRecord(z->ev[0], gq));
     if (z->feed) {
       // cold pipeline (prover_internal.h: ColdFeed): the uploader task that is still sending the key's sections has the witness
       // as its second stage — wait until that stage has been POSTED (its event recorded), then order the front end behind it
       if (int rc = z->feed->wait(ColdFeed::WITNESS)) return fail(rc, "%s", z->feed->err.c_str());
       P_HIP(hipStreamWaitEvent(gq, z->feed->ev[ColdFeed::WITNESS], 0));
-      mark("feed: witness");
+      c.mark("feed: witness");
     } else if (head) {
-      // the head's kernels go to g2; the staging lanes of the upload are three of the streams with nothing to do before the whole
-      // witness is there (QAP, H sort, C's own) — no extra stream, no extra hardware queue
-      const hipStream_t lanes[3] = {gq, g3, z->s_g5}; // (two to five lanes measure the same: profiles/r04_upload_lanes.txt)
-      StagedProgress prog;
-      prog.head_bytes = (size_t)head * 32;
-      int up_rc = 0, wait_rc = 0; // up_rc and up_err belong to the uploader task until it has been waited for
-      std::string up_err;
-      HostTask uploader; // (a pooled worker, workers.h; waited for on every path below)
-      bool uploader_started = false;
-      const void* hint_base;
-      size_t hint_len;
-      int hint_fd;
-      staged_copy_file_hint_get(&hint_base, &hint_len, &hint_fd);
-      if (pinned_src) {
-        // the caller's buffer is pinned: two DMAs straight from it on the QAP stream, an event between them
-        P_HIP(hipMemcpyAsync(z->d_witness, w.values, (size_t)head * 32, hipMemcpyHostToDevice, gq));
-        P_HIP(hipEventRecord(z->ev_head_in, gq));
-        P_HIP(hipMemcpyAsync(z->d_witness + head, (const uint8_t*)w.values + (size_t)head * 32, (size_t)(nv - head) * 32, hipMemcpyHostToDevice, gq));
-        P_HIP(hipStreamWaitEvent(g2, z->ev_head_in, 0));
-      } else {
-        uploader.fn = [&] {
-          staged_copy_file_hint(hint_base, hint_len, hint_fd);
-          up_rc = staged_upload(z->device_id, {{z->d_witness, (const uint8_t*)w.values, (size_t)nv * 32}}, lanes, 3, &prog);
-          if (up_rc) up_err = last_error_text(); // (the text lives in this worker's thread-local slot: hand it to the caller)
-          staged_copy_file_hint(nullptr, 0, -1);
-          prog.done.store(true, std::memory_order_release);
-          prog.notify();
-        };
-        // no worker to be had (thread limit of the container): the upload runs here, the head follows it instead of overlapping it
-        WorkerPool::get().run_or_inline(&uploader);
-        uploader_started = true;
-        prog.wait_head(); // blocks (condition variable) until every lane has recorded the event behind its last chunk of the head
-        mark("head in");
-        const int tot = prog.lanes_total.load(std::memory_order_acquire);
-        for (int t = 0; t < tot; t++)
-          if (prog.ev[t] && hipStreamWaitEvent(g2, prog.ev[t], 0) != hipSuccess) wait_rc = fail((int)ICICLE_UNKNOWN_ERROR, "hipStreamWaitEvent");
-      }
-      // head: digit sort, then the four accumulations (zero-initialising their bucket arrays) — ONE chain on g2, each kernel
-      // launched with no more workgroups than the GPU holds (`resident`).  Four concurrent accumulations with ordinary
-      // grids were measured first: their queued workgroups kept the hardware pipes busy dispatching, the barrier packets
-      // behind the staging DMAs (the events the upload workers wait for before they re-use a pinned buffer) were not
-      // processed until the kernels ended, and the upload stalled for their whole length (70 % of the bytes in 1.8 ms, the
-      // rest 1.1 ms late: profiles/r04_head_concurrent_timeline.txt).
-      int hrc = 0;
-      auto enqueue_head = [&]() -> int {
-        (void)hipEventRecord(z->ev_t_head_start, g2); // (timing, with ev_t_head_end and ev_t_witness: steers head_frac)
-        MsmProfile* ph = &z->prof[5];
-        (void)hipEventRecord(ph->ev[0], g2);
-        P_ICICLE(msm_sort_run(z->d_witness, head, 0, 0, 0, g2, &plan_head, z->geom_w.c, 0, 1, adapted_w ? (uint64_t)((double)z->witness_entries * head / nv) + 1 : 0));
-        for (int e = 1; e < 5; e++) (void)hipEventRecord(ph->ev[e], g2);
-        ph->has_sort_end = ph->valid = true;
-        ph->L = head; ph->nbuckets = plan_head.nbuckets; ph->c = plan_head.g.c; ph->W = plan_head.g.W; ph->is_g2 = 0;
-        // entry count of the head's sort (offset + count of its last bucket) for the key's digit-width rule — on g2, in stream
-        // order behind the sort that writes them (round-4 advisor: on the tail's stream nothing ordered the copies behind it)
-        if (plan_head.nbuckets) {
-          P_HIP(hipMemcpyAsync(&z->h_stats[2], plan_head.offsets + plan_head.nbuckets - 1, 4, hipMemcpyDeviceToHost, g2));
-          P_HIP(hipMemcpyAsync(&z->h_stats[3], plan_head.counts + plan_head.nbuckets - 1, 4, hipMemcpyDeviceToHost, g2));
-        }
-        if (plan_head.g.tab != z->geom_w.tab || plan_head.g.c != z->geom_w.c || plan_head.nbuckets != z->geom_w.NB)
-          return fail((int)ICICLE_UNKNOWN_ERROR, "window geometry of the cached tables does not match the sort of the witness head");
-        for (int k = 0; k < 4; k++) P_HIP(bk[k].alloc(msm_bucket_bytes(&plan_head, k == 2), st4[k]));
-        for (int k : {2, 0, 1, 3})
-          if (int rc = accumulate(k, plan_head, 0, false, g2, nullptr, true)) return rc;
-        P_HIP(hipEventRecord(z->ev_head_done, g2));
-        (void)hipEventRecord(z->ev_t_head_end, g2); // (timing: where the head's chain ends relative to the upload)
-        return 0;
-      };
-      if (!wait_rc) hrc = enqueue_head();
-      mark("head enq");
-      if (uploader_started && uploader.queued) WorkerPool::wait(&uploader);
-      mark("upload");
-      if (up_rc) return fail(up_rc, "%s", up_err.c_str());
-      if (wait_rc) return wait_rc;
-      if (hrc) return hrc;
-      if (pinned_src) P_HIP(hipEventRecord(z->ev_witness, gq));
-    } else if (pinned_src) {
+      if (int rc = upload_with_head(c, w)) return rc;
+    } else if (c.pinned_src) {
       // the caller's buffer is pinned (hipHostMalloc / hipHostRegister) and mapped for this device: one DMA straight from it,
       // in stream order with everything that waits for ev_witness — no staging copy, no host wait (51 MB: 0.9 instead of 1.35 ms)
       P_HIP(hipMemcpyAsync(z->d_witness, w.values, (size_t)nv * 32, hipMemcpyHostToDevice, gq));
@@ -622,9 +673,9 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
       const hipStream_t lanes[3] = {gq, g2, g3};
       if (int rc = staged_upload(z->device_id, {{z->d_witness, (const uint8_t*)w.values, (size_t)nv * 32}}, lanes, 3)) return rc;
     }
-    h2d_host_ms = ms_since(tu);
-    mark("witness in");
-    if (!pinned_src) P_HIP(hipEventRecord(z->ev_witness, gq)); // (the staged upload has returned: every byte is there)
+    c.h2d_host_ms = ms_since(tu);
+    c.mark("witness in");
+    if (!c.pinned_src) P_HIP(hipEventRecord(z->ev_witness, gq)); // (the staged upload has returned: every byte is there)
     z->witness_event_set = true;
   } else
     P_HIP(hipEventRecord(z->ev[0], gq));
@@ -634,47 +685,54 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
   if (!z->witness_event_set) P_HIP(hipEventRecord(z->ev_witness, gq));
   z->witness_event_set = false;
   (void)hipEventRecord(z->ev_t_witness, gq);
+  c.gs = c.head ? g3 : g2;
+  return 0;
+}
 
-  // ---- ONE digit sort of the witness range (shared by A, B1, B2, C) — of its tail when the head was sorted above — on g2
-  // without a head (the G2 bucket stages follow it there) and on g3 with one (g2 still carries B2's head accumulation).
-  // Enqueued BEHIND the front end for the large circuits (round 5): the front end is their critical chain and its first kernel
-  // used to sit behind the nine launches of the sort on the host, ≈ 50 µs after the last byte of the witness had landed; the
-  // small circuits and the shards that start from their own slice begin their accumulations right behind the sort: sort first.
-  hipStream_t gs = head ? g3 : g2;
-  MsmProfile* psort = prof[2]; // the witness sort is timed with the profile of the G2 MSM
-  auto enqueue_witness_sort = [&]() -> int {
-    P_HIP(hipStreamWaitEvent(gs, own_slice_first ? z->ev_own_slice : z->ev_witness, 0));
-    (void)hipEventRecord(psort->ev[0], gs);
-    {
-      const uint32_t tail_len = wlen - head;
-      const uint64_t hint = adapted_w ? (uint64_t)((double)z->witness_entries * tail_len / wlen) + 1 : 0;
-      P_ICICLE(msm_sort_run(z->d_witness + wlo + head, tail_len, 0, 0, 0, gs, &plan_w, z->geom_w.tab ? z->geom_w.c : 0, 0, 1, hint)); // (table mode: the KEY's digit width, whatever msm_geometry's rule says for this length)
-    }
-    if (plan_w.g.tab != z->geom_w.tab || plan_w.g.c != z->geom_w.c || (head && plan_w.nbuckets != plan_head.nbuckets))
-      return fail((int)ICICLE_UNKNOWN_ERROR, "window geometry of the cached tables does not match the witness sort");
-    (void)hipEventRecord(psort->ev[4], gs); // end of the witness digit sort (roofline.scatter)
-    psort->has_sort_end = true;
-    P_HIP(hipEventRecord(z->ev_sort, gs));
-    // entry counts of the sorts (offset + count of the last bucket), read at the end of the prove: they steer the digit width of
-    // the key's witness tables (cache.cpp: rebuild_witness_tables)
-    z->h_stats[0] = z->h_stats[1] = 0;
-    if (!head) z->h_stats[2] = z->h_stats[3] = 0; // (with a head: written by the copies behind the head's sort on g2)
-    if (plan_w.nbuckets) {
-      P_HIP(hipMemcpyAsync(&z->h_stats[0], plan_w.offsets + plan_w.nbuckets - 1, 4, hipMemcpyDeviceToHost, gs));
-      P_HIP(hipMemcpyAsync(&z->h_stats[1], plan_w.counts + plan_w.nbuckets - 1, 4, hipMemcpyDeviceToHost, gs));
-    }
-    mark("wsort");
-    return 0;
-  };
-  if (early)
-    if (int rc = enqueue_witness_sort()) return rc;
+// ---- ONE digit sort of the witness range (shared by A, B1, B2, C) — of its tail when the head was sorted apart — on g2
+// without a head (the G2 bucket stages follow it there) and on g3 with one (g2 still carries B2's head accumulation).
+int enqueue_witness_sort(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t gs = c.gs;
+  MsmProfile* psort = c.psort;
+  SortPlan& plan_w = c.plan_w;
+  const uint32_t head = c.head;
+  P_HIP(hipStreamWaitEvent(gs, c.own_slice_first ? z->ev_own_slice : z->ev_witness, 0));
+  (void)hipEventRecord(psort->ev[0], gs);
+  {
+    const uint32_t tail_len = c.wlen - head;
+    const uint64_t hint = c.adapted_w ? (uint64_t)((double)z->witness_entries * tail_len / c.wlen) + 1 : 0;
+    P_ICICLE(msm_sort_run(z->d_witness + c.wlo + head, tail_len, 0, 0, 0, gs, &plan_w, z->geom_w.tab ? z->geom_w.c : 0, 0, 1, hint)); // (table mode: the KEY's digit width, whatever msm_geometry's rule says for this length)
+  }
+  if (plan_w.g.tab != z->geom_w.tab || plan_w.g.c != z->geom_w.c || (head && plan_w.nbuckets != c.plan_head.nbuckets))
+    return fail((int)ICICLE_UNKNOWN_ERROR, "window geometry of the cached tables does not match the witness sort");
+  (void)hipEventRecord(psort->ev[4], gs); // end of the witness digit sort (roofline.scatter)
+  psort->has_sort_end = true;
+  P_HIP(hipEventRecord(z->ev_sort, gs));
+  // entry counts of the sorts (offset + count of the last bucket), read at the end of the prove: they steer the digit width of
+  // the key's witness tables (cache.cpp: follow_witness)
+  z->h_stats[0] = z->h_stats[1] = 0;
+  if (!head) z->h_stats[2] = z->h_stats[3] = 0; // (with a head: written by the copies behind the head's sort on g2)
+  if (plan_w.nbuckets) {
+    P_HIP(hipMemcpyAsync(&z->h_stats[0], plan_w.offsets + plan_w.nbuckets - 1, 4, hipMemcpyDeviceToHost, gs));
+    P_HIP(hipMemcpyAsync(&z->h_stats[1], plan_w.counts + plan_w.nbuckets - 1, 4, hipMemcpyDeviceToHost, gs));
+  }
+  c.mark("wsort");
+  return 0;
+}
 
-  // ---- stream gq: construct_r1cs (src/proof_helper.rs:31-170) on the device
+// ---- stream gq: construct_r1cs (src/proof_helper.rs:31-170) on the device
+int enqueue_front_end(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t gq = c.gq;
+  const uint32_t n = c.n;
   P_HIP(hipStreamWaitEvent(gq, z->ev_witness, 0));
   P_HIP(hipEventRecord(z->ev[1], gq));
   // the distributed stages left this rank's Z rows in d_fold — honoured only for the witness they were computed from (no new
   // witness in this call) and only once the caller has confirmed that exchange 2 delivered (groth16_dist_exchange_done)
-  const bool dist_ready = !wtns && z->dist_ready && z->H.stride > 1;
+  const bool dist_ready = !c.new_witness && z->dist_ready && z->H.stride > 1;
   z->dist_ready = z->dist_stage2_done = false;
   if (z->feed) { // cold pipeline: the coefficient records have landed and the CSR has been built from them
     if (int rc = z->feed->wait(ColdFeed::COEF)) return fail(rc, "%s", z->feed->err.c_str());
@@ -691,7 +749,7 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
   nc.is_async = true;
   int dom_log = 0;
   const fe* tw = ntt_domain_table(&dom_log);
-  const fe* d_hscalars = z->d_vec + n + z->H.lo; // slot 1 of the result, this rank's range
+  c.d_hscalars = z->d_vec + n + z->H.lo; // slot 1 of the result, this rank's range
   if (z->H.stride > 1) {
     // strided H shard: coset keys, the fold over the shard count and the twist in one pass, then a size-n/G transform
     const uint32_t m = z->H.len();
@@ -707,7 +765,7 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
       P_ICICLE(bn254_ntt((const bn254_scalar_t*)z->d_fold, (int)m, kForward, &nc, (bn254_scalar_t*)z->d_fold));
       P_HIP(qap_final(z->d_fold, m, gq));
     }
-    d_hscalars = z->d_fold + m;
+    c.d_hscalars = z->d_fold + m;
   } else if (ntt_fusable(n)) {
     // inverse transform with 1/n and the coset keys folded into its last pass (:116-141), forward transform with the
     // A·B − C epilogue folded into its last pass (:145-167): no coset sweep, no final sweep, n instead of 3n stores
@@ -728,100 +786,105 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
     P_HIP(qap_final(z->d_vec, n, gq));                                                                        // :154-167
   }
   P_HIP(hipEventRecord(z->ev[2], gq));
-  mark("qap");
+  c.mark("qap");
+  return 0;
+}
 
-  if (!early)
-    if (int rc = enqueue_witness_sort()) return rc;
-  auto fill = [](MsmProfile* p, const SortPlan& pl, int g2flag) {
-    p->L = pl.L; p->nbuckets = pl.nbuckets; p->c = pl.g.c; p->W = pl.g.W; p->is_g2 = g2flag;
-  };
-  uint8_t* DP = z->d_partials;
+// bucket arrays of the four witness MSMs, unless the head's accumulations have allocated them
+int alloc_buckets(ProveCtx& c)
+{
+  if (!c.head)
+    for (int k = 0; k < 4; k++) P_HIP(c.bk[k].alloc(msm_bucket_bytes(&c.plan_w, k == 2), c.st4[k]));
+  return 0;
+}
 
-
-  // ---- groth16_commitments — src/proof_helper.rs:198-206.  A, B1, B2, C share the witness sort and run on four streams.
-  // Held back until the QAP front end is done (large circuits): the accumulations fill every CU with milliseconds-long
-  // workgroups, and the NTT passes measured 8× slower when they had to wait for those to retire (rocprof: 2.9 ms vs 0.35 ms per pass).
-  if (!head)
-    for (int k = 0; k < 4; k++) P_HIP(bk[k].alloc(msm_bucket_bytes(&plan_w, k == 2), st4[k]));
+// ---- groth16_commitments — src/proof_helper.rs:198-206.  A, B1, B2, C share the witness sort and run on four streams.
+// Held back until the QAP front end is done (large circuits): the accumulations fill every CU with milliseconds-long
+// workgroups, and the NTT passes measured 8× slower when they had to wait for those to retire (rocprof: 2.9 ms vs 0.35 ms per pass).
+int enqueue_witness_msm(ProveCtx& c, int k)
+{
+  ZKeyCache* z = c.z;
   const int slot4[4] = {0, 1, 3, 2}; // ticket slots of the plan: A 0, B1 1, B2 3, C 2
-  auto bucket_stages = [&](int k) -> int {
-    MsmProfile* p = prof[k];
-    hipStream_t st = st4[k];
-    fill(p, plan_w, k == 2);
-    P_HIP(hipStreamWaitEvent(st, z->ev_sort, 0));
-    if (!early) P_HIP(hipStreamWaitEvent(st, z->ev[2], 0));
-    if (head && k != 2) P_HIP(hipStreamWaitEvent(st, z->ev_head_done, 0)); // the heads were accumulated on g2
-    if (z->feed) { // cold pipeline: this MSM's bases have landed and are in the bucket kernels' encoding
-      if (int rc = z->feed->wait(ColdFeed::SEC_A + k)) return fail(rc, "%s", z->feed->err.c_str());
-      P_HIP(hipStreamWaitEvent(st, z->feed->ev[ColdFeed::SEC_A + k], 0));
-    }
-    if (p != psort) (void)hipEventRecord(p->ev[0], st);
-    // side streams idle in the MSM phase: the front end's for B2, A and B1; H-sort's (behind H's sort) for C
-    const LargeSide ls = large_side(k, k == 3 ? g3 : gq);
-    if (int rc = accumulate(k, plan_w, wlo ? 0 : head, head != 0, st, p, false, ls.stream ? &ls : nullptr)) return rc;
-    P_ICICLE(k == 2 ? msm_g2_reduce(&plan_w, st, bk[k].p, DP + k * PARTIALS_STRIDE, slot4[k]) : msm_g1_reduce(&plan_w, st, bk[k].p, DP + k * PARTIALS_STRIDE, slot4[k]));
-    (void)hipEventRecord(p->ev[3], st);
-    p->valid = true;
-    return 0;
-  };
-  // ---- stream g3: digit sort of the H scalars (atomics / memory bound) overlaps the ALU-bound A, B1, C stages
-  auto enqueue_h_sort = [&]() -> int {
-    P_HIP(hipStreamWaitEvent(g3, z->ev[2], 0));
-    (void)hipEventRecord(prof[4]->ev[0], g3);
-    // (`crowded`: H's sort runs beside the four witness accumulations of a large circuit)
-    P_ICICLE(msm_sort_run(d_hscalars, z->H.len(), 0, 0, 0, g3, &plan_h, z->geom_h.tab ? z->geom_h.c : 0, 0, 1, 0, /*crowded=*/!early));
-    if (plan_h.g.tab != z->geom_h.tab || plan_h.g.c != z->geom_h.c) return fail((int)ICICLE_UNKNOWN_ERROR, "window geometry of the cached tables does not match the H sort");
-    (void)hipEventRecord(prof[4]->ev[4], g3);
-    prof[4]->has_sort_end = true;
-    P_HIP(hipEventRecord(z->ev_sort_h, g3));
-    mark("hsort");
-    return 0;
-  };
-  // (cold pipeline: the host is about to wait for B2's section — everything that needs no section is enqueued first)
-  if (z->feed)
-    if (int rc = enqueue_h_sort()) return rc;
-  if (int rc = bucket_stages(2)) return rc; // commitment_b (G2) — src/proof_helper.rs:206: the longest chain first
-  mark("g2");
-  if (!z->feed)
-    if (int rc = enqueue_h_sort()) return rc;
+  MsmProfile* p = c.prof[k];
+  hipStream_t st = c.st4[k];
+  uint8_t* DP = z->d_partials;
+  fill_profile(p, c.plan_w, k == 2);
+  P_HIP(hipStreamWaitEvent(st, z->ev_sort, 0));
+  if (!c.early) P_HIP(hipStreamWaitEvent(st, z->ev[2], 0));
+  if (c.head && k != 2) P_HIP(hipStreamWaitEvent(st, z->ev_head_done, 0)); // the heads were accumulated on g2
+  if (z->feed) { // cold pipeline: this MSM's bases have landed and are in the bucket kernels' encoding
+    if (int rc = z->feed->wait(ColdFeed::SEC_A + k)) return fail(rc, "%s", z->feed->err.c_str());
+    P_HIP(hipStreamWaitEvent(st, z->feed->ev[ColdFeed::SEC_A + k], 0));
+  }
+  if (p != c.psort) (void)hipEventRecord(p->ev[0], st);
+  // side streams idle in the MSM phase: the front end's for B2, A and B1; H-sort's (behind H's sort) for C
+  const LargeSide ls = large_side(c, k, k == 3 ? c.g3 : c.gq);
+  if (int rc = accumulate(c, k, c.plan_w, c.wlo ? 0 : c.head, c.head != 0, st, p, false, ls.stream ? &ls : nullptr)) return rc;
+  P_ICICLE(k == 2 ? msm_g2_reduce(&c.plan_w, st, c.bk[k].p, DP + k * PARTIALS_STRIDE, slot4[k]) : msm_g1_reduce(&c.plan_w, st, c.bk[k].p, DP + k * PARTIALS_STRIDE, slot4[k]));
+  (void)hipEventRecord(p->ev[3], st);
+  p->valid = true;
+  return 0;
+}
 
-  for (int k : {0, 1, 3})
-    if (int rc = bucket_stages(k)) return rc;
-  mark("abc");
+// ---- stream g3: digit sort of the H scalars (atomics / memory bound) overlaps the ALU-bound A, B1, C stages
+int enqueue_h_sort(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t g3 = c.g3;
+  P_HIP(hipStreamWaitEvent(g3, z->ev[2], 0));
+  (void)hipEventRecord(c.prof[4]->ev[0], g3);
+  // (`crowded`: H's sort runs beside the four witness accumulations of a large circuit)
+  P_ICICLE(msm_sort_run(c.d_hscalars, z->H.len(), 0, 0, 0, g3, &c.plan_h, z->geom_h.tab ? z->geom_h.c : 0, 0, 1, 0, /*crowded=*/!c.early));
+  if (c.plan_h.g.tab != z->geom_h.tab || c.plan_h.g.c != z->geom_h.c) return fail((int)ICICLE_UNKNOWN_ERROR, "window geometry of the cached tables does not match the H sort");
+  (void)hipEventRecord(c.prof[4]->ev[4], g3);
+  c.prof[4]->has_sort_end = true;
+  P_HIP(hipEventRecord(z->ev_sort_h, g3));
+  c.mark("hsort");
+  return 0;
+}
 
-  // H: behind one of the witness MSMs for the large circuits (measured at 1.6 M constraints: five concurrent accumulations
-  // are slower than four followed by one, 17.7 vs 17.4 ms) — behind B1, whose accumulation is the first of the three G1
-  // ones to start and to finish (behind A: +0.1 ms, behind C: +0.4 ms); on g3 right behind its own sort for the small ones and for
-  // multi-GPU shards, where the GPU is far from full and only the length of the chains counts (200 k: 4.3 → 3.9 ms).  Letting H
-  // wait only for B1's ACCUMULATION kernel instead of B1's whole chain fills a ≈ 1 ms gap in the timeline and still makes the
-  // prove slower (16.35–16.48 against 16.0–16.2 ms; HISTORY.md §4 lists this and the other schedules that were measured).
-  const int h_behind = 1; // B1
-  const bool h_chain = z->H.len() > (1u << 19);
-  hipStream_t gh = h_chain ? st4[h_behind] : g3;
-  if (h_chain) P_HIP(hipStreamWaitEvent(gh, z->ev_sort_h, 0));
-  fill(prof[4], plan_h, 0);
+// H: behind one of the witness MSMs for the large circuits (measured at 1.6 M constraints: five concurrent accumulations
+// are slower than four followed by one, 17.7 vs 17.4 ms) — behind B1, whose accumulation is the first of the three G1
+// ones to start and to finish (behind A: +0.1 ms, behind C: +0.4 ms); on g3 right behind its own sort for the small ones and for
+// multi-GPU shards, where the GPU is far from full and only the length of the chains counts (200 k: 4.3 → 3.9 ms).  Letting H
+// wait only for B1's ACCUMULATION kernel instead of B1's whole chain fills a ≈ 1 ms gap in the timeline and still makes the
+// prove slower (16.35–16.48 against 16.0–16.2 ms; HISTORY.md §4 lists this and the other schedules that were measured).
+int enqueue_h_msm(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  c.h_chain = z->H.len() > (1u << 19);
+  c.gh = c.h_chain ? c.st4[H_BEHIND] : c.g3;
+  const hipStream_t gh = c.gh;
+  if (c.h_chain) P_HIP(hipStreamWaitEvent(gh, z->ev_sort_h, 0));
+  fill_profile(c.prof[4], c.plan_h, 0);
   if (z->feed) {
     if (int rc = z->feed->wait(ColdFeed::SEC_H)) return fail(rc, "%s", z->feed->err.c_str());
     P_HIP(hipStreamWaitEvent(gh, z->feed->ev[ColdFeed::SEC_H], 0));
   }
   {
-    const LargeSide ls = large_side(4, g3);
-    P_ICICLE(msm_g1_partials(&plan_h, z->H.d_points, 2, 0, gh, DP + 4 * PARTIALS_STRIDE, prof[4], z->H.len(), 0, ls.stream && gh != g3 ? &ls : nullptr));
+    const LargeSide ls = large_side(c, 4, c.g3);
+    P_ICICLE(msm_g1_partials(&c.plan_h, z->H.d_points, 2, 0, gh, z->d_partials + 4 * PARTIALS_STRIDE, c.prof[4], z->H.len(), 0, ls.stream && gh != c.g3 ? &ls : nullptr));
   }
-  (void)hipEventRecord(prof[4]->ev[3], gh);
-  prof[4]->valid = true;
-  mark("h");
-  // Each MSM's partial sums go to pinned memory on ITS OWN stream as soon as its reduction is done, and a host
-  // thread per MSM waits for that copy and runs the Horner tail — the tails of the early finishers (B2, A, B1, C)
-  // overlap the GPU work still in flight; only the last one (H) is exposed.
-  uint32_t Ww = 0, bw1 = 0, Wb = 0, bw2 = 0, Wh = 0, bh = 0;
-  const size_t by1 = msm_partials_bytes(&plan_w, false, &Ww, &bw1), by2 = msm_partials_bytes(&plan_w, true, &Wb, &bw2), byh = msm_partials_bytes(&plan_h, false, &Wh, &bh);
+  (void)hipEventRecord(c.prof[4]->ev[3], gh);
+  c.prof[4]->valid = true;
+  c.mark("h");
+  return 0;
+}
+
+// Each MSM's partial sums go to pinned memory on ITS OWN stream as soon as its reduction is done (run_host_tails waits for
+// each copy on a host thread of its own)
+int collect_partials(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  const hipStream_t g1 = c.g1, g3 = c.g3;
+  uint8_t* DP = z->d_partials;
+  const size_t by1 = msm_partials_bytes(&c.plan_w, false, nullptr, nullptr), by2 = msm_partials_bytes(&c.plan_w, true, nullptr, nullptr), byh = msm_partials_bytes(&c.plan_h, false, nullptr, nullptr);
   const size_t sizes[5] = {by1, by1, by2, by1, byh};
-  hipStream_t st5[5] = {st4[0], st4[1], st4[2], st4[3], gh};
-  if (h_chain) {
+  hipStream_t st5[5] = {c.st4[0], c.st4[1], c.st4[2], c.st4[3], c.gh};
+  if (c.h_chain) {
     // the copy of the MSM in front of H must not wait for H (same stream): its partials were complete at its ev[3], copy them on g3 instead
-    P_HIP(hipStreamWaitEvent(g3, prof[h_behind]->ev[3], 0));
-    st5[h_behind] = g3;
+    P_HIP(hipStreamWaitEvent(g3, c.prof[H_BEHIND]->ev[3], 0));
+    st5[H_BEHIND] = g3;
   }
   for (int k = 0; k < 5; k++) {
     P_HIP(hipMemcpyAsync(z->h_partials + k * PARTIALS_STRIDE, DP + k * PARTIALS_STRIDE, sizes[k], hipMemcpyDeviceToHost, st5[k]));
@@ -829,69 +892,114 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
   }
   for (int k = 0; k < 5; k++) P_HIP(hipStreamWaitEvent(g1, z->ev_done[k], 0));
   P_HIP(hipEventRecord(z->ev[3], g1)); // end of the MSM phase: every chain has delivered its partial sums (timing only)
-  mark("copies");
-  {
-    const uint8_t* HP = z->h_partials;
-    const int cw = plan_w.g.c, ch = plan_h.g.c;
-    hipEvent_t* evd = z->ev_done;
-    const int dev = z->device_id;
-    const MsmGeom gw = plan_w.g, gh = plan_h.g;
-    auto g1tail = [&](int k, uint32_t W, uint32_t bpw, int c, size_t off) {
-      (void)hipSetDevice(dev);
-      (void)hipEventSynchronize(evd[k]);
-      const MsmGeom& gg = k == 4 ? gh : gw;
-      if (gg.tab) msm_g1_host_tail_tab(HP + k * PARTIALS_STRIDE, W, (bn254_projective_t*)(out_points + off));
-      else msm_g1_host_tail(HP + k * PARTIALS_STRIDE, W, 1, c, gg.wide, (bn254_projective_t*)(out_points + off));
-      if (et && k < 2) {
-        while (!et->bl_ready.load(std::memory_order_acquire)) std::this_thread::yield();
-        bn254_projective_t p;
-        memcpy(&p, out_points + off, sizeof p);
-        bn254_ecadd(&p, (const bn254_projective_t*)(k == 0 ? &z->vk_alpha_1 : &z->vk_beta_1), &p);
-        bn254_ecadd(&p, k == 0 ? &et->bl->d1r : &et->bl->d1s, &p);
-        bn254_mul_scalar(&p, k == 0 ? &et->bl->s : &et->bl->r, k == 0 ? &et->ta : &et->tb);
-        et->done.fetch_add(1, std::memory_order_release);
-        if (k == 0) early_pi_a(z, *et->bl, &p, et); // p = pi_a
-      }
-    };
-    // the four other tails on pooled workers (workers.h), H's — the last to arrive — on this thread
-    HostTask tt[4];
-    tt[0].fn = [&] { g1tail(0, Ww, bw1, cw, (size_t)0); };
-    tt[1].fn = [&] { g1tail(1, Ww, bw1, cw, (size_t)96); };
-    tt[3].fn = [&] { g1tail(3, Ww, bw1, cw, (size_t)384); };
-    tt[2].fn = [&] {
-      (void)hipSetDevice(dev);
-      (void)hipEventSynchronize(evd[2]);
-      if (gw.tab) msm_g2_host_tail_tab(HP + 2 * PARTIALS_STRIDE, Wb, (bn254_g2_projective_t*)(out_points + 192));
-      else msm_g2_host_tail(HP + 2 * PARTIALS_STRIDE, Wb, 1, cw, gw.wide, (bn254_g2_projective_t*)(out_points + 192));
-      if (et) {
-        while (!et->bl_ready.load(std::memory_order_acquire)) std::this_thread::yield();
-        bn254_g2_projective_t b2;
-        memcpy(&b2, out_points + 192, sizeof b2);
-        early_pi_b(z, *et->bl, &b2, et);
-      }
-    };
-    bool pooled[4];
-    for (int k = 0; k < 4; k++) pooled[k] = WorkerPool::get().submit(&tt[k]);
-    g1tail(4, Wh, bh, ch, 480);
-    for (int k = 0; k < 4; k++) {
-      if (pooled[k]) WorkerPool::wait(&tt[k]);
-      else tt[k].fn(); // (no worker was to be had: after H's, on this thread)
-    }
+  c.mark("copies");
+  return 0;
+}
+
+// Horner tail of G1 MSM k (0 A, 1 B1, 3 C, 4 H) → out, once its partial sums are in pinned memory; A's and B1's go on to the
+// early terms of the proof that need nothing else (EarlyTerms)
+void g1_tail(const ProveCtx& c, int k, uint8_t* out, EarlyTerms* et)
+{
+  const ZKeyCache* z = c.z;
+  (void)hipSetDevice(z->device_id);
+  (void)hipEventSynchronize(z->ev_done[k]);
+  const SortPlan& pl = k == 4 ? c.plan_h : c.plan_w;
+  uint32_t W = 0;
+  (void)msm_partials_bytes(&pl, false, &W, nullptr);
+  const uint8_t* hp = z->h_partials + k * PARTIALS_STRIDE;
+  if (pl.g.tab) msm_g1_host_tail_tab(hp, W, (bn254_projective_t*)out);
+  else msm_g1_host_tail(hp, W, 1, pl.g.c, pl.g.wide, (bn254_projective_t*)out);
+  if (et && k < 2) {
+    while (!et->bl_ready.load(std::memory_order_acquire)) std::this_thread::yield();
+    bn254_projective_t p;
+    memcpy(&p, out, sizeof p);
+    bn254_ecadd(&p, (const bn254_projective_t*)(k == 0 ? &z->vk_alpha_1 : &z->vk_beta_1), &p);
+    bn254_ecadd(&p, k == 0 ? &et->bl->d1r : &et->bl->d1s, &p);
+    bn254_mul_scalar(&p, k == 0 ? &et->bl->s : &et->bl->r, k == 0 ? &et->ta : &et->tb);
+    et->done.fetch_add(1, std::memory_order_release);
+    if (k == 0) early_pi_a(z, *et->bl, &p, et); // p = pi_a
   }
-  mark("tails");
-  // every tail thread has waited for its MSM's ev_done (recorded behind the last operation of that MSM's chain), so all six
-  // streams are drained except for ev[3] on g1, which waits for the five of them: one synchronisation instead of six
-  P_HIP(hipStreamSynchronize(g1));
-  mark("drained");
-  drain.armed = false;
+}
+void g2_tail(const ProveCtx& c, uint8_t* out, EarlyTerms* et)
+{
+  const ZKeyCache* z = c.z;
+  (void)hipSetDevice(z->device_id);
+  (void)hipEventSynchronize(z->ev_done[2]);
+  uint32_t W = 0;
+  (void)msm_partials_bytes(&c.plan_w, true, &W, nullptr);
+  const uint8_t* hp = z->h_partials + 2 * PARTIALS_STRIDE;
+  if (c.plan_w.g.tab) msm_g2_host_tail_tab(hp, W, (bn254_g2_projective_t*)out);
+  else msm_g2_host_tail(hp, W, 1, c.plan_w.g.c, c.plan_w.g.wide, (bn254_g2_projective_t*)out);
+  if (et) {
+    while (!et->bl_ready.load(std::memory_order_acquire)) std::this_thread::yield();
+    bn254_g2_projective_t b2;
+    memcpy(&b2, out, sizeof b2);
+    early_pi_b(z, *et->bl, &b2, et);
+  }
+}
+
+// A host thread per MSM waits for that MSM's copy and runs the Horner tail — the tails of the early finishers (B2, A, B1, C)
+// overlap the GPU work still in flight; only the last one (H) is exposed.
+void run_host_tails(ProveCtx& c, uint8_t* out_points, EarlyTerms* et)
+{
+  // the four other tails on pooled workers (workers.h), H's — the last to arrive — on this thread
+  HostTask tt[4];
+  tt[0].fn = [&c, out_points, et] { g1_tail(c, 0, out_points, et); };
+  tt[1].fn = [&c, out_points, et] { g1_tail(c, 1, out_points + 96, et); };
+  tt[2].fn = [&c, out_points, et] { g2_tail(c, out_points + 192, et); };
+  tt[3].fn = [&c, out_points, et] { g1_tail(c, 3, out_points + 384, et); };
+  bool pooled[4];
+  for (int k = 0; k < 4; k++) pooled[k] = WorkerPool::get().submit(&tt[k]);
+  g1_tail(c, 4, out_points + 480, et);
+  for (int k = 0; k < 4; k++) {
+    if (pooled[k]) WorkerPool::wait(&tt[k]);
+    else tt[k].fn(); // (no worker was to be had: after H's, on this thread)
+  }
+  c.mark("tails");
+}
+
+// The head's share follows the machine: its chain should end just before the last byte of the witness lands — what is left
+// of it then runs beside the transforms of the front end and slows them (long-lived accumulation workgroups hold the
+// registers the transform workgroups need), what ends earlier leaves the GPU idle.  gap > 0: the head ended `gap` ms
+// before the upload; a larger head both starts later (its bytes land later) and runs longer.
+void steer_head_share(ProveCtx& c)
+{
+  ZKeyCache* z = c.z;
+  const uint32_t head = c.head, nv = c.nv;
+  float work = 0, gap = 0, up = 0;
+  if (hipEventElapsedTime(&work, z->ev_t_head_start, z->ev_t_head_end) == hipSuccess && hipEventElapsedTime(&gap, z->ev_t_head_end, z->ev_t_witness) == hipSuccess &&
+      hipEventElapsedTime(&up, z->ev[0], z->ev_t_witness) == hipSuccess && work > 0 && up > 0) {
+    // Measured at 1.6 M constraints (profiles/r04_head_sweep.txt): ending 0.3 ms AFTER the upload is better than ending with
+    // it (12 % of the witness against 8 %: 16.1 against 16.4 ms file to file, 16.9–17.3 without a head) — the transforms
+    // lose less to the last of the head's workgroups than the MSM phase gains — and the optimum is flat beyond that.
+    const double f = (double)head / nv, per_unit = work / f + up; // ms by which the head's end moves per unit of share
+    const double margin = -0.30;
+    double f_new = f + 0.8 * ((double)gap - margin) / per_unit; // (0.8: per_unit is measured, the step lands near the target at once; the hysteresis below absorbs the jitter of the upload)
+    if (f_new > 0.40) f_new = 0.40;
+    // the share moves in whole upload chunks and only when it is off by most of one: a head of another size is another set of
+    // workspace blocks (a fresh hipMalloc inside a prove when it grows)
+    const double target = f_new * nv / HEAD_UNIT, cur = (double)head / HEAD_UNIT;
+    if (!c.head_forced && (target > cur + 0.75 || target < cur - 0.75)) {
+      z->head_units = (int)(target + 0.5);
+      if (z->head_units < 1) z->head_units = 1;
+    }
+    if (knobs().trace_host) fprintf(stderr, "[host] head %.1f %% of the witness: chain %.3f ms, ended %.3f ms before the upload (%.3f ms) -> next %.1f %%\n", 100 * f, work, gap, up, 100.0 * (c.head_forced ? head : (uint32_t)z->head_units * HEAD_UNIT) / nv);
+  } else
+    (void)hipGetLastError();
+}
+
+// the prove is complete and the streams are drained: what it leaves behind in the entry
+void finish_prove(ProveCtx& c, bool sync_rebuild, Groth16Timings* tm)
+{
+  ZKeyCache* z = c.z;
   // (the stats copies sit on g2 / g3 in front of work whose ev_done a tail thread has waited for)
   z->witness_entries = (uint64_t)z->h_stats[0] + z->h_stats[1] + z->h_stats[2] + z->h_stats[3];
   z->proves_since_rebuild++;
-  z->tb.go.store(true, std::memory_order_release); // deferred tables: the key's first proof is out, the build may start
-  if (!sync_rebuild) (void)follow_witness(false);  // (table mode: the digits this prove counted may call for another width)
-  msm_sort_release(&plan_w);
-  msm_sort_release(&plan_head);
-  msm_sort_release(&plan_h);
+  z->tb.go.store(true, std::memory_order_release);  // deferred tables: the key's first proof is out, the build may start
+  if (!sync_rebuild) (void)follow_witness(z, false); // (table mode: the digits this prove counted may call for another width)
+  msm_sort_release(&c.plan_w);
+  msm_sort_release(&c.plan_head);
+  msm_sort_release(&c.plan_h);
   // HIP-event profile of the five MSMs → the ring icicle_snark_msm_profile reads (bench.py: back = 4 … 0 = A, B1, B2, C, H); in
   // a device group only the lead shard publishes
   // (the head's sort first, so that A … H keep their places: back = 5 is the head sort, L = 0 when the witness was not split)
@@ -899,44 +1007,67 @@ int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, s
     msm_profile_publish(&z->prof[5], 1);
     msm_profile_publish(z->prof, 5);
   }
-  if (head) {
-    // The head's share follows the machine: its chain should end just before the last byte of the witness lands — what is left
-    // of it then runs beside the transforms of the front end and slows them (long-lived accumulation workgroups hold the
-    // registers the transform workgroups need), what ends earlier leaves the GPU idle.  gap > 0: the head ended `gap` ms
-    // before the upload; a larger head both starts later (its bytes land later) and runs longer.
-    float work = 0, gap = 0, up = 0;
-    if (hipEventElapsedTime(&work, z->ev_t_head_start, z->ev_t_head_end) == hipSuccess && hipEventElapsedTime(&gap, z->ev_t_head_end, z->ev_t_witness) == hipSuccess &&
-        hipEventElapsedTime(&up, z->ev[0], z->ev_t_witness) == hipSuccess && work > 0 && up > 0) {
-      // Measured at 1.6 M constraints (profiles/r04_head_sweep.txt): ending 0.3 ms AFTER the upload is better than ending with
-      // it (12 % of the witness against 8 %: 16.1 against 16.4 ms file to file, 16.9–17.3 without a head) — the transforms
-      // lose less to the last of the head's workgroups than the MSM phase gains — and the optimum is flat beyond that.
-      const double f = (double)head / nv, per_unit = work / f + up; // ms by which the head's end moves per unit of share
-      const double margin = -0.30;
-      double f_new = f + 0.8 * ((double)gap - margin) / per_unit; // (0.8: per_unit is measured, the step lands near the target at once; the hysteresis below absorbs the jitter of the upload)
-      if (f_new > 0.40) f_new = 0.40;
-      // the share moves in whole upload chunks and only when it is off by most of one: a head of another size is another set of
-      // workspace blocks (a fresh hipMalloc inside a prove when it grows)
-      const double target = f_new * nv / head_unit, cur = (double)head / head_unit;
-      if (!head_forced && (target > cur + 0.75 || target < cur - 0.75)) {
-        z->head_units = (int)(target + 0.5);
-        if (z->head_units < 1) z->head_units = 1;
-      }
-      if (trace_host) fprintf(stderr, "[host] head %.1f %% of the witness: chain %.3f ms, ended %.3f ms before the upload (%.3f ms) -> next %.1f %%\n", 100 * f, work, gap, up, 100.0 * (head_forced ? head : (uint32_t)z->head_units * head_unit) / nv);
-    } else
-      (void)hipGetLastError();
-  }
-  {
-    float a = 0, b = 0, c = 0;
-    (void)hipEventElapsedTime(&a, z->ev[0], z->ev[1]);
-    (void)hipEventElapsedTime(&b, z->ev[1], z->ev[2]);
-    (void)hipEventElapsedTime(&c, z->ev[2], z->ev[3]);
-    z->last_tm.h2d_ms = h2d_host_ms > a ? h2d_host_ms : a; // staged upload: the host waited for it; pinned source: the DMA in front of ev[1]
-    z->last_tm.qap_ms = b;
-    z->last_tm.msm_ms = c;
-    z->last_tm.total_ms = ms_since(t0);
-    if (tm) *tm = z->last_tm;
-  }
-  mark("published");
+  if (c.head) steer_head_share(c);
+  float a = 0, b = 0, m = 0;
+  (void)hipEventElapsedTime(&a, z->ev[0], z->ev[1]);
+  (void)hipEventElapsedTime(&b, z->ev[1], z->ev[2]);
+  (void)hipEventElapsedTime(&m, z->ev[2], z->ev[3]);
+  z->last_tm.h2d_ms = c.h2d_host_ms > a ? c.h2d_host_ms : a; // staged upload: the host waited for it; pinned source: the DMA in front of ev[1]
+  z->last_tm.qap_ms = b;
+  z->last_tm.msm_ms = m;
+  z->last_tm.total_ms = ms_since(c.t0);
+  if (tm) *tm = z->last_tm;
+  c.mark("published");
+}
+} // namespace
+
+// The schedule of one prove on one device: the ORDER in which the stages above are enqueued by this thread is what several
+// measured decisions rest on (HISTORY.md §4) — the stages themselves hold no ordering decisions.
+int shard_commitments(Groth16CacheManager* cm, ZKeyCache* z, const void* wtns, size_t wtns_len, uint8_t* out_points, Groth16Timings* tm, EarlyTerms* et)
+{
+  if (!wtns && !z->witness_resident) return fail(ERR_ARG, "no witness given and none resident on the device");
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = set_active_device(z->device_id)) return rc;
+  if (int rc = ensure_domain(cm, z)) return rc;
+  trace_mark(t0, "domain");
+  // deferred fixed-base tables (cache.cpp): complete → this prove is the first to use them; still building → classic layout
+  (void)adopt_tables(z, false);
+  // the key follows its witnesses (cache.cpp: follow_witness): at the end of the prove that counted the digits, by a worker
+  // beside the next proves — or, with ICICLE_SNARK_SYNC_REBUILD=1 (read per call: tests toggle it), here
+  const bool sync_rebuild = env_int("ICICLE_SNARK_SYNC_REBUILD", 0) != 0;
+  if (sync_rebuild)
+    if (int rc = follow_witness(z, true)) return rc;
+  ProveCtx c(cm, z, wtns != nullptr, t0); // (from here on an error return drains the streams first: ProveCtx::drain)
+  if (int rc = receive_witness(c, wtns, wtns_len)) return rc;
+  // The witness sort is enqueued BEHIND the front end for the large circuits (round 5): the front end is their critical chain and
+  // its first kernel used to sit behind the nine launches of the sort on the host, ≈ 50 µs after the last byte of the witness had
+  // landed; the small circuits and the shards that start from their own slice begin their accumulations right behind the sort:
+  // sort first.
+  if (c.early)
+    if (int rc = enqueue_witness_sort(c)) return rc;
+  if (int rc = enqueue_front_end(c)) return rc;
+  if (!c.early)
+    if (int rc = enqueue_witness_sort(c)) return rc;
+  if (int rc = alloc_buckets(c)) return rc;
+  // (cold pipeline: the host is about to wait for B2's section — everything that needs no section is enqueued first)
+  if (z->feed)
+    if (int rc = enqueue_h_sort(c)) return rc;
+  if (int rc = enqueue_witness_msm(c, 2)) return rc; // commitment_b (G2) — src/proof_helper.rs:206: the longest chain first
+  c.mark("g2");
+  if (!z->feed)
+    if (int rc = enqueue_h_sort(c)) return rc;
+  for (int k : {0, 1, 3})
+    if (int rc = enqueue_witness_msm(c, k)) return rc;
+  c.mark("abc");
+  if (int rc = enqueue_h_msm(c)) return rc; // behind B1 for the large circuits, behind its own sort for the small ones
+  if (int rc = collect_partials(c)) return rc;
+  run_host_tails(c, out_points, et);
+  // every tail thread has waited for its MSM's ev_done (recorded behind the last operation of that MSM's chain), so all six
+  // streams are drained except for ev[3] on g1, which waits for the five of them: one synchronisation instead of six
+  P_HIP(hipStreamSynchronize(c.g1));
+  c.mark("drained");
+  c.drain.armed = false;
+  finish_prove(c, sync_rebuild, tm);
   return 0;
 }
 
@@ -947,14 +1078,6 @@ bool shard_dist_supported(const ZKeyCache* z)
   if (z->H.stride <= 1 || (G != 2 && G != 4 && G != 8)) return false;
   const uint32_t m = z->domain_size / G;
   return m % G == 0 && ntt_fusable(m);
-}
-
-static int check_witness(const ZKeyCache* z, const Wtns& w)
-{
-  // src/proof_helper.rs:253-262
-  if (!Fr::eq(z->r, w.q)) return fail(ERR_FORMAT, "Curve of the witness does not match the curve of the proving key");
-  if (w.n_witness != z->n_vars) return fail(ERR_FORMAT, "Invalid witness length. Circuit: %u, witness: %u", z->n_vars, w.n_witness);
-  return 0;
 }
 
 // this shard's 1/shard_count of the witness → its place in d_witness (returns when the bytes have arrived)
@@ -1124,6 +1247,38 @@ __attribute__((visibility("default"))) int groth16_dist_exchange_done(Groth16Cac
 
 } // extern "C"
 
+// r, s and the commitment-independent blinding terms on a pooled worker while the GPU computes the commitments (inline when no
+// worker is to be had: before the commitments instead of beside them).  One of `grp` / `shard` is the key.  `take_mu`: hold the
+// manager's mutex around the commitments (false: the caller holds it throughout); `join_first`: a helper thread the commitments
+// need the result of, joined once the blinding has been started.
+static int blinded_commitments(Groth16CacheManager* cm, DeviceGroup* grp, ZKeyCache* shard, const void* wtns, size_t wtns_len, const uint8_t* r, const uint8_t* s, bool take_mu,
+                               std::thread* join_first, uint8_t* pts, Groth16Timings* tm, Blinding* bl, EarlyTerms* et)
+{
+  const ZKeyCache* z = grp ? group_lead(grp) : shard;
+  et->bl = bl;
+  int bl_rc = 0;
+  std::string bl_err;
+  HostTask bt;
+  bt.fn = [&] {
+    bl_rc = compute_blinding(z, r, s, bl);
+    if (bl_rc) bl_err = last_error_text();
+    et->bl_ready.store(true, std::memory_order_release);
+  };
+  WorkerPool::get().run_or_inline(&bt);
+  if (join_first && join_first->joinable()) join_first->join();
+  int rc;
+  {
+    std::unique_lock<std::mutex> lk(cm->mu, std::defer_lock);
+    if (take_mu) lk.lock();
+    // a device group sums the shards' commitments first: the early C-term products (EarlyTerms) need the complete A and B1
+    rc = grp ? group_commitments(cm, grp, wtns, wtns_len, pts, tm) : shard_commitments(cm, shard, wtns, wtns_len, pts, tm, et);
+  }
+  if (bt.queued) WorkerPool::wait(&bt);
+  if (rc) return rc;
+  if (bl_rc) return fail(bl_rc, "%s", bl_err.empty() ? "no entropy source for the blinding scalars" : bl_err.c_str());
+  return 0;
+}
+
 extern "C" {
 
 // groth16_prove_mem with the option to re-use the witness already resident on the device (bench.py: inputs in HBM)
@@ -1150,32 +1305,12 @@ __attribute__((visibility("default"))) int groth16_prove_resident(Groth16CacheMa
   // alone would be well-formed but invalid.  Shards prove together as a device group (groth16_cache_load_devices, one
   // process) or through groth16_commitments → all-gather → groth16_sum_commitments → groth16_assemble_proof (one process per GPU).
   if (!grp && z->shard_count != 1) return fail(ERR_ARG, "cache entry '%s' is shard %d of %d: use groth16_commitments + groth16_sum_commitments + groth16_assemble_proof", key ? key : "", z->shard_rank, z->shard_count);
-  // r, s and the commitment-independent blinding terms on a host thread while the GPU computes the commitments
   Blinding bl;
   EarlyTerms et;
-  et.bl = &bl;
-  int bl_rc = 0;
-  std::string bl_err;
-  HostTask bt;
-  bt.fn = [&] {
-    bl_rc = compute_blinding(z, r, s, &bl);
-    if (bl_rc) bl_err = last_error_text();
-    et.bl_ready.store(true, std::memory_order_release);
-  };
-  WorkerPool::get().run_or_inline(&bt); // (inline when no worker is to be had: before the commitments instead of beside them)
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(cm->mu);
-    // a device group sums the shards' commitments first: the early C-term products (EarlyTerms) need the complete A and B1
-    rc = grp ? group_commitments(cm, grp.get(), wtns_resident ? nullptr : wtns, wtns_len, pts, tm)
-             : shard_commitments(cm, zp.get(), wtns_resident ? nullptr : wtns, wtns_len, pts, tm, &et);
-  }
-  if (bt.queued) WorkerPool::wait(&bt);
-  if (rc) return rc;
-  if (bl_rc) return fail(bl_rc, "%s", bl_err.empty() ? "no entropy source for the blinding scalars" : bl_err.c_str());
+  if (int rc = blinded_commitments(cm, grp.get(), zp.get(), wtns_resident ? nullptr : wtns, wtns_len, r, s, /*take_mu=*/true, nullptr, pts, tm, &bl, &et)) return rc;
   const auto ta = std::chrono::steady_clock::now();
-  rc = assemble_impl(z, wtns, wtns_len, pts, bl, proof_json, proof_cap, public_json, public_cap, grp ? nullptr : &et);
-  if (getenv("ICICLE_SNARK_TRACE_HOST")) fprintf(stderr, "[host] assemble %8.1f us (after %8.1f us)\n", ms_since(ta) * 1e3, std::chrono::duration<double, std::micro>(ta - t0).count());
+  const int rc = assemble_impl(z, wtns, wtns_len, pts, bl, proof_json, proof_cap, public_json, public_cap, grp ? nullptr : &et);
+  if (env_set("ICICLE_SNARK_TRACE_HOST")) fprintf(stderr, "[host] assemble %8.1f us (after %8.1f us)\n", ms_since(ta) * 1e3, std::chrono::duration<double, std::micro>(ta - t0).count());
   if (tm) tm->total_ms = ms_since(t0);
   return rc;
 }
@@ -1220,7 +1355,7 @@ static int write_json_pair(const char* proof_path, const char* proof_text, const
 static constexpr int COLD_DECLINED = INT_MIN;
 static int cold_prove(Groth16CacheManager* cm, const std::string& key, const MappedFile& zf, const MappedFile& wf, int device_id, std::vector<char>& pj, std::vector<char>& qj)
 {
-  const bool off = getenv("ICICLE_SNARK_COLD_PIPELINE") && atoi(getenv("ICICLE_SNARK_COLD_PIPELINE")) == 0; // read per call: tests toggle it
+  const bool off = env_int("ICICLE_SNARK_COLD_PIPELINE", 1) == 0; // read per call: tests toggle it
   if (off) return COLD_DECLINED;
   // the witness must fit the key BEFORE anything of it is sent: n_vars of the header (src/zkey.rs:47-85) against the .wtns header
   Wtns w;
@@ -1244,7 +1379,7 @@ static int cold_prove(Groth16CacheManager* cm, const std::string& key, const Map
   try {
     dom_th = std::thread([cm, device_id, dom_n, t0] {
       if (set_active_device(device_id) == 0) (void)ensure_domain_for(cm, device_id, dom_n);
-      if (getenv("ICICLE_SNARK_TRACE_COLD")) fprintf(stderr, "[cold] NTT domain ready at      %8.2f ms\n", ms_since(t0));
+      if (env_set("ICICLE_SNARK_TRACE_COLD")) fprintf(stderr, "[cold] NTT domain ready at      %8.2f ms\n", ms_since(t0));
     });
   } catch (...) {
   }
@@ -1273,19 +1408,8 @@ static int cold_prove(Groth16CacheManager* cm, const std::string& key, const Map
   uint8_t pts[GROTH16_COMMITMENTS_BYTES];
   Blinding bl;
   EarlyTerms et;
-  et.bl = &bl;
-  int bl_rc = 0;
-  std::string bl_err;
-  HostTask bt;
-  bt.fn = [&] {
-    bl_rc = compute_blinding(z, nullptr, nullptr, &bl);
-    if (bl_rc) bl_err = last_error_text();
-    et.bl_ready.store(true, std::memory_order_release);
-  };
-  WorkerPool::get().run_or_inline(&bt);
-  if (dom_th.joinable()) dom_th.join(); // (shard_commitments checks the domain first: it is there, or it is set up now)
-  int rc = shard_commitments(cm, z, wf.data, wf.len, pts, nullptr, &et);
-  if (bt.queued) WorkerPool::wait(&bt);
+  // (dom_th: shard_commitments checks the domain first — it is there, or it is set up now)
+  int rc = blinded_commitments(cm, nullptr, z, wf.data, wf.len, nullptr, nullptr, /*take_mu=*/false, &dom_th, pts, nullptr, &bl, &et);
   // the uploader has to have ended before the mappings go away — and before anybody else proves with this entry
   cold_upload_wait(&cu);
   z->feed = nullptr;
@@ -1298,11 +1422,18 @@ static int cold_prove(Groth16CacheManager* cm, const std::string& key, const Map
     return fail(up_rc, "%s", up_err.c_str());
   }
   if (rc) return rc;
-  if (bl_rc) return fail(bl_rc, "%s", bl_err.empty() ? "no entropy source for the blinding scalars" : bl_err.c_str());
   qj.resize(64 + (size_t)n_public * 84);
   rc = assemble_impl(z, wf.data, wf.len, pts, bl, pj.data(), pj.size(), qj.data(), qj.size(), &et);
-  if (getenv("ICICLE_SNARK_TRACE_HOST")) fprintf(stderr, "[host] cold prove (%s) %8.1f us\n", piped ? "pipelined" : "not pipelined", ms_since(t0) * 1e3);
+  if (env_set("ICICLE_SNARK_TRACE_HOST")) fprintf(stderr, "[host] cold prove (%s) %8.1f us\n", piped ? "pipelined" : "not pipelined", ms_since(t0) * 1e3);
   return rc;
+}
+
+// the reference's line (src/lib.rs:58), unless ICICLE_SNARK_QUIET=1
+static void print_proof_took(std::chrono::steady_clock::time_point t0)
+{
+  if (knobs().quiet) return;
+  printf("proof took: %.3fms\n", ms_since(t0));
+  fflush(stdout);
 }
 
 extern "C" {
@@ -1320,8 +1451,7 @@ __attribute__((visibility("default"))) int groth16_prove(const char* witness_pat
   P_ICICLE(icicle_load_backend_from_env_or_default());
   if (int rc = set_active_device(devs[0])) return rc;
   const std::string key = std::string(zkey_path) + "_" + device; // src/lib.rs:44
-  static const bool trace_host0 = getenv("ICICLE_SNARK_TRACE_HOST") != nullptr;
-  static const bool quiet0 = getenv("ICICLE_SNARK_QUIET") && atoi(getenv("ICICLE_SNARK_QUIET")) != 0;
+  const bool trace_host = knobs().trace_host;
   if (!groth16_cache_contains(cm, key.c_str()) && devs.size() == 1) {
     // no cache entry: the key's sections and the witness cross PCIe while the first proof is being computed (cold_prove)
     MappedFile zf, wf;
@@ -1331,11 +1461,8 @@ __attribute__((visibility("default"))) int groth16_prove(const char* witness_pat
     const int crc = cold_prove(cm, key, zf, wf, devs[0], pj, qj);
     if (crc == 0) {
       if (int rc = write_json_pair(proof_path, pj.data(), public_path, qj.data())) return rc;
-      if (trace_host0) fprintf(stderr, "[host] prove: files written (cold)   %8.1f us\n", ms_since(t0) * 1e3);
-      if (!quiet0) {
-        printf("proof took: %.3fms\n", ms_since(t0)); // src/lib.rs:58
-        fflush(stdout);
-      }
+      if (trace_host) fprintf(stderr, "[host] prove: files written (cold)   %8.1f us\n", ms_since(t0) * 1e3);
+      print_proof_took(t0);
       return 0;
     }
     if (crc != COLD_DECLINED) return crc;
@@ -1350,7 +1477,6 @@ __attribute__((visibility("default"))) int groth16_prove(const char* witness_pat
       if (int rc = groth16_cache_load_devices(cm, key.c_str(), zf.data, zf.len, devs.data(), (int)devs.size())) return rc;
     }
   }
-  static const bool trace_host = getenv("ICICLE_SNARK_TRACE_HOST") != nullptr;
   if (trace_host) fprintf(stderr, "[host] prove: cache key found        %8.1f us\n", ms_since(t0) * 1e3);
   MappedFile wf;
   if (int rc = wf.open_ro(witness_path)) return rc;
@@ -1371,11 +1497,7 @@ __attribute__((visibility("default"))) int groth16_prove(const char* witness_pat
   if (trace_host) fprintf(stderr, "[host] prove: proof assembled        %8.1f us\n", ms_since(t0) * 1e3);
   if (int rc = write_json_pair(proof_path, pj.data(), public_path, qj.data())) return rc;
   if (trace_host) fprintf(stderr, "[host] prove: files written          %8.1f us\n", ms_since(t0) * 1e3);
-  static const bool quiet = getenv("ICICLE_SNARK_QUIET") && atoi(getenv("ICICLE_SNARK_QUIET")) != 0;
-  if (!quiet) {
-    printf("proof took: %.3fms\n", ms_since(t0)); // src/lib.rs:58
-    fflush(stdout);
-  }
+  print_proof_took(t0);
   return 0;
 }
 

@@ -176,6 +176,8 @@ int rebuild_witness_tables(ZKeyCache* z, int c_new);
 // the same in the background (round 5): a worker builds the four tables beside the proves of the key, which go on with the tables
 // they have, and a later prove adopts them (adopt_tables).  Returns at once; nothing happens when a build is already under way.
 void start_witness_rebuild(ZKeyCache* z, int c_new);
+// the policy that decides when either happens (cache.cpp); `sync`: re-build in this call instead of starting the worker
+int follow_witness(ZKeyCache* z, bool sync);
 
 // deferred tables: 1 = the key proves with its tables (or has none coming: classic layout for good), 0 = still building.
 // `wait`: block until the build has ended.  Swaps complete tables in; the caller holds the manager's mutex (no prove in flight).

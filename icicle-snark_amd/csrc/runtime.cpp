@@ -44,7 +44,7 @@ static void isnark_segv(int sig)
 __attribute__((constructor)) static void isnark_runtime_env()
 {
   setenv("GPU_MAX_HW_QUEUES", "12", 0);
-  if (getenv("ICICLE_SNARK_BACKTRACE")) {
+  if (isnark::env_set("ICICLE_SNARK_BACKTRACE")) {
     signal(SIGSEGV, isnark_segv);
     signal(SIGBUS, isnark_segv);
   }
@@ -59,7 +59,7 @@ void set_last_error(const char* fmt, ...)
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof g_err, fmt, ap);
   va_end(ap);
-  if (getenv("ICICLE_SNARK_VERBOSE")) fprintf(stderr, "[icicle-snark-hip] %s\n", g_err);
+  if (env_set("ICICLE_SNARK_VERBOSE")) fprintf(stderr, "[icicle-snark-hip] %s\n", g_err);
 }
 
 static std::mutex g_mu;
@@ -231,7 +231,7 @@ hipError_t staged_copy(int device_id, const CopyJob* jobs, size_t njobs, bool to
   }
   std::atomic<size_t> next{0};
   std::atomic<int> err{(int)hipSuccess};
-  static const bool trace_slow = getenv("ICICLE_SNARK_TRACE_HOST") != nullptr;
+  static const bool trace_slow = env_set("ICICLE_SNARK_TRACE_HOST");
   // chunks of the head (StagedProgress): the first chunks of job 0
   const size_t head_chunks = progress && to_device && njobs ? ((progress->head_bytes < jobs[0].n ? progress->head_bytes : jobs[0].n) + CH - 1) / CH : 0;
   auto worker = [&](int t) {
@@ -267,7 +267,7 @@ hipError_t staged_copy(int device_id, const CopyJob* jobs, size_t njobs, bool to
         if (e == hipSuccess) {
           const uint8_t* src = (const uint8_t*)chunks[i].src;
           bool done = false;
-          static const bool use_pread = !(getenv("ICICLE_SNARK_FILE_PREAD") && atoi(getenv("ICICLE_SNARK_FILE_PREAD")) == 0);
+          static const bool use_pread = env_int("ICICLE_SNARK_FILE_PREAD", 1) != 0;
           if (use_pread && file_fd >= 0 && src >= file_base && src + chunks[i].n <= file_base + file_len) {
             size_t got = 0;
             while (got < chunks[i].n) {
@@ -514,12 +514,12 @@ static std::vector<BaseTable> g_bt_parked; // retired while pinned: freed by the
 static uint64_t g_bt_clock = 0, g_bt_next_id = 1;
 static bool base_tables_enabled()
 {
-  static const bool on = !(getenv("ICICLE_SNARK_MSM_TABLES") && atoi(getenv("ICICLE_SNARK_MSM_TABLES")) == 0);
+  static const bool on = env_int("ICICLE_SNARK_MSM_TABLES", 1) != 0;
   return on;
 }
 static size_t base_tables_budget()
 {
-  static const size_t v = getenv("ICICLE_SNARK_MSM_TABLE_MB") ? (size_t)atoll(getenv("ICICLE_SNARK_MSM_TABLE_MB")) << 20 : (size_t)16 << 30;
+  static const size_t v = (size_t)env_i64("ICICLE_SNARK_MSM_TABLE_MB", 16 << 10) << 20;
   return v;
 }
 static void base_table_free(BaseTable& t) // hipFree waits for whatever enqueued work still reads the table
@@ -754,7 +754,7 @@ ISNARK_API eIcicleError icicle_is_active_device_memory(const void* ptr)
 constexpr size_t ALLOC_CACHE_MIN = 1u << 20;
 static size_t alloc_cache_max()
 {
-  static const size_t v = getenv("ICICLE_SNARK_ALLOC_CACHE_MB") ? (size_t)atoll(getenv("ICICLE_SNARK_ALLOC_CACHE_MB")) << 20 : (size_t)16 << 30;
+  static const size_t v = (size_t)env_i64("ICICLE_SNARK_ALLOC_CACHE_MB", 16 << 10) << 20;
   return v;
 }
 struct AllocCache {
@@ -1093,7 +1093,7 @@ void prewarm_device(int dev, int n_streams)
   (void)hipFree(d);
   (void)hipGetLastError();
   // which of them share a hardware pipe (microbench.hip): the keys built later deal their streams' roles by it (prover/cache.cpp)
-  static const bool pipe_roles = !(getenv("ICICLE_SNARK_PIPE_ROLES") && atoi(getenv("ICICLE_SNARK_PIPE_ROLES")) == 0);
+  static const bool pipe_roles = env_int("ICICLE_SNARK_PIPE_ROLES", 1) != 0;
   if (pipe_roles && fresh.size() >= 2) stream_pipes_measure(fresh.data(), (int)fresh.size());
   std::lock_guard<std::mutex> lk(g_sp_mu);
   std::vector<hipStream_t>& v = g_stream_pool[dev];
