@@ -72,6 +72,41 @@ def test_scalar_montgomery(gpu, O):
     d.free()
 
 
+def test_vec_ops_and_montgomery_over_the_whole_field(gpu, O):
+    """rand_fr above masks the top limb to 61 bits, so a third of the field (2^253 ≤ v < r) never reached these kernels: 4096
+    values uniform in [0, r) and every pair of edge values (0, r − 1, (r − 1)/2, 2^253, limb borders: tests/fr_inputs.py) through
+    add / sub / mul and the Montgomery conversion in both directions, against Python integers."""
+    from fr_inputs import edge_fr, rand_fr_full
+    K = gpu
+    R = O.R_MOD
+    rng = np.random.default_rng(253)
+    e = edge_fr()
+    av = O.arr_to_ints(rand_fr_full(rng, 4096)) + [x for x in e for _ in e]
+    bv = O.arr_to_ints(rand_fr_full(rng, 4096)) + [y for _ in e for y in e]
+    a, b = O.ints_to_arr(av), O.ints_to_arr(bv)
+    assert max(av) >= 1 << 253 and R - 1 in av
+    want = {"add": [(x + y) % R for x, y in zip(av, bv)], "sub": [(x - y) % R for x, y in zip(av, bv)], "mul": [x * y % R for x, y in zip(av, bv)]}
+    fn = {"add": K.add_scalars, "sub": K.sub_scalars, "mul": K.mul_scalars}
+    da, db = K.DeviceVec.from_host(a), K.DeviceVec.from_host(b)
+    out = K.DeviceVec(a.nbytes)
+    for op in want:
+        w = O.ints_to_arr(want[op])
+        assert np.array_equal(fn[op](a, b), w), op                             # host
+        fn[op](da, db, out)                                                     # device
+        assert np.array_equal(out.to_host(a.shape), w), op
+    mont = 1 << 256
+    to_m, from_m = O.ints_to_arr([x * mont % R for x in av]), O.ints_to_arr([x * pow(mont, -1, R) % R for x in av])
+    assert np.array_equal(K.scalar_convert_montgomery(a, True), to_m)
+    assert np.array_equal(K.scalar_convert_montgomery(a, False), from_m)
+    K.scalar_convert_montgomery(da, True)                                       # in place on the device
+    assert np.array_equal(da.to_host(a.shape), to_m)
+    K.scalar_convert_montgomery(da, False)
+    assert np.array_equal(da.to_host(a.shape), a)
+    K.scalar_convert_montgomery(da, False)
+    assert np.array_equal(da.to_host(a.shape), from_m)
+    da.free(); db.free(); out.free()
+
+
 @pytest.mark.parametrize("grp", ["g1", "g2"])
 def test_point_montgomery_golden(gpu, grp):
     K = gpu
@@ -102,8 +137,11 @@ def test_ntt_golden(domain):
 
 @pytest.mark.parametrize("logn", [0, 1, 2, 3, 7, 9, 10, 11, 13, 16, 18, 19, 20])
 def test_ntt_vs_oracle(domain, O, logn):
-    """1-pass (≤2^9), 2-pass (2^10..2^18) and 3-pass (≥2^19) plans, batch 3, in place on device, async —
-    the prover's configuration (icicle_helper.rs:13-32) — forward, inverse and round trip."""
+    """Batch 3, in place on device, async — the prover's configuration (icicle_helper.rs:13-32) — forward, inverse and round
+    trip.  Which kernels run depends on the size: the 8×32-bit kernels take 1 pass up to 2^9 and 2 passes at 2^10; from 2^11 to
+    2^24 the radix-2^29 kernels run with a plan of their own (plan29: 2 passes up to 2^16, 3 passes from 2^17).  The 8×32-bit
+    plan's own pass counts (2-pass up to 2^18, 3-pass from 2^19) apply to those sizes only behind ICICLE_SNARK_NTT29=0 or without
+    the Montgomery-261 twiddle table, and from 2^25 on; tests/test_gpu_ntt_plans.py covers every size on both paths."""
     K = domain
     n = 1 << logn
     rng = np.random.default_rng(logn)
