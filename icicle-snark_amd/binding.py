@@ -102,7 +102,7 @@ bn254_pairing_target_field_add bn254_pairing_target_field_sub bn254_pairing_targ
 bn254_pairing_target_field_pow bn254_pairing_target_field_from_u32 bn254_pairing_target_field_generate_scalars
 icicle_snark_last_error icicle_snark_g1_generator_mul icicle_snark_g2_generator_mul icicle_snark_last_msm_timings
 icicle_snark_msm_profile icicle_snark_microbench icicle_snark_pmc_probes icicle_snark_access_probes
-icicle_snark_pairing_batch
+icicle_snark_pairing_batch icicle_snark_pairing_product
 """.split()
 
 _lib = None
@@ -697,6 +697,7 @@ groth16_dist_supported groth16_dist_stage1 groth16_dist_stage2 groth16_dist_exch
 groth16_witness_ready groth16_cache_load_devices groth16_parse_device groth16_cache_set_budget groth16_cache_info_sized
 groth16_verify groth16_verify_json groth16_verify_last_error groth16_group_describe groth16_cache_tables_ready
 groth16_cache_manager_prewarm groth16_verify_batch groth16_verify_batch_last_timings
+groth16_verify_batch_combined groth16_verify_combined_coefficients
 """.split()
 
 
@@ -777,6 +778,62 @@ def groth16_verify_batch(proofs, publics, vk: str, device: str = "HIP") -> list:
         lib().groth16_verify_last_error.restype = C.c_char_p
         raise ProverError(f"groth16_verify_batch: {lib().groth16_verify_last_error().decode()} (code {rc})")
     return [int(out[i]) for i in range(n)]
+
+
+def groth16_verify_batch_combined(proofs, publics, vk: str, device: str = "HIP", seed=None):
+    """groth16_verify_batch's verdicts through one randomised pairing equation over the whole batch
+    (groth16_verify_batch_combined): returns (verdicts, path) — path 1 when the combined equation accepted every live item, 0
+    when the per-item stage decided.  `seed`: 32 secret bytes, or None for the operating system's randomness; a seed known to
+    whoever made the proofs voids the 2^-127 bound on accepting an invalid item."""
+    n = len(proofs)
+    if len(publics) != n:
+        raise ValueError("groth16_verify_batch_combined: proofs and publics differ in length")
+    if seed is not None and len(seed) != 32:
+        raise ValueError("groth16_verify_batch_combined: the seed is 32 bytes")
+    pa = (C.c_char_p * max(n, 1))(*[p.encode() if isinstance(p, str) else p for p in proofs])
+    qa = (C.c_char_p * max(n, 1))(*[q.encode() if isinstance(q, str) else q for q in publics])
+    out = (C.c_int32 * max(n, 1))()
+    path = C.c_int32(0)
+    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+    rc = lib().groth16_verify_batch_combined(pa, qa, C.c_int(n), vk.encode(), device.encode(), sd, out, C.byref(path))
+    if rc != 0:
+        lib().groth16_verify_last_error.restype = C.c_char_p
+        raise ProverError(f"groth16_verify_batch_combined: {lib().groth16_verify_last_error().decode()} (code {rc})")
+    return [int(out[i]) for i in range(n)], int(path.value)
+
+
+def verify_combined_coefficients(seed: bytes, first: int, count: int) -> list:
+    """the combined verifier's coefficients z_first … z_{first+count−1} for a 32-byte seed, as integers (no GPU)"""
+    if len(seed) != 32:
+        raise ValueError("verify_combined_coefficients: the seed is 32 bytes")
+    out = (C.c_uint8 * (16 * max(count, 1)))()
+    lib().groth16_verify_combined_coefficients.restype = None
+    lib().groth16_verify_combined_coefficients((C.c_uint8 * 32).from_buffer_copy(bytes(seed)), C.c_uint64(first), C.c_uint64(count), out)
+    raw = bytes(out)
+    return [int.from_bytes(raw[16 * k:16 * k + 16], "little") for k in range(count)]
+
+
+def pairing_product(P: np.ndarray, Q: np.ndarray) -> np.ndarray:
+    """Π e(P[i], Q[i]) on the current device (icicle_snark_pairing_product): P (n,2,4) / Q (n,4,4) as pairing_batch takes them;
+    returns one (12,4) value in bn254_pairing's basis and form (1 for n = 0)."""
+    P = np.ascontiguousarray(P, dtype=np.uint64).reshape(-1, 2, 4)
+    Q = np.ascontiguousarray(Q, dtype=np.uint64).reshape(-1, 4, 4)
+    n = len(P)
+    if len(Q) != n:
+        raise ValueError("pairing_product: P and Q differ in length")
+    out = np.zeros((12, 4), dtype=np.uint64)
+    bufs = [DeviceVec(out.nbytes)]
+    if n:
+        bufs += [DeviceVec.from_host(P), DeviceVec.from_host(Q)]
+    try:
+        check(lib().icicle_snark_pairing_product(ptr_of(bufs[1]) if n else None, ptr_of(bufs[2]) if n else None, C.c_uint64(n), None,
+                                                 ptr_of(bufs[0])), "pairing_product")
+        check(lib().icicle_device_synchronize(), "pairing_product")
+        out = bufs[0].to_host(out.shape)
+    finally:
+        for d in bufs:
+            d.free()
+    return out
 
 
 def groth16_verify_batch_last_timings():

@@ -453,5 +453,122 @@ P29_HD void make_verify_key(const fe* alpha, const fe2* beta, const fe2* gamma, 
   vk->n_pub = n_pub;
 }
 
+// ---- randomised batch verification (prover/verify_combined.hip) ------------------------------------------------------------
+// For secret random zᵢ an all-valid batch of one key satisfies
+//   Πᵢ e(−zᵢ·Aᵢ, Bᵢ) · e(Σᵢ zᵢ·cpubᵢ, γ₂) · e(Σᵢ zᵢ·Cᵢ, δ₂) · e((Σᵢ zᵢ)·α₁, β₂) = 1
+// and a batch with an invalid item fails it except with probability ≤ 2⁻¹²⁷ (128-bit zᵢ ≠ 0).  Per proof that is one subgroup
+// test of B, one 128-bit G1 multiplication and one single-pair Miller loop (combined_lane); the Miller values are multiplied
+// together and the three fixed-G2 pairs and the one final exponentiation are paid once per batch (combined_accept).
+
+// ψ = twist⁻¹ ∘ Frobenius ∘ twist on an XYZZ twist point: (x, y) ↦ (conj(x)·g1_2, conj(y)·g1_3), frob_points' Q1, applied to
+// x = X/ZZ, y = Y/ZZZ — conjugation is a field automorphism, so ZZ and ZZZ are conjugated and nothing else.
+// BOUNDS: coordinates I2 in (a G2 XYZZ coordinate is N, < 2p: ec29.h); f2_conj → I2, f2_mul of I2 operands → N, < 1.07p: I2 out.
+// The identity (ZZ all zero) is returned untouched: conj(0) would be the non-zero limb pattern of p.
+P29_HD G2L::X g2_psi(const G2L::X& p)
+{
+  if (G2L::x_is_zero(p)) return p;
+  return {f2_mul(f2_conj(p.x), g1_2()), f2_mul(f2_conj(p.y), g1_3()), f2_conj(p.zz), f2_conj(p.zzz)};
+}
+// Q ∈ G2 for an affine twist point Q (I2, on the twist, not the identity), by the endomorphism: accepts iff
+//   [x+1]Q + ψ([x]Q) + ψ²([x]Q) = ψ³([2x]Q),      x = 4965661367192848881
+// — one 63-bit multiplication (signed digits XNAF, top digit 1) instead of g2_in_subgroup's 254-bit one.  ψ satisfies
+// X² − tX + q on the twist and acts as q on G2; P(X) = (x+1) + xX + xX² − 2xX³ has P(q) ≡ 0 mod r, and the norm of P(ψ) in
+// Z[ψ] is prime to the cofactor, so the kernel of P(ψ) in E′(F_q²) is exactly G2 (tests/test_pairing29_combined.py does that
+// computation with integers).  The right side is 2·ψ(ψ²([x]Q)): ψ is a homomorphism.
+// BOUNDS: every point is built by ec29.h's x_dbl / x_madd / x_add (G2: coordinates N, < 2p in and out) and g2_psi (I2 → I2);
+// the affine operands ±Q are I2 (f2_neg → I2); the negated Y of the right side is f2_neg of an I2 value → I2.
+P29_HD bool g2_in_subgroup_fast(const F2& qx, const F2& qy)
+{
+  const G2L::A q = {qx, qy}, nq = {qx, f2_neg(qy)};
+  G2L::X xq = {qx, qy, f2_one(), f2_one()};
+  for (int i = X_LEN - 2; i >= 0; i--) {
+    xq = G2L::x_dbl(xq);
+    if (XNAF[i] > 0) G2L::x_madd(xq, q);
+    else if (XNAF[i] < 0) G2L::x_madd(xq, nq);
+  }
+  if (G2L::x_is_zero(xq)) return false; // [x]Q = O: the equation reads Q = O, and Q is not the identity
+  G2L::X lhs = xq;
+  G2L::x_madd(lhs, q); // [x+1]Q
+  const G2L::X p1 = g2_psi(xq), p2 = g2_psi(p1);
+  lhs = G2L::x_add(G2L::x_add(lhs, p1), p2);
+  G2L::X rhs = G2L::x_dbl(g2_psi(p2));
+  if (!G2L::x_is_zero(rhs)) rhs.y = f2_neg(rhs.y);
+  return G2L::x_is_zero(G2L::x_add(lhs, rhs));
+}
+// [z]·P, z < 2^bits given as 32-bit words (little endian), P affine I2 and not the identity: double-and-add on ec29.h's G1
+// XYZZ layer (its bounds: X N, < 7p, the others N, < 2p; an affine operand I2).  O for z ≡ 0 mod r.
+P29_HD G1L::X g1_mul_bits(const G1L::A& p, const uint32_t* z, int bits)
+{
+  G1L::X acc = G1L::x_zero();
+  const int top = (bits - 1) >> 5;
+  for (int w = top; w >= 0; w--) {
+    const uint32_t zw = z[w]; // one load per 32 steps
+    for (int b = w == top ? ((bits - 1) & 31) : 31; b >= 0; b--) {
+      acc = G1L::x_dbl(acc);
+      if ((zw >> b) & 1u) G1L::x_madd(acc, p);
+    }
+  }
+  return acc;
+}
+// Miller loop of the one pair (P, Q), neither the identity (I2 affine coordinates): multi_miller with only pair 0
+P29_HD F12 miller_single(const fe9& px, const fe9& py, const F2& qx, const F2& qy)
+{
+  return multi_miller(true, px, py, qx, qy, false, px, py, nullptr, false, px, py, nullptr);
+}
+// One proof's share of the combined equation: f = the Miller value of ([z](−A), B), 1 when A or B is the identity (as
+// verify_proof drops that pair).  a, b standard form, canonical, on their curves, (0, 0) = identity; 0 < z < 2^128 (four words).
+// False when B ≠ O lies outside the order-r subgroup (f = 1 then).
+// BOUNDS: −A = (from_std x, fq_neg(from_std y)): I2; g1_mul_bits → XYZZ, not O (z ≢ 0 mod r and A has order r; f stays 1
+// otherwise); g1_to_affine → products of f29::mul: N, < 1.1p: I2 as multi_miller wants its P coordinates.
+P29_HD bool combined_lane(const fe* a, const fe2* b, const uint32_t* z, F12& f)
+{
+  const bool a_zero = std_is_zero(a[0]) && std_is_zero(a[1]);
+  const bool b_zero = std_is_zero(b[0].c0) && std_is_zero(b[0].c1) && std_is_zero(b[1].c0) && std_is_zero(b[1].c1);
+  f = f12_one();
+  const F2 bx = Fq2_29::load_std(b[0]), by = Fq2_29::load_std(b[1]);
+  if (!b_zero && !g2_in_subgroup_fast(bx, by)) return false;
+  if (a_zero || b_zero) return true;
+  const G1L::A na = {f29::from_std(a[0]), fq_neg(f29::from_std(a[1]))};
+  const G1L::X za = g1_mul_bits(na, z, 128);
+  if (G1L::x_is_zero(za)) return true;
+  fe9 x, y;
+  g1_to_affine(za, x, y);
+  f = miller_single(x, y, bx, by);
+  return true;
+}
+// The batch's tail (host): prod = Πᵢ of the lanes' Miller values (I2); u = n_pub + 1 scalars mod r in standard form, u₀ = Σ zᵢ,
+// u_{j+1} = Σᵢ zᵢ·sᵢⱼ; sc = Σᵢ zᵢ·Cᵢ (standard-form affine, (0, 0) = O); ic1 / ic1_zero = n_pub + 2 entries, the key's IC
+// shifted by one behind an identity entry (ic1_zero[0] = 1), so that public_input's Straus sum gives S_pub = Σⱼ uⱼ·ICⱼ;
+// gamma / delta = the key's precomputed lines, nullptr for an identity γ₂ / δ₂.  True iff
+//   prod · e(S_pub, γ₂) · e(S_C, δ₂) · e(u₀·α₁, β₂) = 1.
+// An identity key point or an identity sum drops its pair, as verify_proof does per proof.  In two steps, so that a caller can
+// run the first — which does not need prod — while the lanes are still at work: combined_tail_miller gives the Miller value t
+// of the three fixed-G2 pairs, combined_finish decides prod·t.
+// BOUNDS: u₀·α₁ through g1_mul_bits / g1_to_affine and S_pub through public_input: I2 affine; S_C from_std: canonical;
+// β₂ load_std: canonical; f12_mul and final_exp take and return I2.
+P29_HD F12 combined_tail_miller(const fe* alpha, const fe2* beta, const Line* gamma, const Line* delta, const G1L::A* ic1, const uint8_t* ic1_zero,
+                                int n_pub, const fe* u, const fe* sc)
+{
+  const bool az = std_is_zero(alpha[0]) && std_is_zero(alpha[1]);
+  const bool bz = std_is_zero(beta[0].c0) && std_is_zero(beta[0].c1) && std_is_zero(beta[1].c0) && std_is_zero(beta[1].c1);
+  fe9 ax = f29::one_m(), ay = ax, px = ax, py = ax;
+  bool use0 = !az && !bz;
+  if (use0) {
+    const G1L::X ua = g1_mul_bits({f29::from_std(alpha[0]), f29::from_std(alpha[1])}, u[0].l, 254);
+    use0 = !G1L::x_is_zero(ua);
+    if (use0) g1_to_affine(ua, ax, ay);
+  }
+  const bool use1 = public_input(ic1, ic1_zero, n_pub + 1, u, 1, px, py) && gamma;
+  const bool use2 = !(std_is_zero(sc[0]) && std_is_zero(sc[1])) && delta;
+  const F2 bx = Fq2_29::load_std(beta[0]), by = Fq2_29::load_std(beta[1]);
+  return multi_miller(use0, ax, ay, bx, by, use1, px, py, gamma, use2, f29::from_std(sc[0]), f29::from_std(sc[1]), delta);
+}
+P29_HD bool combined_finish(const F12& prod, const F12& t) { return f12_eq_canon(final_exp(f12_mul(prod, t)), f12_one()); }
+P29_HD bool combined_accept(const F12& prod, const fe* alpha, const fe2* beta, const Line* gamma, const Line* delta, const G1L::A* ic1,
+                            const uint8_t* ic1_zero, int n_pub, const fe* u, const fe* sc)
+{
+  return combined_finish(prod, combined_tail_miller(alpha, beta, gamma, delta, ic1, ic1_zero, n_pub, u, sc));
+}
+
 } // namespace p29
 } // namespace bn254

@@ -2,7 +2,8 @@
 //   > prove --witness W --zkey Z --proof P --public Q --device HIP
 // prints COMMAND_COMPLETED after every command, COMMAND_EMPTY for blank lines, COMMAND_EXIT on "exit".
 //   > verify --proof P --public Q --vk verification_key.json
-//   > verify-batch --list L --vk verification_key.json [--device HIP]   (L: one "<proof.json> <public.json>" per line)
+//   > verify-batch --list L --vk verification_key.json [--device HIP] [--combined]   (L: one "<proof.json> <public.json>" per line;
+//     --combined: one randomised pairing equation over the batch, the per-item stage only when it fails)
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -13,7 +14,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  exit\n";
 }
 
 int main()
@@ -96,10 +97,12 @@ int main()
     } else if (cmd == "verify-batch") {
       // every "<proof.json> <public.json>" line of the list against one key, on one GPU: one line per item, then the counts
       std::string list, vk = "verification_key.json", device = "HIP", a;
+      bool combined = false;
       while (in >> a) {
         if (a == "--list") in >> list;
         else if (a == "--vk") in >> vk;
         else if (a == "--device") in >> device;
+        else if (a == "--combined") combined = true;
         else print_help();
       }
       auto slurp = [](const std::string& path, std::string* out) {
@@ -136,7 +139,9 @@ int main()
         qj[i] = publics[i].c_str();
       }
       std::vector<int32_t> verdicts(n);
-      const int rc = groth16_verify_batch(pj.data(), qj.data(), n, vk_text.c_str(), device.c_str(), verdicts.data());
+      int32_t path = 0;
+      const int rc = combined ? groth16_verify_batch_combined(pj.data(), qj.data(), n, vk_text.c_str(), device.c_str(), nullptr, verdicts.data(), &path)
+                              : groth16_verify_batch(pj.data(), qj.data(), n, vk_text.c_str(), device.c_str(), verdicts.data());
       if (rc != 0) {
         std::cerr << "verify-batch failed (" << rc << "): " << groth16_verify_last_error() << std::endl;
       } else {
@@ -157,6 +162,7 @@ int main()
           }
         }
         std::cout << "accepted " << acc << " rejected " << rej << " errors " << err << std::endl;
+        if (combined) std::cout << "decided by: " << (path ? "combined equation" : "per-item fallback") << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

@@ -53,47 +53,7 @@ __global__ __launch_bounds__(WG) void verify_batch_kernel(const p29::VerifyKey29
   verdict[i] = p29::verify_proof(*vk, ic, ic_zero, it.a, it.b, it.c, pub + i, m);
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 thread_local double g_last_parse_ms = 0, g_last_device_ms = 0;
-
-// "HIP", "CUDA" (device 0) or "HIP:k" / "CUDA:k"; −1 for anything else (a device list included)
-int parse_one_device(const char* s)
-{
-  const char* colon = strchr(s, ':');
-  const std::string type = colon ? std::string(s, colon) : std::string(s);
-  if (type != "HIP" && type != "CUDA") return -1;
-  if (!colon) return 0;
-  const char* d = colon + 1;
-  if (!*d || strlen(d) > 6 || strspn(d, "0123456789") != strlen(d)) return -1;
-  return atoi(d);
-}
-
-struct DevBuf { // device allocations of one call, freed on every exit path
-  std::vector<void*> ptrs;
-  ~DevBuf()
-  {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <class T>
-  T* alloc(size_t count)
-  {
-    void* p = nullptr;
-    if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
-    ptrs.push_back(p);
-    return (T*)p;
-  }
-};
-
-int device_fail(eIcicleError code, const char* what, hipError_t e)
-{
-  char msg[200];
-  snprintf(msg, sizeof msg, "device: %s: %s", what, hipGetErrorString(e));
-  return isnark::vb::fail((int)code, msg);
-}
 
 } // namespace
 
@@ -113,24 +73,55 @@ ISNARK_API void groth16_verify_batch_last_timings(double* parse_ms, double* devi
   if (device_ms) *device_ms = g_last_device_ms;
 }
 
-ISNARK_API int groth16_verify_batch(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json, const char* device,
-                                    int32_t* verdicts)
+// ---- the stages of a batch call, shared with groth16_verify_batch_combined (verify_combined.hip) ------------------------------
+namespace isnark {
+namespace vb {
+
+// "HIP", "CUDA" (device 0) or "HIP:k" / "CUDA:k"; −1 for anything else (a device list included)
+int parse_one_device(const char* s)
 {
-  using namespace isnark::vb;
+  const char* colon = strchr(s, ':');
+  const std::string type = colon ? std::string(s, colon) : std::string(s);
+  if (type != "HIP" && type != "CUDA") return -1;
+  if (!colon) return 0;
+  const char* d = colon + 1;
+  if (!*d || strlen(d) > 6 || strspn(d, "0123456789") != strlen(d)) return -1;
+  return atoi(d);
+}
+
+void set_last_timings(double parse_ms, double device_ms)
+{
+  g_last_parse_ms = parse_ms;
+  g_last_device_ms = device_ms;
+}
+
+int batch_prologue(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json, const char* device,
+                   const int32_t* verdicts, int* dev, bool* done)
+{
+  *done = true;
   g_last_parse_ms = g_last_device_ms = 0;
   if (n < 0) return fail(-3, "negative batch size");
   if (n == 0) return 0;
   if (!proof_jsons || !public_jsons || !vk_json || !device || !verdicts) return fail(-3, "null argument");
-  const int dev = parse_one_device(device);
-  if (dev < 0) return fail((int)ICICLE_INVALID_DEVICE, "device must be HIP, CUDA or HIP:k (one device)");
+  *dev = parse_one_device(device);
+  if (*dev < 0) return fail((int)ICICLE_INVALID_DEVICE, "device must be HIP, CUDA or HIP:k (one device)");
+  *done = false;
+  return 0;
+}
+
+int parse_stage(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json, int32_t* verdicts, Parsed* out,
+                const std::function<void(const VbKey&)>& meanwhile)
+{
   const auto t0 = std::chrono::steady_clock::now();
-  VbKey key;
+  VbKey& key = out->key;
   if (int rc = parse_vk(vk_json, &key)) return rc;
   const size_t np = key.n_public;
 
-  // items on the pool (≤ 16 tasks of contiguous ranges), the key's device part on this thread meanwhile
-  std::vector<VbItem> items(n);
-  std::vector<fe> pub((size_t)n * np + 1);
+  // items on the pool (≤ 16 tasks of contiguous ranges), the caller's per-key work on this thread meanwhile
+  std::vector<VbItem>& items = out->items;
+  std::vector<fe>& pub = out->pub;
+  items.resize(n);
+  pub.resize((size_t)n * np + 1);
   const int tasks = std::max(1, std::min(16, n / 64));
   std::vector<isnark::HostTask> ht(tasks);
   for (int t = 0; t < tasks; t++) {
@@ -140,24 +131,41 @@ ISNARK_API int groth16_verify_batch(const char* const* proof_jsons, const char* 
     };
     if (t > 0) isnark::WorkerPool::get().run_or_inline(&ht[t]);
   }
-  std::vector<p29::VerifyKey29> vkh(1);
-  p29::make_verify_key(key.alpha, key.beta, key.gamma, key.delta, (int)np, vkh.data());
-  std::vector<G1L::A> ic(np + 1);
-  std::vector<uint8_t> icz(np + 1);
-  for (size_t j = 0; j <= np; j++) {
-    icz[j] = p29::std_is_zero(key.ic[2 * j]) && p29::std_is_zero(key.ic[2 * j + 1]);
-    ic[j] = {f29::from_std(key.ic[2 * j]), f29::from_std(key.ic[2 * j + 1])};
-  }
+  if (meanwhile) meanwhile(key);
   ht[0].fn();
   for (int t = 1; t < tasks; t++)
     if (ht[t].queued) isnark::WorkerPool::wait(&ht[t]);
-  std::vector<int> live;
-  live.reserve(n);
+  out->live.clear();
+  out->live.reserve(n);
   for (int i = 0; i < n; i++)
-    if (verdicts[i] == 0) live.push_back(i);
+    if (verdicts[i] == 0) out->live.push_back(i);
   g_last_parse_ms = ms_since(t0);
-  if (live.empty()) return 0;
+  return 0;
+}
 
+void make_device_key(const VbKey& key, DeviceKey* dk)
+{
+  const size_t np = key.n_public;
+  dk->vk.resize(1);
+  p29::make_verify_key(key.alpha, key.beta, key.gamma, key.delta, (int)np, dk->vk.data());
+  dk->ic.resize(np + 1);
+  dk->icz.resize(np + 1);
+  for (size_t j = 0; j <= np; j++) {
+    dk->icz[j] = p29::std_is_zero(key.ic[2 * j]) && p29::std_is_zero(key.ic[2 * j + 1]);
+    dk->ic[j] = {f29::from_std(key.ic[2 * j]), f29::from_std(key.ic[2 * j + 1])};
+  }
+}
+
+int per_item_stage(const Parsed& pz, const DeviceKey& dk, int dev, int32_t* verdicts)
+{
+  const std::vector<int>& live = pz.live;
+  const std::vector<VbItem>& items = pz.items;
+  const std::vector<fe>& pub = pz.pub;
+  const std::vector<p29::VerifyKey29>& vkh = dk.vk;
+  const std::vector<G1L::A>& ic = dk.ic;
+  const std::vector<uint8_t>& icz = dk.icz;
+  const size_t np = pz.key.n_public;
+  if (live.empty()) return 0;
   // device part
   int prev = -1;
   (void)hipGetDevice(&prev);
@@ -225,6 +233,23 @@ ISNARK_API int groth16_verify_batch(const char* const* proof_jsons, const char* 
   if ((e = hipEventSynchronize(ev1)) != hipSuccess) return device_fail(ICICLE_SYNCHRONIZATION_FAILED, "event", e);
   float dms = 0;
   (void)hipEventElapsedTime(&dms, ev0, ev1);
-  g_last_device_ms = dms;
+  g_last_device_ms += dms;
   return 0;
+}
+
+} // namespace vb
+} // namespace isnark
+
+ISNARK_API int groth16_verify_batch(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json, const char* device,
+                                    int32_t* verdicts)
+{
+  using namespace isnark::vb;
+  int dev = 0;
+  bool done = false;
+  const int rc0 = batch_prologue(proof_jsons, public_jsons, n, vk_json, device, verdicts, &dev, &done);
+  if (done) return rc0;
+  Parsed pz;
+  DeviceKey dk;
+  if (int rc = parse_stage(proof_jsons, public_jsons, n, vk_json, verdicts, &pz, [&dk](const VbKey& key) { make_device_key(key, &dk); })) return rc;
+  return per_item_stage(pz, dk, dev, verdicts);
 }

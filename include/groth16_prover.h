@@ -187,6 +187,30 @@ int groth16_verify_batch(const char* const* proof_jsons, const char* const* publ
 /* host parse time (vk and items) and device time (HIP events, uploads to verdicts) of this thread's last batch, ms */
 void groth16_verify_batch_last_timings(double* parse_ms, double* device_ms);
 
+/* groth16_verify_batch_combined — the same batch decided by ONE randomised pairing equation when every proof is valid.
+ * Arguments, return codes, error texts, the n = 0 behaviour and the meaning of verdicts[i] are groth16_verify_batch's; items the
+ * parser refuses keep their negative code and take part in nothing.  For coefficients z_i derived from the seed, the remaining
+ * ("live") items are checked together:
+ *     Π_i e(−z_i·A_i, B_i) · e(Σ_i z_i·cpub_i, γ₂) · e(Σ_i z_i·C_i, δ₂) · e((Σ_i z_i)·α₁, β₂) = 1
+ * after a subgroup test of every pi_b (an endomorphism test: one 63-bit multiplication).  If all of that holds, every live item
+ * gets 1 and *path = 1.  On any subgroup failure or a failed equation *path = 0 and the live items go through
+ * groth16_verify_batch's per-item device stage.  So the verdicts always equal groth16_verify_batch's, with one exception: an
+ * invalid item is accepted with probability ≤ 2^-127 per call, over the seed.  A valid proof is never rejected.  *path is 1 too
+ * when no item is live (nothing was left to decide); `path` may be NULL.
+ * Coefficients: z_i = the first 16 bytes of SHA-256(seed ‖ LE64(i)) read as a little-endian integer (the low 128 bits of the
+ * digest taken as a little-endian number); 0 is replaced by 1.  i is the index in the caller's arrays, so chunking and parse
+ * errors do not shift them.  seed32 == NULL draws 32 bytes from the operating system (getrandom, else /dev/urandom); when
+ * that fails the call returns −3 — it never falls back to a constant.
+ * THE SEED MUST BE SECRET AND FRESH: whoever knows the seed before choosing the proofs can build invalid proofs whose errors
+ * cancel in the equation, which voids the guarantee.  Pass a seed only for reproducible tests; use NULL otherwise.
+ * groth16_verify_batch_last_timings afterwards: the parse time, and as device time the wall time from the end of the parse
+ * to the verdicts (lanes, product, MSM, the host tail, and the fallback when it ran). */
+int groth16_verify_batch_combined(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json,
+                                  const char* device, const uint8_t* seed32 /* NULL = OS randomness */, int32_t* verdicts,
+                                  int32_t* path /* may be NULL */);
+/* out16[16·k …] = z_{first + k} (16 bytes, little endian) for k < count, as derived above.  Needs no GPU. */
+void groth16_verify_combined_coefficients(const uint8_t seed32[32], uint64_t first, uint64_t count, uint8_t* out16);
+
 #ifdef __cplusplus
 }
 #endif

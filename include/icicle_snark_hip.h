@@ -259,6 +259,11 @@ eIcicleError icicle_snark_g2_generator_mul(const bn254_scalar_t* s, uint64_t n, 
  * the same basis and canonical form as bn254_pairing.  An identity input (0,0) gives 1.  Enqueued on `stream`. */
 eIcicleError icicle_snark_pairing_batch(const bn254_affine_t* p, const bn254_g2_affine_t* q, uint64_t n, icicleStreamHandle stream,
                                         bn254_fq12_t* out);
+/* out (device, ONE Fq12 in the same basis and form) = Π_i e(p[i], q[i]) over n pairs: Miller loops, a product reduction and one
+ * final exponentiation on a single lane.  Device pointers, standard-form affine in.  Identity inputs contribute 1; n = 0
+ * writes 1.  Enqueued on `stream`. */
+eIcicleError icicle_snark_pairing_product(const bn254_affine_t* p, const bn254_g2_affine_t* q, uint64_t n, icicleStreamHandle stream,
+                                          bn254_fq12_t* out);
 /* per-phase device timings of the most recent MSM on this thread, milliseconds (HIP events):
  * [0] recode+sort, [1] bucket accumulation, [2] bucket reduction, [3] total.  Valid only when the
  * environment variable ICICLE_SNARK_PROFILE=1 is set (adds stream synchronisation). */
