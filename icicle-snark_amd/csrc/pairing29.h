@@ -408,7 +408,8 @@ P29_HD bool public_input(const G1L::A* ic, const uint8_t* ic_zero, int n_pub, co
   return true;
 }
 
-// what one verification key contributes to every proof: γ₂ / δ₂ lines, the target conj(e(α₁, β₂)) (canonical)
+// what one verification key contributes to every proof: γ₂ / δ₂ lines, the target conj(e(α₁, β₂)) (canonical); made by
+// make_verify_key below, which prover/verify_host.h (PreparedKey) calls in its two halves
 struct VerifyKey29 {
   Line gamma[N_LINES], delta[N_LINES];
   F12 target;
@@ -421,15 +422,18 @@ FF_HD bool std_is_zero(const fe& a)
   for (int i = 0; i < 8; i++) o |= a.l[i];
   return o == 0;
 }
+// (0, 0), the identity encoding of a standard-form affine point: p = {x, y}
+FF_HD bool g1_std_is_zero(const fe* p) { return std_is_zero(p[0]) && std_is_zero(p[1]); }
+FF_HD bool g2_std_is_zero(const fe2* q) { return std_is_zero(q[0].c0) && std_is_zero(q[0].c1) && std_is_zero(q[1].c0) && std_is_zero(q[1].c1); }
 // one Groth16 proof, points in standard form (canonical, on their curves: the parser checked that; (0, 0) = identity):
 //   e(−A, B) · e(cpub, γ₂) · e(C, δ₂) = conj(e(α₁, β₂))
 // returns 1 accepted, 0 rejected, −2 when B lies outside the order-r subgroup (the host verifier's code for a bad point)
 P29_HD int verify_proof(const VerifyKey29& vk, const G1L::A* ic, const uint8_t* ic_zero, const fe* a, const fe2* b, const fe* c,
                         const fe* sc, size_t stride)
 {
-  const bool a_zero = std_is_zero(a[0]) && std_is_zero(a[1]);
-  const bool b_zero = std_is_zero(b[0].c0) && std_is_zero(b[0].c1) && std_is_zero(b[1].c0) && std_is_zero(b[1].c1);
-  const bool c_zero = std_is_zero(c[0]) && std_is_zero(c[1]);
+  const bool a_zero = g1_std_is_zero(a);
+  const bool b_zero = g2_std_is_zero(b);
+  const bool c_zero = g1_std_is_zero(c);
   const F2 bx = Fq2_29::load_std(b[0]), by = Fq2_29::load_std(b[1]);
   if (!b_zero && !g2_in_subgroup(bx, by)) return -2;
   fe9 px, py;
@@ -439,18 +443,27 @@ P29_HD int verify_proof(const VerifyKey29& vk, const G1L::A* ic, const uint8_t* 
   const F12 f = multi_miller(!a_zero && !b_zero, ax, nay, bx, by, use1, px, py, vk.gamma, !c_zero && vk.use_delta, cx, cy, vk.delta);
   return f12_eq_canon(final_exp(f), vk.target) ? 1 : 0;
 }
-// the per-key part, on the host (or a single lane): α₁, β₂, γ₂, δ₂ standard form, (0, 0) = identity
-P29_HD void make_verify_key(const fe* alpha, const fe2* beta, const fe2* gamma, const fe2* delta, int n_pub, VerifyKey29* vk)
+// the per-key part, on the host (or a single lane): α₁, β₂, γ₂, δ₂ standard form, (0, 0) = identity.  In two halves, because the
+// target costs a pairing that only the per-item verifier compares with (prover/verify_host.h: PreparedKey asks for it late).
+P29_HD void make_verify_lines(const fe2* gamma, const fe2* delta, int n_pub, VerifyKey29* vk)
 {
-  const bool az = std_is_zero(alpha[0]) && std_is_zero(alpha[1]);
-  const bool bz = std_is_zero(beta[0].c0) && std_is_zero(beta[0].c1) && std_is_zero(beta[1].c0) && std_is_zero(beta[1].c1);
-  vk->use_gamma = !(std_is_zero(gamma[0].c0) && std_is_zero(gamma[0].c1) && std_is_zero(gamma[1].c0) && std_is_zero(gamma[1].c1));
-  vk->use_delta = !(std_is_zero(delta[0].c0) && std_is_zero(delta[0].c1) && std_is_zero(delta[1].c0) && std_is_zero(delta[1].c1));
+  vk->use_gamma = !g2_std_is_zero(gamma);
+  vk->use_delta = !g2_std_is_zero(delta);
   if (vk->use_gamma) precompute_lines(Fq2_29::load_std(gamma[0]), Fq2_29::load_std(gamma[1]), vk->gamma);
   if (vk->use_delta) precompute_lines(Fq2_29::load_std(delta[0]), Fq2_29::load_std(delta[1]), vk->delta);
-  const F12 e = (az || bz) ? f12_one() : pairing(f29::from_std(alpha[0]), f29::from_std(alpha[1]), Fq2_29::load_std(beta[0]), Fq2_29::load_std(beta[1]));
-  vk->target = f12_canon(f12_conj(e));
   vk->n_pub = n_pub;
+}
+P29_HD void make_verify_target(const fe* alpha, const fe2* beta, VerifyKey29* vk)
+{
+  const F12 e = (g1_std_is_zero(alpha) || g2_std_is_zero(beta))
+                  ? f12_one()
+                  : pairing(f29::from_std(alpha[0]), f29::from_std(alpha[1]), Fq2_29::load_std(beta[0]), Fq2_29::load_std(beta[1]));
+  vk->target = f12_canon(f12_conj(e));
+}
+P29_HD void make_verify_key(const fe* alpha, const fe2* beta, const fe2* gamma, const fe2* delta, int n_pub, VerifyKey29* vk)
+{
+  make_verify_lines(gamma, delta, n_pub, vk);
+  make_verify_target(alpha, beta, vk);
 }
 
 // ---- randomised batch verification (prover/verify_combined.hip) ------------------------------------------------------------
@@ -522,8 +535,8 @@ P29_HD F12 miller_single(const fe9& px, const fe9& py, const F2& qx, const F2& q
 // otherwise); g1_to_affine → products of f29::mul: N, < 1.1p: I2 as multi_miller wants its P coordinates.
 P29_HD bool combined_lane(const fe* a, const fe2* b, const uint32_t* z, F12& f)
 {
-  const bool a_zero = std_is_zero(a[0]) && std_is_zero(a[1]);
-  const bool b_zero = std_is_zero(b[0].c0) && std_is_zero(b[0].c1) && std_is_zero(b[1].c0) && std_is_zero(b[1].c1);
+  const bool a_zero = g1_std_is_zero(a);
+  const bool b_zero = g2_std_is_zero(b);
   f = f12_one();
   const F2 bx = Fq2_29::load_std(b[0]), by = Fq2_29::load_std(b[1]);
   if (!b_zero && !g2_in_subgroup_fast(bx, by)) return false;
@@ -549,8 +562,8 @@ P29_HD bool combined_lane(const fe* a, const fe2* b, const uint32_t* z, F12& f)
 P29_HD F12 combined_tail_miller(const fe* alpha, const fe2* beta, const Line* gamma, const Line* delta, const G1L::A* ic1, const uint8_t* ic1_zero,
                                 int n_pub, const fe* u, const fe* sc)
 {
-  const bool az = std_is_zero(alpha[0]) && std_is_zero(alpha[1]);
-  const bool bz = std_is_zero(beta[0].c0) && std_is_zero(beta[0].c1) && std_is_zero(beta[1].c0) && std_is_zero(beta[1].c1);
+  const bool az = g1_std_is_zero(alpha);
+  const bool bz = g2_std_is_zero(beta);
   fe9 ax = f29::one_m(), ay = ax, px = ax, py = ax;
   bool use0 = !az && !bz;
   if (use0) {
@@ -559,7 +572,7 @@ P29_HD F12 combined_tail_miller(const fe* alpha, const fe2* beta, const Line* ga
     if (use0) g1_to_affine(ua, ax, ay);
   }
   const bool use1 = public_input(ic1, ic1_zero, n_pub + 1, u, 1, px, py) && gamma;
-  const bool use2 = !(std_is_zero(sc[0]) && std_is_zero(sc[1])) && delta;
+  const bool use2 = !g1_std_is_zero(sc) && delta;
   const F2 bx = Fq2_29::load_std(beta[0]), by = Fq2_29::load_std(beta[1]);
   return multi_miller(use0, ax, ay, bx, by, use1, px, py, gamma, use2, f29::from_std(sc[0]), f29::from_std(sc[1]), delta);
 }

@@ -25,7 +25,7 @@
 #include "../../../include/groth16_prover.h"
 #include "../common.h"
 #include "../ec.h"
-#include "verify_batch.h"
+#include "verify_host.h"
 
 using namespace bn254;
 
@@ -476,7 +476,7 @@ bool read_g1(const JVal* v, G1::A* out) // deserialize_g1_affine — src/convers
   return g1_valid(*out);
 }
 // deserialize_g2_affine — src/conversions.rs:72-96; `subgroup` false leaves the order-r test to the caller (the batched
-// verifier runs it on the device)
+// verifiers run it on the device)
 bool read_g2(const JVal* v, G2::A* out, bool subgroup = true)
 {
   if (!v || v->t != JVal::ARR || v->a.size() < 2 || v->a[0].a.size() < 2 || v->a[1].a.size() < 2) return false;
@@ -519,8 +519,9 @@ void bn254_base_field_generate_scalars_one(bn254_fq_t* out) // unseeded, like ut
 
 } // namespace
 
-// ---- parsing for the batched verifier (prover/verify_batch.hip): the checks of groth16_verify_json, split into the key's
-// and each item's, with the same codes and messages.  Only the order-r test of pi_b is left out (done on the device).
+// ---- the input checks of every verifier entry point (groth16_verify_json below, the batch stages of prover/verify_batch.hip),
+// stated once: the verification key's, then one item's.  Codes: −2 format, −3 null; the message goes to
+// groth16_verify_last_error() of the calling thread.
 namespace isnark {
 namespace vb {
 int fail(int code, const char* msg) { return vfail(code, msg); }
@@ -559,7 +560,8 @@ int parse_vk(const char* vk_json, VbKey* out)
   }
   return 0;
 }
-int parse_item(const char* proof_json, const char* public_json, size_t n_public, VbItem* item, fe* pub)
+// `host_subgroup_test`: run the order-r test of pi_b here (g2_valid) — the batch stages leave it to their kernels
+int parse_item(const char* proof_json, const char* public_json, size_t n_public, VbItem* item, fe* pub, bool host_subgroup_test)
 {
   if (!proof_json || !public_json) return vfail(-3, "null argument");
   JParser pp{proof_json, proof_json + strlen(proof_json)}, pq{public_json, public_json + strlen(public_json)};
@@ -568,7 +570,7 @@ int parse_item(const char* proof_json, const char* public_json, size_t n_public,
   G1::A pi_a, pi_c;
   G2::A pi_b;
   (void)K();
-  if (!read_g1(proof.get("pi_a"), &pi_a) || !read_g2(proof.get("pi_b"), &pi_b, false) || !read_g1(proof.get("pi_c"), &pi_c))
+  if (!read_g1(proof.get("pi_a"), &pi_a) || !read_g2(proof.get("pi_b"), &pi_b, host_subgroup_test) || !read_g1(proof.get("pi_c"), &pi_c))
     return vfail(-2, "proof: bad point (not canonical, not on the curve, or outside the r-torsion)");
   if (pubv.a.size() < n_public) return vfail(-2, "public inputs / IC length mismatch");
   for (size_t i = 0; i < n_public; i++)
@@ -665,47 +667,32 @@ __attribute__((visibility("default"))) void bn254_pairing_target_field_generate_
 
 __attribute__((visibility("default"))) const char* groth16_verify_last_error(void) { return g_verr; }
 
-// groth16_verify on JSON texts: returns 1 (accepted), 0 (rejected) or a negative error code.
+// groth16_verify on JSON texts: returns 1 (accepted), 0 (rejected) or a negative error code (−3 a null argument, −2 anything
+// else the checks refuse).
 //   e(−A, B) · e(Σ pubᵢ·ICᵢ₊₁ + IC₀, γ₂) · e(C, δ₂) · e(α₁, β₂) = 1        — src/proof_helper.rs:345-369
+// The checks are vb::parse_vk and vb::parse_item above, the ones the batch entry points run, so a text gets the same code and
+// message from all three.  Of several independent faults the first is reported in the order key, proof, public signals (a
+// malformed proof or signals text counts as the proof's); the order-r test of pi_b belongs to the proof's point checks.
 __attribute__((visibility("default"))) int groth16_verify_json(const char* proof_json, const char* public_json, const char* vk_json)
 {
   if (!proof_json || !public_json || !vk_json) return vfail(-3, "null argument");
-  JParser pp{proof_json, proof_json + strlen(proof_json)}, pq{public_json, public_json + strlen(public_json)}, pv{vk_json, vk_json + strlen(vk_json)};
-  JVal proof = pp.document(), pub = pq.document(), vk = pv.document();
-  if (!pp.ok || !pq.ok || !pv.ok || proof.t != JVal::OBJ || pub.t != JVal::ARR || vk.t != JVal::OBJ) return vfail(-2, "malformed JSON");
-  G1::A pi_a, pi_c, alpha1;
-  G2::A pi_b, beta2, gamma2, delta2;
-  (void)K(); // constants (twist coefficient) before the point checks
-  if (!read_g1(proof.get("pi_a"), &pi_a) || !read_g2(proof.get("pi_b"), &pi_b) || !read_g1(proof.get("pi_c"), &pi_c))
-    return vfail(-2, "proof: bad point (not canonical, not on the curve, or outside the r-torsion)");
-  if (!read_g1(vk.get("vk_alpha_1"), &alpha1) || !read_g2(vk.get("vk_beta_2"), &beta2) || !read_g2(vk.get("vk_gamma_2"), &gamma2) || !read_g2(vk.get("vk_delta_2"), &delta2))
-    return vfail(-2, "verification key: bad point");
-  const JVal* ic = vk.get("IC");
-  const JVal* np = vk.get("nPublic");
-  if (!ic || ic->t != JVal::ARR || !np) return vfail(-2, "verification key: IC / nPublic missing");
-  if ((np->t != JVal::NUM && np->t != JVal::STR) || np->s.empty() || np->s.size() > 9 || np->s.find_first_not_of("0123456789") != std::string::npos)
-    return vfail(-2, "verification key: nPublic is not a non-negative integer");
-  const size_t n_public = (size_t)strtoul(np->s.c_str(), nullptr, 10);
-  if (ic->a.size() < n_public + 1 || pub.a.size() < n_public) return vfail(-2, "public inputs / IC length mismatch");
-  for (size_t i = 0; i < n_public; i++)
-    if (pub.a[i].t != JVal::STR) return vfail(-2, "public signals must be decimal strings");
+  isnark::vb::VbKey key;
+  if (int rc = isnark::vb::parse_vk(vk_json, &key)) return rc;
+  const size_t n_public = key.n_public;
+  isnark::vb::VbItem item;
+  std::vector<fe> pub(n_public + 1);
+  if (int rc = isnark::vb::parse_item(proof_json, public_json, n_public, &item, pub.data(), true)) return rc;
+  const auto g1_mont = [](const fe* p) { return G1::aff_to_mont(G1::A{p[0], p[1]}); };
+  const auto g2_mont = [](const fe2* q) { return G2::A{Fq2Ops::to_mont(q[0]), Fq2Ops::to_mont(q[1])}; };
+  const G1::A pi_a = g1_mont(item.a), pi_c = g1_mont(item.c), alpha1 = g1_mont(key.alpha);
+  const G2::A pi_b = g2_mont(item.b), beta2 = g2_mont(key.beta), gamma2 = g2_mont(key.gamma), delta2 = g2_mont(key.delta);
   // cpub = IC₀ + Σ pubᵢ·ICᵢ₊₁  (projective host arithmetic through the FFI functions)
   bn254_projective_t cpub, t;
-  {
-    G1::A a0;
-    if (!read_g1(&ic->a[0], &a0)) return vfail(-2, "IC: bad point");
-    G1::A s = {Fq::from_mont(a0.x), Fq::from_mont(a0.y)};
-    bn254_from_affine((const bn254_affine_t*)&s, &cpub);
-  }
+  bn254_from_affine((const bn254_affine_t*)&key.ic[0], &cpub);
   for (size_t i = 0; i < n_public; i++) {
-    G1::A ai;
-    fe sc;
-    if (!read_g1(&ic->a[i + 1], &ai) || !dec_to_fe(pub.a[i].s, &sc)) return vfail(-2, "IC / public: bad value");
-    if (!Fr::is_canonical(sc)) return vfail(-2, "public signal is not below the scalar field modulus");
-    G1::A s = {Fq::from_mont(ai.x), Fq::from_mont(ai.y)};
     bn254_projective_t pi;
-    bn254_from_affine((const bn254_affine_t*)&s, &pi);
-    bn254_mul_scalar(&pi, (const bn254_scalar_t*)&sc, &t);
+    bn254_from_affine((const bn254_affine_t*)&key.ic[2 * (i + 1)], &pi);
+    bn254_mul_scalar(&pi, (const bn254_scalar_t*)&pub[i], &t);
     bn254_ecadd(&cpub, &t, &cpub);
   }
   bn254_affine_t cpub_aff;

@@ -1,54 +1,28 @@
-// verify_batch.h — host-side pieces of the batched Groth16 verifiers.  In pairing.cpp: the JSON checks of groth16_verify_json,
-// split into the verification key's (once per call) and each item's.  In verify_batch.hip: the stages of a batch call (argument
-// checks, parse, per-item device stage), which groth16_verify_batch runs in a row and groth16_verify_batch_combined
-// (verify_combined.hip) shares: the same parser, and the per-item stage as its fallback.
+// verify_batch.h — what the two batched Groth16 verifiers share and that needs HIP: the stages of a batch call in
+// verify_batch.hip (argument checks, parse, per-item device stage), which groth16_verify_batch runs in a row and
+// groth16_verify_batch_combined (verify_combined.hip) shares — the same parser, and the per-item stage as its fallback — and the
+// device session both device stages work in.  The host-only pieces (parsed key and items, the prepared key, the combined sums) are
+// in verify_host.h.
 #pragma once
 #include <chrono>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 #include <functional>
 #include <vector>
 
-#include "../ec29.h"
-
-namespace bn254 {
-namespace p29 {
-struct VerifyKey29;
-}
-} // namespace bn254
+#include "../common.h"
+#include "verify_host.h"
 
 namespace isnark {
 namespace vb {
 
-struct VbKey {                   // standard form, canonical; (0, 0) = identity
-  bn254::fe alpha[2];
-  bn254::fe2 beta[2], gamma[2], delta[2];
-  std::vector<bn254::fe> ic;     // (n_public + 1) affine points, x then y
-  size_t n_public = 0;
-};
-struct VbItem {                  // one proof's points, standard form, canonical, on their curves (pi_b not yet subgroup-checked)
-  bn254::fe a[2];
-  bn254::fe2 b[2];
-  bn254::fe c[2];
-};
-
-// 0, or what groth16_verify_json returns for the same text (−2 format, −3 null); the message goes to
-// groth16_verify_last_error() of the calling thread
-int parse_vk(const char* vk_json, VbKey* out);
-int parse_item(const char* proof_json, const char* public_json, size_t n_public, VbItem* item, bn254::fe* pub);
-int fail(int code, const char* msg);
-
 struct Parsed {                  // what the parse stage leaves: items[i] / pub[i·n_public + j] are valid where verdicts[i] == 0
   VbKey key;
-  std::vector<VbItem> items;
+  std::vector<VbItem> items;     // (pi_b not yet subgroup-checked)
   std::vector<bn254::fe> pub;
   std::vector<int> live;         // the indices the parser let through, ascending
-};
-struct DeviceKey {               // the key as verify_batch_kernel reads it (p29::make_verify_key and the lazy form of IC)
-  std::vector<bn254::p29::VerifyKey29> vk;
-  std::vector<bn254::G1L::A> ic;
-  std::vector<uint8_t> icz;
 };
 int parse_one_device(const char* s);
 // the argument checks every batch entry point starts with; *done: return the result at once (an error, or n = 0)
@@ -58,9 +32,9 @@ int batch_prologue(const char* const* proof_jsons, const char* const* public_jso
 // its negative code otherwise.  Non-zero: the key's error.  Sets the thread's parse time.
 int parse_stage(const char* const* proof_jsons, const char* const* public_jsons, int n, const char* vk_json, int32_t* verdicts, Parsed* out,
                 const std::function<void(const VbKey&)>& meanwhile);
-void make_device_key(const VbKey& key, DeviceKey* dk);
-// every live item through verify_batch_kernel in chunks; adds its device time to the thread's
-int per_item_stage(const Parsed& pz, const DeviceKey& dk, int dev, int32_t* verdicts);
+// every live item through verify_batch_kernel in chunks (pk prepared from pz.key; its target is made here when it is not yet);
+// adds its device time to the thread's
+int per_item_stage(const Parsed& pz, PreparedKey& pk, int dev, int32_t* verdicts);
 void set_last_timings(double parse_ms, double device_ms);
 
 // small helpers of the two device stages
@@ -76,9 +50,11 @@ inline int device_fail(int code, const char* what, hipError_t e)
 }
 struct DevBuf { // device allocations of one call, freed on every exit path
   std::vector<void*> ptrs;
-  ~DevBuf()
+  ~DevBuf() { free_all(); }
+  void free_all()
   {
     for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
   }
   template <class T>
   T* alloc(size_t count)
@@ -87,6 +63,48 @@ struct DevBuf { // device allocations of one call, freed on every exit path
     if (hipMalloc(&p, count * sizeof(T) + 16) != hipSuccess) return nullptr;
     ptrs.push_back(p);
     return (T*)p;
+  }
+};
+
+// One call's stay on a device: selects it through the library (icicle_set_device), takes one or two of the library's pooled
+// streams — the MSM's workspace follows its stream's life, so the MSM must get a stream of the library's own — and owns the call's
+// device buffers.  On every exit path the buffers are freed, the streams drained and handed back, and the calling thread gets back
+// what it had: the library's default device, then its HIP device.
+struct DeviceSession {
+  int prev_hip = -1, prev_lib = -1;
+  icicleStreamHandle streams[2] = {nullptr, nullptr};
+  DevBuf buf;
+
+  // 0, or the call's error code with its "device: …" message set
+  int open(int dev, int n_streams)
+  {
+    (void)hipGetDevice(&prev_hip);
+    prev_lib = default_device_or_none();
+    const IcicleDevice want = hip_device(dev);
+    if (icicle_set_device(&want) != ICICLE_SUCCESS) return fail((int)ICICLE_INVALID_DEVICE, "device: hipSetDevice: invalid device ordinal");
+    for (int k = 0; k < n_streams; k++)
+      if (icicle_create_stream(&streams[k]) != ICICLE_SUCCESS) return fail((int)ICICLE_UNKNOWN_ERROR, "device: stream creation failed");
+    return 0;
+  }
+  hipStream_t stream(int k) const { return (hipStream_t)streams[k]; }
+  ~DeviceSession()
+  {
+    buf.free_all();
+    for (int k = 1; k >= 0; k--)
+      if (streams[k]) (void)icicle_destroy_stream(streams[k]);
+    if (prev_lib >= 0) {
+      const IcicleDevice back = hip_device(prev_lib);
+      (void)icicle_set_device(&back);
+    }
+    if (prev_hip >= 0) (void)hipSetDevice(prev_hip);
+  }
+  static IcicleDevice hip_device(int id)
+  {
+    IcicleDevice d;
+    memset(&d, 0, sizeof d);
+    strcpy(d.type, "HIP");
+    d.id = id;
+    return d;
   }
 };
 

@@ -6,9 +6,10 @@
 //                                (−A, B), (cpub, γ₂), (C, δ₂) with γ₂ / δ₂'s lines precomputed once per call on the host, the
 //                                final exponentiation, and a comparison with conj(e(α₁, β₂)) (also computed once per call)
 //
-// The JSON texts are parsed on the host (pairing.cpp: the same checks and codes as groth16_verify_json) by up to 16 pooled
-// workers; items that fail there keep their negative code and never reach the device.  The rest go to the device in chunks of
-// at most CHUNK proofs, so device memory stays bounded whatever n is.
+// The JSON texts are parsed on the host (pairing.cpp: vb::parse_vk / parse_item, the checks groth16_verify_json runs too) by up
+// to 16 pooled workers; items that fail there keep their negative code and never reach the device.  The rest go to the device in
+// chunks of at most CHUNK proofs, so device memory stays bounded whatever n is.  The per-key preparation is verify_host.h's
+// PreparedKey; the device, the stream and the buffers of a call are verify_batch.h's DeviceSession.
 #include <chrono>
 #include <stdlib.h>
 #include <string.h>
@@ -32,13 +33,12 @@ __global__ __launch_bounds__(WG) void pairing_batch_kernel(const fe* __restrict_
 {
   const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
   if (i >= n) return;
-  const fe* P = p + 2 * i;
-  const fe2* Q = q + 2 * i;
-  const fe px = P[0], py = P[1];
-  const fe2 qx = Q[0], qy = Q[1];
-  const bool pz = p29::std_is_zero(px) && p29::std_is_zero(py);
-  const bool qz = p29::std_is_zero(qx.c0) && p29::std_is_zero(qx.c1) && p29::std_is_zero(qy.c0) && p29::std_is_zero(qy.c1);
-  const p29::F12 e = (pz || qz) ? p29::f12_one() : p29::pairing(f29::from_std(px), f29::from_std(py), Fq2_29::load_std(qx), Fq2_29::load_std(qy));
+  const fe* pi = p + 2 * i;
+  const fe2* qi = q + 2 * i;
+  const fe P[2] = {pi[0], pi[1]};
+  const fe2 Q[2] = {qi[0], qi[1]};
+  const bool pz = p29::g1_std_is_zero(P), qz = p29::g2_std_is_zero(Q);
+  const p29::F12 e = (pz || qz) ? p29::f12_one() : p29::pairing(f29::from_std(P[0]), f29::from_std(P[1]), Fq2_29::load_std(Q[0]), Fq2_29::load_std(Q[1]));
   p29::f12_store_std(e, out + 12 * i);
 }
 
@@ -117,24 +117,19 @@ int parse_stage(const char* const* proof_jsons, const char* const* public_jsons,
   if (int rc = parse_vk(vk_json, &key)) return rc;
   const size_t np = key.n_public;
 
-  // items on the pool (≤ 16 tasks of contiguous ranges), the caller's per-key work on this thread meanwhile
+  // items on the pool (≤ 16 contiguous ranges), the caller's per-key work on this thread meanwhile
   std::vector<VbItem>& items = out->items;
   std::vector<fe>& pub = out->pub;
   items.resize(n);
   pub.resize((size_t)n * np + 1);
-  const int tasks = std::max(1, std::min(16, n / 64));
-  std::vector<isnark::HostTask> ht(tasks);
-  for (int t = 0; t < tasks; t++) {
-    const int lo = (int)((int64_t)n * t / tasks), hi = (int)((int64_t)n * (t + 1) / tasks);
-    ht[t].fn = [&, lo, hi] {
-      for (int i = lo; i < hi; i++) verdicts[i] = parse_item(proof_jsons[i], public_jsons[i], np, &items[i], pub.data() + (size_t)i * np);
-    };
-    if (t > 0) isnark::WorkerPool::get().run_or_inline(&ht[t]);
-  }
-  if (meanwhile) meanwhile(key);
-  ht[0].fn();
-  for (int t = 1; t < tasks; t++)
-    if (ht[t].queued) isnark::WorkerPool::wait(&ht[t]);
+  isnark::run_ranges(
+    (size_t)n, 64,
+    [&](int, size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; i++) verdicts[i] = parse_item(proof_jsons[i], public_jsons[i], np, &items[i], pub.data() + i * np, false);
+    },
+    [&] {
+      if (meanwhile) meanwhile(key);
+    });
   out->live.clear();
   out->live.reserve(n);
   for (int i = 0; i < n; i++)
@@ -143,49 +138,20 @@ int parse_stage(const char* const* proof_jsons, const char* const* public_jsons,
   return 0;
 }
 
-void make_device_key(const VbKey& key, DeviceKey* dk)
-{
-  const size_t np = key.n_public;
-  dk->vk.resize(1);
-  p29::make_verify_key(key.alpha, key.beta, key.gamma, key.delta, (int)np, dk->vk.data());
-  dk->ic.resize(np + 1);
-  dk->icz.resize(np + 1);
-  for (size_t j = 0; j <= np; j++) {
-    dk->icz[j] = p29::std_is_zero(key.ic[2 * j]) && p29::std_is_zero(key.ic[2 * j + 1]);
-    dk->ic[j] = {f29::from_std(key.ic[2 * j]), f29::from_std(key.ic[2 * j + 1])};
-  }
-}
-
-int per_item_stage(const Parsed& pz, const DeviceKey& dk, int dev, int32_t* verdicts)
+int per_item_stage(const Parsed& pz, PreparedKey& pk, int dev, int32_t* verdicts)
 {
   const std::vector<int>& live = pz.live;
   const std::vector<VbItem>& items = pz.items;
   const std::vector<fe>& pub = pz.pub;
-  const std::vector<p29::VerifyKey29>& vkh = dk.vk;
-  const std::vector<G1L::A>& ic = dk.ic;
-  const std::vector<uint8_t>& icz = dk.icz;
   const size_t np = pz.key.n_public;
   if (live.empty()) return 0;
-  // device part
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  struct Restore {
-    int d;
-    ~Restore()
-    {
-      if (d >= 0) (void)hipSetDevice(d);
-    }
-  } restore{prev};
-  hipError_t e = hipSetDevice(dev);
-  if (e != hipSuccess) return device_fail(ICICLE_INVALID_DEVICE, "hipSetDevice", e);
-  hipStream_t st = nullptr;
-  if ((e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "hipStreamCreate", e);
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamDestroy(s); }
-  } sg{st};
+  pk.need_target();
+  DeviceSession ds;
+  if (int rc = ds.open(dev, 1)) return rc;
+  const hipStream_t st = ds.stream(0);
+  hipError_t e;
   const uint32_t cap = (uint32_t)std::min<size_t>(CHUNK, live.size());
-  DevBuf db;
+  DevBuf& db = ds.buf;
   p29::VerifyKey29* d_vk = db.alloc<p29::VerifyKey29>(1);
   G1L::A* d_ic = db.alloc<G1L::A>(np + 1);
   uint8_t* d_icz = db.alloc<uint8_t>(np + 1);
@@ -205,9 +171,9 @@ int per_item_stage(const Parsed& pz, const DeviceKey& dk, int dev, int32_t* verd
     }
   } eg{ev0, ev1};
   (void)hipEventRecord(ev0, st);
-  if ((e = hipMemcpyAsync(d_vk, vkh.data(), sizeof(p29::VerifyKey29), hipMemcpyHostToDevice, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_ic, ic.data(), (np + 1) * sizeof(G1L::A), hipMemcpyHostToDevice, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(d_icz, icz.data(), np + 1, hipMemcpyHostToDevice, st)) != hipSuccess)
+  if ((e = hipMemcpyAsync(d_vk, pk.vk.data(), sizeof(p29::VerifyKey29), hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_ic, pk.ic(), (np + 1) * sizeof(G1L::A), hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_icz, pk.ic_zero(), np + 1, hipMemcpyHostToDevice, st)) != hipSuccess)
     return device_fail(ICICLE_COPY_FAILED, "upload", e);
   std::vector<VbItem> hitems(cap);
   std::vector<fe> hpub((size_t)cap * np + 1);
@@ -249,7 +215,11 @@ ISNARK_API int groth16_verify_batch(const char* const* proof_jsons, const char* 
   const int rc0 = batch_prologue(proof_jsons, public_jsons, n, vk_json, device, verdicts, &dev, &done);
   if (done) return rc0;
   Parsed pz;
-  DeviceKey dk;
-  if (int rc = parse_stage(proof_jsons, public_jsons, n, vk_json, verdicts, &pz, [&dk](const VbKey& key) { make_device_key(key, &dk); })) return rc;
-  return per_item_stage(pz, dk, dev, verdicts);
+  PreparedKey pk;
+  const auto key_part = [&pk](const VbKey& key) {
+    pk.prepare(key);
+    pk.need_target();
+  };
+  if (int rc = parse_stage(proof_jsons, public_jsons, n, vk_json, verdicts, &pz, key_part)) return rc;
+  return per_item_stage(pz, pk, dev, verdicts);
 }

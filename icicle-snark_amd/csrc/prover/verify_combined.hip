@@ -9,6 +9,10 @@
 //                                    the worker pool, and the three fixed-G2 pairs and the final exponentiation are paid once, on
 //                                    the host.  Any subgroup failure or a failed equation sends the live items through the
 //                                    per-item stage of groth16_verify_batch (verify_batch.hip), so the verdicts are its verdicts.
+//
+// The attempt is combined_stage: named stages over one CombinedCtx.  The arithmetic of the sums and the per-key preparation are
+// verify_host.h's (CombinedSums, PreparedKey — prepared once, and handed on to the fallback), the device, the two streams and the
+// buffers are verify_batch.h's DeviceSession.
 #include <chrono>
 #include <errno.h>
 #include <stdio.h>
@@ -51,12 +55,11 @@ __global__ __launch_bounds__(WG) void miller_strided_kernel(const fe* __restrict
   if (i >= lanes) return;
   p29::F12 acc = p29::f12_one();
   for (uint64_t k = i; k < n; k += lanes) {
-    const fe px = p[2 * k], py = p[2 * k + 1];
-    const fe2 qx = q[2 * k], qy = q[2 * k + 1];
-    const bool pz = p29::std_is_zero(px) && p29::std_is_zero(py);
-    const bool qz = p29::std_is_zero(qx.c0) && p29::std_is_zero(qx.c1) && p29::std_is_zero(qy.c0) && p29::std_is_zero(qy.c1);
+    const fe P[2] = {p[2 * k], p[2 * k + 1]};
+    const fe2 Q[2] = {q[2 * k], q[2 * k + 1]};
+    const bool pz = p29::g1_std_is_zero(P), qz = p29::g2_std_is_zero(Q);
     if (pz || qz) continue;
-    acc = p29::f12_mul(acc, p29::miller_single(f29::from_std(px), f29::from_std(py), Fq2_29::load_std(qx), Fq2_29::load_std(qy)));
+    acc = p29::f12_mul(acc, p29::miller_single(f29::from_std(P[0]), f29::from_std(P[1]), Fq2_29::load_std(Q[0]), Fq2_29::load_std(Q[1])));
   }
   f[i] = acc;
 }
@@ -108,165 +111,159 @@ bool os_random(uint8_t* out, size_t n)
   return rd == n;
 }
 
-// The combined attempt over the live items.  0 with *accepted set, or the call's error code.
-int combined_stage(const isnark::vb::Parsed& pz, int dev, const uint8_t seed[32], bool* accepted)
-{
-  using namespace isnark::vb;
-  *accepted = false;
-  const std::vector<int>& live = pz.live;
-  const VbKey& key = pz.key;
-  const size_t np = key.n_public, nl = live.size();
-
-  // coefficients and signal sums on the pool: zₖ for live item k from its index in the caller's arrays, u₀ = Σ z, u_{j+1} = Σ z·sⱼ
-  std::vector<uint32_t> z(4 * nl);
-  const int tasks = (int)std::max<size_t>(1, std::min<size_t>(16, nl / 256));
-  std::vector<std::vector<fe>> part(tasks, std::vector<fe>(np + 1, Fr::zero()));
-  std::vector<isnark::HostTask> ht(tasks);
-  for (int t = 0; t < tasks; t++) {
-    const size_t lo = nl * t / tasks, hi = nl * (t + 1) / tasks;
-    ht[t].fn = [&, t, lo, hi] {
-      std::vector<fe>& u = part[t];
-      for (size_t k = lo; k < hi; k++) {
-        uint8_t c[16];
-        isnark::combined_coefficient(seed, (uint64_t)live[k], c);
-        fe zf = Fr::zero();
-        for (int w = 0; w < 4; w++) zf.l[w] = z[4 * k + w] = (uint32_t)c[4 * w] | (uint32_t)c[4 * w + 1] << 8 | (uint32_t)c[4 * w + 2] << 16 | (uint32_t)c[4 * w + 3] << 24;
-        u[0] = Fr::add(u[0], zf);
-        const fe zm = Fr::to_mont(zf); // (z·R)·s·R⁻¹ = z·s
-        const fe* s = pz.pub.data() + (size_t)live[k] * np;
-        for (size_t j = 0; j < np; j++) u[j + 1] = Fr::add(u[j + 1], Fr::mul(zm, s[j]));
-      }
-    };
-    if (t > 0) isnark::WorkerPool::get().run_or_inline(&ht[t]);
-  }
-  // the key's part on this thread meanwhile: γ₂ / δ₂ lines, IC shifted behind an identity entry (p29::combined_accept)
-  const auto g2_zero = [](const fe2* q) { return p29::std_is_zero(q[0].c0) && p29::std_is_zero(q[0].c1) && p29::std_is_zero(q[1].c0) && p29::std_is_zero(q[1].c1); };
-  std::vector<p29::Line> gl, dl;
-  if (!g2_zero(key.gamma)) {
-    gl.resize(p29::N_LINES);
-    p29::precompute_lines(Fq2_29::load_std(key.gamma[0]), Fq2_29::load_std(key.gamma[1]), gl.data());
-  }
-  if (!g2_zero(key.delta)) {
-    dl.resize(p29::N_LINES);
-    p29::precompute_lines(Fq2_29::load_std(key.delta[0]), Fq2_29::load_std(key.delta[1]), dl.data());
-  }
-  std::vector<G1L::A> ic1(np + 2);
-  std::vector<uint8_t> ic1z(np + 2);
-  ic1[0] = {f29::one_m(), f29::one_m()};
-  ic1z[0] = 1;
-  for (size_t j = 0; j <= np; j++) {
-    ic1z[j + 1] = p29::std_is_zero(key.ic[2 * j]) && p29::std_is_zero(key.ic[2 * j + 1]);
-    ic1[j + 1] = {f29::from_std(key.ic[2 * j]), f29::from_std(key.ic[2 * j + 1])};
-  }
-  ht[0].fn();
-  for (int t = 1; t < tasks; t++)
-    if (ht[t].queued) isnark::WorkerPool::wait(&ht[t]);
-  std::vector<fe> u(np + 1, Fr::zero());
-  for (int t = 0; t < tasks; t++)
-    for (size_t j = 0; j <= np; j++) u[j] = Fr::add(u[j], part[t][j]);
-
-  // device part: the library's device and two pooled streams of its own (the MSM's workspace follows its stream's life): the
-  // lanes on one, the MSM on the other — 4096 lanes are 64 waves on 1024 SIMDs, so the two can run side by side.  (Today they do
-  // not: the downloads below go into pageable memory and hold this thread until the lanes are done — DESIGN §7a.)
-  IcicleDevice want;
-  memset(&want, 0, sizeof want);
-  strcpy(want.type, "HIP");
-  want.id = dev;
-  const int prev = isnark::default_device_or_none();
-  struct Restore {
-    int d;
-    ~Restore()
-    {
-      if (d < 0) return;
-      IcicleDevice b;
-      memset(&b, 0, sizeof b);
-      strcpy(b.type, "HIP");
-      b.id = d;
-      (void)icicle_set_device(&b);
-    }
-  } restore{prev};
-  if (icicle_set_device(&want) != ICICLE_SUCCESS) return fail((int)ICICLE_INVALID_DEVICE, "device: hipSetDevice: invalid device ordinal");
-  icicleStreamHandle sh = nullptr;
-  if (icicle_create_stream(&sh) != ICICLE_SUCCESS) return fail((int)ICICLE_UNKNOWN_ERROR, "device: stream creation failed");
-  struct StreamGuard {
-    icicleStreamHandle s;
-    ~StreamGuard() { (void)icicle_destroy_stream(s); }
-  } sg{sh};
-  hipStream_t st = (hipStream_t)sh;
-  icicleStreamHandle sh2 = nullptr;
-  if (icicle_create_stream(&sh2) != ICICLE_SUCCESS) return fail((int)ICICLE_UNKNOWN_ERROR, "device: stream creation failed");
-  StreamGuard sg2{sh2};
-  const uint32_t cap = (uint32_t)std::min<size_t>(CHUNK, nl);
-  DevBuf db;
-  VbItem* d_items = db.alloc<VbItem>(cap);
-  uint32_t* d_z = db.alloc<uint32_t>(4 * (size_t)cap);
-  p29::F12* d_f = db.alloc<p29::F12>(cap);
-  uint8_t* d_ok = db.alloc<uint8_t>(cap);
-  if (!d_items || !d_z || !d_f || !d_ok) return device_fail(ICICLE_ALLOCATION_FAILED, "hipMalloc", hipErrorOutOfMemory);
-  std::vector<VbItem> hitems(cap);
-  std::vector<uint8_t> hok(cap);
-  std::vector<bn254_scalar_t> msm_s(cap);
-  std::vector<bn254_affine_t> msm_b(cap);
+// What the stages of one combined attempt share.  Lives on combined_stage's stack and outlives the pooled tasks of host_sums,
+// which are waited for there.
+struct CombinedCtx {
+  const isnark::vb::Parsed& pz;
+  isnark::vb::PreparedKey& pk;
+  const uint8_t* const seed;
+  const size_t np, nl; // public signals of the key, live items
+  const uint32_t cap;  // live items per chunk
+  // host_sums
+  std::vector<uint32_t> z; // zₖ of live item k, four words
+  std::vector<fe> u;       // u₀ = Σ z, u_{j+1} = Σ z·sⱼ
+  // open_device: the lanes on stream 0, the MSM on stream 1 — 4096 lanes are 64 waves on 1024 SIMDs, so the two can run side by
+  // side.  (Today they do not: the downloads of enqueue_lanes go into pageable memory and hold this thread until the lanes are
+  // done — DESIGN §7a.)
+  isnark::vb::DeviceSession ds;
+  isnark::vb::VbItem* d_items = nullptr;
+  uint32_t* d_z = nullptr;
+  p29::F12* d_f = nullptr;
+  uint8_t* d_ok = nullptr;
+  std::vector<isnark::vb::VbItem> hitems;
+  std::vector<uint8_t> hok;
+  std::vector<bn254_scalar_t> msm_s;
+  std::vector<bn254_affine_t> msm_b;
+  MSMConfig mc;
+  // what the chunks leave
   p29::F12 prod = p29::f12_one(), part_prod, tail = p29::f12_one();
   bn254_projective_t sum_c;
   bool have_c = false;
-  MSMConfig mc;
-  memset(&mc, 0, sizeof mc);
-  mc.stream = sh2;
-  mc.precompute_factor = 1;
-  mc.bitsize = 128;
-  mc.batch_size = 1;
-  hipError_t e;
-  for (size_t base = 0; base < nl; base += cap) {
-    const uint32_t m = (uint32_t)std::min<size_t>(cap, nl - base);
-    for (uint32_t k = 0; k < m; k++) hitems[k] = pz.items[live[base + k]];
-    if ((e = hipMemcpyAsync(d_items, hitems.data(), m * sizeof(VbItem), hipMemcpyHostToDevice, st)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_z, z.data() + 4 * base, (size_t)m * 16, hipMemcpyHostToDevice, st)) != hipSuccess)
-      return device_fail(ICICLE_COPY_FAILED, "upload", e);
-    hipLaunchKernelGGL(combined_lane_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, st, d_items, d_z, m, d_f, d_ok);
-    if ((e = hipGetLastError()) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "combined_lane_kernel launch", e);
-    if ((e = reduce_product(d_f, m, st)) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "f12_product_pass_kernel launch", e);
-    if ((e = hipMemcpyAsync(hok.data(), d_ok, m, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (e = hipMemcpyAsync(&part_prod, d_f, sizeof(p29::F12), hipMemcpyDeviceToHost, st)) != hipSuccess)
-      return device_fail(ICICLE_COPY_FAILED, "download", e);
-    // Σ zₖ·Cₖ of the chunk: the library's G1 MSM over 128-bit scalars.  An identity C takes part as 0·G₁.
-    for (uint32_t k = 0; k < m; k++) {
-      const VbItem& it = hitems[k];
-      const bool c_zero = p29::std_is_zero(it.c[0]) && p29::std_is_zero(it.c[1]);
-      memset(&msm_s[k], 0, sizeof msm_s[k]);
-      if (!c_zero) memcpy(&msm_s[k], z.data() + 4 * (base + k), 16);
-      memcpy(&msm_b[k].x, &it.c[0], 32);
-      memcpy(&msm_b[k].y, &it.c[1], 32);
-      if (c_zero) {
-        msm_b[k].x.limbs[0] = 1;
-        msm_b[k].y.limbs[0] = 2;
-      }
-    }
-    bn254_projective_t chunk_c;
-    if (eIcicleError me = bn254_msm(msm_s.data(), msm_b.data(), (int)m, &mc, &chunk_c)) {
-      char msg[300];
-      snprintf(msg, sizeof msg, "device: msm: %s", icicle_snark_last_error());
-      return fail((int)me, msg);
-    }
-    if (have_c) bn254_ecadd(&sum_c, &chunk_c, &sum_c);
-    else sum_c = chunk_c;
-    have_c = true;
-    if (base + m == nl) {
-      // the Miller loop of the three fixed-G2 pairs needs the sums only, not the lanes' product
-      bn254_affine_t sc_aff;
-      bn254_to_affine(&sum_c, &sc_aff);
-      fe sc[2];
-      memcpy(&sc[0], &sc_aff.x, 32);
-      memcpy(&sc[1], &sc_aff.y, 32);
-      tail = p29::combined_tail_miller(key.alpha, key.beta, gl.empty() ? nullptr : gl.data(), dl.empty() ? nullptr : dl.data(), ic1.data(), ic1z.data(),
-                                       (int)np, u.data(), sc);
-    }
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return device_fail(ICICLE_SYNCHRONIZATION_FAILED, "combined_lane_kernel", e);
-    for (uint32_t k = 0; k < m; k++)
-      if (!hok[k]) return 0; // a pi_b outside the subgroup: the per-item stage names it
-    prod = p29::f12_mul(prod, part_prod);
+
+  CombinedCtx(const isnark::vb::Parsed& parsed, isnark::vb::PreparedKey& key, const uint8_t* seed32)
+      : pz(parsed), pk(key), seed(seed32), np(parsed.key.n_public), nl(parsed.live.size()), cap((uint32_t)std::min<size_t>(CHUNK, parsed.live.size()))
+  {
   }
-  *accepted = p29::combined_finish(prod, tail);
+};
+
+// coefficients and signal sums on the pool (zₖ for live item k from its index in the caller's arrays), the key's part — γ₂ / δ₂
+// lines, IC in lazy form — on this thread meanwhile
+void host_sums(CombinedCtx& c)
+{
+  using isnark::vb::CombinedSums;
+  c.z.resize(4 * c.nl);
+  std::vector<CombinedSums> part(isnark::ranges_of(c.nl, 256), CombinedSums(c.np));
+  isnark::run_ranges(
+    c.nl, 256,
+    [&](int t, size_t lo, size_t hi) {
+      for (size_t k = lo; k < hi; k++) part[t].add_item(c.seed, (uint64_t)c.pz.live[k], c.pz.pub.data() + (size_t)c.pz.live[k] * c.np, &c.z[4 * k]);
+    },
+    [&] { c.pk.prepare(c.pz.key); });
+  CombinedSums all(c.np);
+  for (const CombinedSums& p : part) all.add(p);
+  c.u = all.u;
+}
+
+int open_device(CombinedCtx& c, int dev)
+{
+  if (int rc = c.ds.open(dev, 2)) return rc;
+  isnark::vb::DevBuf& db = c.ds.buf;
+  c.d_items = db.alloc<isnark::vb::VbItem>(c.cap);
+  c.d_z = db.alloc<uint32_t>(4 * (size_t)c.cap);
+  c.d_f = db.alloc<p29::F12>(c.cap);
+  c.d_ok = db.alloc<uint8_t>(c.cap);
+  if (!c.d_items || !c.d_z || !c.d_f || !c.d_ok) return isnark::vb::device_fail(ICICLE_ALLOCATION_FAILED, "hipMalloc", hipErrorOutOfMemory);
+  c.hitems.resize(c.cap);
+  c.hok.resize(c.cap);
+  c.msm_s.resize(c.cap);
+  c.msm_b.resize(c.cap);
+  memset(&c.mc, 0, sizeof c.mc);
+  c.mc.stream = c.ds.streams[1];
+  c.mc.precompute_factor = 1;
+  c.mc.bitsize = 128;
+  c.mc.batch_size = 1;
+  return 0;
+}
+
+// the chunk's m live items from `base`: upload, lanes, product reduction, and the downloads of the subgroup flags and the product
+int enqueue_lanes(CombinedCtx& c, size_t base, uint32_t m)
+{
+  using isnark::vb::device_fail;
+  using isnark::vb::VbItem;
+  const hipStream_t st = c.ds.stream(0);
+  hipError_t e;
+  for (uint32_t k = 0; k < m; k++) c.hitems[k] = c.pz.items[c.pz.live[base + k]];
+  if ((e = hipMemcpyAsync(c.d_items, c.hitems.data(), m * sizeof(VbItem), hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(c.d_z, c.z.data() + 4 * base, (size_t)m * 16, hipMemcpyHostToDevice, st)) != hipSuccess)
+    return device_fail(ICICLE_COPY_FAILED, "upload", e);
+  hipLaunchKernelGGL(combined_lane_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, st, c.d_items, c.d_z, m, c.d_f, c.d_ok);
+  if ((e = hipGetLastError()) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "combined_lane_kernel launch", e);
+  if ((e = reduce_product(c.d_f, m, st)) != hipSuccess) return device_fail(ICICLE_UNKNOWN_ERROR, "f12_product_pass_kernel launch", e);
+  if ((e = hipMemcpyAsync(c.hok.data(), c.d_ok, m, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(&c.part_prod, c.d_f, sizeof(p29::F12), hipMemcpyDeviceToHost, st)) != hipSuccess)
+    return device_fail(ICICLE_COPY_FAILED, "download", e);
+  return 0;
+}
+
+// Σ zₖ·Cₖ of the chunk, added to sum_c: the library's G1 MSM over 128-bit scalars.  An identity C takes part as 0·G₁.
+int chunk_msm(CombinedCtx& c, size_t base, uint32_t m)
+{
+  for (uint32_t k = 0; k < m; k++) {
+    const isnark::vb::VbItem& it = c.hitems[k];
+    const bool c_zero = p29::g1_std_is_zero(it.c);
+    memset(&c.msm_s[k], 0, sizeof c.msm_s[k]);
+    if (!c_zero) memcpy(&c.msm_s[k], c.z.data() + 4 * (base + k), 16);
+    memcpy(&c.msm_b[k].x, &it.c[0], 32);
+    memcpy(&c.msm_b[k].y, &it.c[1], 32);
+    if (c_zero) {
+      c.msm_b[k].x.limbs[0] = 1;
+      c.msm_b[k].y.limbs[0] = 2;
+    }
+  }
+  bn254_projective_t chunk_c;
+  if (eIcicleError me = bn254_msm(c.msm_s.data(), c.msm_b.data(), (int)m, &c.mc, &chunk_c)) {
+    char msg[300];
+    snprintf(msg, sizeof msg, "device: msm: %s", icicle_snark_last_error());
+    return isnark::vb::fail((int)me, msg);
+  }
+  if (c.have_c) bn254_ecadd(&c.sum_c, &chunk_c, &c.sum_c);
+  else c.sum_c = chunk_c;
+  c.have_c = true;
+  return 0;
+}
+
+// the Miller loop of the three fixed-G2 pairs: needs the sums only, not the lanes' product
+void tail_miller(CombinedCtx& c)
+{
+  bn254_affine_t sc_aff;
+  bn254_to_affine(&c.sum_c, &sc_aff);
+  fe sc[2];
+  memcpy(&sc[0], &sc_aff.x, 32);
+  memcpy(&sc[1], &sc_aff.y, 32);
+  const isnark::vb::VbKey& key = c.pz.key;
+  c.tail = p29::combined_tail_miller(key.alpha, key.beta, c.pk.gamma_lines(), c.pk.delta_lines(), c.pk.ic1.data(), c.pk.ic1_zero.data(), (int)c.np,
+                                     c.u.data(), sc);
+}
+
+// The combined attempt over the live items, pk left prepared for the fallback.  0 with *accepted set, or the call's error code.
+int combined_stage(const isnark::vb::Parsed& pz, isnark::vb::PreparedKey& pk, int dev, const uint8_t seed[32], bool* accepted)
+{
+  *accepted = false;
+  CombinedCtx c(pz, pk, seed);
+  host_sums(c);
+  if (int rc = open_device(c, dev)) return rc;
+  for (size_t base = 0; base < c.nl; base += c.cap) {
+    const uint32_t m = (uint32_t)std::min<size_t>(c.cap, c.nl - base);
+    if (int rc = enqueue_lanes(c, base, m)) return rc;
+    if (int rc = chunk_msm(c, base, m)) return rc;
+    if (base + m == c.nl) tail_miller(c);
+    const hipError_t e = hipStreamSynchronize(c.ds.stream(0));
+    if (e != hipSuccess) return isnark::vb::device_fail(ICICLE_SYNCHRONIZATION_FAILED, "combined_lane_kernel", e);
+    for (uint32_t k = 0; k < m; k++)
+      if (!c.hok[k]) return 0; // a pi_b outside the subgroup: the per-item stage names it
+    c.prod = p29::f12_mul(c.prod, c.part_prod);
+  }
+  *accepted = p29::combined_finish(c.prod, c.tail);
   return 0;
 }
 
@@ -317,7 +314,8 @@ ISNARK_API int groth16_verify_batch_combined(const char* const* proof_jsons, con
   }
   const auto t0 = std::chrono::steady_clock::now();
   bool accepted = false;
-  const int rc = combined_stage(pz, dev, seed, &accepted);
+  PreparedKey pk;
+  const int rc = combined_stage(pz, pk, dev, seed, &accepted);
   double parse_ms = 0;
   groth16_verify_batch_last_timings(&parse_ms, nullptr);
   set_last_timings(parse_ms, ms_since(t0));
@@ -327,7 +325,5 @@ ISNARK_API int groth16_verify_batch_combined(const char* const* proof_jsons, con
     if (path) *path = 1;
     return 0;
   }
-  DeviceKey dk;
-  make_device_key(pz.key, &dk);
-  return per_item_stage(pz, dk, dev, verdicts);
+  return per_item_stage(pz, pk, dev, verdicts);
 }

@@ -1,0 +1,101 @@
+// verify_host.h — the host-only pieces of the Groth16 verifiers: what the parser leaves (VbKey, VbItem), the per-key
+// preparation every device stage and the combined tail read (PreparedKey), and the combined verifier's host sums (CombinedSums).
+// No HIP types: the product's .hip files and the F29_CHECK host builds (tests/pairing29_check.cpp,
+// tests/pairing29_combined_check.cpp) compile the same code, so a bound broken here fires in the checked build.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+
+#include "../pairing29.h"
+#include "sha256.h"
+
+namespace isnark {
+namespace vb {
+
+struct VbKey {                   // standard form, canonical; (0, 0) = identity
+  bn254::fe alpha[2];
+  bn254::fe2 beta[2], gamma[2], delta[2];
+  std::vector<bn254::fe> ic;     // (n_public + 1) affine points, x then y
+  size_t n_public = 0;
+};
+struct VbItem {                  // one proof's points, standard form, canonical, on their curves
+  bn254::fe a[2];
+  bn254::fe2 b[2];
+  bn254::fe c[2];
+};
+
+// The input checks of all three verifier entry points (pairing.cpp).  0, or the code for the text (−2 format, −3 null) with the
+// message in groth16_verify_last_error() of the calling thread.  parse_item runs the order-r test of pi_b only when
+// `host_subgroup_test` is set: the batch stages leave it to their kernels.
+int parse_vk(const char* vk_json, VbKey* out);
+int parse_item(const char* proof_json, const char* public_json, size_t n_public, VbItem* item, bn254::fe* pub, bool host_subgroup_test);
+int fail(int code, const char* msg);
+
+// What one verification key contributes to every proof, made once per call.
+//   vk      as verify_batch_kernel reads it: γ₂ / δ₂'s lines (use_gamma / use_delta = 0 for an identity point, whose pairings are 1)
+//           and the target conj(e(α₁, β₂)).  The target costs a pairing and only the per-item stage compares with it, so it is
+//           left out until need_target().
+//   ic1     the IC points in lazy form behind one identity slot, ic1_zero their identity flags: the combined tail's Straus sum
+//           Σⱼ uⱼ·ICⱼ reads n_public + 2 entries from slot 0 (p29::combined_tail_miller), the per-item stage n_public + 1 from slot 1.
+struct PreparedKey {
+  std::vector<bn254::p29::VerifyKey29> vk; // one entry (≈ 40 KB: not on the stack)
+  std::vector<bn254::G1L::A> ic1;
+  std::vector<uint8_t> ic1_zero;
+  const VbKey* key = nullptr;
+  bool have_target = false;
+
+  void prepare(const VbKey& k)
+  {
+    using namespace bn254;
+    key = &k;
+    have_target = false;
+    vk.resize(1);
+    p29::make_verify_lines(k.gamma, k.delta, (int)k.n_public, &vk[0]);
+    ic1.resize(k.n_public + 2);
+    ic1_zero.resize(k.n_public + 2);
+    ic1[0] = {f29::one_m(), f29::one_m()};
+    ic1_zero[0] = 1;
+    for (size_t j = 0; j <= k.n_public; j++) {
+      ic1_zero[j + 1] = p29::g1_std_is_zero(&k.ic[2 * j]);
+      ic1[j + 1] = {f29::from_std(k.ic[2 * j]), f29::from_std(k.ic[2 * j + 1])};
+    }
+  }
+  void need_target()
+  {
+    using namespace bn254;
+    if (have_target) return;
+    p29::make_verify_target(key->alpha, key->beta, &vk[0]);
+    have_target = true;
+  }
+  const bn254::p29::Line* gamma_lines() const { return vk[0].use_gamma ? vk[0].gamma : nullptr; }
+  const bn254::p29::Line* delta_lines() const { return vk[0].use_delta ? vk[0].delta : nullptr; }
+  const bn254::G1L::A* ic() const { return ic1.data() + 1; } // n_public + 1 entries, as p29::verify_proof / public_input take them
+  const uint8_t* ic_zero() const { return ic1_zero.data() + 1; }
+};
+
+// The combined verifier's host arithmetic over a set of items: u₀ = Σ z, u_{j+1} = Σ z·sⱼ mod r (standard form)
+struct CombinedSums {
+  std::vector<bn254::fe> u;
+  explicit CombinedSums(size_t n_public) : u(n_public + 1, bn254::Fr::zero()) {}
+  // the item at `index` of the caller's arrays, signals s[0 … n_public) in standard form: its coefficient z (sha256.h's rule) goes
+  // to z4 as four 32-bit words, little endian, and into the sums
+  void add_item(const uint8_t seed[32], uint64_t index, const bn254::fe* s, uint32_t z4[4])
+  {
+    using namespace bn254;
+    uint8_t c[16];
+    combined_coefficient(seed, index, c);
+    fe zf = Fr::zero();
+    for (int w = 0; w < 4; w++) zf.l[w] = z4[w] = (uint32_t)c[4 * w] | (uint32_t)c[4 * w + 1] << 8 | (uint32_t)c[4 * w + 2] << 16 | (uint32_t)c[4 * w + 3] << 24;
+    u[0] = Fr::add(u[0], zf);
+    const fe zm = Fr::to_mont(zf); // (z·R)·s·R⁻¹ = z·s
+    for (size_t j = 0; j + 1 < u.size(); j++) u[j + 1] = Fr::add(u[j + 1], Fr::mul(zm, s[j]));
+  }
+  void add(const CombinedSums& o)
+  {
+    for (size_t j = 0; j < u.size(); j++) u[j] = bn254::Fr::add(u[j], o.u[j]);
+  }
+};
+
+} // namespace vb
+} // namespace isnark

@@ -10,11 +10,13 @@
 // The pool is a leaked singleton with detached threads: idle workers sit in a futex wait and simply end with the process — no
 // static destructor has to join them while the HIP runtime is shutting down.
 #pragma once
+#include <algorithm>
 #include <condition_variable>
 #include <deque>
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <vector>
 
 namespace isnark {
 
@@ -97,5 +99,25 @@ private:
   std::deque<HostTask*> q_;
   int idle_ = 0, nthreads_ = 0;
 };
+
+// [0, n) cut into max(1, min(16, n / grain)) contiguous ranges: body(t, lo, hi) runs once per range t.  Ranges 1, 2, … go to the
+// pool, `meanwhile` (may be empty) and then range 0 run on the calling thread, which returns when every range has run.  Returns the
+// number of ranges, known before any of them starts: ranges_of(n, grain) sizes per-range storage.
+inline int ranges_of(size_t n, size_t grain) { return (int)std::max<size_t>(1, std::min<size_t>(16, n / grain)); }
+inline int run_ranges(size_t n, size_t grain, const std::function<void(int, size_t, size_t)>& body, const std::function<void()>& meanwhile = nullptr)
+{
+  const int tasks = ranges_of(n, grain);
+  std::vector<HostTask> ht(tasks);
+  for (int t = 1; t < tasks; t++) {
+    const size_t lo = n * t / tasks, hi = n * (t + 1) / tasks;
+    ht[t].fn = [&body, t, lo, hi] { body(t, lo, hi); };
+    WorkerPool::get().run_or_inline(&ht[t]);
+  }
+  if (meanwhile) meanwhile();
+  body(0, 0, n / tasks);
+  for (int t = 1; t < tasks; t++)
+    if (ht[t].queued) WorkerPool::wait(&ht[t]);
+  return tasks;
+}
 
 } // namespace isnark

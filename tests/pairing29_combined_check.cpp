@@ -1,13 +1,13 @@
 // pairing29_combined_check.cpp — host-side checked build of what the combined batch verifier adds to csrc/pairing29.h.
 // Test infrastructure: compiled with g++ -DF29_CHECK by tests/test_pairing29_combined.py while every bound of ff29.h / ec29.h /
-// pairing29.h is asserted.  p29c_last_failure() names the first violated bound ("" when none fired).
+// pairing29.h is asserted.  The key preparation and the sums are the product's own (prover/verify_host.h: PreparedKey, CombinedSums).
+// p29c_last_failure() names the first violated bound ("" when none fired).
 #include <stdint.h>
 #include <string.h>
 
 #include <vector>
 
-#include "../icicle-snark_amd/csrc/pairing29.h"
-#include "../icicle-snark_amd/csrc/prover/sha256.h"
+#include "../icicle-snark_amd/csrc/prover/verify_host.h"
 
 using namespace bn254;
 
@@ -44,9 +44,7 @@ extern "C" void p29c_pairing_product(const fe* p, const fe2* q, int n, fe* out)
   for (int i = 0; i < n; i++) {
     const fe* P = p + 2 * i;
     const fe2* Q = q + 2 * i;
-    const bool pz = p29::std_is_zero(P[0]) && p29::std_is_zero(P[1]);
-    const bool qz = p29::std_is_zero(Q[0].c0) && p29::std_is_zero(Q[0].c1) && p29::std_is_zero(Q[1].c0) && p29::std_is_zero(Q[1].c1);
-    if (pz || qz) continue;
+    if (p29::g1_std_is_zero(P) || p29::g2_std_is_zero(Q)) continue;
     f = p29::f12_mul(f, p29::miller_single(f29::from_std(P[0]), f29::from_std(P[1]), Fq2_29::load_std(Q[0]), Fq2_29::load_std(Q[1])));
   }
   p29::f12_store_std(p29::final_exp(f), out);
@@ -66,42 +64,26 @@ extern "C" void p29c_sha256(const uint8_t* msg, uint64_t len, uint8_t* out) { is
 extern "C" int p29c_combined(const fe* alpha, const fe2* beta, const fe2* gamma, const fe2* delta, const fe* ic, int n_pub, int m, const fe* pub,
                              const fe* a, const fe2* b, const fe* c, const uint8_t* seed, const uint64_t* index)
 {
-  const auto g2_zero = [](const fe2* q) { return p29::std_is_zero(q[0].c0) && p29::std_is_zero(q[0].c1) && p29::std_is_zero(q[1].c0) && p29::std_is_zero(q[1].c1); };
-  std::vector<p29::Line> gl, dl;
-  if (!g2_zero(gamma)) {
-    gl.resize(p29::N_LINES);
-    p29::precompute_lines(Fq2_29::load_std(gamma[0]), Fq2_29::load_std(gamma[1]), gl.data());
-  }
-  if (!g2_zero(delta)) {
-    dl.resize(p29::N_LINES);
-    p29::precompute_lines(Fq2_29::load_std(delta[0]), Fq2_29::load_std(delta[1]), dl.data());
-  }
-  std::vector<G1L::A> ic1(n_pub + 2);
-  std::vector<uint8_t> ic1z(n_pub + 2);
-  ic1[0] = {f29::one_m(), f29::one_m()};
-  ic1z[0] = 1;
-  for (int j = 0; j <= n_pub; j++) {
-    ic1z[j + 1] = p29::std_is_zero(ic[2 * j]) && p29::std_is_zero(ic[2 * j + 1]);
-    ic1[j + 1] = {f29::from_std(ic[2 * j]), f29::from_std(ic[2 * j + 1])};
-  }
-  std::vector<fe> u(n_pub + 1, Fr::zero());
+  isnark::vb::VbKey key;
+  memcpy(key.alpha, alpha, sizeof key.alpha);
+  memcpy(key.beta, beta, sizeof key.beta);
+  memcpy(key.gamma, gamma, sizeof key.gamma);
+  memcpy(key.delta, delta, sizeof key.delta);
+  key.ic.assign(ic, ic + 2 * (n_pub + 1));
+  key.n_public = (size_t)n_pub;
+  isnark::vb::PreparedKey pk;
+  pk.prepare(key);
+  isnark::vb::CombinedSums sums((size_t)n_pub);
   p29::F12 prod = p29::f12_one();
   G1L::X sc = G1L::x_zero();
   for (int k = 0; k < m; k++) {
-    uint8_t cz[16];
-    isnark::combined_coefficient(seed, index[k], cz);
     uint32_t z[4];
-    fe zf = Fr::zero();
-    for (int w = 0; w < 4; w++) zf.l[w] = z[w] = (uint32_t)cz[4 * w] | (uint32_t)cz[4 * w + 1] << 8 | (uint32_t)cz[4 * w + 2] << 16 | (uint32_t)cz[4 * w + 3] << 24;
+    sums.add_item(seed, index[k], pub + (size_t)k * n_pub, z);
     p29::F12 f;
     if (!p29::combined_lane(a + 2 * k, b + 2 * k, z, f)) return -1;
     prod = p29::f12_mul(prod, f);
-    u[0] = Fr::add(u[0], zf);
-    const fe zm = Fr::to_mont(zf);
-    for (int j = 0; j < n_pub; j++) u[j + 1] = Fr::add(u[j + 1], Fr::mul(zm, pub[(size_t)k * n_pub + j]));
     const fe* C = c + 2 * k;
-    if (!(p29::std_is_zero(C[0]) && p29::std_is_zero(C[1])))
-      sc = G1L::x_add(sc, p29::g1_mul_bits({f29::from_std(C[0]), f29::from_std(C[1])}, z, 128));
+    if (!p29::g1_std_is_zero(C)) sc = G1L::x_add(sc, p29::g1_mul_bits({f29::from_std(C[0]), f29::from_std(C[1])}, z, 128));
   }
   fe scs[2] = {Fq::zero(), Fq::zero()};
   if (!G1L::x_is_zero(sc)) {
@@ -110,8 +92,7 @@ extern "C" int p29c_combined(const fe* alpha, const fe2* beta, const fe2* gamma,
     scs[0] = to_std(x);
     scs[1] = to_std(y);
   }
-  return p29::combined_accept(prod, alpha, beta, gl.empty() ? nullptr : gl.data(), dl.empty() ? nullptr : dl.data(), ic1.data(), ic1z.data(), n_pub,
-                              u.data(), scs)
+  return p29::combined_accept(prod, key.alpha, key.beta, pk.gamma_lines(), pk.delta_lines(), pk.ic1.data(), pk.ic1_zero.data(), n_pub, sums.u.data(), scs)
            ? 1
            : 0;
 }
