@@ -698,7 +698,9 @@ groth16_witness_ready groth16_cache_load_devices groth16_parse_device groth16_ca
 groth16_verify groth16_verify_json groth16_verify_last_error groth16_group_describe groth16_cache_tables_ready
 groth16_cache_manager_prewarm groth16_verify_batch groth16_verify_batch_last_timings
 groth16_verify_batch_combined groth16_verify_combined_coefficients
+groth16_zkey_check groth16_zkey_check_file
 """.split()
+# (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
 
 def parse_device(device: str, cap: int = 64):
@@ -849,6 +851,56 @@ def groth16_verify(proof: str, public: str, vk: str):
     if rc != 0:
         lib().groth16_verify_last_error.restype = C.c_char_p
         raise ProverError(f"groth16_verify: {lib().groth16_verify_last_error().decode()} (code {rc})")
+
+
+class ZkeyReport(C.Structure):
+    """Groth16ZkeyReport (include/groth16_prover.h): kind / section / index of the first fault, faults[s] per zkey section"""
+    _fields_ = [("kind", C.c_int32), ("section", C.c_int32), ("index", C.c_uint64), ("faults", C.c_uint64 * 10),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("pairing_ms", C.c_double)]
+
+
+class ZkeyCheckOptions(C.Structure):
+    _fields_ = [("slice_points", C.c_uint32), ("seed32", C.c_char_p)]
+
+
+ZKEY_NONCANONICAL, ZKEY_OFF_CURVE, ZKEY_OFF_SUBGROUP, ZKEY_IDENTITY, ZKEY_PAIR_MISMATCH, ZKEY_COEFFICIENT = range(1, 7)
+
+
+def _zkey_check(call, what, device, slice_points, seed):
+    if seed is not None and len(seed) != 32:
+        raise ValueError(f"{what}: the seed is 32 bytes")
+    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+    opt = ZkeyCheckOptions(int(slice_points), C.cast(sd, C.c_char_p) if sd is not None else None)
+    rep = ZkeyReport()
+    rc = call(device.encode(), C.byref(opt), C.byref(rep))
+    if rc not in (0, 1):
+        _pcheck(rc, what)
+    return rc == 1, rep
+
+
+def zkey_check(zkey: bytes, device: str = "HIP", slice_points: int = 0, seed=None):
+    """groth16_zkey_check: every point of the key on its curve (B2: in the subgroup), the coefficient records in range, the
+    header pairs and B1 against B2 consistent.  Returns (ok, ZkeyReport); raises ProverError for a malformed file or a device
+    error.  seed: 32 bytes for a reproducible test — leave it None otherwise (a secret, fresh seed is drawn)."""
+    p = zkey.ctypes.data_as(C.c_void_p) if isinstance(zkey, np.ndarray) else C.c_char_p(zkey) if isinstance(zkey, bytes) else (C.c_char * len(zkey)).from_buffer(zkey)
+    return _zkey_check(lambda d, o, r: lib().groth16_zkey_check(p, C.c_size_t(len(zkey)), d, o, r), "zkey_check", device, slice_points, seed)
+
+
+def zkey_check_file(path: str, device: str = "HIP", slice_points: int = 0, seed=None):
+    """groth16_zkey_check_file: zkey_check on a mapped file"""
+    return _zkey_check(lambda d, o, r: lib().groth16_zkey_check_file(os.fsencode(path), d, o, r), "zkey_check_file", device, slice_points, seed)
+
+
+def zkey_export_vk(zkey: bytes) -> str:
+    """groth16_zkey_export_vk: the key's verification_key.json text (host only: needs no GPU)"""
+    f = lib().groth16_zkey_export_vk
+    f.restype = C.c_int64
+    need = f(C.c_char_p(bytes(zkey)), C.c_size_t(len(zkey)), None, C.c_size_t(0))
+    if need < 0:
+        _pcheck(int(need), "zkey_export_vk")
+    buf = C.create_string_buffer(need)
+    f(C.c_char_p(bytes(zkey)), C.c_size_t(len(zkey)), buf, C.c_size_t(need))
+    return buf.value.decode()
 
 
 def sum_commitments(blocks: bytes, count: int) -> bytes:

@@ -26,10 +26,13 @@
 namespace bn254 { namespace f29 {
 inline const char* g_check_failure = nullptr;
 inline void check_fail(const char* what) { if (!g_check_failure) g_check_failure = what; }
+inline unsigned long g_check_products = 0; // multiplications and squarings run so far: a test can show that none ran on a value
 } }
 #define F29_ASSERT(cond, what) do { if (!(cond)) ::bn254::f29::check_fail(what); } while (0)
+#define F29_COUNT_PRODUCT() (void)++::bn254::f29::g_check_products
 #else
 #define F29_ASSERT(cond, what) (void)0
+#define F29_COUNT_PRODUCT() (void)0
 #endif
 
 namespace bn254 {
@@ -111,6 +114,7 @@ FF_HD fe9 mul_core(const fe9& a0, const fe9& b0, const fe9& a1, const fe9& b1, c
   F29_ACC_T acc = 0;
   uint32_t m[9];
   fe9 r;
+  F29_COUNT_PRODUCT();
 #pragma unroll
   for (int k = 0; k < 9; k++) {
 #pragma unroll
@@ -161,6 +165,7 @@ FF_HD fe9 sqr(const fe9& a)
   F29_ACC_T acc = 0;
   uint32_t m[9], a2[9];
   fe9 r;
+  F29_COUNT_PRODUCT();
 #pragma unroll
   for (int i = 0; i < 9; i++) a2[i] = a.l[i] << 1;
 #pragma unroll

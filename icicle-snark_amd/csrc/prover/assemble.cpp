@@ -242,4 +242,42 @@ __attribute__((visibility("default"))) int groth16_assemble_proof(Groth16CacheMa
   return assemble_impl(z, wtns, wtns_len, points, bl, proof_json, proof_cap, public_json, public_cap);
 }
 
+// verification_key.json as snarkjs writes it (one-space indentation; the fields the verifiers read — src/cache.rs:84-106 — plus
+// protocol and curve), from the header's α₁ β₂ γ₂ δ₂ and section 3.  A point is [x, y, "1"] / [[x0, x1], [y0, y1], ["1", "0"]] in
+// decimal standard form; the identity (0, 0) is snarkjs' ["0", "1", "0"] / [["0","0"], ["1","0"], ["0","0"]].  Host only.
+__attribute__((visibility("default"))) int64_t groth16_zkey_export_vk(const void* zkey, size_t len, char* out, size_t cap)
+{
+  std::vector<Section> secs;
+  ZkeyLayout L;
+  if (int rc = zkey_layout((const uint8_t*)zkey, len, secs, &L)) return rc;
+  auto g1 = [](const uint8_t* p, const char* pad) {
+    G1::A a;
+    memcpy(&a, p, 64);
+    const bool zero = G1::aff_is_zero(a);
+    const std::string x = zero ? "0" : to_decimal(Fq::from_mont(a.x)), y = zero ? "1" : to_decimal(Fq::from_mont(a.y));
+    return std::string("[\n") + pad + " \"" + x + "\",\n" + pad + " \"" + y + "\",\n" + pad + " \"" + (zero ? "0" : "1") + "\"\n" + pad + "]";
+  };
+  auto g2 = [](const uint8_t* p) {
+    G2::A a;
+    memcpy(&a, p, 128);
+    const bool zero = G2::aff_is_zero(a);
+    const fe2 x = Fq2Ops::from_mont(a.x), y = Fq2Ops::from_mont(a.y);
+    const std::string c[6] = {zero ? "0" : to_decimal(x.c0), zero ? "0" : to_decimal(x.c1), zero ? "1" : to_decimal(y.c0), zero ? "0" : to_decimal(y.c1), zero ? "0" : "1", "0"};
+    std::string o = "[\n";
+    for (int k = 0; k < 3; k++) o += "  [\n   \"" + c[2 * k] + "\",\n   \"" + c[2 * k + 1] + "\"\n  ]" + (k < 2 ? ",\n" : "\n");
+    return o + " ]";
+  };
+  const uint8_t* h = L.header_points;
+  std::string j = "{\n \"protocol\": \"groth16\",\n \"curve\": \"bn128\",\n \"nPublic\": " + std::to_string(L.n_public) + ",\n";
+  j += " \"vk_alpha_1\": " + g1(h, " ") + ",\n";
+  j += " \"vk_beta_2\": " + g2(h + 128) + ",\n";
+  j += " \"vk_gamma_2\": " + g2(h + 256) + ",\n";
+  j += " \"vk_delta_2\": " + g2(h + 448) + ",\n";
+  j += " \"IC\": [\n";
+  for (uint32_t i = 0; i <= L.n_public; i++) j += "  " + g1(L.sec[3]->p + (size_t)i * 64, "  ") + (i < L.n_public ? ",\n" : "\n");
+  j += " ]\n}";
+  if (out && cap >= j.size() + 1) memcpy(out, j.c_str(), j.size() + 1);
+  return (int64_t)j.size() + 1;
+}
+
 } // extern "C"

@@ -4,6 +4,9 @@
 //   > verify --proof P --public Q --vk verification_key.json
 //   > verify-batch --list L --vk verification_key.json [--device HIP] [--combined]   (L: one "<proof.json> <public.json>" per line;
 //     --combined: one randomised pairing equation over the batch, the per-item stage only when it fails)
+//   > zkey-check --zkey Z [--device HIP]       every point and record of the key tested on the GPU (groth16_zkey_check): one line per
+//     faulty section, then "sound" or "unsound"
+//   > zkey-export-vk --zkey Z --vk OUT         the key's verification_key.json (groth16_zkey_export_vk)
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -14,7 +17,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  exit\n";
 }
 
 int main()
@@ -163,6 +166,55 @@ int main()
         }
         std::cout << "accepted " << acc << " rejected " << rej << " errors " << err << std::endl;
         if (combined) std::cout << "decided by: " << (path ? "combined equation" : "per-item fallback") << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-check") {
+      std::string zkey = "circuit_final.zkey", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--zkey") in >> zkey;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16ZkeyReport rep;
+      const int rc = groth16_zkey_check_file(zkey.c_str(), device.c_str(), nullptr, &rep);
+      if (rc < 0) {
+        std::cerr << "zkey-check failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        static const char* const kinds[7] = {"", "non-canonical coordinate", "point off the curve", "point outside the subgroup", "identity", "pair mismatch", "coefficient out of range"};
+        for (int s = 2; s < 10; s++) {
+          if (!rep.faults[s]) continue;
+          std::cout << "section " << s << ": " << rep.faults[s] << " at fault";
+          if (s == rep.section) { // the report names kind and index of the first fault of the key
+            std::cout << ", first: " << kinds[rep.kind >= 1 && rep.kind <= 6 ? rep.kind : 0];
+            if (rep.index != UINT64_MAX) std::cout << " at index " << rep.index;
+          }
+          std::cout << std::endl;
+        }
+        std::cout << (rc == 1 ? "sound" : "unsound") << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-export-vk") {
+      std::string zkey = "circuit_final.zkey", vk = "verification_key.json", a;
+      while (in >> a) {
+        if (a == "--zkey") in >> zkey;
+        else if (a == "--vk") in >> vk;
+        else print_help();
+      }
+      std::ifstream f(zkey, std::ios::binary);
+      std::ostringstream ss;
+      if (f) ss << f.rdbuf();
+      const std::string image = ss.str();
+      const int64_t need = f ? groth16_zkey_export_vk(image.data(), image.size(), nullptr, 0) : -1;
+      if (need < 0) {
+        std::cerr << "zkey-export-vk failed (" << need << "): " << (f ? groth16_last_error() : "cannot read the zkey") << std::endl;
+      } else {
+        std::string text((size_t)need, '\0');
+        (void)groth16_zkey_export_vk(image.data(), image.size(), &text[0], text.size());
+        text.resize((size_t)need - 1);
+        std::ofstream o(vk, std::ios::binary);
+        o << text;
+        if (!o) std::cerr << "zkey-export-vk: cannot write " << vk << std::endl;
+        else std::cout << "VK_WRITTEN" << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void csr_count_kernel(const uint32_t* __restri
   if (i >= n_coef) return;
   const uint32_t* e = rec + (size_t)i * REC_WORDS;
   const uint32_t m = e[0] & 0xff, c = e[1], s = e[2]; // only byte 0 of m is read — src/cache.rs:159
-  if (m > 1 || c >= n || s >= n_vars) {
+  if (!isnark::qap_record_in_range(e[0], c, s, n, n_vars)) {
     atomicMin(err, i); // first offending record
     return;
   }

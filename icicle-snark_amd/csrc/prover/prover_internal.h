@@ -48,7 +48,7 @@ void set_error_text(const char* text);
     eIcicleError e__ = (call);                                                                                                   \
     if (e__ != ICICLE_SUCCESS) return ::isnark::prover::fail((int)e__, "%s failed (%d): %s", #call, (int)e__, icicle_snark_last_error()); \
   } while (0)
-enum { ERR_IO = -1, ERR_FORMAT = -2, ERR_ARG = -3, ERR_NOCACHE = -4 };
+enum { ERR_IO = -1, ERR_FORMAT = -2, ERR_ARG = -3, ERR_NOCACHE = -4, ERR_DEVICE = -5 /* groth16_zkey_check, where > 0 is a verdict */ };
 
 inline double ms_since(std::chrono::steady_clock::time_point t0)
 {
@@ -63,6 +63,14 @@ struct Section {
 };
 int read_sections(const uint8_t* data, size_t len, const char* type, uint32_t max_version, std::vector<Section>& out);
 int unique_section(const std::vector<Section>& s, size_t id, const Section** sec);
+// what a zkey says about itself: the sections 2 … 9 and the header's sizes, checked as build_cache checks them (protocol, field
+// sizes and moduli, a power-of-two domain, every section's length).  `secs` owns the table L->sec points into.
+struct ZkeyLayout {
+  uint32_t n_vars = 0, n_public = 0, domain = 0, n_coef = 0;
+  const uint8_t* header_points = nullptr; // α₁ β₁ β₂ γ₂ δ₁ δ₂: 64 / 128 bytes each, Montgomery form
+  const Section* sec[10] = {};
+};
+int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L);
 struct MappedFile {
   const uint8_t* data = nullptr;
   size_t len = 0;

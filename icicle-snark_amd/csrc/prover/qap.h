@@ -39,6 +39,9 @@ hipError_t qap_dist_mid(const bn254::fe* recv, bn254::fe* send, const bn254::fe*
 // cold path (csr.hip): CSR of zkey section 4 built on the device from the raw 44-byte records
 // {m:u32 c:u32 s:u32 value[32 B]} (src/cache.rs:126-166); vals come out as Montgomery-form coefficients (:214).
 // rowptr has 2n+1 entries.  *first_bad = index of the first out-of-range record, 0xffffffff if none.  Synchronises `s`.
+// qap_record_in_range is that range rule for one record's first three words (only byte 0 of m is read — src/cache.rs:159); the
+// zkey check (zkey_check.hip) counts with the same rule.
+FF_HD bool qap_record_in_range(uint32_t m_word, uint32_t c, uint32_t s, uint32_t n, uint32_t n_vars) { return (m_word & 0xff) <= 1 && c < n && s < n_vars; }
 hipError_t qap_build_csr(const uint32_t* d_records, uint32_t n_coef, uint32_t n, uint32_t n_vars, uint32_t* d_rowptr, uint32_t* d_cols, bn254::fe* d_vals,
                          uint32_t* first_bad, hipStream_t s);
 

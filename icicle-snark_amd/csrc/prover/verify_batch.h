@@ -5,10 +5,12 @@
 // in verify_host.h.
 #pragma once
 #include <chrono>
+#include <errno.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <sys/random.h>
 #include <functional>
 #include <vector>
 
@@ -47,6 +49,25 @@ inline int device_fail(int code, const char* what, hipError_t e)
   char msg[200];
   snprintf(msg, sizeof msg, "device: %s: %s", what, hipGetErrorString(e));
   return fail(code, msg);
+}
+// n bytes from the operating system (getrandom, else /dev/urandom): the secret seeds of the randomised checks
+inline bool os_random(uint8_t* out, size_t n)
+{
+  size_t got = 0;
+  while (got < n) {
+    const ssize_t r = getrandom(out + got, n - got, 0);
+    if (r < 0) {
+      if (errno == EINTR) continue;
+      break;
+    }
+    got += (size_t)r;
+  }
+  if (got == n) return true;
+  FILE* f = fopen("/dev/urandom", "rb");
+  if (!f) return false;
+  const size_t rd = fread(out, 1, n, f);
+  fclose(f);
+  return rd == n;
 }
 struct DevBuf { // device allocations of one call, freed on every exit path
   std::vector<void*> ptrs;

@@ -14,10 +14,8 @@
 // verify_host.h's (CombinedSums, PreparedKey — prepared once, and handed on to the fallback), the device, the two streams and the
 // buffers are verify_batch.h's DeviceSession.
 #include <chrono>
-#include <errno.h>
 #include <stdio.h>
 #include <string.h>
-#include <sys/random.h>
 #include <vector>
 
 #include "../../../include/groth16_prover.h"
@@ -90,25 +88,6 @@ hipError_t reduce_product(p29::F12* f, uint32_t n, hipStream_t st)
     n = h;
   }
   return hipGetLastError();
-}
-
-bool os_random(uint8_t* out, size_t n)
-{
-  size_t got = 0;
-  while (got < n) {
-    const ssize_t r = getrandom(out + got, n - got, 0);
-    if (r < 0) {
-      if (errno == EINTR) continue;
-      break;
-    }
-    got += (size_t)r;
-  }
-  if (got == n) return true;
-  FILE* f = fopen("/dev/urandom", "rb");
-  if (!f) return false;
-  const size_t rd = fread(out, 1, n, f);
-  fclose(f);
-  return rd == n;
 }
 
 // What the stages of one combined attempt share.  Lives on combined_stage's stack and outlives the pooled tasks of host_sums,
@@ -305,7 +284,7 @@ ISNARK_API int groth16_verify_batch_combined(const char* const* proof_jsons, con
   }
   uint8_t seed[32];
   if (seed32) memcpy(seed, seed32, 32);
-  else if (!os_random(seed, 32)) return fail(-3, "no randomness from the operating system (getrandom, /dev/urandom)");
+  else if (!isnark::vb::os_random(seed, 32)) return fail(-3, "no randomness from the operating system (getrandom, /dev/urandom)");
   Parsed pz;
   if (int rc = parse_stage(proof_jsons, public_jsons, n, vk_json, verdicts, &pz, nullptr)) return rc;
   if (pz.live.empty()) {

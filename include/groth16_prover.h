@@ -211,6 +211,56 @@ int groth16_verify_batch_combined(const char* const* proof_jsons, const char* co
 /* out16[16·k …] = z_{first + k} (16 bytes, little endian) for k < count, as derived above.  Needs no GPU. */
 void groth16_verify_combined_coefficients(const uint8_t seed32[32], uint64_t first, uint64_t count, uint8_t* out16);
 
+/* groth16_zkey_check — is this proving key sound?  Opt-in: groth16_cache_load* and the proves trust the key they are given.
+ * Every point of sections 3 (IC), 5 (A), 6 (B1), 7 (B2), 8 (C), 9 (H) and of the header is tested on one GPU, one lane per point,
+ * in the file's Montgomery form; section 4 gets the loader's range check plus value < r; then three pair checks.
+ * kinds of fault, in the order in which one element is tested: */
+#define GROTH16_ZKEY_NONCANONICAL   1  /* a coordinate's 256-bit residue is >= q */
+#define GROTH16_ZKEY_OFF_CURVE      2  /* not the identity (0,0) and not on y^2 = x^3 + 3 (G1) / x^3 + 3/xi (G2) */
+#define GROTH16_ZKEY_OFF_SUBGROUP   3  /* G2 only: on the twist, outside the order-r subgroup */
+#define GROTH16_ZKEY_IDENTITY       4  /* header points only: alpha1, beta1, beta2, gamma2, delta1, delta2 must not be the identity */
+#define GROTH16_ZKEY_PAIR_MISMATCH  5  /* beta1/beta2, delta1/delta2, or section 6 against section 7 */
+#define GROTH16_ZKEY_COEFFICIENT    6  /* section 4: matrix, constraint or wire out of range, or value >= r */
+
+typedef struct {
+  int32_t  kind;          /* 0 = sound, else the kind of the FIRST fault */
+  int32_t  section;       /* zkey section id of the first fault: 2 (header), 3, 4, 5, 6, 7, 8, 9 */
+  uint64_t index;         /* lowest element index at fault in that section; for the header the position 0..5 in file order;
+                             UINT64_MAX for a section-6/7 mismatch, which the randomised check does not localise */
+  uint64_t faults[10];    /* faults[s] = elements at fault in section s (membership kinds 1-4 and 6); a mismatch counts 1 in faults[2] or faults[6] */
+  double   upload_ms, device_ms, pairing_ms;
+} Groth16ZkeyReport;
+
+typedef struct {
+  uint32_t slice_points;  /* points per upload slice; 0 = the default */
+  const uint8_t* seed32;  /* NULL = 32 bytes from getrandom / /dev/urandom, as groth16_verify_batch_combined */
+} Groth16ZkeyCheckOptions;
+
+/* "First" means: sections in ascending id, within a section the lowest index, within an element the kinds in the order 1, 2, 3
+ * (4 for a header point).  faults[] is complete for every section whatever came first.
+ * Pair checks (kind 5) run only when the sections they read have no membership fault.  The header pairs hold when
+ * e(beta1, G2) = e(G1, beta2) and e(delta1, G2) = e(G1, delta2) by the host pairing (index 1 and 4: the G1 member's slot).
+ * Sections 6 and 7 hold when S1 = Σ z_i·B1_i and S2 = Σ z_i·B2_i satisfy e(S1, G2) = e(G1, S2), z_i =
+ * groth16_verify_combined_coefficients(seed, i) and the sums from the library's MSMs over 128-bit scalars: with every B2_i in G2,
+ * a key with some B1_i that is not the G1 image of its B2_i passes with probability <= 2^-127 over the seed, WHICH MUST BE SECRET
+ * AND FRESH (opt->seed32 is for reproducible tests; NULL draws from the operating system, and the call returns -3 when that fails).
+ * What the check does NOT show: that the key belongs to a given circuit or ceremony (that needs the .r1cs and the .ptau, as
+ * `snarkjs zkey verify`), or any relation between A, C, H and IC.
+ * device as groth16_verify_batch ("HIP", "CUDA", "HIP:k").  opt may be NULL.  The call holds no cache entry and needs no
+ * Groth16CacheManager; the calling thread's device is what it was afterwards.  report->upload_ms: the host to device copies of the
+ * sections, device_ms: the wall time of the device part (buffers, uploads, kernels, MSMs), pairing_ms: the host pairings (the
+ * header's four run on a worker thread beside the device part).  ICICLE_SNARK_TRACE_ZKEY_CHECK=1 prints the stage times on stderr.
+ * 1 sound, 0 at least one fault (report says which), < 0 an error (groth16_last_error): the loader's own codes for format (-2),
+ * I/O (-1) and argument (-3) errors, and -5 for a device failure, whose positive eIcicleError would read as a verdict here. */
+int groth16_zkey_check(const void* zkey, size_t len, const char* device, const Groth16ZkeyCheckOptions* opt, Groth16ZkeyReport* report);
+int groth16_zkey_check_file(const char* zkey_path, const char* device, const Groth16ZkeyCheckOptions* opt, Groth16ZkeyReport* report);
+
+/* snarkjs verification_key.json text of the key (protocol, curve "bn128", nPublic, vk_alpha_1, vk_beta_2, vk_gamma_2, vk_delta_2, IC;
+ * projective third coordinates as snarkjs writes them).  Reads the header and section 3 as they are — groth16_zkey_check is what
+ * tests them.  Host only: never initialises a GPU.  Returns the length needed including the terminator (call with cap = 0 to
+ * size; `out` is written only when cap is at least that), < 0 on a format error (groth16_last_error). */
+int64_t groth16_zkey_export_vk(const void* zkey, size_t len, char* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
