@@ -1,12 +1,7 @@
 // cache.cpp — CacheManager::compute (src/cache.rs:117-241): zkey sections 4-9 → the device-resident ZKeyCache of one
 // device (or of one shard of a device group).
 #include <algorithm>
-#include <fcntl.h>
-#include <errno.h>
-#include <sys/mman.h>
-#include <sys/random.h>
-#include <sys/stat.h>
-#include <unistd.h>
+#include <utility>
 
 #include "prover_internal.h"
 
@@ -29,25 +24,14 @@ ZKeyCache::~ZKeyCache()
     if (tb.th.joinable()) tb.th.join();
     for (void* t : tb.fresh)
       if (t) (void)hipFree(t);
-    if (s_qap) (void)hipStreamSynchronize(s_qap);
-    if (s_g1) (void)hipStreamSynchronize(s_g1);
-    if (s_g2) (void)hipStreamSynchronize(s_g2);
-    if (s_g3) (void)hipStreamSynchronize(s_g3);
-    if (s_g4) (void)hipStreamSynchronize(s_g4);
-    if (s_g5) (void)hipStreamSynchronize(s_g5);
+    for (hipStream_t st : streams())
+      if (st) (void)hipStreamSynchronize(st);
     for (void* p : {(void*)d_rowptr, (void*)d_cols, (void*)d_vals, A.d_points, B1.d_points, B2.d_points, C.d_points, H.d_points, (void*)d_witness, (void*)d_vec, (void*)d_fold, (void*)d_skeys, (void*)d_dist_y, (void*)d_dist_recv1, (void*)d_dist_send2, (void*)d_tw1, (void*)d_partials})
       if (p) (void)hipFree(p);
     if (h_partials) (void)hipHostFree(h_partials);
-    if (s_qap) (void)icicle_destroy_stream(s_qap);
-    if (s_g1) (void)icicle_destroy_stream(s_g1);
-    if (s_g2) (void)icicle_destroy_stream(s_g2);
-    if (s_g3) (void)icicle_destroy_stream(s_g3);
-    if (s_g4) (void)icicle_destroy_stream(s_g4);
-    if (s_g5) (void)icicle_destroy_stream(s_g5);
-    if (ev_witness) (void)hipEventDestroy(ev_witness);
-    if (ev_sort) (void)hipEventDestroy(ev_sort);
-    if (ev_sort_h) (void)hipEventDestroy(ev_sort_h);
-    for (hipEvent_t e : {ev_own_slice, ev_head_in, ev_head_done, ev_t_head_start, ev_t_head_end, ev_t_witness})
+    for (hipStream_t st : streams())
+      if (st) (void)icicle_destroy_stream(st);
+    for (hipEvent_t e : {ev_witness, ev_sort, ev_sort_h, ev_own_slice, ev_head_in, ev_head_done, ev_t_head_start, ev_t_head_end, ev_t_witness})
       if (e) (void)hipEventDestroy(e);
     for (auto e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -76,6 +60,36 @@ G2::P g2_from_mont_affine(const uint8_t* p)
   if (G2::aff_is_zero(a)) return {Fq2Ops::zero(), one, Fq2Ops::zero()};
   return {Fq2Ops::from_mont(a.x), Fq2Ops::from_mont(a.y), one};
 }
+
+// The five base arrays of a key, in the order of the zkey's sections 5 … 9 — which is the order of TableBuild::fresh, of
+// ColdPlan::sec and of the feed's stages ColdFeed::SEC_A + k.
+struct BaseArray {
+  Shard ZKeyCache::*shard;
+  int section; // of the zkey
+  bool g2;     // G2 points: 128 instead of 64 bytes, the msm_g2_… entry points
+  bool h;      // H: its own geometry (geom_h); the other four are the witness MSMs and share geom_w
+  size_t elem() const { return g2 ? 128 : 64; }
+  Shard& of(ZKeyCache* z) const { return z->*shard; }
+  const MsmGeom& geom(const MsmGeom& gw, const MsmGeom& gh) const { return h ? gh : gw; }
+};
+const BaseArray BASES[5] = {{&ZKeyCache::A, 5, false, false}, {&ZKeyCache::B1, 6, false, false}, {&ZKeyCache::B2, 7, true, false}, {&ZKeyCache::C, 8, false, false}, {&ZKeyCache::H, 9, false, true}};
+
+// bytes of one row of the four witness tables (A, B1, B2, C)
+uint64_t witness_row_bytes(const ZKeyCache* z) { return ((uint64_t)z->A.len() + z->B1.len() + z->C.len()) * 64 + (uint64_t)z->B2.len() * 128; }
+
+// msm_plan.h's per-group entry points by the G2 flag; `from_form`: 1 = the file's Montgomery form, 2 = the internal encoding
+eIcicleError points_to_internal(bool g2, const Shard& sh, int from_form, hipStream_t s)
+{
+  return g2 ? msm_g2_points_to_internal(sh.d_points, sh.len(), from_form, s) : msm_g1_points_to_internal(sh.d_points, sh.len(), from_form, s);
+}
+eIcicleError build_table(bool g2, const Shard& sh, int from_form, const MsmGeom& g, hipStream_t s, void** table)
+{
+  return g2 ? msm_g2_build_table(sh.d_points, sh.len(), from_form, g, s, table) : msm_g1_build_table(sh.d_points, sh.len(), from_form, g, s, table);
+}
+eIcicleError build_table_sliced(bool g2, const Shard& sh, int from_form, const MsmGeom& g, hipStream_t s, void** table, const std::atomic<bool>* cancel)
+{
+  return g2 ? msm_g2_build_table_sliced(sh.d_points, sh.len(), from_form, g, s, table, cancel) : msm_g1_build_table_sliced(sh.d_points, sh.len(), from_form, g, s, table, cancel);
+}
 } // namespace
 
 // ---- cold path: host → device ingest ------------------------------------------------------------
@@ -90,20 +104,6 @@ int staged_upload(int device_id, const std::vector<UploadJob>& jobs, const hipSt
   if (e != hipSuccess) return fail((int)ICICLE_COPY_FAILED, "host to device upload: %s", hipGetErrorString(e));
   return 0;
 }
-
-namespace {
-int alloc_shard(Shard& sh, const Section* sec, size_t elem, uint32_t total, uint32_t lo, uint32_t hi, uint64_t& bytes, std::vector<UploadJob>& jobs)
-{
-  if (sec->size != (uint64_t)total * elem) return fail(ERR_FORMAT, "zkey: point section size mismatch");
-  sh.lo = lo;
-  sh.hi = hi;
-  const size_t n = (size_t)sh.len() * elem;
-  P_HIP(hipMalloc(&sh.d_points, n ? n : 256));
-  if (n) jobs.push_back({sh.d_points, sec->p + (size_t)sh.lo * elem, n});
-  bytes += n;
-  return 0;
-}
-} // namespace
 
 // ---- digit width of a key's witness tables (A, B1, B2, C) for DENSE scalars --------------------------------------------------------
 // msm_geometry's table rule takes the widest digit the sort entry holds (c = 20 from 2^19 wires on): fewest additions.  For the four
@@ -141,12 +141,12 @@ void assign_stream_roles(ZKeyCache* z, bool allow_measure)
 {
   static const bool off = env_int("ICICLE_SNARK_PIPE_ROLES", 1) == 0;
   if (off) return;
-  hipStream_t phys[6] = {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5};
+  std::array<hipStream_t, 6> phys = z->streams();
   int cls[6];
   // (the shards of a device group do not measure: with all of them on one device — the aliased test groups — 48 streams share 12
   //  queues and the classes mean nothing, and on G devices G probes would sit in the group's load; a shard whose streams the prewarm
   //  thread has measured — rank-per-GPU processes, the group's first device — still gets its roles)
-  if (!stream_pipe_classes(phys, 6, cls, allow_measure)) return;
+  if (!stream_pipe_classes(phys.data(), 6, cls, allow_measure)) return;
   // roles: 0 front end, 1 A, 2 B2 (+ witness sort / head chain), 3 H sort (+ tail sort of a split witness), 4 B1 + H, 5 C
   auto cost = [&](const int* perm) {
     auto same = [&](int a, int b) { return cls[perm[a]] == cls[perm[b]] ? 1 : 0; };
@@ -164,19 +164,14 @@ void assign_stream_roles(ZKeyCache* z, bool allow_measure)
       memcpy(best, perm, sizeof best);
     }
   }
-  z->s_qap = phys[best[0]];
-  z->s_g1 = phys[best[1]];
-  z->s_g2 = phys[best[2]];
-  z->s_g3 = phys[best[3]];
-  z->s_g4 = phys[best[4]];
-  z->s_g5 = phys[best[5]];
+  int r = 0;
+  for (hipStream_t* role : {&z->s_qap, &z->s_g1, &z->s_g2, &z->s_g3, &z->s_g4, &z->s_g5}) *role = phys[best[r++]];
   if (env_set("ICICLE_SNARK_TRACE_COLD") || env_set("ICICLE_SNARK_VERBOSE"))
     fprintf(stderr, "[icicle-snark-hip] stream pipes %d %d %d %d %d %d -> roles (qap A B2 Hsort B1 C) take streams %d %d %d %d %d %d (cost %d)\n", cls[0], cls[1], cls[2], cls[3], cls[4], cls[5], best[0],
             best[1], best[2], best[3], best[4], best[5], best_cost);
 }
 } // namespace
 
-// CacheManager::compute — src/cache.rs:117-241
 // ---- deferred fixed-base tables (prover_internal.h: TableBuild) --------------------------------------------------------------
 namespace {
 void table_build_thread(ZKeyCache* z)
@@ -209,7 +204,7 @@ void table_build_thread(ZKeyCache* z)
       // taken only when the extra bytes fit what the cache budget has left (narrow_room) and the device has them free beside the
       // slices' temporaries — as start_witness_rebuild checks for a re-build (round-5 advisor)
       if (g.tab && g.c == c_t && g.W > tb.gw.W) {
-        const uint64_t per_row = (uint64_t)z->A.len() * 64 + (uint64_t)z->B1.len() * 64 + (uint64_t)z->B2.len() * 128 + (uint64_t)z->C.len() * 64;
+        const uint64_t per_row = witness_row_bytes(z);
         const uint64_t extra = (uint64_t)(g.W - tb.gw.W) * per_row;
         size_t free_b = 0, total_b = 0;
         const bool mem_ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && (uint64_t)g.W * per_row + (uint64_t)tb.gh.W * z->H.len() * 64 + (1ull << 30) <= free_b;
@@ -234,22 +229,20 @@ void table_build_thread(ZKeyCache* z)
     }
   }
   if (trace_tb) fprintf(stderr, "[tables] thread: stream created at %.1f ms\n", ms_since(t0));
-  struct Job { const Shard* sh; bool g2; const MsmGeom* g; };
   // H first: the longest of the five builds' G1 arrays; B2 (the G2 array, 60 % of the G1 four together) last
-  const Job jobs[5] = {{&z->A, false, &tb.gw}, {&z->B1, false, &tb.gw}, {&z->B2, true, &tb.gw}, {&z->C, false, &tb.gw}, {&z->H, false, &tb.gh}};
+  const int order[5] = {4, 0, 1, 3, 2};
   // (a narrowed first build that fails — out of memory after all — is tried once more with the dense geometry the key was admitted with)
   for (int attempt = 0; attempt < 2; attempt++) {
-    for (int k : {4, 0, 1, 3, 2}) {
-      if (k == 4 && tb.witness_only) continue; // (a re-build for another witness density: row 0 of the current tables is the source)
-      if (k == 4 && tb.fresh[4]) continue;     // (second attempt: H's table is there already)
+    for (int k : order) {
+      const BaseArray& b = BASES[k];
+      if (b.h && tb.witness_only) continue; // (a re-build for another witness density: row 0 of the current tables is the source)
+      if (b.h && tb.fresh[k]) continue;     // (second attempt: H's table is there already)
       if (!ok || tb.cancel.load()) {
         ok = false;
         break;
       }
-      const Job& j = jobs[k];
       // the bases are in the internal encoding already (form 2); the proves of the key only read them
-      const eIcicleError e = j.g2 ? msm_g2_build_table_sliced(j.sh->d_points, j.sh->len(), 2, *j.g, s, &tb.fresh[k], &tb.cancel)
-                                  : msm_g1_build_table_sliced(j.sh->d_points, j.sh->len(), 2, *j.g, s, &tb.fresh[k], &tb.cancel);
+      const eIcicleError e = build_table_sliced(b.g2, b.of(z), 2, b.geom(tb.gw, tb.gh), s, &tb.fresh[k], &tb.cancel);
       if (e != ICICLE_SUCCESS) {
         (void)hipGetLastError();
         ok = false;
@@ -293,15 +286,16 @@ int adopt_tables(ZKeyCache* z, bool wait)
   if (st == 2) {
     // all five at once: pointers and both geometries change together, so no sort of one geometry ever meets tables of another.
     // (synchronising frees: the caller holds the manager's mutex, nothing of this key is in flight and the build has ended)
-    Shard* sh5[5] = {&z->A, &z->B1, &z->B2, &z->C, &z->H};
     for (int k = 0; k < 5; k++) {
-      if (k == 4 && tb.witness_only) continue;
-      const MsmGeom& g = k == 4 ? tb.gh : tb.gw;
+      const BaseArray& b = BASES[k];
+      if (b.h && tb.witness_only) continue;
+      Shard& sh = b.of(z);
+      const MsmGeom& g = b.geom(tb.gw, tb.gh);
       const int64_t w_old = tb.witness_only ? z->geom_w.W : 1; // (tables of another width replace tables; the first build replaces plain arrays)
-      (void)hipFree(sh5[k]->d_points);
-      sh5[k]->d_points = tb.fresh[k];
+      (void)hipFree(sh.d_points);
+      sh.d_points = tb.fresh[k];
       tb.fresh[k] = nullptr;
-      z->device_bytes += (int64_t)sh5[k]->len() * ((int64_t)g.W - w_old) * (k == 2 ? 128 : 64);
+      z->device_bytes += (int64_t)sh.len() * ((int64_t)g.W - w_old) * (int64_t)b.elem();
     }
     z->geom_w = tb.gw;
     if (!tb.witness_only) {
@@ -336,7 +330,7 @@ void start_witness_rebuild(ZKeyCache* z, int c_new)
     (void)hipGetLastError();
     return;
   }
-  const uint64_t need = (uint64_t)g.W * ((uint64_t)z->A.len() * 64 + (uint64_t)z->B1.len() * 64 + (uint64_t)z->B2.len() * 128 + (uint64_t)z->C.len() * 64) + (1ull << 30);
+  const uint64_t need = (uint64_t)g.W * witness_row_bytes(z) + (1ull << 30);
   if (need > free_b) return;
   tb.gw = g;
   tb.gh = z->geom_h;
@@ -426,10 +420,9 @@ void cold_upload_task(ColdPlan* pl)
   // the point sections in the order the prove enqueues their MSMs (B2 — the longest chain — first), each converted in place from the
   // file's Montgomery form to the bucket kernels' encoding as it lands
   const int order[5] = {2, 0, 1, 3, 4};
-  Shard* sh5[5] = {&z->A, &z->B1, &z->B2, &z->C, &z->H};
   for (int k : order) {
     if (!upload(pl->sec[k], false)) return;
-    const eIcicleError e = k == 2 ? msm_g2_points_to_internal(sh5[k]->d_points, sh5[k]->len(), 1, su) : msm_g1_points_to_internal(sh5[k]->d_points, sh5[k]->len(), 1, su);
+    const eIcicleError e = points_to_internal(BASES[k].g2, BASES[k].of(z), 1, su);
     if (e != ICICLE_SUCCESS) return bail((int)e, "cold upload: %s", "points to internal form");
     if (!stage_done(ColdFeed::SEC_A + k)) return;
   }
@@ -456,151 +449,132 @@ void cold_upload_wait(ColdUpload* cu)
   }
 }
 
-int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int count, std::unique_ptr<ZKeyCache>& out, bool defer_tables, ColdUpload* cold)
-{
-  if (count < 1 || rank < 0 || rank >= count) return fail(ERR_ARG, "bad shard %d/%d", rank, count);
+// ---- build_cache: CacheManager::compute — src/cache.rs:117-241 — as a row of stages ---------------------------------------------
+namespace {
+// What the stages of one load share.  Owns the key under construction and the load's device temporaries: whatever of them is
+// still here when the load ends — on an error or regularly — is freed, the temporaries first, then the key.
+struct LoadCtx {
+  const ZkeyLayout& L;
+  const int device_id, rank, count;
+  const bool defer_tables; // the caller lets the tables be built behind the first proofs
+  ColdUpload* const cold;  // the caller proves while the sections arrive, when the layout decision allows it
+  const ShardRanges rg;
+  std::unique_ptr<ZKeyCache> z;
+  std::vector<UploadJob> jobs;   // host → device: the records and this shard's point ranges
+  uint32_t* d_records = nullptr; // the raw coefficient records the CSR is built from
+  size_t rec_bytes = 0;
+  void* h_full = nullptr; // strided H: the whole section, from which the residue class is gathered
+  bool pipeline = false; // decide_layout: the sections arrive behind the caller's prove (the cold uploader task), not in the load
   const bool trace = env_set("ICICLE_SNARK_TRACE_COLD");
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
+  std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+
+  ~LoadCtx()
+  {
+    if (h_full) (void)hipFree(h_full);
+    if (d_records) (void)hipFree(d_records);
+  }
+  void lap(const char* what)
+  {
     if (!trace) return;
-    auto t = std::chrono::steady_clock::now();
+    const auto t = std::chrono::steady_clock::now();
     fprintf(stderr, "[cold] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
     t_prev = t;
-  };
-  std::vector<Section> s;
-  if (int rc = read_sections(data, len, "zkey", 2, s)) return rc;
-  const Section *s1, *s2, *s4, *s5, *s6, *s7, *s8, *s9;
-  if (int rc = unique_section(s, 1, &s1)) return rc;
-  uint32_t protocol = 0;
-  if (s1->size >= 4) memcpy(&protocol, s1->p, 4);
-  if (protocol != 1) return fail(ERR_FORMAT, "Protocol not supported"); // GROTH16_PROTOCOL_ID, file_wrapper.rs:12,196-207
-  if (int rc = unique_section(s, 2, &s2)) return rc;
-  if (int rc = unique_section(s, 4, &s4)) return rc;
-  if (int rc = unique_section(s, 5, &s5)) return rc;
-  if (int rc = unique_section(s, 6, &s6)) return rc;
-  if (int rc = unique_section(s, 7, &s7)) return rc;
-  if (int rc = unique_section(s, 8, &s8)) return rc;
-  if (int rc = unique_section(s, 9, &s9)) return rc;
+  }
+};
 
-  std::unique_ptr<ZKeyCache> z(new ZKeyCache());
-  z->device_id = device_id;
-  z->shard_rank = rank;
-  z->shard_count = count;
-  // read_header_groth16 — src/zkey.rs:47-85
-  const uint8_t* h = s2->p;
-  if (s2->size < 4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128) return fail(ERR_FORMAT, "zkey header too short");
-  memcpy(&z->n8q, h, 4);
-  if (z->n8q != 32) return fail(ERR_FORMAT, "zkey: unsupported base field size");
-  memcpy(z->q.l, h + 4, 32);
-  memcpy(&z->n8r, h + 36, 4);
-  if (z->n8r != 32) return fail(ERR_FORMAT, "zkey: unsupported scalar field size");
-  memcpy(z->r.l, h + 40, 32);
-  memcpy(&z->n_vars, h + 72, 4);
-  memcpy(&z->n_public, h + 76, 4);
-  memcpy(&z->domain_size, h + 80, 4);
-  if (!Fq::eq(z->q, Fq::modulus()) || !Fr::eq(z->r, Fr::modulus())) return fail(ERR_FORMAT, "zkey: not a BN254 key");
-  const uint32_t n = z->domain_size;
-  if (n == 0 || (n & (n - 1))) return fail(ERR_FORMAT, "zkey: domain size %u is not a power of two", n);
-  if (z->n_public + 1 > z->n_vars) return fail(ERR_FORMAT, "zkey: n_public exceeds n_vars");
-  const uint8_t* pp = h + 84;
+// the key's header fields and shard identity, from the layout
+void fill_header(ZKeyCache* z, const LoadCtx& c)
+{
+  const ZkeyLayout& L = c.L;
+  z->device_id = c.device_id;
+  z->shard_rank = c.rank;
+  z->shard_count = c.count;
+  z->slice_aligned = c.rg.slice_aligned;
+  z->n8q = L.n8q;
+  z->q = L.q;
+  z->n8r = L.n8r;
+  z->r = L.r;
+  z->n_vars = L.n_vars;
+  z->n_public = L.n_public;
+  z->domain_size = L.domain;
+  z->n_coef = L.n_coef;
+  const uint8_t* pp = L.header_points;
   z->vk_alpha_1 = g1_from_mont_affine(pp);
   z->vk_beta_1 = g1_from_mont_affine(pp + 64);
   z->vk_beta_2 = g2_from_mont_affine(pp + 128);
   z->vk_gamma_2 = g2_from_mont_affine(pp + 256);
   z->vk_delta_1 = g1_from_mont_affine(pp + 384);
   z->vk_delta_2 = g2_from_mont_affine(pp + 448);
+}
 
-  // coefficients (section 4): {m:u32 c:u32 s:u32 value[32]} — src/cache.rs:126-166 (only byte 0 of m is read, :159)
-  const size_t rec = 12 + 32;
-  if (s4->size < 4 || (s4->size - 4) % rec) return fail(ERR_FORMAT, "zkey: coefficient section size");
-  if ((s4->size - 4) / rec > 0xffffffffull) return fail(ERR_FORMAT, "zkey: too many coefficients");
-  const uint32_t n_coef = (uint32_t)((s4->size - 4) / rec);
-  {
-    const uint64_t nv64 = z->n_vars, np1 = (uint64_t)z->n_public + 1;
-    if (s5->size != nv64 * 64 || s6->size != nv64 * 64 || s7->size != nv64 * 128 || s8->size != (nv64 - np1) * 64 || s9->size != (uint64_t)n * 64)
-      return fail(ERR_FORMAT, "zkey: point section size mismatch");
-  }
-  z->n_coef = n_coef; // from the section length, like src/cache.rs:129 (the declared count in the first 4 bytes is not read)
-  // the container and the header are validated before the device is touched (a malformed key is a format error on any host)
+// the device, and the key's six streams in their roles
+int open_streams(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
   IcicleDevice dev;
   memset(&dev, 0, sizeof dev);
   strcpy(dev.type, "HIP");
-  dev.id = device_id;
+  dev.id = c.device_id;
   P_ICICLE(icicle_set_device(&dev));
   // six streams; the library asks the runtime for eight hardware queues so that they do not share one (runtime.cpp).
   // Stream priorities were tried (QAP chain high, G2 low, …): every variant was 1-2 ms slower than equal priorities.
   // Created BEFORE the ingest, which uses them as its lanes: a fresh stream costs ≈ 4 ms to create and its first host→device
   // copy sets up its DMA queue (another 3 ms) — the eight short-lived upload streams of rounds 1–4 paid both on every cold
   // load (≈ 35 ms of a 57 ms upload at 1.6 M constraints), and the key's own streams then paid them again.
-  P_ICICLE(icicle_create_stream((icicleStreamHandle*)&z->s_qap)); // QAP front end (its own hardware queue; a higher stream priority made no difference)
-  P_ICICLE(icicle_create_stream((icicleStreamHandle*)&z->s_g1));
-  P_ICICLE(icicle_create_stream((icicleStreamHandle*)&z->s_g2));
-  P_ICICLE(icicle_create_stream((icicleStreamHandle*)&z->s_g3));
-  P_ICICLE(icicle_create_stream((icicleStreamHandle*)&z->s_g4));
-  P_ICICLE(icicle_create_stream((icicleStreamHandle*)&z->s_g5));
-  assign_stream_roles(z.get(), /*allow_measure=*/count <= 1);
-  lap("six streams");
-  // device CSR built by kernels from the raw records (prover/csr.hip); the records travel with the points below
-  uint32_t* d_records = nullptr;
-  const size_t rec_bytes = (size_t)n_coef * rec;
-  P_HIP(hipMalloc((void**)&d_records, rec_bytes ? rec_bytes : 4));
-  struct FreeTmp {
-    void* p;
-    ~FreeTmp() { (void)hipFree(p); }
-  } free_records{d_records};
-  P_HIP(hipMalloc((void**)&z->d_rowptr, (2 * (size_t)n + 1) * 4));
-  P_HIP(hipMalloc((void**)&z->d_cols, (size_t)(n_coef ? n_coef : 1) * 4));
-  P_HIP(hipMalloc((void**)&z->d_vals, (size_t)(n_coef ? n_coef : 1) * 32));
-  z->device_bytes += (2 * (size_t)n + 1) * 4 + (size_t)n_coef * 36;
-  std::vector<UploadJob> jobs;
-  if (rec_bytes) jobs.push_back({d_records, s4->p + 4, rec_bytes});
-  lap("header + coefficient buffers");
+  // (s_qap: the QAP front end — its own hardware queue; a higher stream priority made no difference)
+  for (hipStream_t* st : {&z->s_qap, &z->s_g1, &z->s_g2, &z->s_g3, &z->s_g4, &z->s_g5}) P_ICICLE(icicle_create_stream((icicleStreamHandle*)st));
+  assign_stream_roles(z, /*allow_measure=*/c.count <= 1);
+  c.lap("six streams");
+  return 0;
+}
 
-  // bases (sections 5-9), this process's point range only
-  // A, B1, B2 share the witness range [wlo, whi); C (= witness[n_public+1..]) takes the part of that SAME
-  // witness range it covers, so that one digit sort of witness[wlo:whi] serves all four MSMs.
-  // The range of shard `rank` is the witness SLICE that rank uploads itself (witness_slice_elems: ⌈n_vars / count⌉ wires from
-  // rank·slice; groth16_upload_witness_slice, multi.cpp) whenever that leaves no shard empty: its digit sort and its four witness
-  // accumulations then need nothing from the other devices and run while the in-place all-gather, the distributed front end and its
-  // two all-to-alls are still under way (prover.cpp: own_slice_first).  Otherwise the even split ⌊n_vars·rank / count⌋.
-  const uint64_t slice = witness_slice_elems(z->n_vars, count);
-  z->slice_aligned = count > 1 && slice * (uint64_t)(count - 1) < z->n_vars;
-  const uint32_t wlo = z->slice_aligned ? (uint32_t)(slice * (uint64_t)rank) : (uint32_t)((uint64_t)z->n_vars * rank / count);
-  const uint32_t whi = z->slice_aligned ? (uint32_t)std::min<uint64_t>(z->n_vars, slice * (uint64_t)(rank + 1)) : (uint32_t)((uint64_t)z->n_vars * (rank + 1) / count);
-  const uint32_t skip = z->n_public + 1;
-  const uint32_t clo = (wlo > skip ? wlo : skip) - skip, chi = (whi > skip ? whi : skip) - skip;
-  const uint32_t hlo = (uint32_t)((uint64_t)n * rank / count), hhi = (uint32_t)((uint64_t)n * (rank + 1) / count);
-  if (int rc = alloc_shard(z->A, s5, 64, z->n_vars, wlo, whi, z->device_bytes, jobs)) return rc;
-  if (int rc = alloc_shard(z->B1, s6, 64, z->n_vars, wlo, whi, z->device_bytes, jobs)) return rc;
-  if (int rc = alloc_shard(z->B2, s7, 128, z->n_vars, wlo, whi, z->device_bytes, jobs)) return rc;
-  if (int rc = alloc_shard(z->C, s8, 64, z->n_vars - skip, clo, chi, z->device_bytes, jobs)) return rc;
-  // H: a power-of-two shard count takes the residue class k ≡ rank (mod count) instead of a contiguous range — the rank
-  // then needs the coset evaluations only at those k, which the folded forward transform delivers at 1/count of the cost
-  // (qap.h: qap_coset_fold3); the whole section is uploaded once and the class is gathered on the device
-  const bool h_strided = count > 1 && (count & (count - 1)) == 0 && n / (uint32_t)count >= 1024;
-  void* h_full = nullptr;
-  struct FreeFull {
-    void** p;
-    ~FreeFull() { if (*p) (void)hipFree(*p); }
-  } free_full{&h_full};
-  if (h_strided) {
-    if (s9->size != (uint64_t)n * 64) return fail(ERR_FORMAT, "zkey: point section size mismatch");
-    const uint32_t m = n / (uint32_t)count;
-    P_HIP(hipMalloc(&h_full, (size_t)n * 64));
-    P_HIP(hipMalloc(&z->H.d_points, (size_t)m * 64));
-    z->H.lo = 0;
-    z->H.hi = m;
-    z->H.stride = (uint32_t)count;
-    z->H.first = (uint32_t)rank;
-    jobs.push_back({h_full, s9->p, (size_t)n * 64});
-    z->device_bytes += (size_t)m * 64;
-  } else if (int rc = alloc_shard(z->H, s9, 64, n, hlo, hhi, z->device_bytes, jobs)) return rc;
-  lap("point buffers (hipMalloc)");
-  // bases: the file's Montgomery form (R = 2^256) → the bucket kernels' internal encoding (R' = 2^261), once.  Table mode
-  // (msm_plan.h; ICICLE_SNARK_TABLES=0 disables it): every base array becomes W rows 2^(c·w)·P so that all digits of a
-  // scalar share one bucket set — 13 instead of 16 mixed additions per scalar at 1.6 M constraints for 13× the base memory.
-  // (decided BEFORE the upload since round 5: the cold pipeline below only applies when no table has to be built in here)
-  const int tables_env = env_int("ICICLE_SNARK_TABLES", 1);
+// Coefficient and point buffers, and the jobs that will fill them.
+// Device CSR built by kernels from the raw records (prover/csr.hip); the records travel with the points.
+int alloc_key_buffers(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  const size_t n = c.L.domain, n_coef = c.L.n_coef;
+  c.rec_bytes = n_coef * COEF_RECORD_BYTES;
+  P_HIP(hipMalloc((void**)&c.d_records, c.rec_bytes ? c.rec_bytes : 4));
+  P_HIP(hipMalloc((void**)&z->d_rowptr, (2 * n + 1) * 4));
+  P_HIP(hipMalloc((void**)&z->d_cols, (n_coef ? n_coef : 1) * 4));
+  P_HIP(hipMalloc((void**)&z->d_vals, (n_coef ? n_coef : 1) * 32));
+  z->device_bytes += (2 * n + 1) * 4 + n_coef * 36;
+  if (c.rec_bytes) c.jobs.push_back({c.d_records, c.L.records(), c.rec_bytes});
+  c.lap("header + coefficient buffers");
+  // bases (sections 5-9), this shard's point ranges only (shard_ranges.h)
+  const ShardRanges& r = c.rg;
+  z->A.lo = z->B1.lo = z->B2.lo = r.wlo;
+  z->A.hi = z->B1.hi = z->B2.hi = r.whi;
+  z->C.lo = r.clo;
+  z->C.hi = r.chi;
+  z->H.lo = r.hlo;
+  z->H.hi = r.hhi;
+  z->H.stride = r.h_stride;
+  z->H.first = r.h_first;
+  for (const BaseArray& b : BASES) {
+    Shard& sh = b.of(z);
+    const Section* sec = c.L.sec[b.section];
+    const size_t bytes = (size_t)sh.len() * b.elem();
+    const bool whole = b.h && r.h_strided; // the whole section is uploaded once and the class is gathered on the device (ingest)
+    if (whole) P_HIP(hipMalloc(&c.h_full, (size_t)sec->size));
+    P_HIP(hipMalloc(&sh.d_points, bytes ? bytes : 256));
+    z->device_bytes += bytes;
+    if (whole) c.jobs.push_back({c.h_full, sec->p, (size_t)sec->size});
+    else if (bytes) c.jobs.push_back({sh.d_points, sec->p + (size_t)sh.lo * b.elem(), bytes});
+  }
+  c.lap("point buffers (hipMalloc)");
+  return 0;
+}
+
+// Tables or classic layout, the tables deferred or not, the load pipelined or not.
+// Table mode (msm_plan.h; ICICLE_SNARK_TABLES=0 disables it): every base array becomes W rows 2^(c·w)·P so that all digits of a
+// scalar share one bucket set — 13 instead of 16 mixed additions per scalar at 1.6 M constraints for 13× the base memory.
+// (decided BEFORE the upload since round 5: the cold pipeline only applies when no table has to be built in the load)
+int decide_layout(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  const int tables_env = env_int("ICICLE_SNARK_TABLES", 1); // (this and the next knob: read per load, tests toggle them)
   bool tables = tables_env != 0;
   // Above 2^22 points the 32-bit sort entry has no room for 20-bit digits beside the point index (msm_sort.hip: tab_low_bits):
   // the tables would fall back to c = 19 / 14 digits, and measured at 6.4 M constraints (domain 2^23) that is no faster than the
@@ -616,9 +590,9 @@ int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int co
     size_t free_b = 0, total_b = 0;
     release_cached_device_memory(); // blocks parked by icicle_free count as free
     P_HIP(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t ww = (uint64_t)z->geom_w.W, wh = (uint64_t)z->geom_h.W, wb = ww;
-    const uint64_t need = ww * ((uint64_t)z->A.len() * 64 + (uint64_t)z->C.len() * 64) + wb * (uint64_t)z->B1.len() * (64 + 128) + wh * (uint64_t)z->H.len() * 64 +
-                          wb * (uint64_t)z->B2.len() * (192 + 64) + ((uint64_t)n * 128 + (uint64_t)z->n_vars * 32 + (64u << 20));
+    const uint64_t ww = (uint64_t)z->geom_w.W, wh = (uint64_t)z->geom_h.W;
+    const uint64_t need = ww * witness_row_bytes(z) + wh * (uint64_t)z->H.len() * 64 + ww * (uint64_t)z->B2.len() * (192 + 64) +
+                          ((uint64_t)c.L.domain * 128 + (uint64_t)z->n_vars * 32 + (64u << 20));
     if (need > free_b) {
       tables = false;
       z->geom_w = msm_geometry(z->A.len(), 0, 0);
@@ -626,133 +600,153 @@ int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int co
     }
   }
   const bool defer_env = env_int("ICICLE_SNARK_DEFER_TABLES", 1) != 0;
-  const bool defer = tables && defer_tables && defer_env && count == 1;
-  // cold pipeline: the caller's prove starts while the sections are still on their way (nothing in here needs their contents then)
-  const bool pipeline = cold != nullptr && count == 1 && !h_strided && (defer || !tables);
-  if (!pipeline) {
-    {
-      const hipStream_t lanes[6] = {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5};
-      if (int rc = staged_upload(device_id, jobs, lanes, 6)) return rc;
-    }
-    if (h_strided) {
-      P_HIP(qap_gather_strided((const fe*)h_full, (fe*)z->H.d_points, 2, z->H.len(), z->H.stride, z->H.first, nullptr));
-      P_HIP(hipStreamSynchronize(nullptr));
-      P_HIP(hipFree(h_full));
-      h_full = nullptr;
-    }
-    lap("staged upload");
-    {
-      uint32_t first_bad = 0;
-      P_HIP(qap_build_csr(d_records, n_coef, n, z->n_vars, z->d_rowptr, z->d_cols, z->d_vals, &first_bad, nullptr));
-      if (first_bad != 0xffffffffu) return fail(ERR_FORMAT, "zkey: coefficient %u out of range", first_bad);
-    }
-    lap("device CSR build");
+  const bool defer = tables && c.defer_tables && defer_env && c.count == 1;
+  // cold pipeline: the caller's prove starts while the sections are still on their way (nothing in the load needs their contents then)
+  c.pipeline = c.cold != nullptr && c.count == 1 && !c.rg.h_strided && (defer || !tables);
+  if (defer) {
+    // the key proves in the classic layout until the worker thread (start_table_thread) has built the tables of these
+    // geometries; adopt_tables swaps them in
+    z->tb.gw = z->geom_w;
+    z->tb.gh = z->geom_h;
+    z->tb.dense_c = z->geom_w.c;
+    // the tables count towards the entry's size from now on (the cache budget admits and evicts keys by device_bytes: a key must not
+    // look small while its tables are still being built)
+    z->tb.pending_bytes = (uint64_t)(z->geom_w.W - 1) * witness_row_bytes(z) + (uint64_t)(z->geom_h.W - 1) * (uint64_t)z->H.len() * 64;
+    z->device_bytes += z->tb.pending_bytes;
+    z->geom_w = msm_geometry(z->A.len(), 0, 0);
+    z->geom_h = msm_geometry(z->H.len(), 0, 0);
+    z->tb.state.store(1);
   }
-  {
-    if (defer) {
-      // the key proves in the classic layout until the worker thread (started at the end of this function) has built the
-      // tables of these geometries; adopt_tables swaps them in
-      z->tb.gw = z->geom_w;
-      z->tb.gh = z->geom_h;
-      z->tb.dense_c = z->geom_w.c;
-      // the tables count towards the entry's size from now on (the cache budget admits and evicts keys by device_bytes: a key must not
-      // look small while its tables are still being built)
-      z->tb.pending_bytes = (uint64_t)(z->geom_w.W - 1) * ((uint64_t)z->A.len() * 64 + (uint64_t)z->B1.len() * 64 + (uint64_t)z->B2.len() * 128 + (uint64_t)z->C.len() * 64) +
-                            (uint64_t)(z->geom_h.W - 1) * (uint64_t)z->H.len() * 64;
-      z->device_bytes += z->tb.pending_bytes;
-      z->geom_w = msm_geometry(z->A.len(), 0, 0);
-      z->geom_h = msm_geometry(z->H.len(), 0, 0);
-      z->tb.state.store(1);
-    }
-    struct Job { Shard* sh; bool g2; const MsmGeom* g; };
-    const Job jobs5[5] = {{&z->A, false, &z->geom_w}, {&z->B1, false, &z->geom_w}, {&z->B2, true, &z->geom_w}, {&z->C, false, &z->geom_w}, {&z->H, false, &z->geom_h}};
-    for (const Job& j : jobs5) {
-      if (pipeline) break; // (the uploader task converts every section as it lands)
-      if (j.g->tab) {
-        void* table = nullptr;
-        P_ICICLE(j.g2 ? msm_g2_build_table(j.sh->d_points, j.sh->len(), 1, *j.g, nullptr, &table) : msm_g1_build_table(j.sh->d_points, j.sh->len(), 1, *j.g, nullptr, &table));
-        P_HIP(hipFree(j.sh->d_points));
-        j.sh->d_points = table;
-        z->device_bytes += (uint64_t)j.sh->len() * (j.g->W - 1) * (j.g2 ? 128 : 64);
-      } else {
-        P_ICICLE(j.g2 ? msm_g2_points_to_internal(j.sh->d_points, j.sh->len(), 1, nullptr) : msm_g1_points_to_internal(j.sh->d_points, j.sh->len(), 1, nullptr));
-      }
+  return 0;
+}
+
+// the sections over the key's six streams, the strided H gathered, the CSR built (a load that is not pipelined)
+int ingest(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  if (int rc = staged_upload(c.device_id, c.jobs, z->streams().data(), 6)) return rc;
+  if (c.rg.h_strided) {
+    P_HIP(qap_gather_strided((const fe*)c.h_full, (fe*)z->H.d_points, 2, z->H.len(), z->H.stride, z->H.first, nullptr));
+    P_HIP(hipStreamSynchronize(nullptr));
+    P_HIP(hipFree(c.h_full));
+    c.h_full = nullptr;
+  }
+  c.lap("staged upload");
+  uint32_t first_bad = 0;
+  P_HIP(qap_build_csr(c.d_records, c.L.n_coef, c.L.domain, z->n_vars, z->d_rowptr, z->d_cols, z->d_vals, &first_bad, nullptr));
+  if (first_bad != 0xffffffffu) return fail(ERR_FORMAT, "zkey: coefficient %u out of range", first_bad);
+  c.lap("device CSR build");
+  return 0;
+}
+
+// bases: the file's Montgomery form (R = 2^256) → the bucket kernels' internal encoding (R' = 2^261), once — in place, or as
+// the rows of a table.  (Pipelined: the uploader task converts every section as it lands.)
+int convert_bases(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  for (const BaseArray& b : BASES) {
+    if (c.pipeline) break;
+    Shard& sh = b.of(z);
+    const MsmGeom& g = b.geom(z->geom_w, z->geom_h);
+    if (g.tab) {
+      void* table = nullptr;
+      P_ICICLE(build_table(b.g2, sh, 1, g, nullptr, &table));
+      P_HIP(hipFree(sh.d_points));
+      sh.d_points = table;
+      z->device_bytes += (uint64_t)sh.len() * (g.W - 1) * b.elem();
+    } else {
+      P_ICICLE(points_to_internal(b.g2, sh, 1, nullptr));
     }
   }
   P_HIP(hipStreamSynchronize(nullptr));
-  lap("points to internal form / tables");
+  c.lap("points to internal form / tables");
+  return 0;
+}
 
+int alloc_work_buffers(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  const size_t n = c.L.domain;
   // room for shard_count equal slices (groth16_upload_witness_slice: the in-place all-gather wants equal counts)
-  P_HIP(hipMalloc((void**)&z->d_witness, (size_t)witness_slice_elems(z->n_vars, count) * count * 32));
-  P_HIP(hipMalloc((void**)&z->d_vec, (size_t)n * 3 * 32));
+  P_HIP(hipMalloc((void**)&z->d_witness, (size_t)witness_slice_elems(z->n_vars, c.count) * c.count * 32));
+  P_HIP(hipMalloc((void**)&z->d_vec, n * 3 * 32));
   if (z->H.stride > 1) P_HIP(hipMalloc((void**)&z->d_fold, (size_t)z->H.len() * 3 * 32));
   P_HIP(hipMalloc((void**)&z->d_partials, 5 * PARTIALS_STRIDE));
   P_HIP(hipHostMalloc((void**)&z->h_partials, 5 * PARTIALS_STRIDE + 64)); // + the sort statistics read back per prove (h_stats)
   z->h_stats = reinterpret_cast<uint32_t*>(z->h_partials + 5 * PARTIALS_STRIDE);
   z->h_stats[0] = z->h_stats[1] = 0;
   z->geom_w_default_c = z->geom_w.c;
-  z->device_bytes += (size_t)z->n_vars * 32 + (size_t)n * 96;
-  {
-    // the first host→device copy on a stream sets up its DMA queue (milliseconds, measured 20 ms over six streams): the
-    // ingest above has done that for every stream it used as a lane; a key of a few chunks leaves some untouched
-    const hipStream_t all[6] = {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5};
-    for (hipStream_t st : all) P_HIP(hipMemcpyAsync(z->d_partials, z->h_partials, 4096, hipMemcpyHostToDevice, st));
-    for (hipStream_t st : all) P_HIP(hipStreamSynchronize(st));
-  }
-  P_HIP(hipEventCreateWithFlags(&z->ev_witness, hipEventDisableTiming));
-  P_HIP(hipEventCreateWithFlags(&z->ev_sort, hipEventDisableTiming));
-  P_HIP(hipEventCreateWithFlags(&z->ev_sort_h, hipEventDisableTiming));
-  P_HIP(hipEventCreateWithFlags(&z->ev_own_slice, hipEventDisableTiming));
-  P_HIP(hipEventCreateWithFlags(&z->ev_head_in, hipEventDisableTiming));
-  P_HIP(hipEventCreateWithFlags(&z->ev_head_done, hipEventDisableTiming));
-  P_HIP(hipEventCreate(&z->ev_t_head_start));
-  P_HIP(hipEventCreate(&z->ev_t_head_end));
-  P_HIP(hipEventCreate(&z->ev_t_witness));
+  z->device_bytes += (size_t)z->n_vars * 32 + n * 96;
+  // the first host→device copy on a stream sets up its DMA queue (milliseconds, measured 20 ms over six streams): the
+  // ingest has done that for every stream it used as a lane; a key of a few chunks leaves some untouched
+  for (hipStream_t st : z->streams()) P_HIP(hipMemcpyAsync(z->d_partials, z->h_partials, 4096, hipMemcpyHostToDevice, st));
+  for (hipStream_t st : z->streams()) P_HIP(hipStreamSynchronize(st));
+  for (hipEvent_t* e : {&z->ev_witness, &z->ev_sort, &z->ev_sort_h, &z->ev_own_slice, &z->ev_head_in, &z->ev_head_done}) P_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  for (hipEvent_t* e : {&z->ev_t_head_start, &z->ev_t_head_end, &z->ev_t_witness}) P_HIP(hipEventCreate(e));
   for (auto& e : z->ev) P_HIP(hipEventCreate(&e));
   for (auto& e : z->ev_done) P_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : z->ev_lfork) P_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : z->ev_ljoin) P_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  lap("work buffers, events");
-  out = std::move(z);
-  if (pipeline) {
-    // the uploader task (a pooled worker; inline when none can be had: then everything has arrived when this returns)
-    ZKeyCache* zz = out.get();
-    for (auto& e : cold->feed.ev) P_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& st : cold->lanes) P_ICICLE(icicle_create_stream((icicleStreamHandle*)&st));
-    ColdPlan* pl = new ColdPlan();
-    pl->cu = cold;
-    pl->z = zz;
-    pl->device_id = device_id;
-    pl->d_records = d_records;
-    pl->rec_bytes = rec_bytes;
-    pl->rec_src = s4->p + 4;
-    pl->n_coef = n_coef;
-    const Section* psec[5] = {s5, s6, s7, s8, s9};
-    Shard* sh5[5] = {&zz->A, &zz->B1, &zz->B2, &zz->C, &zz->H};
-    for (int k = 0; k < 5; k++) {
-      const size_t esz = k == 2 ? 128 : 64;
-      pl->sec[k] = {sh5[k]->d_points, psec[k]->p + (size_t)sh5[k]->lo * esz, (size_t)sh5[k]->len() * esz};
-    }
-    free_records.p = nullptr; // the records belong to the task now (freed behind the CSR build)
-    zz->feed = &cold->feed;
-    zz->tb.hold.store(true, std::memory_order_release); // the deferred table build reads the base arrays: not before they are complete
-    cold->task.fn = [pl] { cold_upload_task(pl); };
-    cold->started = true;
-    WorkerPool::get().run_or_inline(&cold->task);
-    lap("cold upload task started");
+  c.lap("work buffers, events");
+  return 0;
+}
+
+// the uploader task (a pooled worker; inline when none can be had: then everything has arrived when this returns).  `z` is the
+// entry in its final place.
+int start_cold_upload(LoadCtx& c, ZKeyCache* z)
+{
+  ColdUpload* cold = c.cold;
+  for (auto& e : cold->feed.ev) P_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (auto& st : cold->lanes) P_ICICLE(icicle_create_stream((icicleStreamHandle*)&st));
+  // (the records belong to the task from here on: freed behind the CSR build)
+  ColdPlan* pl = new ColdPlan{cold, z, c.device_id, std::exchange(c.d_records, nullptr), c.rec_bytes, c.L.records(), c.L.n_coef, {}};
+  for (int k = 0; k < 5; k++) {
+    const Shard& sh = BASES[k].of(z);
+    const size_t esz = BASES[k].elem();
+    pl->sec[k] = {sh.d_points, c.L.sec[BASES[k].section]->p + (size_t)sh.lo * esz, (size_t)sh.len() * esz};
   }
-  // (the entry does not move any more: the worker keeps a pointer to it and ~ZKeyCache joins the worker)
-  if (out->tb.state.load() == 1) {
-    try {
-      out->tb.th = std::thread(table_build_thread, out.get());
-    } catch (...) {
-      // no thread to be had: the key keeps the classic layout — and gives back what was counted for tables that will not come
-      out->tb.state.store(0);
-      out->device_bytes -= out->tb.pending_bytes;
-      out->tb.pending_bytes = 0;
-      out->tb.hold.store(false, std::memory_order_release);
-    }
+  z->feed = &cold->feed;
+  z->tb.hold.store(true, std::memory_order_release); // the deferred table build reads the base arrays: not before they are complete
+  cold->task.fn = [pl] { cold_upload_task(pl); };
+  cold->started = true;
+  WorkerPool::get().run_or_inline(&cold->task);
+  c.lap("cold upload task started");
+  return 0;
+}
+
+// the deferred table build (the entry does not move any more: the worker keeps a pointer to it and ~ZKeyCache joins the worker)
+void start_table_thread(ZKeyCache* z)
+{
+  if (z->tb.state.load() != 1) return;
+  try {
+    z->tb.th = std::thread(table_build_thread, z);
+  } catch (...) {
+    // no thread to be had: the key keeps the classic layout — and gives back what was counted for tables that will not come
+    z->tb.state.store(0);
+    z->device_bytes -= z->tb.pending_bytes;
+    z->tb.pending_bytes = 0;
+    z->tb.hold.store(false, std::memory_order_release);
   }
+}
+} // namespace
+
+// 0 ≤ rank < count (groth16_cache_load checks what a caller passes).  The key was validated by zkey_layout: nothing in here is a
+// format error but a coefficient out of range, which the CSR build finds on the device.
+int build_cache(const ZkeyLayout& L, int device_id, int rank, int count, std::unique_ptr<ZKeyCache>& out, bool defer_tables, ColdUpload* cold)
+{
+  LoadCtx c{L, device_id, rank, count, defer_tables, cold, shard_ranges(L.n_vars, L.n_public, L.domain, rank, count), std::unique_ptr<ZKeyCache>(new ZKeyCache())};
+  fill_header(c.z.get(), c);
+  if (int rc = open_streams(c)) return rc;
+  if (int rc = alloc_key_buffers(c)) return rc;
+  if (int rc = decide_layout(c)) return rc;
+  if (!c.pipeline)
+    if (int rc = ingest(c)) return rc;
+  if (int rc = convert_bases(c)) return rc;
+  if (int rc = alloc_work_buffers(c)) return rc;
+  out = std::move(c.z);
+  if (c.pipeline)
+    if (int rc = start_cold_upload(c, out.get())) return rc;
+  start_table_thread(out.get());
   return 0;
 }
 
@@ -790,19 +784,15 @@ int rebuild_witness_tables(ZKeyCache* z, int c_new)
   // the one-by-one swap left A and B1 in the new geometry when B2's build failed).  Memory: the four new tables plus the
   // temporaries of the largest build (projective rows + inversion scratch of the G2 set); when the device cannot hold that
   // next to the old tables the key simply keeps its width.
-  struct Job { Shard* sh; bool g2; };
-  const Job jobs[4] = {{&z->A, false}, {&z->B1, false}, {&z->B2, true}, {&z->C, false}};
   size_t free_b = 0, total_b = 0;
   release_cached_device_memory();
   P_HIP(hipMemGetInfo(&free_b, &total_b));
-  uint64_t need = (uint64_t)z->B2.len() * g.W * (192 + 64) + (64u << 20);
-  for (const Job& j : jobs) need += (uint64_t)j.sh->len() * g.W * (j.g2 ? 128 : 64);
+  const uint64_t need = (uint64_t)g.W * witness_row_bytes(z) + (uint64_t)z->B2.len() * g.W * (192 + 64) + (64u << 20);
   if (need > free_b) return 0;
   void* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < 4; k++) {
-    const Job& j = jobs[k];
+  for (int k = 0; k < 4; k++) { // (BASES[4] is H: it stays)
     // row 0 of the old table = the bases themselves, in the internal encoding (form 2)
-    const eIcicleError e = j.g2 ? msm_g2_build_table(j.sh->d_points, j.sh->len(), 2, g, nullptr, &fresh[k]) : msm_g1_build_table(j.sh->d_points, j.sh->len(), 2, g, nullptr, &fresh[k]);
+    const eIcicleError e = build_table(BASES[k].g2, BASES[k].of(z), 2, g, nullptr, &fresh[k]);
     if (e != ICICLE_SUCCESS) {
       (void)hipGetLastError();
       for (void* t : fresh)
@@ -813,10 +803,10 @@ int rebuild_witness_tables(ZKeyCache* z, int c_new)
     }
   }
   for (int k = 0; k < 4; k++) {
-    const Job& j = jobs[k];
-    (void)hipFree(j.sh->d_points); // (a synchronising free: nothing of a prove is in flight here)
-    j.sh->d_points = fresh[k];
-    z->device_bytes += (int64_t)j.sh->len() * ((int64_t)g.W - (int64_t)z->geom_w.W) * (j.g2 ? 128 : 64);
+    Shard& sh = BASES[k].of(z);
+    (void)hipFree(sh.d_points); // (a synchronising free: nothing of a prove is in flight here)
+    sh.d_points = fresh[k];
+    z->device_bytes += (int64_t)sh.len() * ((int64_t)g.W - (int64_t)z->geom_w.W) * (int64_t)BASES[k].elem();
   }
   z->geom_w = g;
   return 0;

@@ -64,8 +64,8 @@ int unique_section(const std::vector<Section>& s, size_t id, const Section** sec
   return 0;
 }
 
-// sections and header of a zkey, with the size checks of build_cache (cache.cpp); `secs` keeps the section table alive
-int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L)
+// sections and header of a zkey (prover_internal.h: ZkeyLayout) — the only code that knows the container's and the header's rules
+int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, bool need_ic)
 {
   if (!data) return fail(ERR_ARG, "null zkey");
   if (int rc = read_sections(data, len, "zkey", 2, secs)) return rc;
@@ -73,35 +73,39 @@ int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Zke
   if (int rc = unique_section(secs, 1, &s1)) return rc;
   uint32_t protocol = 0;
   if (s1->size >= 4) memcpy(&protocol, s1->p, 4);
-  if (protocol != 1) return fail(ERR_FORMAT, "Protocol not supported");
-  for (int id : {2, 3, 4, 5, 6, 7, 8, 9})
+  if (protocol != 1) return fail(ERR_FORMAT, "Protocol not supported"); // GROTH16_PROTOCOL_ID, file_wrapper.rs:12,196-207
+  for (int id : {2, 3, 4, 5, 6, 7, 8, 9}) {
+    if (id == 3 && !need_ic) {
+      L->sec[3] = secs[3].count == 1 ? &secs[3] : nullptr; // (read_sections makes room for the ids below 16)
+      continue;
+    }
     if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
+  }
+  // read_header_groth16 — src/zkey.rs:47-85
   const Section* s2 = L->sec[2];
   const uint8_t* h = s2->p;
   if (s2->size < 4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128) return fail(ERR_FORMAT, "zkey header too short");
-  uint32_t n8q, n8r;
-  fe q, r;
-  memcpy(&n8q, h, 4);
-  if (n8q != 32) return fail(ERR_FORMAT, "zkey: unsupported base field size");
-  memcpy(q.l, h + 4, 32);
-  memcpy(&n8r, h + 36, 4);
-  if (n8r != 32) return fail(ERR_FORMAT, "zkey: unsupported scalar field size");
-  memcpy(r.l, h + 40, 32);
+  memcpy(&L->n8q, h, 4);
+  if (L->n8q != 32) return fail(ERR_FORMAT, "zkey: unsupported base field size");
+  memcpy(L->q.l, h + 4, 32);
+  memcpy(&L->n8r, h + 36, 4);
+  if (L->n8r != 32) return fail(ERR_FORMAT, "zkey: unsupported scalar field size");
+  memcpy(L->r.l, h + 40, 32);
   memcpy(&L->n_vars, h + 72, 4);
   memcpy(&L->n_public, h + 76, 4);
   memcpy(&L->domain, h + 80, 4);
-  if (!Fq::eq(q, Fq::modulus()) || !Fr::eq(r, Fr::modulus())) return fail(ERR_FORMAT, "zkey: not a BN254 key");
+  if (!Fq::eq(L->q, Fq::modulus()) || !Fr::eq(L->r, Fr::modulus())) return fail(ERR_FORMAT, "zkey: not a BN254 key");
   const uint32_t n = L->domain;
   if (n == 0 || (n & (n - 1))) return fail(ERR_FORMAT, "zkey: domain size %u is not a power of two", n);
   if (L->n_public + 1 > L->n_vars) return fail(ERR_FORMAT, "zkey: n_public exceeds n_vars");
   L->header_points = h + 84;
-  const size_t rec = 12 + 32;
+  // coefficients (section 4): a declared count, then the records — src/cache.rs:126-166
   const Section* s4 = L->sec[4];
-  if (s4->size < 4 || (s4->size - 4) % rec) return fail(ERR_FORMAT, "zkey: coefficient section size");
-  if ((s4->size - 4) / rec > 0xffffffffull) return fail(ERR_FORMAT, "zkey: too many coefficients");
-  L->n_coef = (uint32_t)((s4->size - 4) / rec);
+  if (s4->size < 4 || (s4->size - 4) % COEF_RECORD_BYTES) return fail(ERR_FORMAT, "zkey: coefficient section size");
+  if ((s4->size - 4) / COEF_RECORD_BYTES > 0xffffffffull) return fail(ERR_FORMAT, "zkey: too many coefficients");
+  L->n_coef = (uint32_t)((s4->size - 4) / COEF_RECORD_BYTES);
   const uint64_t nv = L->n_vars, np1 = (uint64_t)L->n_public + 1;
-  if (L->sec[3]->size != np1 * 64 || L->sec[5]->size != nv * 64 || L->sec[6]->size != nv * 64 || L->sec[7]->size != nv * 128 || L->sec[8]->size != (nv - np1) * 64 ||
+  if ((need_ic && L->sec[3]->size != np1 * 64) || L->sec[5]->size != nv * 64 || L->sec[6]->size != nv * 64 || L->sec[7]->size != nv * 128 || L->sec[8]->size != (nv - np1) * 64 ||
       L->sec[9]->size != (uint64_t)n * 64)
     return fail(ERR_FORMAT, "zkey: point section size mismatch");
   return 0;

@@ -445,6 +445,9 @@ int group_load(Groth16CacheManager* cm, const char* key, const uint8_t* zkey, si
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail((int)ICICLE_INVALID_DEVICE, "no HIP device available (this library has no CPU fallback)");
   for (int d : devs)
     if (d < 0 || d >= ndev) return fail((int)ICICLE_INVALID_DEVICE, "device %d of the group does not exist (%d visible)", d, ndev);
+  std::vector<Section> secs; // the key is read once for all the shards
+  ZkeyLayout L;
+  if (int rc = zkey_layout(zkey, len, secs, &L, /*need_ic=*/false)) return rc;
   std::shared_ptr<DeviceGroup> g(new DeviceGroup());
   g->devs = devs;
   g->shards.resize(G);
@@ -467,7 +470,7 @@ int group_load(Groth16CacheManager* cm, const char* key, const uint8_t* zkey, si
         for (int r = 0; r < G; r++) {
           if (devs[r] != d || st.failed) continue;
           std::unique_ptr<ZKeyCache> z;
-          const int rc = build_cache(zkey, len, d, r, G, z);
+          const int rc = build_cache(L, d, r, G, z);
           st.note(rc);
           if (!rc) {
             z->in_group = true;

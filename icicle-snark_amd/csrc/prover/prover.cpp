@@ -210,16 +210,15 @@ __attribute__((visibility("default"))) int groth16_cache_load(Groth16CacheManage
   if (find(cm, key) || find_group(cm, key)) return 0;
   if (cm->warm.joinable()) cm->warm.join(); // (what it creates is what the build below would create itself)
   evict_for_budget(cm, device_id, estimate_entry_bytes(zkey_len) / (uint64_t)(shard_count > 0 ? shard_count : 1));
+  if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(ERR_ARG, "bad shard %d/%d", shard_rank, shard_count);
+  // the container and the header are validated before the device is touched (a malformed key is a format error on any host)
+  std::vector<Section> secs;
+  ZkeyLayout L;
+  if (int rc = zkey_layout((const uint8_t*)zkey, zkey_len, secs, &L, /*need_ic=*/false)) return rc;
   std::unique_ptr<ZKeyCache> z;
   // The NTT domain of the key (twiddle tables of 2·domain_size roots: 9–13 ms at 1.6 M constraints) is set up on a helper
   // thread WHILE the sections cross PCIe — the GPU has nothing else to do then — instead of inside the first prove.
-  uint32_t dom_n = 0;
-  {
-    std::vector<Section> secs;
-    const Section* s2 = nullptr;
-    if (read_sections((const uint8_t*)zkey, zkey_len, "zkey", 2, secs) == 0 && unique_section(secs, 2, &s2) == 0 && s2->size >= 84) memcpy(&dom_n, s2->p + 80, 4);
-    if (dom_n == 0 || (dom_n & (dom_n - 1)) || dom_n > (1u << 27)) dom_n = 0; // (a malformed header is build_cache's to report)
-  }
+  const uint32_t dom_n = L.domain <= (1u << 27) ? L.domain : 0;
   std::thread dom_th;
   if (dom_n && shard_count == 1) {
     try {
@@ -230,7 +229,7 @@ __attribute__((visibility("default"))) int groth16_cache_load(Groth16CacheManage
     }
   }
   // the fixed-base tables of a single-device key are built behind its first proofs (cache.cpp: TableBuild)
-  const int brc = build_cache((const uint8_t*)zkey, zkey_len, device_id, shard_rank, shard_count, z, /*defer_tables=*/true);
+  const int brc = build_cache(L, device_id, shard_rank, shard_count, z, /*defer_tables=*/true);
   if (dom_th.joinable()) dom_th.join();
   if (brc) return brc;
   std::shared_ptr<ZKeyCache> zp(z.release());
@@ -412,7 +411,7 @@ struct DrainOnError {
   ~DrainOnError()
   {
     if (!armed) return;
-    for (hipStream_t st : {z->s_qap, z->s_g1, z->s_g2, z->s_g3, z->s_g4, z->s_g5})
+    for (hipStream_t st : z->streams())
       if (st) (void)hipStreamSynchronize(st);
   }
 };
@@ -1360,16 +1359,12 @@ static int cold_prove(Groth16CacheManager* cm, const std::string& key, const Map
   // the witness must fit the key BEFORE anything of it is sent: n_vars of the header (src/zkey.rs:47-85) against the .wtns header
   Wtns w;
   if (parse_wtns(wf.data, wf.len, w)) return COLD_DECLINED;
-  uint32_t n_vars = 0, dom_n = 0, n_public = 0;
-  {
-    std::vector<Section> secs;
-    const Section* s2 = nullptr;
-    if (read_sections(zf.data, zf.len, "zkey", 2, secs) != 0 || unique_section(secs, 2, &s2) != 0 || s2->size < 84) return COLD_DECLINED;
-    memcpy(&n_vars, s2->p + 72, 4);
-    memcpy(&n_public, s2->p + 76, 4);
-    memcpy(&dom_n, s2->p + 80, 4);
-    if (w.n_witness != n_vars || dom_n == 0 || (dom_n & (dom_n - 1)) || dom_n > (1u << 27) || memcmp(w.q.l, s2->p + 40, 32) != 0) return COLD_DECLINED;
-  }
+  // (a malformed key declines too: the load that follows reports it)
+  std::vector<Section> secs;
+  ZkeyLayout L;
+  if (zkey_layout(zf.data, zf.len, secs, &L, /*need_ic=*/false)) return COLD_DECLINED;
+  if (w.n_witness != L.n_vars || L.domain > (1u << 27) || !Fr::eq(w.q, L.r)) return COLD_DECLINED;
+  const uint32_t dom_n = L.domain, n_public = L.n_public;
   const auto t0 = std::chrono::steady_clock::now();
   std::unique_lock<std::mutex> lk(cm->mu);
   if (find(cm, key.c_str()) || find_group(cm, key.c_str())) return COLD_DECLINED; // (somebody else loaded it meanwhile)
@@ -1389,7 +1384,7 @@ static int cold_prove(Groth16CacheManager* cm, const std::string& key, const Map
   cu.zkey_base = zf.data; cu.zkey_len = zf.len; cu.zkey_fd = zf.fd;
   cu.wtns_base = wf.data; cu.wtns_len = wf.len; cu.wtns_fd = wf.fd;
   std::unique_ptr<ZKeyCache> zu;
-  const int brc = build_cache(zf.data, zf.len, device_id, 0, 1, zu, /*defer_tables=*/true, &cu);
+  const int brc = build_cache(L, device_id, 0, 1, zu, /*defer_tables=*/true, &cu);
   if (brc) {
     cold_upload_wait(&cu);
     if (dom_th.joinable()) dom_th.join();

@@ -7,6 +7,7 @@
 //   assemble.cpp    blinding, affine conversion, JSON       ← src/proof_helper.rs:274-316, src/conversions.rs:30-56
 //   multi.cpp       the same prove over a GROUP of devices in one process (device string "HIP:0-7"), SURVEY.md §8e
 #pragma once
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -27,6 +28,7 @@
 #include "../workers.h"
 #include "cold_feed.h"
 #include "qap.h"
+#include "shard_ranges.h"
 
 namespace isnark {
 const bn254::fe* ntt_domain_table(int* log_n); // ntt.hip
@@ -63,14 +65,23 @@ struct Section {
 };
 int read_sections(const uint8_t* data, size_t len, const char* type, uint32_t max_version, std::vector<Section>& out);
 int unique_section(const std::vector<Section>& s, size_t id, const Section** sec);
-// what a zkey says about itself: the sections 2 … 9 and the header's sizes, checked as build_cache checks them (protocol, field
-// sizes and moduli, a power-of-two domain, every section's length).  `secs` owns the table L->sec points into.
+// What a zkey says about itself: the sections 2 … 9 and the header's fields.  zkey_layout is the ONE statement of the container
+// and header rules — the loader (build_cache), the key check and the vk export all read a key through it.  Checked, in this
+// order: section 1 and the protocol; sections 2, (3,) 4 … 9 present once; header length, field sizes, moduli, a power-of-two
+// domain, n_public; the coefficient section's size and count (n_coef comes from the section's length — the declared count in its
+// first four bytes is not read, like src/cache.rs:129); the point sections' sizes.  Unknown sections are ignored.
+// `need_ic`: section 3 (IC) is part of the checks, as the key check and the vk export want it; the prover does not read it and
+// loads keys without it (need_ic = false: sec[3] is the section when there is exactly one, else null, and nothing of it is checked).
+// `secs` owns the table L->sec points into; all pointers lead into the caller's `data`.
+constexpr size_t COEF_RECORD_BYTES = 12 + 32;
 struct ZkeyLayout {
-  uint32_t n_vars = 0, n_public = 0, domain = 0, n_coef = 0;
+  uint32_t n8q = 0, n8r = 0, n_vars = 0, n_public = 0, domain = 0, n_coef = 0;
+  fe q, r;
   const uint8_t* header_points = nullptr; // α₁ β₁ β₂ γ₂ δ₁ δ₂: 64 / 128 bytes each, Montgomery form
   const Section* sec[10] = {};
+  const uint8_t* records() const { return sec[4]->p + 4; } // n_coef × COEF_RECORD_BYTES: {m:u32 c:u32 s:u32 value[32]}, src/cache.rs:126-166
 };
-int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L);
+int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, bool need_ic = true);
 struct MappedFile {
   const uint8_t* data = nullptr;
   size_t len = 0;
@@ -172,11 +183,9 @@ struct ZKeyCache {
   TableBuild tb;                         // deferred fixed-base tables (single-device keys)
   ColdFeed* feed = nullptr;              // set for the ONE prove that runs while the key's sections are still arriving (cold pipeline)
 
+  std::array<hipStream_t, 6> streams() const { return {s_qap, s_g1, s_g2, s_g3, s_g4, s_g5}; }
   ~ZKeyCache();
 };
-
-// elements per rank when the witness is uploaded in shard_count slices
-inline uint64_t witness_slice_elems(uint32_t n_vars, int count) { return ((uint64_t)n_vars + count - 1) / count; }
 
 // digit width of the witness MSMs adapted to the witnesses seen (cache.cpp)
 int witness_digit_target(const ZKeyCache* z, uint64_t entries);
@@ -191,7 +200,11 @@ int follow_witness(ZKeyCache* z, bool sync);
 // `wait`: block until the build has ended.  Swaps complete tables in; the caller holds the manager's mutex (no prove in flight).
 int adopt_tables(ZKeyCache* z, bool wait);
 
-// CacheManager::compute — src/cache.rs:117-241.  `defer_tables`: return once the key can prove in the classic layout and build
+// CacheManager::compute — src/cache.rs:117-241, from a key that zkey_layout has read (a load, every shard of a device group and the
+// cold prove parse once and hand the layout on).  A row of stages over one LoadCtx (cache.cpp): fill_header → open_streams →
+// alloc_key_buffers (shard_ranges.h) → decide_layout → ingest (not when pipelined) → convert_bases → alloc_work_buffers →
+// start_cold_upload / start_table_thread.
+// `defer_tables`: return once the key can prove in the classic layout and build
 // the fixed-base tables on a worker thread (single-device keys; ICICLE_SNARK_DEFER_TABLES=0 builds them before returning)
 // `cold` (single-device keys with deferred or no tables): return as soon as the buffers exist and an uploader task has been started —
 // the sections, the CSR and the witness of `cold->wtns` arrive behind the stages of cold->feed; the caller waits for cold->task
@@ -210,7 +223,7 @@ struct ColdUpload {
   bool started = false;
 };
 void cold_upload_wait(ColdUpload* cu); // blocks until the uploader task has ended (no-op when it never started); returns its lanes to the pool
-int build_cache(const uint8_t* data, size_t len, int device_id, int rank, int count, std::unique_ptr<ZKeyCache>& out, bool defer_tables = false, ColdUpload* cold = nullptr);
+int build_cache(const ZkeyLayout& L, int device_id, int rank, int count, std::unique_ptr<ZKeyCache>& out, bool defer_tables = false, ColdUpload* cold = nullptr);
 typedef CopyJob UploadJob;
 int staged_upload(int device_id, const std::vector<UploadJob>& jobs, const hipStream_t* lanes_in = nullptr, int n_lanes = 0, StagedProgress* progress = nullptr);
 

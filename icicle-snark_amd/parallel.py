@@ -2,8 +2,8 @@
 
 One process per GPU (torchrun / torch.distributed gives rank, world size and the rendezvous).  Every rank
 builds a cache holding only its range of each base array — the witness slice it uploads itself, [rank·⌈L/W⌉, (rank+1)·⌈L/W⌉), when that
-leaves no rank empty, else [rank·L/W, (rank+1)·L/W) — (C++: build_cache in
-csrc/prover/cache.cpp — `shard_range` below is the same arithmetic), runs the replicated QAP/NTT front end
+leaves no rank empty, else [rank·L/W, (rank+1)·L/W) — (C++: shard_ranges in
+csrc/prover/shard_ranges.h — `shard_range` below is the same arithmetic), runs the replicated QAP/NTT front end
 and its five partial MSMs, then all ranks all-gather their 576-byte commitment blocks and sum them with
 the group law.  The data-path collective is RCCL over xGMI (csrc/comm/rccl_comm.cpp) driven by this
 library's own HIP runtime; torch.distributed (gloo) is only the control plane that broadcasts the
@@ -43,7 +43,7 @@ def preload_rccl():
 
 
 def shard_range(total: int, rank: int, world: int):
-    """range of rank `rank` of `world` (csrc/prover/cache.cpp: build_cache): the slice of ⌈total / world⌉ elements the rank uploads
+    """range of rank `rank` of `world` (csrc/prover/shard_ranges.h): the slice of ⌈total / world⌉ elements the rank uploads
     itself when that leaves no rank empty, else the even split"""
     s = (total + world - 1) // world
     if world > 1 and s * (world - 1) < total:
