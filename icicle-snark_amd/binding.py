@@ -699,6 +699,8 @@ groth16_verify groth16_verify_json groth16_verify_last_error groth16_group_descr
 groth16_cache_manager_prewarm groth16_verify_batch groth16_verify_batch_last_timings
 groth16_verify_batch_combined groth16_verify_combined_coefficients
 groth16_zkey_check groth16_zkey_check_file
+groth16_r1cs_info groth16_r1cs_load groth16_r1cs_load_file groth16_r1cs_get_info groth16_r1cs_free
+groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -901,6 +903,90 @@ def zkey_export_vk(zkey: bytes) -> str:
     buf = C.create_string_buffer(need)
     f(C.c_char_p(bytes(zkey)), C.c_size_t(len(zkey)), buf, C.c_size_t(need))
     return buf.value.decode()
+
+
+class R1csInfo(C.Structure):
+    """Groth16R1csInfo (include/groth16_prover.h)"""
+    _fields_ = [("n_wires", C.c_uint32), ("n_public", C.c_uint32), ("n_constraints", C.c_uint32), ("n_terms", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("walk_ms", C.c_double), ("upload_ms", C.c_double), ("device_ms", C.c_double)]
+
+
+class WitnessReport(C.Structure):
+    """Groth16WitnessReport: kind / index of the first fault, the counts"""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_uint64), ("noncanonical", C.c_uint64), ("failed", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double)]
+
+
+class MatchReport(C.Structure):
+    """Groth16R1csMatchReport: kind / index of the first fault, the differing rows of A and of B"""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_uint64), ("rows_a", C.c_uint64), ("rows_b", C.c_uint64), ("device_ms", C.c_double)]
+
+
+WTNS_NONCANONICAL, WTNS_ONE, WTNS_CONSTRAINT = 1, 2, 3
+MATCH_SIZES, MATCH_ROW_A, MATCH_ROW_B = 1, 2, 3
+
+
+def _image(data):
+    return data.ctypes.data_as(C.c_void_p) if isinstance(data, np.ndarray) else C.c_char_p(data) if isinstance(data, bytes) else (C.c_char * len(data)).from_buffer(data)
+
+
+def r1cs_info(r1cs: bytes) -> R1csInfo:
+    """groth16_r1cs_info: the counts of an .r1cs after the host walk that bounds every record (host only: needs no GPU)"""
+    info = R1csInfo()
+    _pcheck(lib().groth16_r1cs_info(_image(r1cs), C.c_size_t(len(r1cs)), C.byref(info)), "r1cs_info")
+    return info
+
+
+class R1cs:
+    """An .r1cs (bytes, or a path that is mapped) kept on one GPU: groth16_r1cs_load / groth16_witness_check."""
+
+    def __init__(self, r1cs, device: str = "HIP"):
+        self._h = C.c_void_p()
+        if isinstance(r1cs, (str, os.PathLike)):
+            _pcheck(lib().groth16_r1cs_load_file(os.fsencode(r1cs), device.encode(), C.byref(self._h)), "r1cs_load_file")
+        else:
+            _pcheck(lib().groth16_r1cs_load(_image(r1cs), C.c_size_t(len(r1cs)), device.encode(), C.byref(self._h)), "r1cs_load")
+        self.info = R1csInfo()
+        _pcheck(lib().groth16_r1cs_get_info(self._h, C.byref(self.info)), "r1cs_get_info")
+
+    def _verdict(self, rc, rep, what):
+        if rc not in (0, 1):
+            _pcheck(rc, what)
+        return rc == 1, rep
+
+    def check(self, wtns):
+        """groth16_witness_check → (ok, WitnessReport); wtns: the .wtns image, or a path.  Raises ProverError for a malformed
+        file, a witness of another size or a device error."""
+        rep = WitnessReport()
+        if isinstance(wtns, (str, os.PathLike)):
+            return self._verdict(lib().groth16_witness_check_file(self._h, os.fsencode(wtns), C.byref(rep)), rep, "witness_check_file")
+        return self._verdict(lib().groth16_witness_check(self._h, _image(wtns), C.c_size_t(len(wtns)), C.byref(rep)), rep, "witness_check")
+
+    def match_zkey(self, zkey, seed=None):
+        """groth16_r1cs_match_zkey → (ok, MatchReport): the key's section 4 against this circuit's A and B.  seed: 32 bytes for a
+        reproducible test — leave it None otherwise (a secret, fresh seed is drawn)."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("match_zkey: the seed is 32 bytes")
+        sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+        rep = MatchReport()
+        return self._verdict(lib().groth16_r1cs_match_zkey(self._h, _image(zkey), C.c_size_t(len(zkey)), sd, C.byref(rep)), rep, "r1cs_match_zkey")
+
+    def close(self):
+        if self._h:
+            lib().groth16_r1cs_free(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def sum_commitments(blocks: bytes, count: int) -> bytes:

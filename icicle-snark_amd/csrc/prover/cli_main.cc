@@ -7,6 +7,9 @@
 //   > zkey-check --zkey Z [--device HIP]       every point and record of the key tested on the GPU (groth16_zkey_check): one line per
 //     faulty section, then "sound" or "unsound"
 //   > zkey-export-vk --zkey Z --vk OUT         the key's verification_key.json (groth16_zkey_export_vk)
+//   > wtns-check --r1cs R --wtns W [--device HIP]    does the witness satisfy the circuit (groth16_witness_check): "satisfied", or
+//     the first fault with the counts and "not satisfied"
+//   > r1cs-match --r1cs R --zkey Z [--device HIP]    does the key carry the circuit's A and B (groth16_r1cs_match_zkey)
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -17,7 +20,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -216,6 +219,49 @@ int main()
         if (!o) std::cerr << "zkey-export-vk: cannot write " << vk << std::endl;
         else std::cout << "VK_WRITTEN" << std::endl;
       }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "wtns-check" || cmd == "r1cs-match") {
+      std::string r1cs = "circuit.r1cs", wtns = "witness.wtns", zkey = "circuit_final.zkey", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--r1cs") in >> r1cs;
+        else if (a == "--wtns") in >> wtns;
+        else if (a == "--zkey") in >> zkey;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16R1cs* h = nullptr;
+      int rc = groth16_r1cs_load_file(r1cs.c_str(), device.c_str(), &h);
+      if (rc < 0) {
+        std::cerr << cmd << " failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else if (cmd == "wtns-check") {
+        Groth16WitnessReport rep;
+        rc = groth16_witness_check_file(h, wtns.c_str(), &rep);
+        if (rc < 0) {
+          std::cerr << "wtns-check failed (" << rc << "): " << groth16_last_error() << std::endl;
+        } else {
+          if (rep.kind == GROTH16_WTNS_NONCANONICAL) std::cout << rep.noncanonical << " values not below r, first: wire " << rep.index << std::endl;
+          else if (rep.kind == GROTH16_WTNS_ONE) std::cout << "wire 0 is not 1" << std::endl;
+          if (rep.failed) std::cout << rep.failed << " constraints violated" << (rep.kind == GROTH16_WTNS_CONSTRAINT ? ", first: constraint " + std::to_string(rep.index) : std::string()) << std::endl;
+          std::cout << (rc == 1 ? "satisfied" : "not satisfied") << std::endl;
+        }
+      } else {
+        std::ifstream f(zkey, std::ios::binary);
+        std::ostringstream ss;
+        if (f) ss << f.rdbuf();
+        const std::string image = ss.str();
+        Groth16R1csMatchReport rep;
+        rc = f ? groth16_r1cs_match_zkey(h, image.data(), image.size(), nullptr, &rep) : -1;
+        if (rc < 0) {
+          std::cerr << "r1cs-match failed (" << rc << "): " << (f ? groth16_last_error() : "cannot read the zkey") << std::endl;
+        } else {
+          static const char* const sizes[3] = {"n_vars against nWires", "n_public", "domain_size"};
+          if (rep.kind == GROTH16_MATCH_SIZES) std::cout << "sizes differ: " << sizes[rep.index < 3 ? rep.index : 0] << std::endl;
+          if (rep.rows_a) std::cout << rep.rows_a << " rows of A differ" << (rep.kind == GROTH16_MATCH_ROW_A ? ", first: row " + std::to_string(rep.index) : std::string()) << std::endl;
+          if (rep.rows_b) std::cout << rep.rows_b << " rows of B differ" << (rep.kind == GROTH16_MATCH_ROW_B ? ", first: row " + std::to_string(rep.index) : std::string()) << std::endl;
+          std::cout << (rc == 1 ? "match" : "no match") << std::endl;
+        }
+      }
+      groth16_r1cs_free(h);
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {
       print_help();

@@ -1,4 +1,4 @@
-// containers.cpp — snarkjs binary containers (.zkey / .wtns) and the prover host's error text.
+// containers.cpp — snarkjs binary containers (.zkey / .wtns / .r1cs) and the prover host's error text.
 //   FileWrapper::read_bin_file ← src/file_wrapper.rs:45-103;  read_wtns_header ← :169-177, src/proof_helper.rs:247-268
 #include <algorithm>
 #include <fcntl.h>
@@ -37,7 +37,9 @@ int read_sections(const uint8_t* data, size_t len, const char* type, uint32_t ma
   memcpy(&version, data + 4, 4);
   memcpy(&nsec, data + 8, 4);
   if (version > max_version) return fail(ERR_FORMAT, "Version not supported");
-  out.assign(nsec + 1 > 16 ? nsec + 1 : 16, Section());
+  // (ids up to the section count, but no more slots than the file has room for section headers: a hostile count sizes nothing)
+  const uint64_t slots = std::min<uint64_t>(nsec, (len - 12) / 12) + 1;
+  out.assign(slots > 16 ? (size_t)slots : 16, Section());
   size_t pos = 12;
   for (uint32_t i = 0; i < nsec; i++) {
     if (len - pos < 12) return fail(ERR_FORMAT, "truncated section table");
@@ -111,6 +113,63 @@ int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Zke
   return 0;
 }
 
+// sections and header of an .r1cs (prover_internal.h: R1csLayout) — iden3's binary format: sections by id in any order, unknown
+// ids (the wire → label map 3, the custom-gate sections 4 and 5) ignored
+int r1cs_layout(const uint8_t* data, size_t len, R1csLayout* L)
+{
+  if (!data) return fail(ERR_ARG, "null r1cs");
+  std::vector<Section> secs;
+  if (int rc = read_sections(data, len, "r1cs", 1, secs)) return rc;
+  const Section *h, *c;
+  if (int rc = unique_section(secs, 1, &h)) return rc;
+  if (int rc = unique_section(secs, 2, &c)) return rc;
+  uint32_t n8 = 0;
+  if (h->size >= 4) memcpy(&n8, h->p, 4);
+  if (n8 != 32) return fail(ERR_FORMAT, "r1cs: unsupported field size %u", n8);
+  if (h->size != 4 + 32 + 16 + 8 + 4) return fail(ERR_FORMAT, "r1cs: header size mismatch");
+  fe prime;
+  memcpy(prime.l, h->p + 4, 32);
+  if (!Fr::eq(prime, Fr::modulus())) return fail(ERR_FORMAT, "r1cs: the prime is not the BN254 scalar field's");
+  memcpy(&L->n_wires, h->p + 36, 4);
+  memcpy(&L->n_pub_out, h->p + 40, 4);
+  memcpy(&L->n_pub_in, h->p + 44, 4);
+  memcpy(&L->n_prv_in, h->p + 48, 4);
+  memcpy(&L->n_labels, h->p + 52, 8);
+  memcpy(&L->n_constraints, h->p + 60, 4);
+  if ((uint64_t)L->n_pub_out + L->n_pub_in + 1 > L->n_wires) return fail(ERR_FORMAT, "r1cs: the public signals exceed nWires");
+  // (a constraint is at least its three count words: a hostile mConstraints must not size the row table)
+  if (L->n_constraints > 0xfffffffeu / 3) return fail(ERR_FORMAT, "r1cs: too many constraints"); // row ids 3j + k are 32 bits
+  if ((uint64_t)L->n_constraints * 12 > c->size) return fail(ERR_FORMAT, "r1cs: %u constraints do not fit section 2", L->n_constraints);
+  L->payload = c->p;
+  L->payload_bytes = c->size;
+  return 0;
+}
+
+// One sequential pass over section 2 that reads the count words alone: rowptr[3m + 1] in terms, row 3j + k = linear combination
+// k (A, B, C) of constraint j.  Every record the kernels will read lies inside the payload once this has passed.
+int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_terms)
+{
+  const uint64_t rows = 3 * (uint64_t)L.n_constraints, size = L.payload_bytes;
+  rowptr.assign((size_t)rows + 1, 0);
+  uint64_t pos = 0, terms = 0;
+  for (uint64_t row = 0; row < rows; row++) {
+    const unsigned j = (unsigned)(row / 3);
+    const char mat = "ABC"[row % 3];
+    if (size - pos < 4) return fail(ERR_FORMAT, "r1cs: constraint %u, matrix %c: section 2 ends before its count", j, mat);
+    uint32_t cnt;
+    memcpy(&cnt, L.payload + pos, 4);
+    pos += 4;
+    if ((size - pos) / R1CS_TERM_BYTES < cnt) return fail(ERR_FORMAT, "r1cs: constraint %u, matrix %c: a count of %u overruns section 2", j, mat, cnt);
+    pos += (uint64_t)cnt * R1CS_TERM_BYTES;
+    terms += cnt;
+    if (terms > 0xffffffffull) return fail(ERR_FORMAT, "r1cs: more than 2^32 - 1 terms");
+    rowptr[(size_t)row + 1] = (uint32_t)terms;
+  }
+  if (pos != size) return fail(ERR_FORMAT, "r1cs: section 2 has %llu bytes left behind its %u constraints", (unsigned long long)(size - pos), L.n_constraints);
+  *n_terms = terms;
+  return 0;
+}
+
 MappedFile::~MappedFile()
 {
   if (data) munmap((void*)data, len);
@@ -150,3 +209,20 @@ int parse_wtns(const uint8_t* data, size_t len, Wtns& w)
 
 } // namespace prover
 } // namespace isnark
+
+// host only: never initialises a GPU
+__attribute__((visibility("default"))) int groth16_r1cs_info(const void* r1cs, size_t len, Groth16R1csInfo* info)
+{
+  if (!info) return fail(ERR_ARG, "null info");
+  memset(info, 0, sizeof *info);
+  R1csLayout L;
+  if (int rc = r1cs_layout((const uint8_t*)r1cs, len, &L)) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint32_t> rowptr;
+  if (int rc = r1cs_walk(L, rowptr, &info->n_terms)) return rc;
+  info->walk_ms = ms_since(t0);
+  info->n_wires = L.n_wires;
+  info->n_public = L.n_public();
+  info->n_constraints = L.n_constraints;
+  return 0;
+}

@@ -95,6 +95,20 @@ struct Wtns {
   const uint8_t* values = nullptr; // n_witness × 32 B standard form
 };
 int parse_wtns(const uint8_t* data, size_t len, Wtns& w);
+// What an .r1cs says about itself (iden3 binary format): the header's fields and section 2, the constraints —
+// n_constraints × {A, B, C}, each linear combination a u32 count and count × {u32 wire, 32-byte standard-form value}.
+// r1cs_layout checks the container, section 1 and 2 present once, the field; r1cs_walk bounds every record (containers.cpp).
+// With rowptr from the walk, term t of row ρ sits at byte R1CS_TERM_BYTES·t + 4·(ρ + 1) of the payload.
+constexpr size_t R1CS_TERM_BYTES = 4 + 32;
+struct R1csLayout {
+  uint32_t n_wires = 0, n_pub_out = 0, n_pub_in = 0, n_prv_in = 0, n_constraints = 0;
+  uint64_t n_labels = 0;
+  const uint8_t* payload = nullptr; // section 2
+  uint64_t payload_bytes = 0;
+  uint32_t n_public() const { return n_pub_out + n_pub_in; }
+};
+int r1cs_layout(const uint8_t* data, size_t len, R1csLayout* L);
+int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_terms);
 
 // ---- the device-resident cache of one zkey on ONE device (cache.cpp)
 constexpr size_t PARTIALS_STRIDE = 64 * 16 * 256; // ≥ W·bpw·sizeof(XYZZ) for any geometry (W ≤ 64, bpw ≤ 16, G2 256 B)

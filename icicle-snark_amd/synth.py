@@ -9,6 +9,8 @@ a known-toxic-waste setup.  The files follow the snarkjs container the reference
         sec3 IC | sec4 coefficients {m:u32 c:u32 s:u32 value·R² (32 B)} | sec5 A | sec6 B1 | sec7 B2
         sec8 C | sec9 H | sec10 contributions (empty);  all coordinates Montgomery form, LE.
   wtns: sec1 n8 q n_witness | sec2 witness (standard form, LE)
+  r1cs: sec1 n8 r nWires nPubOut nPubIn nPrvIn nLabels:u64 mConstraints | sec2 per constraint A, B, C, each
+        {count:u32, count × {wire:u32, value (32 B standard form)}} | sec3 wire → label map (u64 each); iden3's binary format
 
 Section-9 basis (SURVEY.md §8 a-H): with g = ω_{2n}, Z(x) = xⁿ − 1 the prover's H scalars are
 d_j = (A·B − C)(g·ωʲ) = −2·h(g·ωʲ), hence H_j = [ L_j(τ/g) · Z(τ) / (−2δ) ]₁ with L_j the Lagrange
@@ -171,6 +173,42 @@ def write_wtns(witness) -> bytes:
     hdr = struct.pack("<I", 32) + R_MOD.to_bytes(32, "little") + struct.pack("<I", len(witness))
     body = b"".join(int(x).to_bytes(32, "little") for x in witness)
     return b"wtns" + struct.pack("<II", 2, 2) + _section(1, hdr) + _section(2, body)
+
+
+def _r1cs_file(n_vars, n_public, n_constraints, n_pub_out, sec2: bytes, section_order, extra_sections=()) -> bytes:
+    assert 0 <= n_pub_out <= n_public
+    hdr = struct.pack("<I", 32) + R_MOD.to_bytes(32, "little")
+    hdr += struct.pack("<IIIIQI", n_vars, n_pub_out, n_public - n_pub_out, n_vars - 1 - n_public, n_vars, n_constraints)
+    payload = {1: hdr, 2: sec2, 3: np.arange(n_vars, dtype=np.uint64).tobytes()}
+    secs = [(sid, payload[sid]) for sid in section_order] + list(extra_sections)
+    return b"r1cs" + struct.pack("<II", 1, len(secs)) + b"".join(_section(sid, p) for sid, p in secs)
+
+
+def write_r1cs(r: R1CS, n_pub_out: int = 0, section_order=(1, 2, 3), extra_sections=()) -> bytes:
+    """The circuit as an iden3 `.r1cs`: nPubOut = n_pub_out, nPubIn = n_public − n_pub_out, nPrvIn the rest, labels the
+    identity.  Terms keep the order of r's lists (a wire listed twice in one row is written twice).  section_order: circom
+    writes (1, 2, 3), snarkjs (2, 3, 1)-like orders — readers find sections by id; extra_sections: (id, payload) appended."""
+    rows = [[[], [], []] for _ in range(r.n_constraints)]
+    for k, mat in enumerate((r.A, r.B, r.C)):
+        for (j, i, v) in mat:
+            rows[j][k].append(struct.pack("<I", i) + (int(v) % R_MOD).to_bytes(32, "little"))
+    sec2 = b"".join(struct.pack("<I", len(lc)) + b"".join(lc) for row in rows for lc in row)
+    return _r1cs_file(r.n_vars, r.n_public, r.n_constraints, n_pub_out, sec2, section_order, extra_sections)
+
+
+def write_r1cs_squaring_chain(N: int) -> bytes:
+    """write_r1cs(squaring_chain(N)[0]) byte for byte (tested), vectorised for the benchmark sizes: every constraint is three
+    one-term rows {1, wire, 1} — A and B name the previous wire, C the current one."""
+    j = np.arange(N, dtype=np.uint32)
+    prev = np.where(j == 0, 2, j + 2).astype(np.uint32)
+    cur = np.where(j == N - 1, 1, j + 3).astype(np.uint32)
+    rec = np.zeros((N, 3, 10), dtype=np.uint32)     # {count, wire, value[8]}
+    rec[:, :, 0] = 1
+    rec[:, 0, 1] = prev
+    rec[:, 1, 1] = prev
+    rec[:, 2, 1] = cur
+    rec[:, :, 2] = 1
+    return _r1cs_file(N + 2, 1, N, 0, rec.tobytes(), (1, 2, 3))
 
 
 def _toxic(seed):

@@ -244,8 +244,8 @@ typedef struct {
  * groth16_verify_combined_coefficients(seed, i) and the sums from the library's MSMs over 128-bit scalars: with every B2_i in G2,
  * a key with some B1_i that is not the G1 image of its B2_i passes with probability <= 2^-127 over the seed, WHICH MUST BE SECRET
  * AND FRESH (opt->seed32 is for reproducible tests; NULL draws from the operating system, and the call returns -3 when that fails).
- * What the check does NOT show: that the key belongs to a given circuit or ceremony (that needs the .r1cs and the .ptau, as
- * `snarkjs zkey verify`), or any relation between A, C, H and IC.
+ * What the check does NOT show: that the key belongs to a given circuit or ceremony (groth16_r1cs_match_zkey compares section 4
+ * with an .r1cs; the point sections need the .ptau, as `snarkjs zkey verify`), or any relation between A, C, H and IC.
  * device as groth16_verify_batch ("HIP", "CUDA", "HIP:k").  opt may be NULL.  The call holds no cache entry and needs no
  * Groth16CacheManager; the calling thread's device is what it was afterwards.  report->upload_ms: the host to device copies of the
  * sections, device_ms: the wall time of the device part (buffers, uploads, kernels, MSMs), pairing_ms: the host pairings (the
@@ -260,6 +260,80 @@ int groth16_zkey_check_file(const char* zkey_path, const char* device, const Gro
  * tests them.  Host only: never initialises a GPU.  Returns the length needed including the terminator (call with cap = 0 to
  * size; `out` is written only when cap is at least that), < 0 on a format error (groth16_last_error). */
 int64_t groth16_zkey_export_vk(const void* zkey, size_t len, char* out, size_t cap);
+
+/* An .r1cs (iden3 binary format, as circom and snarkjs write it) read once and kept on one GPU: the circuit's A, B and C as rows
+ * of (wire, coefficient) terms.  Sections are found by id in any order, unknown ids (3: the wire -> label map, 4 and 5: custom
+ * gates) are ignored, a missing or duplicated section 1 or 2 is a format error; n_public = nPubOut + nPubIn.
+ * groth16_r1cs_info is the host half alone — container, header, and ONE pass over section 2's count words that checks that every
+ * count keeps the walk inside the section, that the walk consumes it exactly and that the term total fits 32 bits.  It never
+ * initialises a GPU.  groth16_r1cs_load then uploads the section in slices and a kernel unpacks the 36-byte records into aligned
+ * (wire, Montgomery coefficient) arrays, testing wire < nWires and coefficient < r first; a bad record fails the load with -2
+ * and a text naming the lowest constraint at fault, its matrix and the kind.  A handle exists only when every wire id is in range.
+ * SAFETY: no byte of a hostile or truncated file can make a kernel read outside its buffers — the host walk bounds every record
+ * before anything is uploaded, and the fill kernel bounds every wire id before anything gathers with it.
+ * device as groth16_verify_batch ("HIP", "CUDA", "HIP:k"; a list is an error).  -1 I/O, -2 format, -3 argument, -5 device failure
+ * (groth16_last_error).  The calling thread's device is afterwards what it was before.  A handle serves one call at a time (calls
+ * on one handle are serialised); groth16_r1cs_free(NULL) does nothing. */
+typedef struct Groth16R1cs Groth16R1cs;
+typedef struct {
+  uint32_t n_wires, n_public, n_constraints;
+  uint64_t n_terms;        /* non-zero entries of A, B and C together */
+  uint64_t device_bytes;   /* what the handle keeps on the device (0 from groth16_r1cs_info) */
+  double   walk_ms;        /* the host pass over the count words */
+  double   upload_ms;      /* host to device copies of section 2 (0 from groth16_r1cs_info) */
+  double   device_ms;      /* wall time of the device part: buffers, uploads, the fill kernel */
+} Groth16R1csInfo;
+int  groth16_r1cs_info(const void* r1cs, size_t len, Groth16R1csInfo* info);
+int  groth16_r1cs_load(const void* r1cs, size_t len, const char* device, Groth16R1cs** out);
+int  groth16_r1cs_load_file(const char* path, const char* device, Groth16R1cs** out); /* maps the file */
+int  groth16_r1cs_get_info(const Groth16R1cs* h, Groth16R1csInfo* info); /* what the load measured */
+void groth16_r1cs_free(Groth16R1cs* h);
+
+/* groth16_witness_check — does this witness satisfy this circuit?  Exact, on the GPU; what `snarkjs wtns check` answers.
+ * Opt-in: the proves do not run it (their QAP front end takes A∘B for the third row, so an unsatisfying witness yields a proof
+ * that fails verification and nothing says why).  kinds of fault, in the order of testing: */
+#define GROTH16_WTNS_NONCANONICAL 1   /* a witness value >= r; index = the lowest such wire */
+#define GROTH16_WTNS_ONE          2   /* wire 0 is not 1; index = 0 */
+#define GROTH16_WTNS_CONSTRAINT   3   /* (A_j·w)(B_j·w) != C_j·w; index = the lowest such j */
+typedef struct {
+  int32_t  kind;           /* 0 = satisfied, else the kind of the FIRST fault */
+  uint64_t index;
+  uint64_t noncanonical;   /* witness values >= r */
+  uint64_t failed;         /* violated constraints, all of them; 0 when noncanonical != 0: the constraints are evaluated only
+                              over canonical values, which the field routines' bounds assume */
+  double   upload_ms, device_ms; /* the witness's host to device copy; wall time of the device part (upload and both kernels) */
+} Groth16WitnessReport;
+/* The .wtns is parsed as the proves parse it; a witness count other than nWires is -3.  An empty linear combination evaluates
+ * to 0, a wire named twice in one sums.  Only the tallies come back from the device.  1 satisfied, 0 not (report says why),
+ * < 0 an error with the loader's codes. */
+int groth16_witness_check(Groth16R1cs* h, const void* wtns, size_t wtns_len, Groth16WitnessReport* report);
+int groth16_witness_check_file(Groth16R1cs* h, const char* wtns_path, Groth16WitnessReport* report);
+
+/* groth16_r1cs_match_zkey — does this proving key carry this circuit's A and B?  kinds of fault, in the order of reporting: */
+#define GROTH16_MATCH_SIZES 1   /* index: 0 n_vars vs nWires, 1 n_public vs nPubOut + nPubIn, 2 domain_size */
+#define GROTH16_MATCH_ROW_A 2   /* index = the lowest row of the domain whose A differs */
+#define GROTH16_MATCH_ROW_B 3
+typedef struct {
+  int32_t  kind;           /* 0 = match, else the kind of the FIRST fault: sizes, then A, then B */
+  uint64_t index;
+  uint64_t rows_a, rows_b; /* rows that differ, all of them (0 after a sizes fault: nothing was compared) */
+  double   device_ms;      /* wall time of the device part: buffers, uploads, kernels */
+} Groth16R1csMatchReport;
+/* Sizes first, on the host: n_vars = nWires, n_public = nPubOut + nPubIn, and domain_size the smallest power of two
+ * >= mConstraints + n_public + 1 (snarkjs' rule).  Then both sides are evaluated at ONE vector z of nWires coefficients, z_i =
+ * groth16_verify_combined_coefficients(seed, i): the circuit's rows A_j·z and B_j·z by the witness check's kernel, the key's
+ * section 4 by the prover's own CSR build and sparse product with z in the witness's place.  Row j of the key's A must equal
+ * A_j·z for j < m, z_{j-m} for m <= j <= m + n_public (the rows snarkjs adds to bind the public signals) and 0 above; row j of its
+ * B must equal B_j·z for j < m and 0 above.  A row whose coefficients differ from the circuit's is a non-zero linear form in the
+ * z_i, zero for at most one value of one z_i: it is accepted with probability <= 2^-127 over the seed, WHICH MUST BE SECRET AND
+ * FRESH (seed32 is for reproducible tests; NULL draws from the operating system, and the call returns -3 when that fails).  The
+ * comparison does not depend on the order of section 4's records or on records of one entry that sum.
+ * What it does NOT show: anything about C, which section 4 does not hold; and that the point sections 3 and 5 to 9 belong to
+ * these matrices, which needs the .ptau (`snarkjs zkey verify`).  Section 4's values are taken as the prover takes them —
+ * groth16_zkey_check is what tests value < r.
+ * 1 match, 0 not (report says where), < 0 an error with the loader's codes (-2 also for a section-4 record out of range). */
+int groth16_r1cs_match_zkey(Groth16R1cs* h, const void* zkey, size_t len, const uint8_t* seed32 /* NULL = OS randomness */,
+                            Groth16R1csMatchReport* report);
 
 #ifdef __cplusplus
 }
