@@ -701,6 +701,7 @@ groth16_verify_batch_combined groth16_verify_combined_coefficients
 groth16_zkey_check groth16_zkey_check_file
 groth16_r1cs_info groth16_r1cs_load groth16_r1cs_load_file groth16_r1cs_get_info groth16_r1cs_free
 groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
+groth16_ptau_info groth16_zkey_verify_ptau groth16_zkey_verify_ptau_file
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -926,6 +927,22 @@ WTNS_NONCANONICAL, WTNS_ONE, WTNS_CONSTRAINT = 1, 2, 3
 MATCH_SIZES, MATCH_ROW_A, MATCH_ROW_B = 1, 2, 3
 
 
+class PtauInfo(C.Structure):
+    """Groth16PtauInfo: power, ceremonyPower, payload bytes per section id (0 = absent)"""
+    _fields_ = [("power", C.c_uint32), ("ceremony_power", C.c_uint32), ("section_bytes", C.c_uint64 * 16)]
+
+
+class VerifyReport(C.Structure):
+    """Groth16ZkeyVerifyReport: kind (/ index for SIZES and HEADER) of the first fault, failed_mask with bit (kind − VERIFY_HEADER)
+    per failing equation, `key` the embedded groth16_zkey_check report"""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_uint64), ("failed_mask", C.c_uint32), ("key", ZkeyReport),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("pairing_ms", C.c_double)]
+
+
+VERIFY_SIZES, VERIFY_KEY, VERIFY_HEADER, VERIFY_A, VERIFY_B1, VERIFY_B2, VERIFY_IC, VERIFY_C, VERIFY_H = range(1, 10)
+VERIFY_KIND_NAMES = ["ok", "SIZES", "KEY", "HEADER", "A", "B1", "B2", "IC", "C", "H"]
+
+
 def _image(data):
     return data.ctypes.data_as(C.c_void_p) if isinstance(data, np.ndarray) else C.c_char_p(data) if isinstance(data, bytes) else (C.c_char * len(data)).from_buffer(data)
 
@@ -934,6 +951,23 @@ def r1cs_info(r1cs: bytes) -> R1csInfo:
     """groth16_r1cs_info: the counts of an .r1cs after the host walk that bounds every record (host only: needs no GPU)"""
     info = R1csInfo()
     _pcheck(lib().groth16_r1cs_info(_image(r1cs), C.c_size_t(len(r1cs)), C.byref(info)), "r1cs_info")
+    return info
+
+
+def ptau_info(ptau, domain_power: int = -1) -> PtauInfo:
+    """groth16_ptau_info: power and sections of a prepared .ptau (bytes, or a path that is mapped; host only: needs no GPU).
+    domain_power >= 0 also asks whether the file serves a key of that domain (ProverError −3 / −2 when not)."""
+    info = PtauInfo()
+    if isinstance(ptau, (str, os.PathLike)):
+        import mmap
+        with open(ptau, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            view = np.frombuffer(mm, dtype=np.uint8)
+            try:
+                _pcheck(lib().groth16_ptau_info(_image(view), C.c_size_t(len(view)), C.c_int32(domain_power), C.byref(info)), "ptau_info")
+            finally:
+                del view
+        return info
+    _pcheck(lib().groth16_ptau_info(_image(ptau), C.c_size_t(len(ptau)), C.c_int32(domain_power), C.byref(info)), "ptau_info")
     return info
 
 
@@ -970,6 +1004,22 @@ class R1cs:
         sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
         rep = MatchReport()
         return self._verdict(lib().groth16_r1cs_match_zkey(self._h, _image(zkey), C.c_size_t(len(zkey)), sd, C.byref(rep)), rep, "r1cs_match_zkey")
+
+    def verify_zkey(self, zkey, ptau, seed=None):
+        """groth16_zkey_verify_ptau → (ok, VerifyReport): is the key this circuit's Groth16 key over this prepared .ptau?  zkey
+        and ptau: both images, or both paths (mapped; only the ptau ranges that are read are touched).  seed: 32 bytes for a
+        reproducible test — leave it None otherwise (a secret, fresh seed is drawn)."""
+        if seed is not None and len(seed) != 32:
+            raise ValueError("verify_zkey: the seed is 32 bytes")
+        sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+        rep = VerifyReport()
+        paths = [isinstance(x, (str, os.PathLike)) for x in (zkey, ptau)]
+        if all(paths):
+            return self._verdict(lib().groth16_zkey_verify_ptau_file(self._h, os.fsencode(zkey), os.fsencode(ptau), sd, C.byref(rep)), rep, "zkey_verify_ptau_file")
+        if any(paths):
+            raise TypeError("verify_zkey: zkey and ptau are both images or both paths")
+        return self._verdict(lib().groth16_zkey_verify_ptau(self._h, _image(zkey), C.c_size_t(len(zkey)), _image(ptau), C.c_size_t(len(ptau)), sd, C.byref(rep)),
+                             rep, "zkey_verify_ptau")
 
     def close(self):
         if self._h:

@@ -10,6 +10,7 @@
 //   > wtns-check --r1cs R --wtns W [--device HIP]    does the witness satisfy the circuit (groth16_witness_check): "satisfied", or
 //     the first fault with the counts and "not satisfied"
 //   > r1cs-match --r1cs R --zkey Z [--device HIP]    does the key carry the circuit's A and B (groth16_r1cs_match_zkey)
+//   > zkey-verify --r1cs R --zkey Z --ptau P [--device HIP]   r1cs-match, then the point sections against circuit and ceremony (groth16_zkey_verify_ptau)
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -20,7 +21,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -259,6 +260,58 @@ int main()
           if (rep.rows_a) std::cout << rep.rows_a << " rows of A differ" << (rep.kind == GROTH16_MATCH_ROW_A ? ", first: row " + std::to_string(rep.index) : std::string()) << std::endl;
           if (rep.rows_b) std::cout << rep.rows_b << " rows of B differ" << (rep.kind == GROTH16_MATCH_ROW_B ? ", first: row " + std::to_string(rep.index) : std::string()) << std::endl;
           std::cout << (rc == 1 ? "match" : "no match") << std::endl;
+        }
+      }
+      groth16_r1cs_free(h);
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-verify") {
+      // the two questions `snarkjs zkey verify` asks of a key, one line each: section 4 against the circuit (r1cs-match), then the
+      // point sections against the circuit and the ceremony
+      std::string r1cs = "circuit.r1cs", zkey = "circuit_final.zkey", ptau = "pot_final.ptau", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--r1cs") in >> r1cs;
+        else if (a == "--zkey") in >> zkey;
+        else if (a == "--ptau") in >> ptau;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16R1cs* h = nullptr;
+      int rc = groth16_r1cs_load_file(r1cs.c_str(), device.c_str(), &h);
+      if (rc < 0) {
+        std::cerr << "zkey-verify failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        std::ifstream f(zkey, std::ios::binary);
+        std::ostringstream ss;
+        if (f) ss << f.rdbuf();
+        const std::string image = ss.str();
+        Groth16R1csMatchReport mrep;
+        const int mrc = f ? groth16_r1cs_match_zkey(h, image.data(), image.size(), nullptr, &mrep) : -1;
+        if (mrc < 0) {
+          std::cerr << "zkey-verify: r1cs-match failed (" << mrc << "): " << (f ? groth16_last_error() : "cannot read the zkey") << std::endl;
+        } else {
+          static const char* const mkinds[4] = {"match", "no match: SIZES", "no match: ROW_A", "no match: ROW_B"};
+          std::cout << "section 4 against the circuit: " << mkinds[mrep.kind >= 0 && mrep.kind <= 3 ? mrep.kind : 0] << std::endl;
+        }
+        Groth16ZkeyVerifyReport rep;
+        rc = groth16_zkey_verify_ptau_file(h, zkey.c_str(), ptau.c_str(), nullptr, &rep);
+        if (rc < 0) {
+          std::cerr << "zkey-verify failed (" << rc << "): " << groth16_last_error() << std::endl;
+        } else {
+          static const char* const kinds[10] = {"", "SIZES", "KEY", "HEADER", "A", "B1", "B2", "IC", "C", "H"};
+          std::cout << "point sections against the circuit and the ptau: ";
+          if (rc == 1) std::cout << "verified";
+          else {
+            std::cout << "not verified: " << kinds[rep.kind >= 1 && rep.kind <= 9 ? rep.kind : 0];
+            if (rep.kind == GROTH16_VERIFY_SIZES || rep.kind == GROTH16_VERIFY_HEADER) std::cout << " " << rep.index;
+            if (rep.kind == GROTH16_VERIFY_KEY) std::cout << " (zkey-check: kind " << rep.key.kind << ", section " << rep.key.section << ")";
+            if (rep.failed_mask) {
+              std::cout << ", failing:";
+              for (int k = GROTH16_VERIFY_HEADER; k <= GROTH16_VERIFY_H; k++)
+                if (rep.failed_mask >> (k - GROTH16_VERIFY_HEADER) & 1) std::cout << " " << kinds[k];
+            }
+          }
+          std::cout << std::endl;
+          std::cout << (rc == 1 && mrc == 1 ? "ZKEY_OK" : "ZKEY_NOT_OK") << std::endl;
         }
       }
       groth16_r1cs_free(h);

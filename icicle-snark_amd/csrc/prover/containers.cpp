@@ -1,4 +1,4 @@
-// containers.cpp — snarkjs binary containers (.zkey / .wtns / .r1cs) and the prover host's error text.
+// containers.cpp — snarkjs binary containers (.zkey / .wtns / .r1cs / .ptau) and the prover host's error text.
 //   FileWrapper::read_bin_file ← src/file_wrapper.rs:45-103;  read_wtns_header ← :169-177, src/proof_helper.rs:247-268
 #include <algorithm>
 #include <fcntl.h>
@@ -170,12 +170,59 @@ int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_te
   return 0;
 }
 
+// sections and header of a prepared .ptau (prover_internal.h: PtauLayout)
+int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L)
+{
+  if (!data) return fail(ERR_ARG, "null ptau");
+  if (int rc = read_sections(data, len, "ptau", 1, secs)) return rc;
+  const Section* h;
+  if (int rc = unique_section(secs, 1, &h)) return rc;
+  uint32_t n8 = 0;
+  if (h->size >= 4) memcpy(&n8, h->p, 4);
+  if (n8 != 32) return fail(ERR_FORMAT, "ptau: unsupported base field size %u", n8);
+  if (h->size != 4 + 32 + 8) return fail(ERR_FORMAT, "ptau: header size mismatch");
+  fe q;
+  memcpy(q.l, h->p + 4, 32);
+  if (!Fq::eq(q, Fq::modulus())) return fail(ERR_FORMAT, "ptau: the prime is not the BN254 base field's");
+  memcpy(&L->power, h->p + 36, 4);
+  memcpy(&L->ceremony_power, h->p + 40, 4);
+  if (L->power > 28) return fail(ERR_FORMAT, "ptau: power %u is above the field's two-adicity", L->power);
+  L->sec[1] = h;
+  for (int id : {4, 5, 6})
+    if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
+  if (L->sec[4]->size < 64 || L->sec[5]->size < 64 || L->sec[6]->size < 128) return fail(ERR_FORMAT, "ptau: section 4, 5 or 6 is shorter than one point");
+  bool prepared = false;
+  for (int id = 12; id < 16; id++) prepared = prepared || secs[(size_t)id].count != 0; // (read_sections makes room for the ids below 16)
+  if (!prepared) return fail(ERR_FORMAT, "ptau: sections 12 to 15 are missing: the file has not been prepared for phase 2 (snarkjs powersoftau prepare phase2)");
+  for (int id = 12; id < 16; id++)
+    if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
+  return 0;
+}
+
+int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out)
+{
+  const uint64_t first = ((uint64_t)1 << p) - 1, end = (first + ((uint64_t)1 << p)) * elem_bytes; // p <= 29: no overflow
+  if (end > L.sec[sid]->size)
+    return fail(ERR_FORMAT, "ptau: section %d holds %llu bytes, its block for power %u ends at byte %llu", sid, (unsigned long long)L.sec[sid]->size, p, (unsigned long long)end);
+  *out = L.sec[sid]->p + first * elem_bytes;
+  return 0;
+}
+
+int ptau_blocks_for_domain(const PtauLayout& L, uint32_t k)
+{
+  if (L.power < k) return fail(ERR_ARG, "ptau: power %u is below the key's domain 2^%u", L.power, k);
+  const uint8_t* p;
+  for (int id : {12, 13, 14, 15})
+    if (int rc = ptau_block(L, id, k, id == 13 ? 128 : 64, &p)) return rc;
+  return ptau_block(L, 12, k + 1, 64, &p);
+}
+
 MappedFile::~MappedFile()
 {
   if (data) munmap((void*)data, len);
   if (fd >= 0) close(fd);
 }
-int MappedFile::open_ro(const char* path)
+int MappedFile::open_ro(const char* path, bool read_ahead)
   {
     fd = ::open(path, O_RDONLY); // the reference opens read-write although it only reads (file_wrapper.rs:50-54)
     if (fd < 0) return fail(ERR_IO, "cannot open %s", path);
@@ -185,7 +232,7 @@ int MappedFile::open_ro(const char* path)
     void* p = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
     if (p == MAP_FAILED) return fail(ERR_IO, "cannot mmap %s", path);
     data = (const uint8_t*)p;
-    (void)madvise(p, len, MADV_WILLNEED); // start the read-ahead; the upload workers touch the pages in parallel
+    if (read_ahead) (void)madvise(p, len, MADV_WILLNEED); // start the read-ahead; the upload workers touch the pages in parallel
     return 0;
   }
 
@@ -224,5 +271,22 @@ __attribute__((visibility("default"))) int groth16_r1cs_info(const void* r1cs, s
   info->n_wires = L.n_wires;
   info->n_public = L.n_public();
   info->n_constraints = L.n_constraints;
+  return 0;
+}
+
+// host only: never initialises a GPU
+__attribute__((visibility("default"))) int groth16_ptau_info(const void* ptau, size_t len, int32_t domain_power, Groth16PtauInfo* info)
+{
+  if (!info) return fail(ERR_ARG, "null info");
+  memset(info, 0, sizeof *info);
+  std::vector<Section> secs;
+  PtauLayout L;
+  if (int rc = ptau_layout((const uint8_t*)ptau, len, secs, &L)) return rc;
+  if (domain_power > 28) return fail(ERR_ARG, "domain power %d is above the field's two-adicity", domain_power);
+  if (domain_power >= 0)
+    if (int rc = ptau_blocks_for_domain(L, (uint32_t)domain_power)) return rc;
+  info->power = L.power;
+  info->ceremony_power = L.ceremony_power;
+  for (size_t id = 0; id < 16; id++) info->section_bytes[id] = secs[id].count == 1 ? secs[id].size : 0;
   return 0;
 }

@@ -87,7 +87,7 @@ struct MappedFile {
   size_t len = 0;
   int fd = -1;
   ~MappedFile();
-  int open_ro(const char* path);
+  int open_ro(const char* path, bool read_ahead = true); // read_ahead = false: a file of which only ranges are read (a .ptau)
 };
 struct Wtns {
   uint32_t n8 = 0, n_witness = 0;
@@ -109,6 +109,22 @@ struct R1csLayout {
 };
 int r1cs_layout(const uint8_t* data, size_t len, R1csLayout* L);
 int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_terms);
+// What a prepared .ptau says about itself (snarkjs' powers-of-tau container after `powersoftau prepare phase2`): section 1 is
+// {n8 = 32, q, power, ceremonyPower}; sections 4, 5, 6 hold [α·τ^i]₁, [β·τ^i]₁ and [β]₂; sections 12, 13, 14, 15 hold [L_j(τ)]₁,
+// [L_j(τ)]₂, [α·L_j(τ)]₁ and [β·L_j(τ)]₁, one block per power p = 0, 1, … of 2^p elements beginning at element 2^p − 1 (section
+// 12 goes on to power + 1).  All points uncompressed, affine, Montgomery form.  ptau_layout checks the container, the header
+// and that sections 4, 5, 6 (with their first element) and 12 … 15 are present once; of the lengths it demands nothing more —
+// ptau_block is what bounds a block a caller is about to read.
+struct PtauLayout {
+  uint32_t power = 0, ceremony_power = 0;
+  const Section* sec[16] = {};
+};
+int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L);
+// block p of section sid (elements of elem_bytes): its first byte, after checking that it lies inside the section
+int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out);
+// the blocks a verify of a key with domain 2^k reads — block k of 12 … 15 and block k + 1 of 12 — lie inside their sections
+// (ERR_FORMAT), after power >= k (ERR_ARG, both numbers in the text)
+int ptau_blocks_for_domain(const PtauLayout& L, uint32_t k);
 
 // ---- the device-resident cache of one zkey on ONE device (cache.cpp)
 constexpr size_t PARTIALS_STRIDE = 64 * 16 * 256; // ≥ W·bpw·sizeof(XYZZ) for any geometry (W ≤ 64, bpw ≤ 16, G2 256 B)
@@ -272,6 +288,22 @@ int assemble_impl(const ZKeyCache* z, const void* wtns, size_t wtns_len, const u
 
 // ---- one device (prover.cpp)
 struct DeviceGroup; // multi.cpp
+
+// ---- an .r1cs resident on one device (r1cs_check.hip), as groth16_zkey_verify_ptau (zkey_verify.hip) uses it
+struct R1csShape {
+  int dev;
+  uint32_t n_wires, n_public, m;
+};
+} // namespace prover
+} // namespace isnark
+struct Groth16R1cs;
+namespace isnark {
+namespace prover {
+R1csShape r1cs_shape(const Groth16R1cs* h);
+std::mutex& r1cs_mutex(Groth16R1cs* h); // a handle serves one call at a time
+// a_j = A_j·v, b_j = B_j·v, c_j = C_j·v for j < m to abc[j], abc[m + j], abc[2m + j] (standard form): the witness check's kernel
+// with v (n_wires canonical standard-form values on the handle's device) in the witness's place; enqueued on `stream`
+int r1cs_emit_abc(Groth16R1cs* h, const fe* d_v, fe* d_abc, hipStream_t stream);
 } // namespace prover
 } // namespace isnark
 

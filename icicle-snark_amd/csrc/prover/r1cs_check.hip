@@ -13,6 +13,8 @@
 //   match    groth16_r1cs_match_zkey: a secret vector z takes the witness's place.  The constraint kernel in its emit mode writes
 //            a_j = A_j·z and b_j = B_j·z; the zkey's section 4 goes through the prover's own qap_build_csr and qap_spmv with the
 //            same z; r1cs_compare_kernel (one lane per row of the domain) compares, public-binding rows included.
+//   verify   groth16_zkey_verify_ptau (zkey_verify.hip) takes the rows a, b AND c at vectors of its own: the kernel's third mode,
+//            through r1cs_emit_abc.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -86,17 +88,18 @@ __global__ __launch_bounds__(256) void witness_range_kernel(const fe* __restrict
   if (i == 0 && !Fr::eq(v, Fr::one_std())) t->not_one = 1;
 }
 
-// EMIT: a_j to ab[j] and b_j to ab[m + j] instead of a verdict
-template <bool EMIT>
+// MODE 0: a verdict.  MODE 1 (match): a_j to ab[j] and b_j to ab[m + j] instead.  MODE 2 (zkey verify): as 1, and c_j to ab[2m + j]
+template <int MODE>
 __global__ __launch_bounds__(256) void r1cs_constraint_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, const fe* __restrict__ vals,
                                                                const fe* __restrict__ w, uint32_t m, Tally* __restrict__ t, fe* __restrict__ ab)
 {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
   if (j >= m) return;
   const isnark::R1csRows r = isnark::r1cs_eval(rowptr, cols, vals, w, j);
-  if (EMIT) {
+  if (MODE) {
     st(ab + j, r.a);
     st(ab + (size_t)m + j, r.b);
+    if (MODE == 2) st(ab + 2 * (size_t)m + j, r.c);
   } else if (!isnark::r1cs_holds(r)) {
     atomicAdd(&t->failed, 1ull);
     atomicMin(&t->first_failed, (unsigned long long)j);
@@ -277,7 +280,7 @@ int witness_check_impl(Groth16R1cs* h, const uint8_t* wtns, size_t wtns_len, Gro
   if (int rc = read_tally(h, &t, "range kernel")) return rc;
   // the constraints only over canonical values: Fr::mul's bounds assume them
   if (t.noncanonical == 0 && h->m) {
-    hipLaunchKernelGGL(r1cs_constraint_kernel<false>, dim3((h->m + 255) / 256), dim3(256), 0, h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, h->m, h->d_tally, (fe*)nullptr);
+    hipLaunchKernelGGL(r1cs_constraint_kernel<0>, dim3((h->m + 255) / 256), dim3(256), 0, h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, h->m, h->d_tally, (fe*)nullptr);
     if (hipError_t he = hipGetLastError()) return dev_fail("constraint kernel launch", he);
     if (int rc = read_tally(h, &t, "constraint kernel")) return rc;
   }
@@ -333,7 +336,7 @@ int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8
   const isnark::CopyJob jobs[2] = {{h->d_w, z.data(), z.size() * sizeof z[0]}, {d_rec, L.records(), (size_t)L.n_coef * pv::COEF_RECORD_BYTES}};
   if (hipError_t he = isnark::staged_copy(h->dev, jobs, 2, true)) return dev_fail("host to device upload", he);
   if (m) {
-    hipLaunchKernelGGL(r1cs_constraint_kernel<true>, dim3((m + 255) / 256), dim3(256), 0, h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, m, h->d_tally, d_ab);
+    hipLaunchKernelGGL(r1cs_constraint_kernel<1>, dim3((m + 255) / 256), dim3(256), 0, h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, m, h->d_tally, d_ab);
     if (hipError_t he = hipGetLastError()) return dev_fail("emit kernel launch", he);
   }
   // the key's side by the prover's own front end: the same CSR build (with its range rule) and the same spmv
@@ -354,6 +357,21 @@ int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8
 }
 
 } // namespace
+
+// what groth16_zkey_verify_ptau (zkey_verify.hip) needs of a handle: its shape, its lock, and the rows at a vector of its own
+namespace isnark {
+namespace prover {
+R1csShape r1cs_shape(const Groth16R1cs* h) { return {h->dev, h->n_wires, h->n_public, h->m}; }
+std::mutex& r1cs_mutex(Groth16R1cs* h) { return h->mu; }
+int r1cs_emit_abc(Groth16R1cs* h, const fe* d_v, fe* d_abc, hipStream_t stream)
+{
+  if (!h->m) return 0;
+  hipLaunchKernelGGL(r1cs_constraint_kernel<2>, dim3((h->m + 255) / 256), dim3(256), 0, stream, h->d_rowptr, h->d_cols, h->d_vals, d_v, h->m, h->d_tally, d_abc);
+  if (hipError_t he = hipGetLastError()) return dev_fail("emit kernel launch", he);
+  return 0;
+}
+} // namespace prover
+} // namespace isnark
 
 ISNARK_API int groth16_r1cs_match_zkey(Groth16R1cs* h, const void* zkey, size_t len, const uint8_t* seed32, Groth16R1csMatchReport* report)
 {

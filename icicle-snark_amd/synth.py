@@ -9,6 +9,7 @@ a known-toxic-waste setup.  The files follow the snarkjs container the reference
         sec3 IC | sec4 coefficients {m:u32 c:u32 s:u32 value·R² (32 B)} | sec5 A | sec6 B1 | sec7 B2
         sec8 C | sec9 H | sec10 contributions (empty);  all coordinates Montgomery form, LE.
   wtns: sec1 n8 q n_witness | sec2 witness (standard form, LE)
+  ptau: a prepared powers-of-tau file for the same τ, α, β (write_ptau)
   r1cs: sec1 n8 r nWires nPubOut nPubIn nPrvIn nLabels:u64 mConstraints | sec2 per constraint A, B, C, each
         {count:u32, count × {wire:u32, value (32 B standard form)}} | sec3 wire → label map (u64 each); iden3's binary format
 
@@ -216,6 +217,11 @@ def _toxic(seed):
     return tuple(pr.fr() for _ in range(5))  # tau, alpha, beta, gamma, delta
 
 
+def toxic_waste(seed: int = SEED):
+    """(τ, α, β, γ, δ) as setup() and write_ptau() draw them from `seed`"""
+    return _toxic(seed)
+
+
 def _finish(m, npub, n, a_tau, b_tau, c_s, ic_s, h_s, mcs, vals_r2, toxic, fixed_base_mul, points_to_mont):
     """Common tail of setup(): scalar arrays (numpy (k,4) u64, standard form) → points → zkey bytes."""
     tau, alpha, beta, gamma, delta = toxic
@@ -254,16 +260,11 @@ def _finish(m, npub, n, a_tau, b_tau, c_s, ic_s, h_s, mcs, vals_r2, toxic, fixed
     return zkey, vk
 
 
-def setup(r1cs: R1CS, fixed_base_mul, points_to_mont=None, seed: int = SEED):
-    """Groth16 setup with toxic waste (τ, α, β, γ, δ) = first five outputs of the fixed-seed PRNG.
-    Returns (zkey_bytes, vk dict with standard-form affine numpy points).  Generic (any R1CS), pure Python
-    field arithmetic — fine up to ~10^5 constraints; setup_squaring_chain() is the vectorised path for the
-    benchmark sizes.
-
-    points_to_mont(arr_u64[..., 4]) -> same shape: optional fast Fq std→Montgomery converter for the big
-    point arrays (the HIP library's or the oracle's); defaults to pure Python."""
-    toxic = _toxic(seed)
-    tau, alpha, beta, gamma, delta = toxic
+def key_scalars(r1cs: R1CS, toxic=None, seed: int = SEED) -> dict:
+    """The discrete logarithms of everything setup() turns into points, as Python integers, for toxic waste (τ, α, β, γ, δ):
+    n (the domain), a, b (A's and B's wire polynomials at τ, public-binding rows included), ic, c (the γ and δ quotients),
+    h (section 9's basis) and coeffs (section 4's (matrix, row, wire, value))."""
+    tau, alpha, beta, gamma, delta = toxic if toxic is not None else _toxic(seed)
     m, npub, nc = r1cs.n_vars, r1cs.n_public, r1cs.n_constraints
     n = 1
     while n < nc + npub + 1:
@@ -291,6 +292,21 @@ def setup(r1cs: R1CS, fixed_base_mul, points_to_mont=None, seed: int = SEED):
     Lc = lagrange_at(n, logn, tau * pow(g, -1, R_MOD) % R_MOD)
     zt = (pow(tau, n, R_MOD) - 1) * pow((-2 * delta) % R_MOD, -1, R_MOD) % R_MOD
     h_s = [x * zt % R_MOD for x in Lc]
+    return dict(n=n, a=a_tau, b=b_tau, ic=ic_s, c=c_s, h=h_s, coeffs=coeffs)
+
+
+def setup(r1cs: R1CS, fixed_base_mul, points_to_mont=None, seed: int = SEED, toxic=None):
+    """Groth16 setup with toxic waste (τ, α, β, γ, δ) = first five outputs of the fixed-seed PRNG, or `toxic` when given (a key
+    with other γ, δ over the τ, α, β of a write_ptau() file).
+    Returns (zkey_bytes, vk dict with standard-form affine numpy points).  Generic (any R1CS), pure Python
+    field arithmetic — fine up to ~10^5 constraints; setup_squaring_chain() is the vectorised path for the
+    benchmark sizes.
+
+    points_to_mont(arr_u64[..., 4]) -> same shape: optional fast Fq std→Montgomery converter for the big
+    point arrays (the HIP library's or the oracle's); defaults to pure Python."""
+    toxic = tuple(toxic) if toxic is not None else _toxic(seed)
+    ks = key_scalars(r1cs, toxic)
+    coeffs = ks["coeffs"]
     R2 = MONT_R * MONT_R % R_MOD
     mcs = np.array([(c[0], c[1], c[2]) for c in coeffs], dtype=np.uint32).reshape(-1, 3)
     cache = {}
@@ -299,7 +315,48 @@ def setup(r1cs: R1CS, fixed_base_mul, points_to_mont=None, seed: int = SEED):
             cache[c[3]] = (c[3] * R2 % R_MOD).to_bytes(32, "little")
     vals = np.frombuffer(b"".join(cache[c[3]] for c in coeffs), dtype=np.uint64).reshape(-1, 4)
     _e = lambda xs: ints_to_arr(xs) if len(xs) else np.zeros((0, 4), dtype=np.uint64)
-    return _finish(m, npub, n, _e(a_tau), _e(b_tau), _e(c_s), _e(ic_s), _e(h_s), mcs, vals, toxic, fixed_base_mul, points_to_mont)
+    return _finish(r1cs.n_vars, r1cs.n_public, ks["n"], _e(ks["a"]), _e(ks["b"]), _e(ks["c"]), _e(ks["ic"]), _e(ks["h"]), mcs, vals, toxic, fixed_base_mul,
+                   points_to_mont)
+
+
+def write_ptau(power: int, fixed_base_mul, points_to_mont=None, toxic=None, seed: int = SEED) -> bytes:
+    """A prepared powers-of-tau file (snarkjs `.ptau` after `powersoftau prepare phase2`) for the τ, α, β of `toxic` (default: the
+    toxic waste setup() draws from `seed`, so setup()'s keys are keys over this file):
+      sec1 n8 q power ceremonyPower | sec2 [τ^i]₁, i < 2^(power+1) − 1 | sec3 [τ^i]₂, i < 2^power | sec4 [α·τ^i]₁ | sec5 [β·τ^i]₁
+      sec6 [β]₂ | sec7 contributions (empty) | sec12 [L_j(τ)]₁ | sec13 [L_j(τ)]₂ | sec14 [α·L_j(τ)]₁ | sec15 [β·L_j(τ)]₁
+    Sections 12-15 hold one block per power p = 0, 1, … — the 2^p Lagrange values of the size-2^p domain, block p starting at
+    element 2^p − 1 — up to `power`; section 12 goes on to power + 1.  Points are uncompressed, affine, Montgomery form."""
+    tau, alpha, beta = (toxic if toxic is not None else _toxic(seed))[:3]
+    N = 1 << power
+    pw = [1] * (2 * N - 1)
+    for i in range(1, 2 * N - 1):
+        pw[i] = pw[i - 1] * tau % R_MOD
+    lag = []
+    for p in range(power + 2):
+        lag += lagrange_at(1 << p, p, tau) if p else [1]
+    low = lag[:2 * N - 1]                            # blocks 0 … power
+    scale = lambda k, xs: [k * x % R_MOD for x in xs]
+    g1_lists = [pw, scale(alpha, pw[:N]), scale(beta, pw[:N]), lag, scale(alpha, low), scale(beta, low)]
+    g2_lists = [pw[:N], [beta], low]
+    g1 = fixed_base_mul("g1", ints_to_arr([x for xs in g1_lists for x in xs]))
+    g2 = fixed_base_mul("g2", ints_to_arr([x for xs in g2_lists for x in xs]))
+    if points_to_mont is None:
+        def points_to_mont(arr):
+            flat = arr_to_ints(arr.reshape(-1, 4))
+            return ints_to_arr([v * MONT_R % Q_MOD for v in flat]).reshape(arr.shape)
+    pm = lambda arr: np.ascontiguousarray(points_to_mont(np.ascontiguousarray(arr))).tobytes()
+
+    def split(points, lists):
+        out, o = [], 0
+        for xs in lists:
+            out.append(pm(points[o:o + len(xs)]))
+            o += len(xs)
+        return out
+    s2, s4, s5, s12, s14, s15 = split(g1, g1_lists)
+    s3, s6, s13 = split(g2, g2_lists)
+    hdr = struct.pack("<I", 32) + Q_MOD.to_bytes(32, "little") + struct.pack("<II", power, power)
+    secs = [(1, hdr), (2, s2), (3, s3), (4, s4), (5, s5), (6, s6), (7, struct.pack("<I", 0)), (12, s12), (13, s13), (14, s14), (15, s15)]
+    return b"ptau" + struct.pack("<II", 1, len(secs)) + b"".join(_section(sid, p) for sid, p in secs)
 
 
 def vk_to_json(vk: dict) -> str:

@@ -244,8 +244,9 @@ typedef struct {
  * groth16_verify_combined_coefficients(seed, i) and the sums from the library's MSMs over 128-bit scalars: with every B2_i in G2,
  * a key with some B1_i that is not the G1 image of its B2_i passes with probability <= 2^-127 over the seed, WHICH MUST BE SECRET
  * AND FRESH (opt->seed32 is for reproducible tests; NULL draws from the operating system, and the call returns -3 when that fails).
- * What the check does NOT show: that the key belongs to a given circuit or ceremony (groth16_r1cs_match_zkey compares section 4
- * with an .r1cs; the point sections need the .ptau, as `snarkjs zkey verify`), or any relation between A, C, H and IC.
+ * What the check does NOT show: that the key belongs to a given circuit or ceremony, or any relation between A, C, H and IC —
+ * groth16_r1cs_match_zkey compares section 4 with an .r1cs, and groth16_zkey_verify_ptau the point sections with the .r1cs and
+ * the .ptau, as `snarkjs zkey verify` does.
  * device as groth16_verify_batch ("HIP", "CUDA", "HIP:k").  opt may be NULL.  The call holds no cache entry and needs no
  * Groth16CacheManager; the calling thread's device is what it was afterwards.  report->upload_ms: the host to device copies of the
  * sections, device_ms: the wall time of the device part (buffers, uploads, kernels, MSMs), pairing_ms: the host pairings (the
@@ -329,11 +330,79 @@ typedef struct {
  * FRESH (seed32 is for reproducible tests; NULL draws from the operating system, and the call returns -3 when that fails).  The
  * comparison does not depend on the order of section 4's records or on records of one entry that sum.
  * What it does NOT show: anything about C, which section 4 does not hold; and that the point sections 3 and 5 to 9 belong to
- * these matrices, which needs the .ptau (`snarkjs zkey verify`).  Section 4's values are taken as the prover takes them —
+ * these matrices — both are groth16_zkey_verify_ptau's, which needs the .ptau.  Section 4's values are taken as the prover takes them —
  * groth16_zkey_check is what tests value < r.
  * 1 match, 0 not (report says where), < 0 an error with the loader's codes (-2 also for a section-4 record out of range). */
 int groth16_r1cs_match_zkey(Groth16R1cs* h, const void* zkey, size_t len, const uint8_t* seed32 /* NULL = OS randomness */,
                             Groth16R1csMatchReport* report);
+
+/* A prepared .ptau (snarkjs' powers-of-tau container after `powersoftau prepare phase2`), as groth16_zkey_verify_ptau reads it:
+ * magic "ptau", version 1; section 1 = {n8 = 32, q, power, ceremonyPower}; sections 4, 5, 6 = [alpha*tau^i]1, [beta*tau^i]1, [beta]2;
+ * sections 12, 13, 14, 15 = [L_j(tau)]1, [L_j(tau)]2, [alpha*L_j(tau)]1, [beta*L_j(tau)]1 with one block per power p = 0, 1, ... of
+ * 2^p elements beginning at element 2^p - 1 (section 12 goes on to power + 1).  Points are uncompressed, affine, Montgomery form.
+ * groth16_ptau_info reads container and header: -2 for a malformed file, with a text of its own when sections 12 to 15 are
+ * missing (the file has not been prepared for phase 2).  domain_power >= 0 also asks whether the file serves a key of domain
+ * 2^domain_power: -3 when power is below it (both numbers in the text), -2 when a block the verify would read — block k of
+ * sections 12 to 15, block k + 1 of section 12 — does not lie inside its section.  Nothing more is demanded of the lengths.
+ * Host only: never initialises a GPU. */
+typedef struct {
+  uint32_t power, ceremony_power;
+  uint64_t section_bytes[16];  /* payload bytes per section id; 0 = absent */
+} Groth16PtauInfo;
+int groth16_ptau_info(const void* ptau, size_t len, int32_t domain_power /* -1: none */, Groth16PtauInfo* info);
+
+/* groth16_zkey_verify_ptau — is this proving key the Groth16 key of THIS circuit over THIS ceremony?  What `snarkjs zkey verify
+ * circuit.r1cs pot.ptau key.zkey` answers for the point sections, on the GPU.  Opt-in, like the other checks.
+ * Notation: nc constraints, m wires, npub public signals, n = 2^k the domain; L_j the Lagrange basis of the size-n domain, L'_j
+ * that of the size-2n domain; tau, alpha, beta the ptau's; gamma2, delta2 the key header's.  From a seed, z_s =
+ * groth16_verify_combined_coefficients(seed, s) for s < m and y_i = ...(seed, m + i) for i < n; z^pub is z with the private wires
+ * (s > npub) zeroed, z^priv = z - z^pub.  For a vector v, a(v)_j = A_j*v for j < nc, v_{j-nc} on the public-binding rows
+ * nc <= j <= nc + npub, 0 above; b(v)_j = B_j*v and c(v)_j = C_j*v for j < nc, 0 above.  kinds of fault, in the order of testing: */
+#define GROTH16_VERIFY_SIZES   1   /* index: 0 n_vars vs nWires, 1 n_public, 2 domain_size (as groth16_r1cs_match_zkey) */
+#define GROTH16_VERIFY_KEY     2   /* groth16_zkey_check finds a fault: report->key says which; no equation was evaluated (but see below) */
+#define GROTH16_VERIFY_HEADER  3   /* index: 0 alpha1 != section 4 element 0, 1 beta1 != section 5 element 0, 2 beta2 != section 6 */
+#define GROTH16_VERIFY_A       4   /* sum_s z_s*A_s (section 5)   !=  sum_j a(z)_j*[L_j]1                    in G1 */
+#define GROTH16_VERIFY_B1      5   /* sum_s z_s*B1_s (section 6)  !=  sum_j b(z)_j*[L_j]1                    in G1 */
+#define GROTH16_VERIFY_B2      6   /* sum_s z_s*B2_s (section 7)  !=  sum_j b(z)_j*[L_j]2                    in G2 */
+#define GROTH16_VERIFY_IC      7   /* e(sum_{s<=npub} z_s*IC_s, gamma2) != e(T(z^pub), G2),
+                                      T(v) = sum_j ( a(v)_j*[beta*L_j]1 + b(v)_j*[alpha*L_j]1 + c(v)_j*[L_j]1 ) */
+#define GROTH16_VERIFY_C       8   /* e(sum_{s>npub} z_s*C_{s-npub-1}, delta2) != e(T(z^priv), G2) */
+#define GROTH16_VERIFY_H       9   /* e(sum_i y_i*H_i, delta2) != e(sum_i y_i*[L'_{2i+1}]1, G2)   (section 12, block k + 1, odd elements) */
+typedef struct {
+  int32_t  kind;           /* 0 = the key verifies, else the kind of the FIRST fault in the order above */
+  uint64_t index;          /* for SIZES and HEADER only */
+  uint32_t failed_mask;    /* bit (kind - GROTH16_VERIFY_HEADER) for HEADER, A, B1, B2, IC, C, H: every equation that fails,
+                              whatever failed first (0 after SIZES or KEY: nothing was evaluated) */
+  Groth16ZkeyReport key;   /* groth16_zkey_check's report on the key (zeroed after a SIZES fault) */
+  double   upload_ms, device_ms, pairing_ms; /* this call's own uploads; wall time of its device part (buffers, uploads, kernels,
+                                                MSMs); the six host pairings — the embedded report has the key check's */
+} Groth16ZkeyVerifyReport;
+/* The left sides are the library's MSMs over 128-bit scalars, the right sides full-width MSMs over the ptau's block for n; A, B1
+ * and B2 are compared as points, IC, C and H by two host pairings each; the identity on both sides holds, on one side fails (a
+ * circuit without private wires has an empty section 8, and C holds).  The H row is snarkjs' H from the odd Lagrange points of
+ * the doubled domain; this library's synthesised keys use the same basis (L_i(tau/g)*(tau^n - 1)/(-2*delta) = L'_{2i+1}(tau)/delta).
+ * SOUNDNESS.  Every equation is a linear form in the z_s or the y_i; a section that differs from the true one in any element is
+ * accepted with probability <= 2^-127 per equation, so < 2^-124 for the call, over the seed, WHICH MUST BE SECRET AND FRESH
+ * (seed32 is for reproducible tests; NULL draws from the operating system, and the call returns -3 when that fails).  The
+ * argument needs every key point on its curve and every B2_s in the subgroup, so groth16_zkey_check runs first, with the same
+ * seed, and the verdict is 1 only when it says sound; delta1/delta2 and beta1/beta2 are its pair tests.  One fault of its does
+ * not end the call: a mismatch of section 6 against section 7 as the key's only fault leaves every point where the sums are
+ * defined, so the equations run and B1 or B2 names the section that is not the circuit's (report->key still shows the
+ * mismatch; should both hold nonetheless, the kind is KEY).  The ptau ranges that are
+ * read get the same lane tests (coordinates < q, on the curve, section 13 in the subgroup); a ptau point that fails is a format
+ * error (-2) naming section and element.  HEADER compares the stored Montgomery words, which the key check has found canonical.
+ * What it does NOT show: anything about the .ptau itself, which is taken as given (`powersoftau verify` is another question);
+ * the phase-2 contribution chain of section 10 and snarkjs' circuit hash; WHICH element of a section is wrong (a failing
+ * equation is not localised); section 4, which remains groth16_r1cs_match_zkey's.
+ * The key's sections go up twice — once inside the key check, once for the MSMs — so that the key check stays what it is.
+ * report->upload_ms etc. as groth16_zkey_check.  ICICLE_SNARK_TRACE_ZKEY_VERIFY=1 prints the stage times on stderr.
+ * 1 verifies, 0 not (report says why), < 0 an error (groth16_last_error): -1 I/O, -2 format (either file), -3 argument (also a
+ * ptau whose power is below the domain's), -5 device failure.  The _file variant maps both files and uploads only the ranges
+ * it reads: a power-22 .ptau is several GB. */
+int groth16_zkey_verify_ptau(Groth16R1cs* h, const void* zkey, size_t zkey_len, const void* ptau, size_t ptau_len,
+                             const uint8_t* seed32 /* NULL = OS randomness */, Groth16ZkeyVerifyReport* report);
+int groth16_zkey_verify_ptau_file(Groth16R1cs* h, const char* zkey_path, const char* ptau_path, const uint8_t* seed32,
+                                  Groth16ZkeyVerifyReport* report);
 
 #ifdef __cplusplus
 }
