@@ -702,6 +702,7 @@ groth16_zkey_check groth16_zkey_check_file
 groth16_r1cs_info groth16_r1cs_load groth16_r1cs_load_file groth16_r1cs_get_info groth16_r1cs_free
 groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
 groth16_ptau_info groth16_zkey_verify_ptau groth16_zkey_verify_ptau_file
+groth16_zkey_new_size groth16_zkey_new groth16_zkey_new_file
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -943,6 +944,17 @@ VERIFY_SIZES, VERIFY_KEY, VERIFY_HEADER, VERIFY_A, VERIFY_B1, VERIFY_B2, VERIFY_
 VERIFY_KIND_NAMES = ["ok", "SIZES", "KEY", "HEADER", "A", "B1", "B2", "IC", "C", "H"]
 
 
+class ZkeyNewOptions(C.Structure):
+    _fields_ = [("heavy_column_terms", C.c_uint32)]
+
+
+class ZkeyNewReport(C.Structure):
+    """Groth16ZkeyNewReport: the key's sizes, the longest column, the heavy columns and their items, the stage times"""
+    _fields_ = [("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("domain", C.c_uint32), ("n_coeffs", C.c_uint64), ("zkey_bytes", C.c_uint64),
+                ("longest_column", C.c_uint32), ("heavy_columns", C.c_uint32), ("heavy_items", C.c_uint32),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
 def _image(data):
     return data.ctypes.data_as(C.c_void_p) if isinstance(data, np.ndarray) else C.c_char_p(data) if isinstance(data, bytes) else (C.c_char * len(data)).from_buffer(data)
 
@@ -952,6 +964,13 @@ def r1cs_info(r1cs: bytes) -> R1csInfo:
     info = R1csInfo()
     _pcheck(lib().groth16_r1cs_info(_image(r1cs), C.c_size_t(len(r1cs)), C.byref(info)), "r1cs_info")
     return info
+
+
+def zkey_new_size(r1cs: bytes):
+    """groth16_zkey_new_size → (bytes of the key R1cs.new_zkey writes for this circuit, section 4's record count); host only"""
+    size, coeffs = C.c_uint64(), C.c_uint64()
+    _pcheck(lib().groth16_zkey_new_size(_image(r1cs), C.c_size_t(len(r1cs)), C.byref(size), C.byref(coeffs)), "zkey_new_size")
+    return size.value, coeffs.value
 
 
 def ptau_info(ptau, domain_power: int = -1) -> PtauInfo:
@@ -1020,6 +1039,27 @@ class R1cs:
             raise TypeError("verify_zkey: zkey and ptau are both images or both paths")
         return self._verdict(lib().groth16_zkey_verify_ptau(self._h, _image(zkey), C.c_size_t(len(zkey)), _image(ptau), C.c_size_t(len(ptau)), sd, C.byref(rep)),
                              rep, "zkey_verify_ptau")
+
+    def new_zkey(self, ptau, out=None, heavy_column_terms: int = 0):
+        """groth16_zkey_new → (zkey bytes | None, ZkeyNewReport): this circuit's proving key over the prepared .ptau, before any
+        phase-2 contribution (gamma = delta = 1: NOT a key to prove with in production).  ptau: the image, and the key comes back
+        as bytes; or a path together with `out`, the path the key is written to (None comes back).  heavy_column_terms: 0 = the
+        default.  Raises ProverError (−2 an unprepared ptau or a ptau point failing its lane test, −3 a ptau of too low a power)."""
+        opt, rep = ZkeyNewOptions(int(heavy_column_terms)), ZkeyNewReport()
+        if isinstance(ptau, (str, os.PathLike)):
+            if out is None:
+                raise TypeError("new_zkey: a ptau path needs the path to write the key to")
+            _pcheck(lib().groth16_zkey_new_file(self._h, os.fsencode(ptau), os.fsencode(out), C.byref(opt), C.byref(rep)), "zkey_new_file")
+            return None, rep
+        if out is not None:
+            raise TypeError("new_zkey: `out` goes with a ptau path")
+        # sized by the library itself: a first call with no room reports the bytes it needs
+        rc = lib().groth16_zkey_new(self._h, _image(ptau), C.c_size_t(len(ptau)), None, C.c_size_t(0), C.byref(opt), C.byref(rep))
+        if rc != -3 or rep.zkey_bytes == 0:
+            _pcheck(rc, "zkey_new")
+        buf = C.create_string_buffer(rep.zkey_bytes)
+        _pcheck(lib().groth16_zkey_new(self._h, _image(ptau), C.c_size_t(len(ptau)), buf, C.c_size_t(rep.zkey_bytes), C.byref(opt), C.byref(rep)), "zkey_new")
+        return buf.raw, rep
 
     def close(self):
         if self._h:

@@ -11,6 +11,8 @@
 //     the first fault with the counts and "not satisfied"
 //   > r1cs-match --r1cs R --zkey Z [--device HIP]    does the key carry the circuit's A and B (groth16_r1cs_match_zkey)
 //   > zkey-verify --r1cs R --zkey Z --ptau P [--device HIP]   r1cs-match, then the point sections against circuit and ceremony (groth16_zkey_verify_ptau)
+//   > zkey-new --r1cs R --ptau P --zkey OUT [--device HIP]    the circuit's key over the ceremony before any contribution, gamma = delta = 1
+//     (groth16_zkey_new_file): one line with sizes and times, then ZKEY_WRITTEN
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -21,7 +23,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -313,6 +315,29 @@ int main()
           std::cout << std::endl;
           std::cout << (rc == 1 && mrc == 1 ? "ZKEY_OK" : "ZKEY_NOT_OK") << std::endl;
         }
+      }
+      groth16_r1cs_free(h);
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-new") {
+      std::string r1cs = "circuit.r1cs", zkey = "circuit_0000.zkey", ptau = "pot_final.ptau", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--r1cs") in >> r1cs;
+        else if (a == "--zkey") in >> zkey;
+        else if (a == "--ptau") in >> ptau;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16R1cs* h = nullptr;
+      int rc = groth16_r1cs_load_file(r1cs.c_str(), device.c_str(), &h);
+      Groth16ZkeyNewReport rep;
+      if (rc == 0) rc = groth16_zkey_new_file(h, ptau.c_str(), zkey.c_str(), nullptr, &rep);
+      if (rc < 0) {
+        std::cerr << "zkey-new failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        std::cout << "wires " << rep.n_vars << " public " << rep.n_public << " domain " << rep.domain << " coefficients " << rep.n_coeffs << " bytes " << rep.zkey_bytes
+                  << " longest column " << rep.longest_column << " heavy columns " << rep.heavy_columns << " in " << rep.heavy_items << " items; upload " << rep.upload_ms
+                  << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
+        std::cout << "ZKEY_WRITTEN" << std::endl;
       }
       groth16_r1cs_free(h);
       std::cout << "COMMAND_COMPLETED" << std::endl;

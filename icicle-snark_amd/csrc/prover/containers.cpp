@@ -290,3 +290,26 @@ __attribute__((visibility("default"))) int groth16_ptau_info(const void* ptau, s
   for (size_t id = 0; id < 16; id++) info->section_bytes[id] = secs[id].count == 1 ? secs[id].size : 0;
   return 0;
 }
+
+// host only: never initialises a GPU.  The sizes of groth16_zkey_new's file (zkey_new.hip has its layout).
+__attribute__((visibility("default"))) int groth16_zkey_new_size(const void* r1cs, size_t len, uint64_t* zkey_bytes, uint64_t* n_coeffs)
+{
+  if (!zkey_bytes || !n_coeffs) return fail(ERR_ARG, "null output");
+  *zkey_bytes = *n_coeffs = 0;
+  R1csLayout L;
+  if (int rc = r1cs_layout((const uint8_t*)r1cs, len, &L)) return rc;
+  std::vector<uint32_t> rowptr;
+  uint64_t n_terms = 0;
+  if (int rc = r1cs_walk(L, rowptr, &n_terms)) return rc;
+  const uint64_t m = L.n_wires, npub = L.n_public(), nc = L.n_constraints;
+  if (m < npub + 1) return fail(ERR_FORMAT, "r1cs: %u wires cannot hold the constant and %u public signals", L.n_wires, L.n_public());
+  uint64_t ab = 0;
+  for (uint64_t j = 0; j < nc; j++) ab += rowptr[3 * j + 2] - rowptr[3 * j]; // A's and B's terms; C has no records
+  uint64_t n = 1;
+  while (n < nc + npub + 1) n <<= 1; // the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule)
+  *n_coeffs = ab + npub + 1;
+  const uint64_t payload = 4 + (4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128) + 64 * (npub + 1) + (4 + COEF_RECORD_BYTES * *n_coeffs) + 64 * m + 64 * m + 128 * m +
+                           64 * (m - npub - 1) + 64 * n + 4;
+  *zkey_bytes = 12 + 10 * 12 + payload;
+  return 0;
+}

@@ -304,6 +304,14 @@ std::mutex& r1cs_mutex(Groth16R1cs* h); // a handle serves one call at a time
 // a_j = A_j·v, b_j = B_j·v, c_j = C_j·v for j < m to abc[j], abc[m + j], abc[2m + j] (standard form): the witness check's kernel
 // with v (n_wires canonical standard-form values on the handle's device) in the witness's place; enqueued on `stream`
 int r1cs_emit_abc(Groth16R1cs* h, const fe* d_v, fe* d_abc, hipStream_t stream);
+// the handle's rows as groth16_zkey_new (zkey_new.hip) transposes them: rowptr[3m + 1] in terms (rows A_0 B_0 C_0 A_1 …), the wire
+// and the Montgomery coefficient of each term.  Read-only, on the handle's device, valid while the caller holds r1cs_mutex.
+struct R1csDeviceRows {
+  const uint32_t *d_rowptr, *d_cols;
+  const fe* d_vals;
+  uint64_t n_terms;
+};
+R1csDeviceRows r1cs_device_rows(const Groth16R1cs* h);
 } // namespace prover
 } // namespace isnark
 

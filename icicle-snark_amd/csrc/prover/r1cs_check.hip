@@ -363,6 +363,7 @@ namespace isnark {
 namespace prover {
 R1csShape r1cs_shape(const Groth16R1cs* h) { return {h->dev, h->n_wires, h->n_public, h->m}; }
 std::mutex& r1cs_mutex(Groth16R1cs* h) { return h->mu; }
+R1csDeviceRows r1cs_device_rows(const Groth16R1cs* h) { return {h->d_rowptr, h->d_cols, h->d_vals, h->n_terms}; }
 int r1cs_emit_abc(Groth16R1cs* h, const fe* d_v, fe* d_abc, hipStream_t stream)
 {
   if (!h->m) return 0;

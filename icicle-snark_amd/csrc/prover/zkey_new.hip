@@ -1,0 +1,634 @@
+// zkey_new.hip — groth16_zkey_new: the Groth16 proving key of an .r1cs over a prepared .ptau, before any phase-2 contribution
+// (γ = δ = 1; what `snarkjs zkey new` writes, without its circuit hash).  include/groth16_prover.h has the contract and the file's
+// layout; DESIGN.md §7e.
+//
+//   transpose   the handle's rows become column lists, one per (matrix, wire): zn_count_kernel (one lane per row: an atomic per
+//               term on its column's counter; the public-binding rows nc … nc + npub count as terms of A), msm_sort.hip's scan, and
+//               zn_scatter_kernel with an atomic cursor per column.  The order inside a column is whatever the atomics gave: the
+//               sums do not depend on it, and the affine bytes that leave are canonical.  The same pass counts A's and B's terms
+//               per constraint; their scan places section 4's records, which zn_records_kernel writes.
+//   ptau        block k of sections 12, 13, 14, 15 and block k + 1 of section 12 go up and through ptau_g1_kernel / ptau_g2_kernel
+//               (ptau_ranges.h), as groth16_zkey_verify_ptau stages them; odd_gather_kernel makes section 9.
+//   columns     zn_g1_kernel: one lane per (output, wire) for A_s, B1_s and comb_s; zn_g2_kernel: one lane per wire for B2_s — a
+//               kernel of its own, so that G2's registers do not set G1's occupancy.  Each lane walks its column through
+//               zkey_new29.h's zn_walk in lazy XYZZ registers.  A column of more than heavy_column_terms terms is left out: the
+//               plan kernel has cut it into items of that many terms, zn_item_kernel sums an item with one workgroup (each lane a
+//               slice, then an LDS tree of x_add), and zn_combine_kernel adds a column's items the same way.
+//   output      projective sums → batch_to_affine_kernel → affine_to_mont_kernel (msm_impl.h's), the identity kept as zeros, and
+//               down into the caller's buffer or the mapped output file through the pinned staging.
+#include <algorithm>
+#include <chrono>
+#include <fcntl.h>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <vector>
+
+#include "../msm_impl.h"
+#include "../workers.h"
+#include "prover_internal.h"
+#include "ptau_ranges.h"
+#include "verify_batch.h"
+#include "zkey_new29.h"
+
+using namespace bn254;
+using bn254::zn29::ZnEntry;
+using bn254::zn29::ZnList;
+
+namespace {
+
+namespace pv = isnark::prover;
+
+constexpr uint32_t DEFAULT_HEAVY_COLUMN_TERMS = 64; // the large-bucket rule's floor (msm_sort.hip): a starting point, not yet swept
+constexpr uint32_t MIN_HEAVY_COLUMN_TERMS = 8;
+constexpr int ITEM_WG = 64;                          // lanes of an item's / a heavy column's workgroup: one wave
+
+// what the kernels know of the transposed circuit: column (mat, s) is entries[colptr[mat·m + s] … colptr[mat·m + s + 1])
+struct Columns {
+  const uint32_t* colptr; // 3m + 1
+  const ZnEntry* entries;
+  const fe* vals;
+  uint32_t m, thr;
+};
+// G1 job o·m + s: o = 0 A_s, 1 B1_s, 2 comb_s; the G2 job s: B2_s
+enum { OUT_A = 0, OUT_B1 = 1, OUT_COMB = 2, G1_OUTPUTS = 3 };
+struct Counters {
+  uint32_t heavy[2], items[2]; // [0] G1, [1] G2
+  uint32_t longest;
+};
+struct Heavy {
+  uint32_t job, first, n_items;
+};
+struct Item {
+  uint32_t job, lo, hi;
+};
+
+__device__ __forceinline__ ZnList<G1L> list_of(const Columns& c, int mat, uint32_t s, const G1::A* bases)
+{
+  const uint32_t lo = c.colptr[(size_t)mat * c.m + s];
+  return {c.entries + lo, c.colptr[(size_t)mat * c.m + s + 1] - lo, bases};
+}
+// the lists of a G1 job: A and B1 read one column against [L]₁ (the other two lists stay empty), comb all three
+struct G1Job {
+  ZnList<G1L> ls[3];
+  uint32_t len;
+};
+__device__ __forceinline__ G1Job g1_job(const Columns& c, uint32_t job, const G1::A* l, const G1::A* al, const G1::A* bl)
+{
+  const uint32_t o = job / c.m, s = job - o * c.m;
+  G1Job j;
+  const ZnList<G1L> none = {c.entries, 0, l};
+  if (o == OUT_COMB) {
+    j.ls[0] = list_of(c, 0, s, bl);
+    j.ls[1] = list_of(c, 1, s, al);
+    j.ls[2] = list_of(c, 2, s, l);
+  } else {
+    j.ls[0] = list_of(c, (int)o, s, l);
+    j.ls[1] = none;
+    j.ls[2] = none;
+  }
+  j.len = j.ls[0].len + j.ls[1].len + j.ls[2].len;
+  return j;
+}
+__device__ __forceinline__ ZnList<G2L> g2_job(const Columns& c, uint32_t s, const G2::A* l2)
+{
+  const uint32_t lo = c.colptr[(size_t)c.m + s];
+  return {c.entries + lo, c.colptr[(size_t)c.m + s + 1] - lo, l2};
+}
+
+// one lane per row ρ < 3·nc of the handle (ρ = 3j + matrix), then one per public-binding row
+__global__ __launch_bounds__(256) void zn_count_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, uint32_t nc, uint32_t m, uint32_t npub,
+                                                        uint32_t* __restrict__ counts, uint32_t* __restrict__ ab_terms)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t rows = 3 * (uint64_t)nc;
+  if (i < rows) {
+    const uint32_t mat = (uint32_t)(i % 3);
+    for (uint32_t t = rowptr[i]; t < rowptr[i + 1]; t++) atomicAdd(&counts[(size_t)mat * m + cols[t]], 1u);
+    if (mat == 0) ab_terms[i / 3] = rowptr[i + 2] - rowptr[i];
+  } else if (i - rows <= npub) {
+    atomicAdd(&counts[i - rows], 1u);
+  }
+}
+__global__ __launch_bounds__(256) void zn_scatter_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, uint32_t nc, uint32_t m, uint32_t npub,
+                                                          const uint32_t* __restrict__ colptr, uint32_t* __restrict__ cursor, ZnEntry* __restrict__ entries)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t rows = 3 * (uint64_t)nc;
+  if (i < rows) {
+    const uint32_t mat = (uint32_t)(i % 3), j = (uint32_t)(i / 3);
+    for (uint32_t t = rowptr[i]; t < rowptr[i + 1]; t++) {
+      const size_t col = (size_t)mat * m + cols[t];
+      entries[colptr[col] + atomicAdd(&cursor[col], 1u)] = {j, t};
+    }
+  } else if (i - rows <= npub) {
+    const uint32_t s = (uint32_t)(i - rows);
+    entries[colptr[s] + atomicAdd(&cursor[s], 1u)] = {nc + s, zn29::ZN_BINDING};
+  }
+}
+// section 4: record {matrix, row, wire, value·R² mod r} of A's and B's terms, constraint by constraint in the file's order
+// (rec_off[j] = the records before constraint j, rec_off[nc] = all of them), then the binding records (0, nc + s, s, 1)
+__global__ __launch_bounds__(256) void zn_records_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, const fe* __restrict__ vals, uint32_t nc, uint32_t npub,
+                                                          const uint32_t* __restrict__ rec_off, uint32_t* __restrict__ rec)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t rows = 3 * (uint64_t)nc;
+  if (i < rows) {
+    const uint32_t mat = (uint32_t)(i % 3), j = (uint32_t)(i / 3);
+    if (mat == 2) return;
+    const uint32_t t0 = rowptr[i];
+    const size_t base = (size_t)rec_off[j] + (mat ? t0 - rowptr[i - 1] : 0u);
+    for (uint32_t t = t0; t < rowptr[i + 1]; t++) {
+      uint32_t* e = rec + (base + (t - t0)) * 11;
+      const fe v = Fr::to_mont(ld(vals + t)); // value·R in the handle, value·R² in the file
+      e[0] = mat, e[1] = j, e[2] = cols[t];
+#pragma unroll
+      for (int k = 0; k < 8; k++) e[3 + k] = v.l[k];
+    }
+  } else if (i - rows <= npub) {
+    const uint32_t s = (uint32_t)(i - rows);
+    uint32_t* e = rec + ((size_t)rec_off[nc] + s) * 11;
+    const fe v = Fr::r2();
+    e[0] = 0, e[1] = nc + s, e[2] = s;
+#pragma unroll
+    for (int k = 0; k < 8; k++) e[3 + k] = v.l[k];
+  }
+}
+
+// one lane per job: a job of more than thr terms is cut into items of thr terms.  heavy / items have room for every job that can
+// be heavy and every item they can have (the host sizes them from the term total).
+template <bool G2_JOBS>
+__global__ __launch_bounds__(256) void zn_plan_kernel(Columns c, Counters* __restrict__ cnt, Heavy* __restrict__ heavy, Item* __restrict__ items)
+{
+  const uint64_t job64 = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (job64 >= (uint64_t)(G2_JOBS ? 1 : G1_OUTPUTS) * c.m) return;
+  const uint32_t job = (uint32_t)job64;
+  uint32_t len;
+  if (G2_JOBS) {
+    len = c.colptr[(size_t)c.m + job + 1] - c.colptr[(size_t)c.m + job];
+  } else {
+    const uint32_t o = job / c.m, s = job - o * c.m;
+    if (o == OUT_COMB) {
+      const uint32_t lc = c.colptr[2 * (size_t)c.m + s + 1] - c.colptr[2 * (size_t)c.m + s];
+      len = lc + (c.colptr[s + 1] - c.colptr[s]) + (c.colptr[(size_t)c.m + s + 1] - c.colptr[(size_t)c.m + s]);
+      atomicMax(&cnt->longest, lc);
+    } else {
+      len = c.colptr[(size_t)o * c.m + s + 1] - c.colptr[(size_t)o * c.m + s];
+      atomicMax(&cnt->longest, len);
+    }
+  }
+  if (len <= c.thr) return;
+  const uint32_t n_items = (len + c.thr - 1) / c.thr;
+  const uint32_t slot = atomicAdd(&cnt->heavy[G2_JOBS], 1u), first = atomicAdd(&cnt->items[G2_JOBS], n_items);
+  heavy[slot] = {job, first, n_items};
+  for (uint32_t i = 0; i < n_items; i++) items[first + i] = {job, i * c.thr, min(len, (i + 1) * c.thr)};
+}
+
+template <class C, class CL>
+__device__ __forceinline__ void store_sum(typename C::P* out, const typename CL::X& x)
+{
+  *out = C::x_to_projective(CL::x_store(x)); // Montgomery-256 projective, the identity (0, 1, 0)
+}
+
+__global__ __launch_bounds__(64) void zn_g1_kernel(Columns c, const G1::A* __restrict__ l, const G1::A* __restrict__ al, const G1::A* __restrict__ bl, G1::P* __restrict__ out)
+{
+  const uint64_t job = (uint64_t)blockIdx.x * 64 + threadIdx.x;
+  if (job >= (uint64_t)G1_OUTPUTS * c.m) return;
+  const G1Job j = g1_job(c, (uint32_t)job, l, al, bl);
+  if (j.len > c.thr) return; // the item kernels'
+  store_sum<G1, G1L>(out + job, zn29::zn_walk<G1L, 3>(j.ls, c.vals, 0, j.len));
+}
+__global__ __launch_bounds__(64) void zn_g2_kernel(Columns c, const G2::A* __restrict__ l2, G2::P* __restrict__ out)
+{
+  const uint32_t s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= c.m) return;
+  const ZnList<G2L> ls[1] = {g2_job(c, s, l2)};
+  if (ls[0].len > c.thr) return;
+  store_sum<G2, G2L>(out + s, zn29::zn_walk<G2L, 1>(ls, c.vals, 0, ls[0].len));
+}
+
+// Σ over the workgroup's lanes, left in sh[0]
+template <class CL>
+__device__ __forceinline__ void tree_sum(typename CL::X* sh, const typename CL::X& mine)
+{
+  sh[threadIdx.x] = mine;
+  __syncthreads();
+  for (int half = ITEM_WG / 2; half; half >>= 1) {
+    if ((int)threadIdx.x < half) sh[threadIdx.x] = CL::x_add(sh[threadIdx.x], sh[threadIdx.x + half]);
+    __syncthreads();
+  }
+}
+
+// one workgroup per item: lane t walks the t-th slice of the item's positions
+__global__ __launch_bounds__(ITEM_WG) void zn_item_g1_kernel(Columns c, const Item* __restrict__ items, const G1::A* __restrict__ l, const G1::A* __restrict__ al,
+                                                              const G1::A* __restrict__ bl, G1L::X* __restrict__ partial)
+{
+  __shared__ G1L::X sh[ITEM_WG];
+  const Item it = items[blockIdx.x];
+  const G1Job j = g1_job(c, it.job, l, al, bl);
+  const uint32_t per = (it.hi - it.lo + ITEM_WG - 1) / ITEM_WG;
+  const uint32_t lo = min(it.hi, it.lo + threadIdx.x * per), hi = min(it.hi, lo + per);
+  tree_sum<G1L>(sh, zn29::zn_walk<G1L, 3>(j.ls, c.vals, lo, hi));
+  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+__global__ __launch_bounds__(ITEM_WG) void zn_item_g2_kernel(Columns c, const Item* __restrict__ items, const G2::A* __restrict__ l2, G2L::X* __restrict__ partial)
+{
+  __shared__ G2L::X sh[ITEM_WG];
+  const Item it = items[blockIdx.x];
+  const ZnList<G2L> ls[1] = {g2_job(c, it.job, l2)};
+  const uint32_t per = (it.hi - it.lo + ITEM_WG - 1) / ITEM_WG;
+  const uint32_t lo = min(it.hi, it.lo + threadIdx.x * per), hi = min(it.hi, lo + per);
+  tree_sum<G2L>(sh, zn29::zn_walk<G2L, 1>(ls, c.vals, lo, hi));
+  if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+// one workgroup per heavy column: its items' sums, added
+template <class C, class CL>
+__global__ __launch_bounds__(ITEM_WG) void zn_combine_kernel(const Heavy* __restrict__ heavy, const typename CL::X* __restrict__ partial, typename C::P* __restrict__ out)
+{
+  __shared__ typename CL::X sh[ITEM_WG];
+  const Heavy h = heavy[blockIdx.x];
+  typename CL::X acc = CL::x_zero();
+  for (uint32_t i = threadIdx.x; i < h.n_items; i += ITEM_WG) acc = CL::x_add(acc, partial[h.first + i]);
+  tree_sum<CL>(sh, acc);
+  if (threadIdx.x == 0) store_sum<C, CL>(out + h.job, sh[0]);
+}
+
+int dev_fail(const char* what, hipError_t e) { return pv::fail(pv::ERR_DEVICE, "device: %s: %s", what, hipGetErrorString(e)); }
+
+struct Event {
+  hipEvent_t e = nullptr;
+  ~Event()
+  {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// byte offsets of the payloads in the file: sections 1 … 10 in this order, each behind its 12-byte {id, length}
+struct FileLayout {
+  uint64_t off[11], len[11], total;
+  FileLayout(uint64_t m, uint64_t npub, uint64_t n, uint64_t n_coeffs)
+  {
+    const uint64_t l[11] = {0, 4, 4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128, 64 * (npub + 1), 4 + pv::COEF_RECORD_BYTES * n_coeffs, 64 * m, 64 * m, 128 * m, 64 * (m - npub - 1), 64 * n, 4};
+    uint64_t pos = 12;
+    for (int s = 1; s <= 10; s++) {
+      len[s] = l[s];
+      off[s] = pos + 12;
+      pos += 12 + l[s];
+    }
+    total = pos;
+  }
+};
+
+uint64_t domain_of(uint64_t nc, uint64_t npub, uint32_t* k)
+{
+  uint64_t domain = 1;
+  *k = 0;
+  while (domain < nc + npub + 1) domain <<= 1, (*k)++; // the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule)
+  return domain;
+}
+
+// where the key goes, once its size is known: the caller's buffer, or the mapped temporary of the _file entry
+typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+
+int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau_fd, const Groth16ZkeyNewOptions* opt, Groth16ZkeyNewReport* rep, const Sink& sink)
+{
+  if (!rep) return pv::fail(pv::ERR_ARG, "null report");
+  memset(rep, 0, sizeof *rep);
+  if (!h) return pv::fail(pv::ERR_ARG, "null r1cs handle");
+  std::vector<pv::Section> psecs;
+  pv::PtauLayout PL;
+  if (int rc = pv::ptau_layout(ptau, ptau_len, psecs, &PL)) return rc;
+  const pv::R1csShape shape = pv::r1cs_shape(h);
+  const uint32_t m = shape.n_wires, npub = shape.n_public, nc = shape.m;
+  if ((uint64_t)m < (uint64_t)npub + 1) return pv::fail(pv::ERR_FORMAT, "r1cs: %u wires cannot hold the constant and %u public signals", m, npub);
+  uint32_t k;
+  const uint64_t domain = domain_of(nc, npub, &k);
+  if (k > 28) return pv::fail(pv::ERR_ARG, "the circuit's domain 2^%u is above the field's two-adicity", k);
+  if (int rc = pv::ptau_blocks_for_domain(PL, k)) return rc;
+  const uint32_t n = (uint32_t)domain;
+  rep->n_vars = m, rep->n_public = npub, rep->domain = n;
+  const pv::R1csDeviceRows rows = pv::r1cs_device_rows(h);
+  const uint64_t n_entries = rows.n_terms + npub + 1;
+  if (3 * (uint64_t)m + 1 > 0xffffffffull || n_entries > 0xffffffffull) return pv::fail(pv::ERR_ARG, "the circuit's columns do not fit 32-bit offsets");
+  // the header's α₁, β₁, β₂ are copied words: the lane tests on the host first, as the key check runs them on a header
+  {
+    fe p1[2];
+    fe2 p2[2];
+    const int hdr_sec[2] = {4, 5};
+    for (int sid : hdr_sec) {
+      memcpy(p1, PL.sec[sid]->p, 64);
+      if (const int kind = p29::classify_g1(p1)) return pv::fail(pv::ERR_FORMAT, "ptau: section %d, element 0: %s", sid, POINT_FAULT[kind & 3]);
+    }
+    memcpy(p2, PL.sec[6]->p, 128);
+    if (const int kind = p29::classify_g2(p2)) return pv::fail(pv::ERR_FORMAT, "ptau: section 6, element 0: %s", POINT_FAULT[kind & 3]);
+  }
+
+  static const bool trace = isnark::env_set("ICICLE_SNARK_TRACE_ZKEY_NEW");
+  auto t_prev = std::chrono::steady_clock::now();
+  auto lap = [&](const char* what) {
+    if (!trace) return;
+    const auto t = std::chrono::steady_clock::now();
+    fprintf(stderr, "[zkey-new] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
+    t_prev = t;
+  };
+
+  uint32_t thr = opt && opt->heavy_column_terms ? opt->heavy_column_terms : DEFAULT_HEAVY_COLUMN_TERMS;
+  thr = std::max(thr, MIN_HEAVY_COLUMN_TERMS);
+
+  std::lock_guard<std::mutex> lk(pv::r1cs_mutex(h));
+  const auto t_dev = std::chrono::steady_clock::now();
+  isnark::vb::DeviceSession ds;
+  if (ds.open(shape.dev, 2)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  const hipStream_t st = ds.stream(0), st2 = ds.stream(1);
+  Event ev_cols, ev_g2;
+  if (hipError_t he = hipEventCreateWithFlags(&ev_cols.e, hipEventDisableTiming)) return dev_fail("hipEventCreate", he);
+  if (hipError_t he = hipEventCreateWithFlags(&ev_g2.e, hipEventDisableTiming)) return dev_fail("hipEventCreate", he);
+  bool oom = false;
+  auto alloc = [&](auto** p, size_t count) {
+    typedef typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type T;
+    *p = ds.buf.alloc<T>(std::max<size_t>(count, 1));
+    if (!*p) oom = true;
+  };
+
+  // ---- transpose: column lists, and section 4's records
+  const uint32_t n_cols = 3 * m + 1;
+  // a heavy job has more than thr terms and the jobs of a group share at most 2·n_entries (G1) / n_entries (G2) of them
+  const uint64_t cap_heavy[2] = {2 * n_entries / thr + 1, n_entries / thr + 1};
+  const uint64_t cap_items[2] = {2 * cap_heavy[0] + 1, 2 * cap_heavy[1] + 1};
+  uint32_t *d_counts, *d_colptr, *d_ab, *d_recoff, *d_scan, *d_rec;
+  ZnEntry* d_entries;
+  Counters* d_cnt;
+  unsigned long long* d_first; // [0 … 4]: the five ptau ranges
+  Heavy* d_heavy[2];
+  Item* d_items[2];
+  alloc(&d_counts, n_cols);
+  alloc(&d_colptr, n_cols);
+  alloc(&d_ab, (size_t)nc + 1);
+  alloc(&d_recoff, (size_t)nc + 1);
+  alloc(&d_scan, std::max(isnark::exclusive_scan_u32_scratch_words(n_cols), isnark::exclusive_scan_u32_scratch_words(nc + 1)));
+  alloc(&d_rec, (size_t)n_entries * 11);
+  alloc(&d_entries, (size_t)n_entries);
+  alloc(&d_cnt, 1);
+  alloc(&d_first, 5);
+  for (int g = 0; g < 2; g++) {
+    alloc(&d_heavy[g], (size_t)cap_heavy[g]);
+    alloc(&d_items[g], (size_t)cap_items[g]);
+  }
+  if (oom) return dev_fail("hipMalloc", hipErrorOutOfMemory);
+  if (hipError_t he = hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st)) return dev_fail("hipMemset", he);
+  if (hipError_t he = hipMemsetAsync(d_ab, 0, ((size_t)nc + 1) * 4, st)) return dev_fail("hipMemset", he);
+  if (hipError_t he = hipMemsetAsync(d_cnt, 0, sizeof(Counters), st)) return dev_fail("hipMemset", he);
+  if (hipError_t he = hipMemsetAsync(d_first, 0xff, 5 * sizeof *d_first, st)) return dev_fail("hipMemset", he);
+  const uint64_t row_lanes = 3 * (uint64_t)nc + npub + 1;
+  const dim3 row_grid((uint32_t)((row_lanes + 255) / 256));
+  hipLaunchKernelGGL(zn_count_kernel, row_grid, dim3(256), 0, st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_counts, d_ab);
+  if (hipError_t he = hipGetLastError()) return dev_fail("count kernel launch", he);
+  if (hipError_t he = isnark::exclusive_scan_u32(d_counts, n_cols, d_colptr, d_scan, st)) return dev_fail("column scan", he);
+  if (hipError_t he = isnark::exclusive_scan_u32(d_ab, nc + 1, d_recoff, d_scan, st)) return dev_fail("record scan", he);
+  if (hipError_t he = hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st)) return dev_fail("hipMemset", he); // now the cursors
+  hipLaunchKernelGGL(zn_scatter_kernel, row_grid, dim3(256), 0, st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_colptr, d_counts, d_entries);
+  if (hipError_t he = hipGetLastError()) return dev_fail("scatter kernel launch", he);
+  hipLaunchKernelGGL(zn_records_kernel, row_grid, dim3(256), 0, st, rows.d_rowptr, rows.d_cols, rows.d_vals, nc, npub, d_recoff, d_rec);
+  if (hipError_t he = hipGetLastError()) return dev_fail("records kernel launch", he);
+  const Columns cols = {d_colptr, d_entries, rows.d_vals, m, thr};
+  hipLaunchKernelGGL(zn_plan_kernel<false>, dim3((uint32_t)((3 * (uint64_t)m + 255) / 256)), dim3(256), 0, st, cols, d_cnt, d_heavy[0], d_items[0]);
+  if (hipError_t he = hipGetLastError()) return dev_fail("plan kernel launch", he);
+  hipLaunchKernelGGL(zn_plan_kernel<true>, dim3((m + 255) / 256), dim3(256), 0, st, cols, d_cnt, d_heavy[1], d_items[1]);
+  if (hipError_t he = hipGetLastError()) return dev_fail("plan kernel launch", he);
+  // (the second stream's first kernel writes d_first: behind the memsets)
+  if (hipError_t he = hipEventRecord(ev_cols.e, st)) return dev_fail("hipEventRecord", he);
+  if (hipError_t he = hipStreamWaitEvent(st2, ev_cols.e, 0)) return dev_fail("hipStreamWaitEvent", he);
+  lap("session, transpose enqueued");
+
+  // ---- the ptau's ranges: block k of 12, 13, 14, 15 and block k + 1 of 12, each tested where it lands
+  const int blk_sec[5] = {12, 13, 14, 15, 12};
+  const uint32_t blk_pow[5] = {k, k, k, k, k + 1};
+  uint8_t* d_blk[5];
+  if (ptau_fd >= 0) isnark::staged_copy_file_hint(ptau, ptau_len, ptau_fd);
+  for (int i = 0; i < 5; i++) {
+    const size_t elem = blk_sec[i] == 13 ? 128 : 64;
+    const uint64_t cnt = (uint64_t)1 << blk_pow[i];
+    const uint8_t* src;
+    int rc = pv::ptau_block(PL, blk_sec[i], blk_pow[i], elem, &src);
+    if (!rc) {
+      alloc(&d_blk[i], (size_t)(cnt * elem));
+      if (oom) rc = dev_fail("hipMalloc", hipErrorOutOfMemory);
+    }
+    if (!rc) {
+      const auto t0 = std::chrono::steady_clock::now();
+      const isnark::CopyJob job = {d_blk[i], src, (size_t)(cnt * elem)};
+      if (hipError_t he = isnark::staged_copy(shape.dev, &job, 1, true)) rc = dev_fail("host to device upload", he);
+      rep->upload_ms += pv::ms_since(t0);
+    }
+    if (rc) {
+      isnark::staged_copy_file_hint(nullptr, 0, -1);
+      return rc;
+    }
+    // (the G2 block's test on the second stream: it is the long one, and the uploads behind it do not wait for it)
+    if (elem == 64) hipLaunchKernelGGL(ptau_g1_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, (const fe*)d_blk[i], (uint32_t)cnt, d_first + i);
+    else hipLaunchKernelGGL(ptau_g2_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, st2, (const fe2*)d_blk[i], (uint32_t)cnt, d_first + i);
+    if (hipError_t he = hipGetLastError()) {
+      isnark::staged_copy_file_hint(nullptr, 0, -1);
+      return dev_fail("ptau membership kernel launch", he);
+    }
+  }
+  isnark::staged_copy_file_hint(nullptr, 0, -1);
+  lap("ptau ranges uploaded");
+
+  // ---- what the host has to know before the columns run: the lane tests' verdicts, the record count, the heavy columns
+  if (hipError_t he = hipEventRecord(ev_g2.e, st2)) return dev_fail("hipEventRecord", he);
+  if (hipError_t he = hipStreamWaitEvent(st, ev_g2.e, 0)) return dev_fail("hipStreamWaitEvent", he);
+  unsigned long long first[5];
+  Counters cnt;
+  uint32_t n_ab = 0;
+  if (hipError_t he = hipMemcpyAsync(first, d_first, sizeof first, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
+  if (hipError_t he = hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
+  if (hipError_t he = hipMemcpyAsync(&n_ab, d_recoff + nc, 4, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
+  if (hipError_t he = hipStreamSynchronize(st)) return dev_fail("transpose and ptau kernels", he);
+  for (int i = 0; i < 5; i++)
+    if (first[i] != NO_FAULT)
+      return pv::fail(pv::ERR_FORMAT, "ptau: section %d, block %u, element %llu: %s", blk_sec[i], blk_pow[i], (unsigned long long)(first[i] >> 3), POINT_FAULT[first[i] & 3]);
+  lap("lane tests, plan");
+  const uint64_t n_coeffs = (uint64_t)n_ab + npub + 1;
+  const FileLayout F(m, npub, n, n_coeffs);
+  rep->n_coeffs = n_coeffs;
+  rep->zkey_bytes = F.total;
+  rep->longest_column = cnt.longest;
+  rep->heavy_columns = cnt.heavy[0] + cnt.heavy[1];
+  rep->heavy_items = cnt.items[0] + cnt.items[1];
+  if (cnt.heavy[0] > cap_heavy[0] || cnt.heavy[1] > cap_heavy[1] || cnt.items[0] > cap_items[0] || cnt.items[1] > cap_items[1])
+    return pv::fail(pv::ERR_DEVICE, "device: the heavy-column plan overran its bounds"); // (cannot happen: the bounds are sums of terms)
+  uint8_t* out = nullptr;
+  if (int rc = sink(F.total, &out)) return rc;
+
+  // ---- columns
+  G1::P* d_p1;
+  G2::P* d_p2;
+  G1::A* d_a1;
+  G2::A* d_a2;
+  fe* d_s1;
+  fe2* d_s2;
+  uint8_t* d_odd;
+  G1L::X* d_part1;
+  G2L::X* d_part2;
+  alloc(&d_p1, (size_t)G1_OUTPUTS * m);
+  alloc(&d_p2, (size_t)m);
+  alloc(&d_a1, (size_t)G1_OUTPUTS * m);
+  alloc(&d_a2, (size_t)m);
+  alloc(&d_s1, (size_t)G1_OUTPUTS * m);
+  alloc(&d_s2, (size_t)m);
+  alloc(&d_odd, (size_t)n * 64);
+  alloc(&d_part1, (size_t)cnt.items[0]);
+  alloc(&d_part2, (size_t)cnt.items[1]);
+  if (oom) return dev_fail("hipMalloc", hipErrorOutOfMemory);
+  const G1::A *l1 = (const G1::A*)d_blk[0], *al = (const G1::A*)d_blk[2], *bl = (const G1::A*)d_blk[3];
+  const G2::A* l2 = (const G2::A*)d_blk[1];
+  // G2 on the second stream, beside the G1 kernels
+  hipLaunchKernelGGL(zn_g2_kernel, dim3((m + 63) / 64), dim3(64), 0, st2, cols, l2, d_p2);
+  if (hipError_t he = hipGetLastError()) return dev_fail("G2 column kernel launch", he);
+  if (cnt.heavy[1]) {
+    hipLaunchKernelGGL(zn_item_g2_kernel, dim3(cnt.items[1]), dim3(ITEM_WG), 0, st2, cols, d_items[1], l2, d_part2);
+    if (hipError_t he = hipGetLastError()) return dev_fail("G2 item kernel launch", he);
+    hipLaunchKernelGGL((zn_combine_kernel<G2, G2L>), dim3(cnt.heavy[1]), dim3(ITEM_WG), 0, st2, d_heavy[1], d_part2, d_p2);
+    if (hipError_t he = hipGetLastError()) return dev_fail("G2 combine kernel launch", he);
+  }
+  const int chunk = 32;
+  {
+    const uint64_t threads = ((uint64_t)m + chunk - 1) / chunk;
+    hipLaunchKernelGGL((batch_to_affine_kernel<G2, Fq2Ops>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st2, d_p2, (uint64_t)m, chunk, d_a2, d_s2);
+    if (hipError_t he = hipGetLastError()) return dev_fail("batch_to_affine launch", he);
+    const uint64_t ncoord = 4 * (uint64_t)m;
+    hipLaunchKernelGGL((affine_to_mont_kernel<G2::A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), 0, st2, d_a2, ncoord);
+    if (hipError_t he = hipGetLastError()) return dev_fail("affine_to_mont launch", he);
+  }
+  hipLaunchKernelGGL(zn_g1_kernel, dim3((uint32_t)((G1_OUTPUTS * (uint64_t)m + 63) / 64)), dim3(64), 0, st, cols, l1, al, bl, d_p1);
+  if (hipError_t he = hipGetLastError()) return dev_fail("G1 column kernel launch", he);
+  if (cnt.heavy[0]) {
+    hipLaunchKernelGGL(zn_item_g1_kernel, dim3(cnt.items[0]), dim3(ITEM_WG), 0, st, cols, d_items[0], l1, al, bl, d_part1);
+    if (hipError_t he = hipGetLastError()) return dev_fail("G1 item kernel launch", he);
+    hipLaunchKernelGGL((zn_combine_kernel<G1, G1L>), dim3(cnt.heavy[0]), dim3(ITEM_WG), 0, st, d_heavy[0], d_part1, d_p1);
+    if (hipError_t he = hipGetLastError()) return dev_fail("G1 combine kernel launch", he);
+  }
+  {
+    const uint64_t pts = G1_OUTPUTS * (uint64_t)m, threads = (pts + chunk - 1) / chunk;
+    hipLaunchKernelGGL((batch_to_affine_kernel<G1, FqOps>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st, d_p1, pts, chunk, d_a1, d_s1);
+    if (hipError_t he = hipGetLastError()) return dev_fail("batch_to_affine launch", he);
+    hipLaunchKernelGGL((affine_to_mont_kernel<G1::A>), dim3((uint32_t)((2 * pts + 255) / 256)), dim3(256), 0, st, d_a1, 2 * pts);
+    if (hipError_t he = hipGetLastError()) return dev_fail("affine_to_mont launch", he);
+  }
+  hipLaunchKernelGGL(odd_gather_kernel, dim3((uint32_t)((4 * (uint64_t)n + 255) / 256)), dim3(256), 0, st, (const uint4*)d_blk[4], (uint64_t)n, (uint4*)d_odd);
+  if (hipError_t he = hipGetLastError()) return dev_fail("gather kernel launch", he);
+  if (hipError_t he = hipStreamSynchronize(st)) return dev_fail("G1 column kernels", he);
+  lap("G1 kernels done");
+  if (hipError_t he = hipStreamSynchronize(st2)) return dev_fail("G2 column kernels", he);
+  lap("G2 kernels done");
+  rep->device_ms = pv::ms_since(t_dev);
+
+  // ---- the file
+  const auto t_down = std::chrono::steady_clock::now();
+  const uint8_t *a1 = (const uint8_t*)d_a1, *a2 = (const uint8_t*)d_a2;
+  const size_t per = (size_t)m * 64;
+  const isnark::CopyJob jobs[7] = {
+    {out + F.off[3], a1 + OUT_COMB * per, (size_t)F.len[3]},                   // comb_s, s <= npub
+    {out + F.off[4] + 4, d_rec, (size_t)(n_coeffs * pv::COEF_RECORD_BYTES)},
+    {out + F.off[5], a1 + OUT_A * per, per},
+    {out + F.off[6], a1 + OUT_B1 * per, per},
+    {out + F.off[7], a2, (size_t)m * 128},
+    {out + F.off[8], a1 + OUT_COMB * per + F.len[3], (size_t)F.len[8]},        // comb_s, s > npub
+    {out + F.off[9], d_odd, (size_t)n * 64},
+  };
+  if (hipError_t he = isnark::staged_copy(shape.dev, jobs, 7, false)) return dev_fail("device to host download", he);
+  rep->download_ms = pv::ms_since(t_down);
+  memcpy(out, "zkey", 4);
+  const uint32_t version = 1, n_sections = 10, protocol = 1, n8 = 32, zero = 0, n_coeffs32 = (uint32_t)n_coeffs;
+  memcpy(out + 4, &version, 4);
+  memcpy(out + 8, &n_sections, 4);
+  for (uint32_t s = 1; s <= 10; s++) {
+    memcpy(out + F.off[s] - 12, &s, 4);
+    memcpy(out + F.off[s] - 8, &F.len[s], 8);
+  }
+  memcpy(out + F.off[1], &protocol, 4);
+  uint8_t* hd = out + F.off[2];
+  const fe q = Fq::modulus(), r = Fr::modulus();
+  memcpy(hd, &n8, 4);
+  memcpy(hd + 4, q.l, 32);
+  memcpy(hd + 36, &n8, 4);
+  memcpy(hd + 40, r.l, 32);
+  memcpy(hd + 72, &m, 4);
+  memcpy(hd + 76, &npub, 4);
+  memcpy(hd + 80, &n, 4);
+  // α₁ β₁ β₂ the ptau's stored words; γ₂ = G₂, δ₁ = G₁, δ₂ = G₂ in Montgomery form
+  bn254_projective_t g1p;
+  bn254_g2_projective_t g2p;
+  bn254_affine_t g1s;
+  bn254_g2_affine_t g2s;
+  bn254_generator(&g1p);
+  bn254_to_affine(&g1p, &g1s);
+  bn254_g2_generator(&g2p);
+  bn254_g2_to_affine(&g2p, &g2s);
+  G1::A g1;
+  G2::A g2;
+  memcpy(&g1, &g1s, sizeof g1);
+  memcpy(&g2, &g2s, sizeof g2);
+  g1 = G1::aff_to_mont(g1);
+  g2 = G2::aff_to_mont(g2);
+  memcpy(hd + 84, PL.sec[4]->p, 64);
+  memcpy(hd + 148, PL.sec[5]->p, 64);
+  memcpy(hd + 212, PL.sec[6]->p, 128);
+  memcpy(hd + 340, &g2, 128);
+  memcpy(hd + 468, &g1, 64);
+  memcpy(hd + 532, &g2, 128);
+  memcpy(out + F.off[4], &n_coeffs32, 4);
+  memcpy(out + F.off[10], &zero, 4);
+  lap("download, header");
+  return 0;
+}
+
+} // namespace
+
+ISNARK_API int groth16_zkey_new(Groth16R1cs* h, const void* ptau, size_t ptau_len, void* zkey_out, size_t cap, const Groth16ZkeyNewOptions* opt, Groth16ZkeyNewReport* report)
+{
+  const Sink sink = [&](uint64_t bytes, uint8_t** out) {
+    if (!zkey_out || cap < bytes) return pv::fail(pv::ERR_ARG, "the key needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(zkey_out ? cap : 0));
+    *out = (uint8_t*)zkey_out;
+    return 0;
+  };
+  return zkey_new_impl(h, (const uint8_t*)ptau, ptau_len, -1, opt, report, sink);
+}
+
+ISNARK_API int groth16_zkey_new_file(Groth16R1cs* h, const char* ptau_path, const char* zkey_path, const Groth16ZkeyNewOptions* opt, Groth16ZkeyNewReport* report)
+{
+  if (!ptau_path || !zkey_path) return pv::fail(pv::ERR_ARG, "null path");
+  pv::MappedFile pf;
+  if (int rc = pf.open_ro(ptau_path, /*read_ahead=*/false)) return rc; // only the ranges that are read are touched
+  // a temporary beside zkey_path, renamed over it at the end: a failed call leaves nothing there
+  const std::string tmp = std::string(zkey_path) + ".tmp." + std::to_string((long)getpid());
+  int fd = -1;
+  uint8_t* map = nullptr;
+  uint64_t map_len = 0;
+  const Sink sink = [&](uint64_t bytes, uint8_t** out) {
+    fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) return pv::fail(pv::ERR_IO, "cannot create %s", tmp.c_str());
+    if (ftruncate(fd, (off_t)bytes) != 0) return pv::fail(pv::ERR_IO, "cannot size %s to %llu bytes", tmp.c_str(), (unsigned long long)bytes);
+    void* p = mmap(nullptr, (size_t)bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+    if (p == MAP_FAILED) return pv::fail(pv::ERR_IO, "cannot mmap %s", tmp.c_str());
+    map = (uint8_t*)p;
+    map_len = bytes;
+    *out = map;
+    return 0;
+  };
+  int rc = zkey_new_impl(h, pf.data, pf.len, pf.fd, opt, report, sink);
+  const auto t_write = std::chrono::steady_clock::now();
+  if (map) {
+    if (rc == 0 && msync(map, (size_t)map_len, MS_SYNC) != 0) rc = pv::fail(pv::ERR_IO, "cannot write %s", tmp.c_str());
+    munmap(map, (size_t)map_len);
+  }
+  if (fd >= 0) close(fd);
+  if (rc == 0 && rename(tmp.c_str(), zkey_path) != 0) rc = pv::fail(pv::ERR_IO, "cannot rename %s to %s", tmp.c_str(), zkey_path);
+  if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
+  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
+  return rc;
+}

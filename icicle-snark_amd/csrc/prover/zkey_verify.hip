@@ -10,7 +10,7 @@
 //             a, b, c at each; verify_assemble_kernel — one lane per row j < n — writes the eight scalar vectors of the right sides
 //             with the public-binding rows and the zero tail applied.
 //   ptau      block k of sections 12, 13, 14, 15 and block k + 1 of section 12 go up (nothing else of the file is touched) and
-//             through ptau_g1_kernel / ptau_g2_kernel (zkey_check29.h's tests, one lane per point); odd_gather_kernel makes
+//             through ptau_g1_kernel / ptau_g2_kernel (ptau_ranges.h: zkey_check29.h's tests, one lane per point); odd_gather_kernel makes
 //             [L'_{2i+1}]₁ contiguous.
 //   sums      six left sides with bitsize = 128 over the key's sections (uploaded here a second time: the key check keeps only 6 and
 //             7 and frees them with its session), ten full-width right sides; bases in slices of MSM_SLICE, partial sums added.
@@ -22,6 +22,7 @@
 
 #include "../workers.h"
 #include "prover_internal.h"
+#include "ptau_ranges.h"
 #include "sha256.h"
 #include "verify_batch.h"
 #include "zkey_check29.h"
@@ -33,18 +34,8 @@ namespace {
 namespace pv = isnark::prover;
 
 constexpr uint32_t MSM_SLICE = 1u << 24; // bases per MSM call (partial sums add), as zkey_check.hip
-constexpr unsigned long long NO_FAULT = ~0ull;
 enum { V_A = 0, V_B, V_A_PUB, V_B_PUB, V_C_PUB, V_A_PRIV, V_B_PRIV, V_C_PRIV, N_VEC };
 
-__device__ __forceinline__ fe ld(const fe* p)
-{
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  const uint4 lo = q[0], hi = q[1];
-  fe v;
-  v.l[0] = lo.x, v.l[1] = lo.y, v.l[2] = lo.z, v.l[3] = lo.w;
-  v.l[4] = hi.x, v.l[5] = hi.y, v.l[6] = hi.z, v.l[7] = hi.w;
-  return v;
-}
 __device__ __forceinline__ void st(fe* p, const fe& v)
 {
   uint4* q = reinterpret_cast<uint4*>(p);
@@ -86,33 +77,6 @@ __global__ __launch_bounds__(256) void verify_assemble_kernel(const fe* __restri
   }
 #pragma unroll
   for (int k = 0; k < N_VEC; k++) st(out + (size_t)k * n + j, v[k]);
-}
-
-// out point i < cnt (64-byte rows) = in point 2i + 1.  One lane per 16 bytes of the output: the stores of a wave are 1 KB
-// contiguous, its loads sixteen 64-byte rows at a stride of 128 bytes.
-__global__ __launch_bounds__(256) void odd_gather_kernel(const uint4* __restrict__ in, uint64_t cnt, uint4* __restrict__ out)
-{
-  const uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (q >= 4 * cnt) return;
-  out[q] = in[(q >> 2) * 8 + 4 + (q & 3)];
-}
-
-// membership of the ptau ranges that are read, zkey_check29.h's tests: min over the faulting lanes of (index << 3 | kind)
-__global__ __launch_bounds__(256) void ptau_g1_kernel(const fe* __restrict__ pts, uint32_t cnt, unsigned long long* __restrict__ first)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= cnt) return;
-  const fe p[2] = {ld(pts + 2 * (size_t)i), ld(pts + 2 * (size_t)i + 1)};
-  const int kind = p29::classify_g1(p);
-  if (kind) atomicMin(first, (unsigned long long)i << 3 | (unsigned long long)kind);
-}
-__global__ __launch_bounds__(64) void ptau_g2_kernel(const fe2* __restrict__ pts, uint32_t cnt, unsigned long long* __restrict__ first)
-{
-  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= cnt) return;
-  const fe2 p[2] = {pts[2 * (size_t)i], pts[2 * (size_t)i + 1]};
-  const int kind = p29::classify_g2(p);
-  if (kind) atomicMin(first, (unsigned long long)i << 3 | (unsigned long long)kind);
 }
 
 int dev_fail(const char* what, hipError_t e) { return pv::fail(pv::ERR_DEVICE, "device: %s: %s", what, hipGetErrorString(e)); }
@@ -253,8 +217,6 @@ struct Verify {
     return 0;
   }
 };
-
-const char* const POINT_FAULT[4] = {"", "a coordinate is not below q", "the point is not on the curve", "the point is outside the subgroup"};
 
 int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint8_t* ptau, size_t ptau_len, const uint8_t* seed32, Groth16ZkeyVerifyReport* rep, int zkey_fd, int ptau_fd)
 {

@@ -404,6 +404,50 @@ int groth16_zkey_verify_ptau(Groth16R1cs* h, const void* zkey, size_t zkey_len, 
 int groth16_zkey_verify_ptau_file(Groth16R1cs* h, const char* zkey_path, const char* ptau_path, const uint8_t* seed32,
                                   Groth16ZkeyVerifyReport* report);
 
+/* groth16_zkey_new — the Groth16 proving key of THIS circuit over THIS ceremony, before any phase-2 contribution: what `snarkjs
+ * zkey new circuit.r1cs pot.ptau out.zkey` writes, made on the GPU.  Opt-in; nothing else in the library calls it.
+ * WHAT IT IS NOT: a key to prove with in production.  Its gamma and delta are 1 (gamma2 = delta2 = G2, delta1 = G1): whoever knows
+ * that can forge proofs, until a phase-2 contribution has replaced delta.  The call builds and does not verify — the .ptau is taken
+ * as given; groth16_zkey_check, groth16_r1cs_match_zkey and groth16_zkey_verify_ptau are what judge the result.
+ * Notation as above: nc constraints, m wires, npub public signals, n = 2^k the smallest power of two >= nc + npub + 1.  For a wire s
+ *   A_s  = sum_j A[j,s]*[L_j]1 (+ [L_{nc+s}]1 for s <= npub: the rows snarkjs adds to bind the public signals)
+ *   B1_s = sum_j B[j,s]*[L_j]1,   B2_s = sum_j B[j,s]*[L_j]2
+ *   comb_s = sum_j ( A[j,s]*[beta*L_j]1 + B[j,s]*[alpha*L_j]1 + C[j,s]*[L_j]1 ) (+ [beta*L_{nc+s}]1 for s <= npub)
+ * THE FILE: sections 1 to 10 in this order.  2: n8, q, n8, r, m, npub, n, then alpha1 = ptau section 4 element 0, beta1 = section 5
+ * element 0, beta2 = section 6 (the stored words, copied), gamma2 = G2, delta1 = G1, delta2 = G2.  3: comb_s for s <= npub.  4: a
+ * count and one record {matrix, row, wire, value*R^2 mod r} per term of A and of B as the .r1cs lists them — zero coefficients and
+ * repeated wires kept — constraint by constraint, A's terms then B's, then the npub + 1 binding records (0, nc + s, s, 1).  5, 6,
+ * 7: A, B1, B2.  8: comb_s for s > npub (empty for a circuit without private wires).  9: [L'_{2i+1}]1, i < n — section 12, block
+ * k + 1, odd elements.  10: a zero contribution count; snarkjs' 64-byte circuit hash is NOT written.  Points are affine,
+ * Montgomery form, the identity (0, 0); a wire that appears in no matrix is all-zero bytes.
+ * groth16_zkey_new_size is the host half: the file's size and section 4's record count (terms of A + terms of B + npub + 1) from
+ * the .r1cs alone, with groth16_r1cs_info's walk and its codes.  It never initialises a GPU.
+ * The .ptau is read as groth16_zkey_verify_ptau reads it: block k of sections 12 to 15 and block k + 1 of section 12 go up and
+ * through the lane tests before anything reads them.  A column of more than heavy_column_terms terms (the constant wire can sit in
+ * every constraint) is cut into items that a workgroup each sums; the result does not depend on the threshold. */
+typedef struct {
+  uint32_t heavy_column_terms;   /* 0 = the default */
+} Groth16ZkeyNewOptions;
+typedef struct {
+  uint32_t n_vars, n_public, domain;
+  uint64_t n_coeffs, zkey_bytes;           /* section 4's records; the file (also when cap was too small) */
+  uint32_t longest_column;                  /* terms of the longest (matrix, wire) column, binding rows included */
+  uint32_t heavy_columns, heavy_items;      /* sums that were cut, and the items they were cut into */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the ptau ranges' copies; wall time of the device part up to the last
+                                               kernel; the copies into the buffer or the mapped file; msync and rename (_file) */
+} Groth16ZkeyNewReport;
+/* 0 built; -1 I/O; -2 format: a ptau that is not prepared for phase 2, or a ptau point of a range that is read failing its lane
+ * test (the text names section, block and element); -3 argument: a ptau whose power is below the domain's (both numbers in the
+ * text), or cap too small (report->zkey_bytes still says what is needed); -5 device failure (groth16_last_error).  The _file
+ * variant maps the .ptau and uploads only the ranges it reads, writes to a temporary beside zkey_path and renames it: a failed
+ * call leaves no file there.  The calling thread's device is what it was afterwards; calls on one handle are serialised.
+ * ICICLE_SNARK_TRACE_ZKEY_NEW=1 prints the stage times on stderr. */
+int groth16_zkey_new_size(const void* r1cs, size_t len, uint64_t* zkey_bytes, uint64_t* n_coeffs);
+int groth16_zkey_new(Groth16R1cs* h, const void* ptau, size_t ptau_len, void* zkey_out, size_t cap, const Groth16ZkeyNewOptions* opt,
+                     Groth16ZkeyNewReport* report);
+int groth16_zkey_new_file(Groth16R1cs* h, const char* ptau_path, const char* zkey_path, const Groth16ZkeyNewOptions* opt,
+                          Groth16ZkeyNewReport* report);
+
 #ifdef __cplusplus
 }
 #endif
