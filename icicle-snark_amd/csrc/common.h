@@ -1,6 +1,7 @@
 // common.h — shared plumbing of the C-ABI implementation (error handling, staging of host operands).
 #pragma once
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <hip/hip_runtime.h>
 #include <mutex>
@@ -30,6 +31,11 @@ inline long long env_i64(const char* name, long long dflt)
 {
   const char* v = getenv(name);
   return v ? atoll(v) : dflt;
+}
+
+inline double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 #define ISNARK_API extern "C" __attribute__((visibility("default")))

@@ -29,6 +29,25 @@ struct alignas(16) fe {
   uint32_t l[8];
 };
 
+#if defined(__HIPCC__)
+// an element as two 16-byte accesses
+__device__ __forceinline__ fe ld(const fe* p)
+{
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 lo = q[0], hi = q[1];
+  fe v;
+  v.l[0] = lo.x, v.l[1] = lo.y, v.l[2] = lo.z, v.l[3] = lo.w;
+  v.l[4] = hi.x, v.l[5] = hi.y, v.l[6] = hi.z, v.l[7] = hi.w;
+  return v;
+}
+__device__ __forceinline__ void st(fe* p, const fe& v)
+{
+  uint4* q = reinterpret_cast<uint4*>(p);
+  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+#endif
+
 // Scalar field Fr — icicle/include/icicle/fields/snark_fields/bn254_scalar.h:9-10
 struct FrP {
   static constexpr uint32_t MOD[8] = {0xf0000001, 0x43e1f593, 0x79b97091, 0x2833e848,

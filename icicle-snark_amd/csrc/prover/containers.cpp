@@ -305,8 +305,8 @@ __attribute__((visibility("default"))) int groth16_zkey_new_size(const void* r1c
   if (m < npub + 1) return fail(ERR_FORMAT, "r1cs: %u wires cannot hold the constant and %u public signals", L.n_wires, L.n_public());
   uint64_t ab = 0;
   for (uint64_t j = 0; j < nc; j++) ab += rowptr[3 * j + 2] - rowptr[3 * j]; // A's and B's terms; C has no records
-  uint64_t n = 1;
-  while (n < nc + npub + 1) n <<= 1; // the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule)
+  uint32_t k;
+  const uint64_t n = circuit_domain(nc, npub, &k);
   *n_coeffs = ab + npub + 1;
   const uint64_t payload = 4 + (4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128) + 64 * (npub + 1) + (4 + COEF_RECORD_BYTES * *n_coeffs) + 64 * m + 64 * m + 128 * m +
                            64 * (m - npub - 1) + 64 * n + 4;

@@ -1,0 +1,157 @@
+// device_call.h — the host plumbing every key tool wraps its device work in (zkey_check.hip, r1cs_check.hip, zkey_verify.hip,
+// zkey_new.hip; verify_combined.hip takes its MSM configuration from here): one error text and the checked call and launch that
+// return it, stage times, the scoped file hint of the pinned staging, the timed upload, an event that destroys itself, the
+// library's MSMs over device operands in slices, and the seed and coefficients of the randomised checks.  The device session and
+// its buffers are verify_batch.h's; the host point helpers are verify_host.h's; the ptau's ranges are ptau_ranges.h's.
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <stdio.h>
+#include <string.h>
+
+#include "../workers.h"
+#include "prover_internal.h"
+#include "sha256.h"
+#include "verify_batch.h"
+
+namespace isnark {
+namespace prover {
+
+// ---- errors and status
+inline int dev_fail(const char* what, hipError_t e) { return fail(ERR_DEVICE, "%s", vb::DeviceErrorText(what, e).msg); }
+// return "device: <what>: <HIP's text>" from the calling function when a HIP call fails
+#define DEV_TRY(what, call)                                                      \
+  do {                                                                           \
+    if (hipError_t he__ = (call)) return ::isnark::prover::dev_fail(what, he__); \
+  } while (0)
+// launch (no dynamic LDS) and test the launch the same way; a kernel with template arguments goes in parentheses
+#define DEV_LAUNCH(what, kernel, grid, block, stream, ...)                \
+  do {                                                                    \
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);      \
+    DEV_TRY(what, hipGetLastError());                                     \
+  } while (0)
+
+// stage times on stderr when `env` is set (read at every call: common.h's rule for a knob an in-process caller may change), as
+// ICICLE_SNARK_TRACE_COLD for a load
+struct StageTrace {
+  const char* const tag;
+  const bool on;
+  std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+  StageTrace(const char* tag_, const char* env) : tag(tag_), on(env_set(env)) {}
+  void lap(const char* what)
+  {
+    if (!on) return;
+    const auto t = std::chrono::steady_clock::now();
+    fprintf(stderr, "[%s] %-28s %8.2f ms\n", tag, what, std::chrono::duration<double, std::milli>(t - prev).count());
+    prev = t;
+  }
+};
+
+// ---- uploads
+// A mapped file a call reads its input from (fd < 0: plain memory).
+struct FileRange {
+  const uint8_t* base = nullptr;
+  size_t len = 0;
+  int fd = -1;
+  bool holds(const void* p) const { return fd >= 0 && (const uint8_t*)p >= base && (const uint8_t*)p < base + len; }
+};
+// While one lives, the calling thread's staged copies pread() the file instead of copying out of its mapping; the hint is cleared
+// on every way out of the scope, so none is left for the thread's next call.
+struct FileHint {
+  FileHint(const void* base, size_t len, int fd)
+  {
+    if (fd >= 0) staged_copy_file_hint(base, len, fd);
+  }
+  explicit FileHint(const FileRange& f) : FileHint(f.base, f.len, f.fd) {}
+  ~FileHint() { staged_copy_file_hint(nullptr, 0, -1); }
+  FileHint(const FileHint&) = delete;
+  FileHint& operator=(const FileHint&) = delete;
+};
+// one range up through the pinned staging (it has landed on return), its wall time added to *ms; nothing for an empty range
+inline int timed_upload(int dev, void* dst, const void* src, size_t bytes, double* ms)
+{
+  if (!bytes) return 0;
+  const auto t0 = std::chrono::steady_clock::now();
+  const CopyJob job = {dst, src, bytes};
+  const hipError_t he = staged_copy(dev, &job, 1, true);
+  *ms += ms_since(t0);
+  return he ? dev_fail("host to device upload", he) : 0;
+}
+
+struct Event { // ordering only: no timing
+  hipEvent_t e = nullptr;
+  int create()
+  {
+    DEV_TRY("hipEventCreate", hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return 0;
+  }
+  ~Event()
+  {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// ---- the library's MSMs
+constexpr uint32_t MSM_SLICE = 1u << 24; // bases per MSM call (partial sums add)
+inline MSMConfig msm_config(icicleStreamHandle stream, int bitsize) // host operands
+{
+  MSMConfig mc;
+  memset(&mc, 0, sizeof mc);
+  mc.stream = stream;
+  mc.precompute_factor = 1;
+  mc.bitsize = bitsize;
+  mc.batch_size = 1;
+  return mc;
+}
+inline MSMConfig device_msm_config(icicleStreamHandle stream, int bitsize) // scalars and Montgomery-form affine bases on the device
+{
+  MSMConfig mc = msm_config(stream, bitsize);
+  mc.are_scalars_on_device = true;
+  mc.are_points_on_device = true;
+  mc.are_points_montgomery_form = true;
+  return mc;
+}
+// Σ scalars[i]·bases[i] over `count` bases in slices of MSM_SLICE; count = 0 is the identity.  The group is out's.
+template <class A, class P>
+int sliced_msm_of(eIcicleError (*msm)(const bn254_scalar_t*, const A*, int, const MSMConfig*, P*), void (*add)(const P*, const P*, P*), const MSMConfig& mc,
+                  const void* scalars, const void* bases, uint64_t count, P* out)
+{
+  memset(out, 0, sizeof *out);
+  for (uint64_t off = 0; off < count; off += MSM_SLICE) {
+    const int cnt = (int)std::min<uint64_t>(MSM_SLICE, count - off);
+    P p;
+    if (eIcicleError me = msm((const bn254_scalar_t*)scalars + off, (const A*)bases + off, cnt, &mc, &p))
+      return fail(ERR_DEVICE, "device: msm (%d): %s", (int)me, icicle_snark_last_error());
+    if (off) add(out, &p, out);
+    else *out = p;
+  }
+  return 0;
+}
+inline int sliced_msm(const MSMConfig& mc, const void* scalars, const void* bases, uint64_t count, bn254_projective_t* out)
+{
+  return sliced_msm_of<bn254_affine_t>(bn254_msm, bn254_ecadd, mc, scalars, bases, count, out);
+}
+inline int sliced_msm(const MSMConfig& mc, const void* scalars, const void* bases, uint64_t count, bn254_g2_projective_t* out)
+{
+  return sliced_msm_of<bn254_g2_affine_t>(bn254_g2_msm, bn254_g2_ecadd, mc, scalars, bases, count, out);
+}
+
+// ---- the randomised checks' secrets
+// the caller's 32 bytes, or the operating system's
+inline int seed_or_random(const uint8_t* seed32, uint8_t out[32])
+{
+  if (seed32) memcpy(out, seed32, 32);
+  else if (!vb::os_random(out, 32)) return fail(ERR_ARG, "no randomness from the operating system (getrandom, /dev/urandom)");
+  return 0;
+}
+// out[i] = the combined verifier's coefficient first + i of `seed` (sha256.h): 128 bits in 32-byte standard form, on the worker pool
+inline void fill_coefficients(const uint8_t seed[32], uint64_t first, size_t count, fe* out)
+{
+  memset(out, 0, count * sizeof out[0]);
+  run_ranges(count, 4096, [&](int, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) combined_coefficient(seed, first + (uint64_t)i, (uint8_t*)&out[i]);
+  });
+}
+
+} // namespace prover
+} // namespace isnark

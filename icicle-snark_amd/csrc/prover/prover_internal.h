@@ -52,9 +52,15 @@ void set_error_text(const char* text);
   } while (0)
 enum { ERR_IO = -1, ERR_FORMAT = -2, ERR_ARG = -3, ERR_NOCACHE = -4, ERR_DEVICE = -5 /* groth16_zkey_check, where > 0 is a verdict */ };
 
-inline double ms_since(std::chrono::steady_clock::time_point t0)
+using isnark::ms_since; // common.h
+
+// the domain of a circuit: the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule), *log2 its exponent
+inline uint64_t circuit_domain(uint64_t n_constraints, uint64_t n_public, uint32_t* log2)
 {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  uint64_t domain = 1;
+  *log2 = 0;
+  while (domain < n_constraints + n_public + 1) domain <<= 1, (*log2)++;
+  return domain;
 }
 
 // ---- containers (containers.cpp)

@@ -8,22 +8,7 @@ using namespace bn254;
 
 namespace {
 
-__device__ __forceinline__ fe ld(const fe* p)
-{
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  fe r;
-  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-  return r;
-}
-__device__ __forceinline__ void st(fe* p, const fe& v)
-{
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-
+// (element loads and stores: ff.h's ld / st)
 __global__ __launch_bounds__(256) void qap_spmv_kernel(const fe* __restrict__ w, const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols,
                                                         const fe* __restrict__ vals, uint32_t n, fe* __restrict__ d_vec)
 {

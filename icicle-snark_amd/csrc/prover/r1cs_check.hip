@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../workers.h"
+#include "device_call.h"
 #include "prover_internal.h"
 #include "r1cs_check.h"
 #include "sha256.h"
@@ -42,13 +43,6 @@ struct Tally {
   unsigned long long failed, first_failed;
   unsigned long long rows_a, first_a, rows_b, first_b; // match: rows of the key's A / B that differ from the circuit's
 };
-
-__device__ __forceinline__ void st(fe* p, const fe& v)
-{
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 
 // rows [row_lo, row_hi) of the raw payload (32-bit words): term t of row ρ starts at word 9·t + ρ + 1 — behind the ρ + 1 count
 // words of the rows up to it.  The host walk has bounded all of these reads; this kernel bounds the wire ids and the values.
@@ -125,7 +119,7 @@ __global__ __launch_bounds__(256) void r1cs_compare_kernel(const fe* __restrict_
   }
 }
 
-int dev_fail(const char* what, hipError_t e) { return pv::fail(pv::ERR_DEVICE, "device: %s: %s", what, hipGetErrorString(e)); }
+using pv::dev_fail;
 
 } // namespace
 
@@ -153,14 +147,14 @@ namespace {
 int reset_tally(Groth16R1cs* h)
 {
   const Tally z = {NONE, 0, NONE, 0, 0, NONE, 0, NONE, 0, NONE};
-  if (hipError_t he = hipMemcpyAsync(h->d_tally, &z, sizeof z, hipMemcpyHostToDevice, h->st)) return dev_fail("upload", he);
-  if (hipError_t he = hipStreamSynchronize(h->st)) return dev_fail("upload", he); // (`z` is pageable: the copy has read it)
+  DEV_TRY("upload", hipMemcpyAsync(h->d_tally, &z, sizeof z, hipMemcpyHostToDevice, h->st));
+  DEV_TRY("upload", hipStreamSynchronize(h->st)); // (`z` is pageable: the copy has read it)
   return 0;
 }
 int read_tally(Groth16R1cs* h, Tally* out, const char* what)
 {
-  if (hipError_t he = hipMemcpyAsync(out, h->d_tally, sizeof *out, hipMemcpyDeviceToHost, h->st)) return dev_fail("download", he);
-  if (hipError_t he = hipStreamSynchronize(h->st)) return dev_fail(what, he);
+  DEV_TRY("download", hipMemcpyAsync(out, h->d_tally, sizeof *out, hipMemcpyDeviceToHost, h->st));
+  DEV_TRY(what, hipStreamSynchronize(h->st));
   return 0;
 }
 
@@ -168,7 +162,7 @@ template <class T>
 int dev_alloc(T** p, size_t count, uint64_t* total)
 {
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  if (hipError_t he = hipMalloc((void**)p, bytes)) return dev_fail("hipMalloc", he);
+  DEV_TRY("hipMalloc", hipMalloc((void**)p, bytes));
   *total += bytes;
   return 0;
 }
@@ -199,7 +193,7 @@ int r1cs_load_impl(const uint8_t* data, size_t len, const char* device, Groth16R
   h->n_terms = n_terms;
   const uint32_t rows = 3 * L.n_constraints;
   uint64_t bytes = 0;
-  if (hipError_t he = hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking)) return dev_fail("hipStreamCreate", he);
+  DEV_TRY("hipStreamCreate", hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
   if (int rc = dev_alloc(&h->d_rowptr, (size_t)rows + 1, &bytes)) return rc;
   if (int rc = dev_alloc(&h->d_cols, (size_t)n_terms, &bytes)) return rc;
   if (int rc = dev_alloc(&h->d_vals, (size_t)n_terms, &bytes)) return rc;
@@ -210,20 +204,13 @@ int r1cs_load_impl(const uint8_t* data, size_t len, const char* device, Groth16R
   if (int rc = reset_tally(h.get())) return rc;
 
   double upload_ms = 0;
-  auto upload = [&](void* dst, const void* src, size_t n) -> hipError_t {
-    const auto t0 = std::chrono::steady_clock::now();
-    const isnark::CopyJob job = {dst, src, n};
-    const hipError_t he = isnark::staged_copy(dev, &job, 1, true);
-    upload_ms += pv::ms_since(t0);
-    return he;
-  };
-  if (hipError_t he = upload(h->d_rowptr, rowptr.data(), rowptr.size() * 4)) return dev_fail("host to device upload", he);
+  if (int rc = pv::timed_upload(dev, h->d_rowptr, rowptr.data(), rowptr.size() * 4, &upload_ms)) return rc;
   // row ρ is complete once byte 36·rowptr[ρ + 1] + 4·(ρ + 1) has landed: its kernel runs while the next slice is on its way
   auto row_end = [&](uint32_t row) { return pv::R1CS_TERM_BYTES * (uint64_t)rowptr[(size_t)row + 1] + 4 * ((uint64_t)row + 1); };
   uint32_t row_lo = 0;
   for (uint64_t off = 0; off < L.payload_bytes; off += SLICE_BYTES) {
     const size_t n = (size_t)std::min<uint64_t>(SLICE_BYTES, L.payload_bytes - off);
-    if (hipError_t he = upload(d_raw + off, L.payload + off, n)) return dev_fail("host to device upload", he);
+    if (int rc = pv::timed_upload(dev, d_raw + off, L.payload + off, n, &upload_ms)) return rc;
     uint32_t lo = row_lo, hi = rows; // the first row in [lo, hi] that is not complete
     while (lo < hi) {
       const uint32_t mid = lo + (hi - lo) / 2;
@@ -231,9 +218,8 @@ int r1cs_load_impl(const uint8_t* data, size_t len, const char* device, Groth16R
       else hi = mid;
     }
     if (lo > row_lo) {
-      hipLaunchKernelGGL(r1cs_fill_kernel, dim3((lo - row_lo + 255) / 256), dim3(256), 0, h->st, (const uint32_t*)d_raw, h->d_rowptr, row_lo, lo, L.n_wires, h->d_cols, h->d_vals,
-                         h->d_tally);
-      if (hipError_t he = hipGetLastError()) return dev_fail("fill kernel launch", he);
+      DEV_LAUNCH("fill kernel launch", r1cs_fill_kernel, dim3((lo - row_lo + 255) / 256), dim3(256), h->st, (const uint32_t*)d_raw, h->d_rowptr, row_lo, lo, L.n_wires, h->d_cols,
+                 h->d_vals, h->d_tally);
       row_lo = lo;
     }
   }
@@ -270,18 +256,13 @@ int witness_check_impl(Groth16R1cs* h, const uint8_t* wtns, size_t wtns_len, Gro
   isnark::vb::DeviceSession ds;
   if (ds.open(h->dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
   if (int rc = reset_tally(h)) return rc;
-  const auto t_up = std::chrono::steady_clock::now();
-  const isnark::CopyJob job = {h->d_w, w.values, (size_t)h->n_wires * 32};
-  if (hipError_t he = isnark::staged_copy(h->dev, &job, 1, true)) return dev_fail("host to device upload", he);
-  rep->upload_ms = pv::ms_since(t_up);
-  hipLaunchKernelGGL(witness_range_kernel, dim3((h->n_wires + 255) / 256), dim3(256), 0, h->st, h->d_w, h->n_wires, h->d_tally);
-  if (hipError_t he = hipGetLastError()) return dev_fail("range kernel launch", he);
+  if (int rc = pv::timed_upload(h->dev, h->d_w, w.values, (size_t)h->n_wires * 32, &rep->upload_ms)) return rc;
+  DEV_LAUNCH("range kernel launch", witness_range_kernel, dim3((h->n_wires + 255) / 256), dim3(256), h->st, h->d_w, h->n_wires, h->d_tally);
   Tally t;
   if (int rc = read_tally(h, &t, "range kernel")) return rc;
   // the constraints only over canonical values: Fr::mul's bounds assume them
   if (t.noncanonical == 0 && h->m) {
-    hipLaunchKernelGGL(r1cs_constraint_kernel<0>, dim3((h->m + 255) / 256), dim3(256), 0, h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, h->m, h->d_tally, (fe*)nullptr);
-    if (hipError_t he = hipGetLastError()) return dev_fail("constraint kernel launch", he);
+    DEV_LAUNCH("constraint kernel launch", r1cs_constraint_kernel<0>, dim3((h->m + 255) / 256), dim3(256), h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, h->m, h->d_tally, (fe*)nullptr);
     if (int rc = read_tally(h, &t, "constraint kernel")) return rc;
   }
   rep->device_ms = pv::ms_since(t_dev);
@@ -301,9 +282,9 @@ int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8
   std::vector<pv::Section> secs;
   pv::ZkeyLayout L;
   if (int rc = pv::zkey_layout(zkey, len, secs, &L, /*need_ic=*/false)) return rc;
-  // sizes: the domain is the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule)
-  uint64_t domain = 1;
-  while (domain < (uint64_t)h->m + h->n_public + 1) domain <<= 1;
+  // sizes
+  uint32_t k;
+  const uint64_t domain = pv::circuit_domain(h->m, h->n_public, &k);
   const bool size_ok[3] = {L.n_vars == h->n_wires, L.n_public == h->n_public, L.domain == domain};
   for (int k = 0; k < 3; k++)
     if (!size_ok[k]) {
@@ -312,13 +293,9 @@ int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8
       return 0;
     }
   uint8_t seed[32];
-  if (seed32) memcpy(seed, seed32, 32);
-  else if (!isnark::vb::os_random(seed, 32)) return pv::fail(pv::ERR_ARG, "no randomness from the operating system (getrandom, /dev/urandom)");
+  if (int rc = pv::seed_or_random(seed32, seed)) return rc;
   std::vector<fe> z(h->n_wires);
-  memset(z.data(), 0, z.size() * sizeof z[0]);
-  isnark::run_ranges(h->n_wires, 4096, [&](int, size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; i++) isnark::combined_coefficient(seed, (uint64_t)i, (uint8_t*)&z[i]);
-  });
+  pv::fill_coefficients(seed, 0, z.size(), z.data());
 
   std::lock_guard<std::mutex> lk(h->mu);
   const auto t_dev = std::chrono::steady_clock::now();
@@ -334,18 +311,14 @@ int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8
   if (!d_rec || !k_rowptr || !k_cols || !k_vals || !d_vec || !d_ab) return dev_fail("hipMalloc", hipErrorOutOfMemory);
   if (int rc = reset_tally(h)) return rc;
   const isnark::CopyJob jobs[2] = {{h->d_w, z.data(), z.size() * sizeof z[0]}, {d_rec, L.records(), (size_t)L.n_coef * pv::COEF_RECORD_BYTES}};
-  if (hipError_t he = isnark::staged_copy(h->dev, jobs, 2, true)) return dev_fail("host to device upload", he);
-  if (m) {
-    hipLaunchKernelGGL(r1cs_constraint_kernel<1>, dim3((m + 255) / 256), dim3(256), 0, h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, m, h->d_tally, d_ab);
-    if (hipError_t he = hipGetLastError()) return dev_fail("emit kernel launch", he);
-  }
+  DEV_TRY("host to device upload", isnark::staged_copy(h->dev, jobs, 2, true));
+  if (m) DEV_LAUNCH("emit kernel launch", r1cs_constraint_kernel<1>, dim3((m + 255) / 256), dim3(256), h->st, h->d_rowptr, h->d_cols, h->d_vals, h->d_w, m, h->d_tally, d_ab);
   // the key's side by the prover's own front end: the same CSR build (with its range rule) and the same spmv
   uint32_t first_bad = 0;
-  if (hipError_t he = isnark::qap_build_csr(d_rec, L.n_coef, n, L.n_vars, k_rowptr, k_cols, k_vals, &first_bad, h->st)) return dev_fail("coefficient CSR", he);
+  DEV_TRY("coefficient CSR", isnark::qap_build_csr(d_rec, L.n_coef, n, L.n_vars, k_rowptr, k_cols, k_vals, &first_bad, h->st));
   if (first_bad != 0xffffffffu) return pv::fail(pv::ERR_FORMAT, "zkey: coefficient %u out of range", first_bad);
-  if (hipError_t he = isnark::qap_spmv(h->d_w, k_rowptr, k_cols, k_vals, n, d_vec, h->st)) return dev_fail("spmv launch", he);
-  hipLaunchKernelGGL(r1cs_compare_kernel, dim3((n + 255) / 256), dim3(256), 0, h->st, d_vec, d_ab, h->d_w, n, m, h->n_public, h->d_tally);
-  if (hipError_t he = hipGetLastError()) return dev_fail("compare kernel launch", he);
+  DEV_TRY("spmv launch", isnark::qap_spmv(h->d_w, k_rowptr, k_cols, k_vals, n, d_vec, h->st));
+  DEV_LAUNCH("compare kernel launch", r1cs_compare_kernel, dim3((n + 255) / 256), dim3(256), h->st, d_vec, d_ab, h->d_w, n, m, h->n_public, h->d_tally);
   Tally t;
   if (int rc = read_tally(h, &t, "match kernels")) return rc;
   rep->device_ms = pv::ms_since(t_dev);
@@ -367,8 +340,7 @@ R1csDeviceRows r1cs_device_rows(const Groth16R1cs* h) { return {h->d_rowptr, h->
 int r1cs_emit_abc(Groth16R1cs* h, const fe* d_v, fe* d_abc, hipStream_t stream)
 {
   if (!h->m) return 0;
-  hipLaunchKernelGGL(r1cs_constraint_kernel<2>, dim3((h->m + 255) / 256), dim3(256), 0, stream, h->d_rowptr, h->d_cols, h->d_vals, d_v, h->m, h->d_tally, d_abc);
-  if (hipError_t he = hipGetLastError()) return dev_fail("emit kernel launch", he);
+  DEV_LAUNCH("emit kernel launch", r1cs_constraint_kernel<2>, dim3((h->m + 255) / 256), dim3(256), stream, h->d_rowptr, h->d_cols, h->d_vals, d_v, h->m, h->d_tally, d_abc);
   return 0;
 }
 } // namespace prover
@@ -390,11 +362,8 @@ ISNARK_API int groth16_r1cs_load_file(const char* path, const char* device, Grot
   if (!path) return pv::fail(pv::ERR_ARG, "null path");
   pv::MappedFile mf;
   if (int rc = mf.open_ro(path)) return rc;
-  // (the staging workers pread() the file instead of copying out of the mapping)
-  isnark::staged_copy_file_hint(mf.data, mf.len, mf.fd);
-  const int rc = r1cs_load_impl(mf.data, mf.len, device, out);
-  isnark::staged_copy_file_hint(nullptr, 0, -1);
-  return rc;
+  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
+  return r1cs_load_impl(mf.data, mf.len, device, out);
 }
 
 ISNARK_API int groth16_r1cs_get_info(const Groth16R1cs* h, Groth16R1csInfo* info)
@@ -422,8 +391,6 @@ ISNARK_API int groth16_witness_check_file(Groth16R1cs* h, const char* wtns_path,
   if (!wtns_path) return pv::fail(pv::ERR_ARG, "null path");
   pv::MappedFile mf;
   if (int rc = mf.open_ro(wtns_path)) return rc;
-  isnark::staged_copy_file_hint(mf.data, mf.len, mf.fd);
-  const int rc = witness_check_impl(h, mf.data, mf.len, report);
-  isnark::staged_copy_file_hint(nullptr, 0, -1);
-  return rc;
+  const pv::FileHint hint(mf.data, mf.len, mf.fd);
+  return witness_check_impl(h, mf.data, mf.len, report);
 }

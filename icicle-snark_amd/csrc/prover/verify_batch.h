@@ -40,16 +40,14 @@ int per_item_stage(const Parsed& pz, PreparedKey& pk, int dev, int32_t* verdicts
 void set_last_timings(double parse_ms, double device_ms);
 
 // small helpers of the two device stages
-inline double ms_since(std::chrono::steady_clock::time_point t0)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-inline int device_fail(int code, const char* what, hipError_t e)
-{
+using isnark::ms_since; // common.h
+// the one text of a failed device call; the key tools' dev_fail (device_call.h) reports it through the prover's error channel
+struct DeviceErrorText {
   char msg[200];
-  snprintf(msg, sizeof msg, "device: %s: %s", what, hipGetErrorString(e));
-  return fail(code, msg);
-}
+  DeviceErrorText(const char* what, hipError_t e) { snprintf(msg, sizeof msg, "device: %s: %s", what, hipGetErrorString(e)); }
+};
+// the batch verifiers' own: their return codes are ICICLE's
+inline int device_fail(int code, const char* what, hipError_t e) { return fail(code, DeviceErrorText(what, e).msg); }
 // n bytes from the operating system (getrandom, else /dev/urandom): the secret seeds of the randomised checks
 inline bool os_random(uint8_t* out, size_t n)
 {

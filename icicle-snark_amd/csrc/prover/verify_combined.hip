@@ -22,6 +22,7 @@
 #include "../common.h"
 #include "../pairing29.h"
 #include "../workers.h"
+#include "device_call.h"
 #include "sha256.h"
 #include "verify_batch.h"
 
@@ -156,11 +157,7 @@ int open_device(CombinedCtx& c, int dev)
   c.hok.resize(c.cap);
   c.msm_s.resize(c.cap);
   c.msm_b.resize(c.cap);
-  memset(&c.mc, 0, sizeof c.mc);
-  c.mc.stream = c.ds.streams[1];
-  c.mc.precompute_factor = 1;
-  c.mc.bitsize = 128;
-  c.mc.batch_size = 1;
+  c.mc = isnark::prover::msm_config(c.ds.streams[1], 128); // (scalars and bases on the host)
   return 0;
 }
 
@@ -283,8 +280,7 @@ ISNARK_API int groth16_verify_batch_combined(const char* const* proof_jsons, con
     return rc0;
   }
   uint8_t seed[32];
-  if (seed32) memcpy(seed, seed32, 32);
-  else if (!isnark::vb::os_random(seed, 32)) return fail(-3, "no randomness from the operating system (getrandom, /dev/urandom)");
+  if (int rc = isnark::prover::seed_or_random(seed32, seed)) return fail(rc, isnark::prover::last_error_text()); // (the text through this entry's own channel)
   Parsed pz;
   if (int rc = parse_stage(proof_jsons, public_jsons, n, vk_json, verdicts, &pz, nullptr)) return rc;
   if (pz.live.empty()) {

@@ -1,12 +1,15 @@
 // verify_host.h — the host-only pieces of the Groth16 verifiers: what the parser leaves (VbKey, VbItem), the per-key
-// preparation every device stage and the combined tail read (PreparedKey), and the combined verifier's host sums (CombinedSums).
+// preparation every device stage and the combined tail read (PreparedKey), the combined verifier's host sums (CombinedSums), and the
+// host point helpers of the key tools (identity-aware affine forms, the generators, one pairing equation).
 // No HIP types: the product's .hip files and the F29_CHECK host builds (tests/pairing29_check.cpp,
 // tests/pairing29_combined_check.cpp) compile the same code, so a bound broken here fires in the checked build.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 #include <vector>
 
+#include "../../../include/icicle_snark_hip.h"
 #include "../pairing29.h"
 #include "sha256.h"
 
@@ -96,6 +99,78 @@ struct CombinedSums {
     for (size_t j = 0; j < u.size(); j++) u[j] = bn254::Fr::add(u[j], o.u[j]);
   }
 };
+
+
+// ---- host point helpers: the C ABI's standard-form points, an affine (0, 0) or a projective z = 0 the identity
+inline bool words_zero(const void* p, size_t bytes)
+{
+  const uint8_t* b = (const uint8_t*)p;
+  for (size_t i = 0; i < bytes; i++)
+    if (b[i]) return false;
+  return true;
+}
+inline bn254_affine_t affine_or_zero(const bn254_projective_t& p)
+{
+  bn254_affine_t a;
+  memset(&a, 0, sizeof a);
+  if (!words_zero(&p.z, sizeof p.z)) bn254_to_affine(&p, &a);
+  return a;
+}
+inline bn254_g2_affine_t affine_or_zero(const bn254_g2_projective_t& p)
+{
+  bn254_g2_affine_t a;
+  memset(&a, 0, sizeof a);
+  if (!words_zero(&p.z, sizeof p.z)) bn254_g2_to_affine(&p, &a);
+  return a;
+}
+template <class P>
+bool same_point(const P& l, const P& r)
+{
+  const auto a = affine_or_zero(l), b = affine_or_zero(r);
+  return memcmp(&a, &b, sizeof a) == 0;
+}
+inline bn254_affine_t g1_generator_affine()
+{
+  bn254_projective_t p;
+  bn254_affine_t a;
+  bn254_generator(&p);
+  bn254_to_affine(&p, &a);
+  return a;
+}
+inline bn254_g2_affine_t g2_generator_affine()
+{
+  bn254_g2_projective_t p;
+  bn254_g2_affine_t a;
+  bn254_g2_generator(&p);
+  bn254_g2_to_affine(&p, &a);
+  return a;
+}
+// the same two in Montgomery form, as a zkey stores its points
+inline bn254::G1::A g1_generator_mont()
+{
+  const bn254_affine_t s = g1_generator_affine();
+  bn254::G1::A g;
+  memcpy(&g, &s, sizeof g);
+  return bn254::G1::aff_to_mont(g);
+}
+inline bn254::G2::A g2_generator_mont()
+{
+  const bn254_g2_affine_t s = g2_generator_affine();
+  bn254::G2::A g;
+  memcpy(&g, &s, sizeof g);
+  return bn254::G2::aff_to_mont(g);
+}
+// e(a1, a2) = e(b1, b2) by the host pairing.  A side with an identity operand is 1, and when either side is 1 the equation holds
+// exactly when both are.
+inline bool pairing_eq(const bn254_affine_t& a1, const bn254_g2_affine_t& a2, const bn254_affine_t& b1, const bn254_g2_affine_t& b2)
+{
+  const bool one_a = words_zero(&a1, sizeof a1) || words_zero(&a2, sizeof a2), one_b = words_zero(&b1, sizeof b1) || words_zero(&b2, sizeof b2);
+  if (one_a || one_b) return one_a && one_b;
+  alignas(16) bn254_fq12_t l, r; // (bn254_pairing stores 16-byte-aligned field elements; the C type alone asks for 4)
+  (void)bn254_pairing(&a1, &a2, &l);
+  (void)bn254_pairing(&b1, &b2, &r);
+  return memcmp(&l, &r, sizeof l) == 0;
+}
 
 } // namespace vb
 } // namespace isnark

@@ -16,10 +16,10 @@
 // buffers.  The header's two pair checks run on a pooled worker beside all that.
 #include <algorithm>
 #include <chrono>
-#include <functional>
 #include <vector>
 
 #include "../workers.h"
+#include "device_call.h"
 #include "prover_internal.h"
 #include "sha256.h"
 #include "verify_batch.h"
@@ -34,7 +34,6 @@ namespace pv = isnark::prover;
 constexpr int G1_WG = 256;                      // points per block of zkey_g1_kernel (its LDS tile: 256 rows of 64 + 16 B)
 constexpr int G2_WG = 64;
 constexpr uint32_t DEFAULT_SLICE = 1u << 20;    // points per upload slice: 64 MB of G1 rows, 128 MB of G2 rows
-constexpr uint32_t MSM_SLICE = 1u << 24;        // bases per MSM call (partial sums add)
 constexpr unsigned long long NO_FAULT = ~0ull;
 
 // per zkey section id: how many elements are at fault, and min over them of (index << 3 | kind)
@@ -97,8 +96,6 @@ __global__ __launch_bounds__(256) void zkey_coef_kernel(const uint32_t* __restri
   if (!isnark::qap_record_in_range(e[0], e[1], e[2], n, n_vars) || !Fr::is_canonical(v)) tally_fault(t, 4, base + i, GROTH16_ZKEY_COEFFICIENT);
 }
 
-int dev_fail(const char* what, hipError_t e) { return pv::fail(pv::ERR_DEVICE, "device: %s: %s", what, hipGetErrorString(e)); }
-
 using pv::ZkeyLayout;
 
 // the device side of one call
@@ -109,7 +106,7 @@ struct Check {
   isnark::vb::DeviceSession ds;
   Tally* d_tally = nullptr;
   uint8_t* ring[2] = {nullptr, nullptr};
-  hipEvent_t ring_ev[2] = {nullptr, nullptr};
+  pv::Event ring_ev[2]; // (destroyed before the session, whose destructor drains the streams before it frees the buffers)
   bool ring_used[2] = {false, false};
   int ring_k = 0;
   uint8_t *d_b1 = nullptr, *d_b2 = nullptr;
@@ -117,12 +114,6 @@ struct Check {
   Tally tally;
 
   Check(const ZkeyLayout& layout, int device, uint32_t slice_points) : L(layout), dev(device), slice(slice_points) {}
-  ~Check()
-  {
-    // (the session's destructor, which runs after this one, drains the streams before it frees the buffers)
-    for (hipEvent_t e : ring_ev)
-      if (e) (void)hipEventDestroy(e);
-  }
 
   int open()
   {
@@ -134,15 +125,15 @@ struct Check {
     ring[1] = ds.buf.alloc<uint8_t>(ring_bytes);
     d_b1 = ds.buf.alloc<uint8_t>((size_t)L.n_vars * 64);
     d_b2 = ds.buf.alloc<uint8_t>((size_t)L.n_vars * 128);
-    if (!d_tally || !ring[0] || !ring[1] || !d_b1 || !d_b2) return dev_fail("hipMalloc", hipErrorOutOfMemory);
-    for (hipEvent_t& e : ring_ev)
-      if (hipError_t he = hipEventCreateWithFlags(&e, hipEventDisableTiming)) return dev_fail("hipEventCreate", he);
+    if (!d_tally || !ring[0] || !ring[1] || !d_b1 || !d_b2) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
+    for (pv::Event& e : ring_ev)
+      if (int rc = e.create()) return rc;
     for (int s = 0; s < 10; s++) {
       tally.count[s] = 0;
       tally.first[s] = NO_FAULT;
     }
-    if (hipError_t he = hipMemcpyAsync(d_tally, &tally, sizeof tally, hipMemcpyHostToDevice, ds.stream(0))) return dev_fail("upload", he);
-    if (hipError_t he = hipStreamSynchronize(ds.stream(0))) return dev_fail("upload", he); // (`tally` is pageable: the copy has read it)
+    DEV_TRY("upload", hipMemcpyAsync(d_tally, &tally, sizeof tally, hipMemcpyHostToDevice, ds.stream(0)));
+    DEV_TRY("upload", hipStreamSynchronize(ds.stream(0))); // (`tally` is pageable: the copy has read it)
     return 0;
   }
 
@@ -156,18 +147,14 @@ struct Check {
     for (uint64_t off = 0; off < count; off += slice) {
       const uint32_t m = (uint32_t)std::min<uint64_t>(slice, count - off);
       uint8_t* dst = keep ? keep + off * elem : ring[ring_k];
-      if (!keep && ring_used[ring_k])
-        if (hipError_t he = hipEventSynchronize(ring_ev[ring_k])) return dev_fail("membership kernel", he); // the kernel that last read this buffer
-      const auto t0 = std::chrono::steady_clock::now();
-      const isnark::CopyJob job = {dst, src + off * elem, (size_t)m * elem};
-      if (hipError_t he = isnark::staged_copy(dev, &job, 1, true)) return dev_fail("host to device upload", he);
-      upload_ms += pv::ms_since(t0);
-      if (kind == 1) hipLaunchKernelGGL(zkey_g1_kernel, dim3((m + G1_WG - 1) / G1_WG), dim3(G1_WG), 0, st, (const uint4*)dst, m, (unsigned long long)off, sec, d_tally);
-      else if (kind == 2) hipLaunchKernelGGL(zkey_g2_kernel, dim3((m + G2_WG - 1) / G2_WG), dim3(G2_WG), 0, st, (const fe2*)dst, m, (unsigned long long)off, sec, d_tally);
-      else hipLaunchKernelGGL(zkey_coef_kernel, dim3((m + 255) / 256), dim3(256), 0, st, (const uint32_t*)dst, m, (unsigned long long)off, L.domain, L.n_vars, d_tally);
-      if (hipError_t he = hipGetLastError()) return dev_fail("membership kernel launch", he);
+      if (!keep && ring_used[ring_k]) DEV_TRY("membership kernel", hipEventSynchronize(ring_ev[ring_k].e)); // the kernel that last read this buffer
+      if (int rc = pv::timed_upload(dev, dst, src + off * elem, (size_t)m * elem, &upload_ms)) return rc;
+      const char* const what = "membership kernel launch";
+      if (kind == 1) DEV_LAUNCH(what, zkey_g1_kernel, dim3((m + G1_WG - 1) / G1_WG), dim3(G1_WG), st, (const uint4*)dst, m, (unsigned long long)off, sec, d_tally);
+      else if (kind == 2) DEV_LAUNCH(what, zkey_g2_kernel, dim3((m + G2_WG - 1) / G2_WG), dim3(G2_WG), st, (const fe2*)dst, m, (unsigned long long)off, sec, d_tally);
+      else DEV_LAUNCH(what, zkey_coef_kernel, dim3((m + 255) / 256), dim3(256), st, (const uint32_t*)dst, m, (unsigned long long)off, L.domain, L.n_vars, d_tally);
       if (!keep) {
-        if (hipError_t he = hipEventRecord(ring_ev[ring_k], st)) return dev_fail("hipEventRecord", he);
+        DEV_TRY("hipEventRecord", hipEventRecord(ring_ev[ring_k].e, st));
         ring_used[ring_k] = true;
         ring_k ^= 1;
       }
@@ -176,7 +163,7 @@ struct Check {
   }
 
   // B2 first: its kernel is the long one, and every later upload runs beside it
-  int membership(const std::function<void(const char*)>& lap)
+  int membership(pv::StageTrace& trace)
   {
     const uint64_t nv = L.n_vars;
     if (int rc = walk(7, 2, L.sec[7]->p, nv, d_b2)) return rc;
@@ -186,12 +173,12 @@ struct Check {
     if (int rc = walk(5, 1, L.sec[5]->p, nv, nullptr)) return rc;
     if (int rc = walk(8, 1, L.sec[8]->p, nv - L.n_public - 1, nullptr)) return rc;
     if (int rc = walk(9, 1, L.sec[9]->p, L.domain, nullptr)) return rc;
-    lap("sections uploaded");
-    if (hipError_t he = hipStreamSynchronize(ds.stream(1))) return dev_fail("membership kernels", he);
-    lap("G1 kernels done");
-    if (hipError_t he = hipMemcpyAsync(&tally, d_tally, sizeof tally, hipMemcpyDeviceToHost, ds.stream(0))) return dev_fail("download", he);
-    if (hipError_t he = hipStreamSynchronize(ds.stream(0))) return dev_fail("membership kernels", he);
-    lap("membership kernels done");
+    trace.lap("sections uploaded");
+    DEV_TRY("membership kernels", hipStreamSynchronize(ds.stream(1)));
+    trace.lap("G1 kernels done");
+    DEV_TRY("download", hipMemcpyAsync(&tally, d_tally, sizeof tally, hipMemcpyDeviceToHost, ds.stream(0)));
+    DEV_TRY("membership kernels", hipStreamSynchronize(ds.stream(0)));
+    trace.lap("membership kernels done");
     return 0;
   }
 
@@ -200,72 +187,21 @@ struct Check {
   {
     // the coefficients go up once and serve both MSMs
     bn254_scalar_t* d_z = ds.buf.alloc<bn254_scalar_t>(z.size());
-    if (!d_z) return dev_fail("hipMalloc", hipErrorOutOfMemory);
+    if (!d_z) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
     const isnark::CopyJob job = {d_z, z.data(), z.size() * sizeof z[0]};
-    if (hipError_t he = isnark::staged_copy(dev, &job, 1, true)) return dev_fail("host to device upload", he);
-    MSMConfig mc;
-    memset(&mc, 0, sizeof mc);
-    mc.stream = ds.streams[1];
-    mc.precompute_factor = 1;
-    mc.bitsize = 128;
-    mc.batch_size = 1;
-    mc.are_scalars_on_device = true;
-    mc.are_points_on_device = true;
-    mc.are_points_montgomery_form = true;
-    for (uint64_t off = 0; off < L.n_vars; off += MSM_SLICE) {
-      const int m = (int)std::min<uint64_t>(MSM_SLICE, L.n_vars - off);
-      bn254_projective_t p1;
-      bn254_g2_projective_t p2;
-      eIcicleError me = bn254_msm(d_z + off, (const bn254_affine_t*)(d_b1 + off * 64), m, &mc, &p1);
-      if (me == ICICLE_SUCCESS) me = bn254_g2_msm(d_z + off, (const bn254_g2_affine_t*)(d_b2 + off * 128), m, &mc, &p2);
-      if (me != ICICLE_SUCCESS) return pv::fail(pv::ERR_DEVICE, "device: msm (%d): %s", (int)me, icicle_snark_last_error());
-      if (off) {
-        bn254_ecadd(s1, &p1, s1);
-        bn254_g2_ecadd(s2, &p2, s2);
-      } else {
-        *s1 = p1;
-        *s2 = p2;
-      }
-    }
-    return 0;
+    DEV_TRY("host to device upload", isnark::staged_copy(dev, &job, 1, true));
+    const MSMConfig mc = pv::device_msm_config(ds.streams[1], 128);
+    if (int rc = pv::sliced_msm(mc, d_z, d_b1, L.n_vars, s1)) return rc;
+    return pv::sliced_msm(mc, d_z, d_b2, L.n_vars, s2);
   }
 };
 
-bool words_zero(const void* p, size_t bytes)
-{
-  const uint8_t* b = (const uint8_t*)p;
-  for (size_t i = 0; i < bytes; i++)
-    if (b[i]) return false;
-  return true;
-}
+using isnark::vb::words_zero;
 
 // e(P₁, G₂) = e(G₁, P₂) for standard-form affine points, (0, 0) = the identity, by the host pairing
 bool pair_holds(const bn254_affine_t& p1, const bn254_g2_affine_t& p2)
 {
-  const bool z1 = words_zero(&p1, sizeof p1), z2 = words_zero(&p2, sizeof p2);
-  if (z1 || z2) return z1 && z2;
-  bn254_projective_t g1p;
-  bn254_g2_projective_t g2p;
-  bn254_affine_t g1;
-  bn254_g2_affine_t g2;
-  bn254_generator(&g1p);
-  bn254_to_affine(&g1p, &g1);
-  bn254_g2_generator(&g2p);
-  bn254_g2_to_affine(&g2p, &g2);
-  bn254_fq12_t l, r;
-  (void)bn254_pairing(&p1, &g2, &l);
-  (void)bn254_pairing(&g1, &p2, &r);
-  return memcmp(&l, &r, sizeof l) == 0;
-}
-bool pair_holds(const bn254_projective_t& s1, const bn254_g2_projective_t& s2)
-{
-  bn254_affine_t a1;
-  bn254_g2_affine_t a2;
-  memset(&a1, 0, sizeof a1);
-  memset(&a2, 0, sizeof a2);
-  if (!words_zero(&s1.z, sizeof s1.z)) bn254_to_affine(&s1, &a1);
-  if (!words_zero(&s2.z, sizeof s2.z)) bn254_g2_to_affine(&s2, &a2);
-  return pair_holds(a1, a2);
+  return isnark::vb::pairing_eq(p1, isnark::vb::g2_generator_affine(), isnark::vb::g1_generator_affine(), p2);
 }
 
 struct First { // the first fault so far, in the header's order of reporting
@@ -289,8 +225,7 @@ int zkey_check_impl(const uint8_t* data, size_t len, const char* device, const G
   ZkeyLayout L;
   if (int rc = pv::zkey_layout(data, len, secs, &L)) return rc;
   uint8_t seed[32];
-  if (opt && opt->seed32) memcpy(seed, opt->seed32, 32);
-  else if (!isnark::vb::os_random(seed, 32)) return pv::fail(pv::ERR_ARG, "no randomness from the operating system (getrandom, /dev/urandom)");
+  if (int rc = pv::seed_or_random(opt ? opt->seed32 : nullptr, seed)) return rc;
 
   // the header's six points, in file order, on the host: kinds 1 2 3 by the kernels' functions, then 4
   First first;
@@ -319,19 +254,12 @@ int zkey_check_impl(const uint8_t* data, size_t len, const char* device, const G
 
   // the device part; the coefficients of the 6/7 check are made on the pool meanwhile
   const auto t_dev = std::chrono::steady_clock::now();
-  static const bool trace = isnark::env_set("ICICLE_SNARK_TRACE_ZKEY_CHECK");
-  auto t_prev = t_dev;
-  const std::function<void(const char*)> lap = [&](const char* what) { // stage times on stderr, as ICICLE_SNARK_TRACE_COLD for a load
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[zkey-check] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-    t_prev = t;
-  };
+  pv::StageTrace trace("zkey-check", "ICICLE_SNARK_TRACE_ZKEY_CHECK");
   Check c(L, dev, opt && opt->slice_points ? opt->slice_points : DEFAULT_SLICE);
   std::vector<bn254_scalar_t> z(L.n_vars);
   memset(z.data(), 0, z.size() * sizeof z[0]);
-  // (every range on the pool, none kept for this thread as run_ranges would: this thread's part is the walk, and a range behind it
-  //  would run after the device has finished)
+  // (every range on the pool, none kept for this thread as run_ranges — and with it device_call.h's fill_coefficients — would: this
+  //  thread's part is the walk, and a range behind it would run after the device has finished)
   const int tasks = isnark::ranges_of(L.n_vars, 4096);
   std::vector<isnark::HostTask> ht(tasks);
   for (int t = 0; t < tasks; t++) {
@@ -366,12 +294,12 @@ int zkey_check_impl(const uint8_t* data, size_t len, const char* device, const G
   };
   if (header_pairs) isnark::WorkerPool::get().run_or_inline(&header_task);
   int rc = c.open();
-  lap("session, buffers");
-  if (!rc) rc = c.membership(lap);
+  trace.lap("session, buffers");
+  if (!rc) rc = c.membership(trace);
   for (int t = 0; t < tasks; t++)
     if (ht[t].queued) isnark::WorkerPool::wait(&ht[t]);
   if (header_task.queued) isnark::WorkerPool::wait(&header_task);
-  lap("pool joined");
+  trace.lap("pool joined");
   if (rc) return rc;
   for (int s = 3; s < 10; s++) {
     rep->faults[s] = c.tally.count[s];
@@ -382,7 +310,7 @@ int zkey_check_impl(const uint8_t* data, size_t len, const char* device, const G
   const bool pair67 = rep->faults[6] == 0 && rep->faults[7] == 0;
   if (pair67)
     if (int rc2 = c.sums(z, &s1, &s2)) return rc2;
-  lap("sums");
+  trace.lap("sums");
   rep->upload_ms = c.upload_ms;
   rep->device_ms = pv::ms_since(t_dev);
 
@@ -393,12 +321,12 @@ int zkey_check_impl(const uint8_t* data, size_t len, const char* device, const G
       rep->faults[2]++;
       first.offer(GROTH16_ZKEY_PAIR_MISMATCH, 2, (uint64_t)header_g1_slot[k]);
     }
-  if (pair67 && !pair_holds(s1, s2)) {
+  if (pair67 && !pair_holds(isnark::vb::affine_or_zero(s1), isnark::vb::affine_or_zero(s2))) {
     rep->faults[6]++;
     first.offer(GROTH16_ZKEY_PAIR_MISMATCH, 6, UINT64_MAX);
   }
   rep->pairing_ms = pv::ms_since(t_pair) + header_pair_ms;
-  lap("pair checks");
+  trace.lap("pair checks");
   rep->kind = first.kind;
   rep->section = first.section;
   rep->index = first.index;
@@ -418,8 +346,6 @@ ISNARK_API int groth16_zkey_check_file(const char* zkey_path, const char* device
   pv::MappedFile mf;
   if (int rc = mf.open_ro(zkey_path)) return rc;
   // (the staging workers pread() the file instead of copying out of the mapping)
-  isnark::staged_copy_file_hint(mf.data, mf.len, mf.fd);
-  const int rc = zkey_check_impl(mf.data, mf.len, device, opt, report);
-  isnark::staged_copy_file_hint(nullptr, 0, -1);
-  return rc;
+  const pv::FileHint hint(mf.data, mf.len, mf.fd);
+  return zkey_check_impl(mf.data, mf.len, device, opt, report);
 }

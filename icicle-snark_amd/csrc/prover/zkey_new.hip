@@ -8,7 +8,7 @@
 //               sums do not depend on it, and the affine bytes that leave are canonical.  The same pass counts A's and B's terms
 //               per constraint; their scan places section 4's records, which zn_records_kernel writes.
 //   ptau        block k of sections 12, 13, 14, 15 and block k + 1 of section 12 go up and through ptau_g1_kernel / ptau_g2_kernel
-//               (ptau_ranges.h), as groth16_zkey_verify_ptau stages them; odd_gather_kernel makes section 9.
+//               (ptau_ranges.h's PtauRanges), as groth16_zkey_verify_ptau stages them; odd_gather_kernel makes section 9.
 //   columns     zn_g1_kernel: one lane per (output, wire) for A_s, B1_s and comb_s; zn_g2_kernel: one lane per wire for B2_s — a
 //               kernel of its own, so that G2's registers do not set G1's occupancy.  Each lane walks its column through
 //               zkey_new29.h's zn_walk in lazy XYZZ registers.  A column of more than heavy_column_terms terms is left out: the
@@ -29,6 +29,7 @@
 
 #include "../msm_impl.h"
 #include "../workers.h"
+#include "device_call.h"
 #include "prover_internal.h"
 #include "ptau_ranges.h"
 #include "verify_batch.h"
@@ -256,16 +257,6 @@ __global__ __launch_bounds__(ITEM_WG) void zn_combine_kernel(const Heavy* __rest
   if (threadIdx.x == 0) store_sum<C, CL>(out + h.job, sh[0]);
 }
 
-int dev_fail(const char* what, hipError_t e) { return pv::fail(pv::ERR_DEVICE, "device: %s: %s", what, hipGetErrorString(e)); }
-
-struct Event {
-  hipEvent_t e = nullptr;
-  ~Event()
-  {
-    if (e) (void)hipEventDestroy(e);
-  }
-};
-
 // byte offsets of the payloads in the file: sections 1 … 10 in this order, each behind its 12-byte {id, length}
 struct FileLayout {
   uint64_t off[11], len[11], total;
@@ -282,14 +273,6 @@ struct FileLayout {
   }
 };
 
-uint64_t domain_of(uint64_t nc, uint64_t npub, uint32_t* k)
-{
-  uint64_t domain = 1;
-  *k = 0;
-  while (domain < nc + npub + 1) domain <<= 1, (*k)++; // the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule)
-  return domain;
-}
-
 // where the key goes, once its size is known: the caller's buffer, or the mapped temporary of the _file entry
 typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
 
@@ -305,7 +288,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   const uint32_t m = shape.n_wires, npub = shape.n_public, nc = shape.m;
   if ((uint64_t)m < (uint64_t)npub + 1) return pv::fail(pv::ERR_FORMAT, "r1cs: %u wires cannot hold the constant and %u public signals", m, npub);
   uint32_t k;
-  const uint64_t domain = domain_of(nc, npub, &k);
+  const uint64_t domain = pv::circuit_domain(nc, npub, &k);
   if (k > 28) return pv::fail(pv::ERR_ARG, "the circuit's domain 2^%u is above the field's two-adicity", k);
   if (int rc = pv::ptau_blocks_for_domain(PL, k)) return rc;
   const uint32_t n = (uint32_t)domain;
@@ -326,14 +309,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
     if (const int kind = p29::classify_g2(p2)) return pv::fail(pv::ERR_FORMAT, "ptau: section 6, element 0: %s", POINT_FAULT[kind & 3]);
   }
 
-  static const bool trace = isnark::env_set("ICICLE_SNARK_TRACE_ZKEY_NEW");
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[zkey-new] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-    t_prev = t;
-  };
+  pv::StageTrace trace("zkey-new", "ICICLE_SNARK_TRACE_ZKEY_NEW");
 
   uint32_t thr = opt && opt->heavy_column_terms ? opt->heavy_column_terms : DEFAULT_HEAVY_COLUMN_TERMS;
   thr = std::max(thr, MIN_HEAVY_COLUMN_TERMS);
@@ -343,9 +319,9 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   isnark::vb::DeviceSession ds;
   if (ds.open(shape.dev, 2)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
   const hipStream_t st = ds.stream(0), st2 = ds.stream(1);
-  Event ev_cols, ev_g2;
-  if (hipError_t he = hipEventCreateWithFlags(&ev_cols.e, hipEventDisableTiming)) return dev_fail("hipEventCreate", he);
-  if (hipError_t he = hipEventCreateWithFlags(&ev_g2.e, hipEventDisableTiming)) return dev_fail("hipEventCreate", he);
+  pv::Event ev_cols, ev_g2;
+  if (int rc = ev_cols.create()) return rc;
+  if (int rc = ev_g2.create()) return rc;
   bool oom = false;
   auto alloc = [&](auto** p, size_t count) {
     typedef typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type T;
@@ -361,7 +337,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   uint32_t *d_counts, *d_colptr, *d_ab, *d_recoff, *d_scan, *d_rec;
   ZnEntry* d_entries;
   Counters* d_cnt;
-  unsigned long long* d_first; // [0 … 4]: the five ptau ranges
+  PtauRanges ranges;
   Heavy* d_heavy[2];
   Item* d_items[2];
   alloc(&d_counts, n_cols);
@@ -372,86 +348,51 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   alloc(&d_rec, (size_t)n_entries * 11);
   alloc(&d_entries, (size_t)n_entries);
   alloc(&d_cnt, 1);
-  alloc(&d_first, 5);
   for (int g = 0; g < 2; g++) {
     alloc(&d_heavy[g], (size_t)cap_heavy[g]);
     alloc(&d_items[g], (size_t)cap_items[g]);
   }
-  if (oom) return dev_fail("hipMalloc", hipErrorOutOfMemory);
-  if (hipError_t he = hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st)) return dev_fail("hipMemset", he);
-  if (hipError_t he = hipMemsetAsync(d_ab, 0, ((size_t)nc + 1) * 4, st)) return dev_fail("hipMemset", he);
-  if (hipError_t he = hipMemsetAsync(d_cnt, 0, sizeof(Counters), st)) return dev_fail("hipMemset", he);
-  if (hipError_t he = hipMemsetAsync(d_first, 0xff, 5 * sizeof *d_first, st)) return dev_fail("hipMemset", he);
+  if (oom) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
+  DEV_TRY("hipMemset", hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st));
+  DEV_TRY("hipMemset", hipMemsetAsync(d_ab, 0, ((size_t)nc + 1) * 4, st));
+  DEV_TRY("hipMemset", hipMemsetAsync(d_cnt, 0, sizeof(Counters), st));
+  if (int rc = ranges.reset(ds, st)) return rc;
   const uint64_t row_lanes = 3 * (uint64_t)nc + npub + 1;
   const dim3 row_grid((uint32_t)((row_lanes + 255) / 256));
-  hipLaunchKernelGGL(zn_count_kernel, row_grid, dim3(256), 0, st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_counts, d_ab);
-  if (hipError_t he = hipGetLastError()) return dev_fail("count kernel launch", he);
-  if (hipError_t he = isnark::exclusive_scan_u32(d_counts, n_cols, d_colptr, d_scan, st)) return dev_fail("column scan", he);
-  if (hipError_t he = isnark::exclusive_scan_u32(d_ab, nc + 1, d_recoff, d_scan, st)) return dev_fail("record scan", he);
-  if (hipError_t he = hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st)) return dev_fail("hipMemset", he); // now the cursors
-  hipLaunchKernelGGL(zn_scatter_kernel, row_grid, dim3(256), 0, st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_colptr, d_counts, d_entries);
-  if (hipError_t he = hipGetLastError()) return dev_fail("scatter kernel launch", he);
-  hipLaunchKernelGGL(zn_records_kernel, row_grid, dim3(256), 0, st, rows.d_rowptr, rows.d_cols, rows.d_vals, nc, npub, d_recoff, d_rec);
-  if (hipError_t he = hipGetLastError()) return dev_fail("records kernel launch", he);
+  DEV_LAUNCH("count kernel launch", zn_count_kernel, row_grid, dim3(256), st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_counts, d_ab);
+  DEV_TRY("column scan", isnark::exclusive_scan_u32(d_counts, n_cols, d_colptr, d_scan, st));
+  DEV_TRY("record scan", isnark::exclusive_scan_u32(d_ab, nc + 1, d_recoff, d_scan, st));
+  DEV_TRY("hipMemset", hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st)); // now the cursors
+  DEV_LAUNCH("scatter kernel launch", zn_scatter_kernel, row_grid, dim3(256), st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_colptr, d_counts, d_entries);
+  DEV_LAUNCH("records kernel launch", zn_records_kernel, row_grid, dim3(256), st, rows.d_rowptr, rows.d_cols, rows.d_vals, nc, npub, d_recoff, d_rec);
   const Columns cols = {d_colptr, d_entries, rows.d_vals, m, thr};
-  hipLaunchKernelGGL(zn_plan_kernel<false>, dim3((uint32_t)((3 * (uint64_t)m + 255) / 256)), dim3(256), 0, st, cols, d_cnt, d_heavy[0], d_items[0]);
-  if (hipError_t he = hipGetLastError()) return dev_fail("plan kernel launch", he);
-  hipLaunchKernelGGL(zn_plan_kernel<true>, dim3((m + 255) / 256), dim3(256), 0, st, cols, d_cnt, d_heavy[1], d_items[1]);
-  if (hipError_t he = hipGetLastError()) return dev_fail("plan kernel launch", he);
-  // (the second stream's first kernel writes d_first: behind the memsets)
-  if (hipError_t he = hipEventRecord(ev_cols.e, st)) return dev_fail("hipEventRecord", he);
-  if (hipError_t he = hipStreamWaitEvent(st2, ev_cols.e, 0)) return dev_fail("hipStreamWaitEvent", he);
-  lap("session, transpose enqueued");
+  DEV_LAUNCH("plan kernel launch", zn_plan_kernel<false>, dim3((uint32_t)((3 * (uint64_t)m + 255) / 256)), dim3(256), st, cols, d_cnt, d_heavy[0], d_items[0]);
+  DEV_LAUNCH("plan kernel launch", zn_plan_kernel<true>, dim3((m + 255) / 256), dim3(256), st, cols, d_cnt, d_heavy[1], d_items[1]);
+  // (the second stream's first kernel writes the ranges' d_first: behind the memsets)
+  DEV_TRY("hipEventRecord", hipEventRecord(ev_cols.e, st));
+  DEV_TRY("hipStreamWaitEvent", hipStreamWaitEvent(st2, ev_cols.e, 0));
+  trace.lap("session, transpose enqueued");
 
-  // ---- the ptau's ranges: block k of 12, 13, 14, 15 and block k + 1 of 12, each tested where it lands
-  const int blk_sec[5] = {12, 13, 14, 15, 12};
-  const uint32_t blk_pow[5] = {k, k, k, k, k + 1};
-  uint8_t* d_blk[5];
-  if (ptau_fd >= 0) isnark::staged_copy_file_hint(ptau, ptau_len, ptau_fd);
-  for (int i = 0; i < 5; i++) {
-    const size_t elem = blk_sec[i] == 13 ? 128 : 64;
-    const uint64_t cnt = (uint64_t)1 << blk_pow[i];
-    const uint8_t* src;
-    int rc = pv::ptau_block(PL, blk_sec[i], blk_pow[i], elem, &src);
-    if (!rc) {
-      alloc(&d_blk[i], (size_t)(cnt * elem));
-      if (oom) rc = dev_fail("hipMalloc", hipErrorOutOfMemory);
-    }
-    if (!rc) {
-      const auto t0 = std::chrono::steady_clock::now();
-      const isnark::CopyJob job = {d_blk[i], src, (size_t)(cnt * elem)};
-      if (hipError_t he = isnark::staged_copy(shape.dev, &job, 1, true)) rc = dev_fail("host to device upload", he);
-      rep->upload_ms += pv::ms_since(t0);
-    }
-    if (rc) {
-      isnark::staged_copy_file_hint(nullptr, 0, -1);
-      return rc;
-    }
-    // (the G2 block's test on the second stream: it is the long one, and the uploads behind it do not wait for it)
-    if (elem == 64) hipLaunchKernelGGL(ptau_g1_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, (const fe*)d_blk[i], (uint32_t)cnt, d_first + i);
-    else hipLaunchKernelGGL(ptau_g2_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, st2, (const fe2*)d_blk[i], (uint32_t)cnt, d_first + i);
-    if (hipError_t he = hipGetLastError()) {
-      isnark::staged_copy_file_hint(nullptr, 0, -1);
-      return dev_fail("ptau membership kernel launch", he);
-    }
+  // ---- the ptau's ranges, each tested where it lands.  (The G2 block's test on the second stream: it is the long one, and the
+  // uploads behind it do not wait for it.)
+  {
+    const pv::FileHint hint(ptau, ptau_len, ptau_fd);
+    if (int rc = ranges.stage(PL, k, ds, shape.dev, st, st2, &rep->upload_ms)) return rc;
   }
-  isnark::staged_copy_file_hint(nullptr, 0, -1);
-  lap("ptau ranges uploaded");
+  trace.lap("ptau ranges uploaded");
 
   // ---- what the host has to know before the columns run: the lane tests' verdicts, the record count, the heavy columns
-  if (hipError_t he = hipEventRecord(ev_g2.e, st2)) return dev_fail("hipEventRecord", he);
-  if (hipError_t he = hipStreamWaitEvent(st, ev_g2.e, 0)) return dev_fail("hipStreamWaitEvent", he);
-  unsigned long long first[5];
+  DEV_TRY("hipEventRecord", hipEventRecord(ev_g2.e, st2));
+  DEV_TRY("hipStreamWaitEvent", hipStreamWaitEvent(st, ev_g2.e, 0));
+  unsigned long long first[PtauRanges::N];
   Counters cnt;
   uint32_t n_ab = 0;
-  if (hipError_t he = hipMemcpyAsync(first, d_first, sizeof first, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
-  if (hipError_t he = hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
-  if (hipError_t he = hipMemcpyAsync(&n_ab, d_recoff + nc, 4, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
-  if (hipError_t he = hipStreamSynchronize(st)) return dev_fail("transpose and ptau kernels", he);
-  for (int i = 0; i < 5; i++)
-    if (first[i] != NO_FAULT)
-      return pv::fail(pv::ERR_FORMAT, "ptau: section %d, block %u, element %llu: %s", blk_sec[i], blk_pow[i], (unsigned long long)(first[i] >> 3), POINT_FAULT[first[i] & 3]);
-  lap("lane tests, plan");
+  DEV_TRY("download", hipMemcpyAsync(first, ranges.d_first, sizeof first, hipMemcpyDeviceToHost, st));
+  DEV_TRY("download", hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
+  DEV_TRY("download", hipMemcpyAsync(&n_ab, d_recoff + nc, 4, hipMemcpyDeviceToHost, st));
+  DEV_TRY("transpose and ptau kernels", hipStreamSynchronize(st));
+  if (int rc = ranges.verdict(first)) return rc;
+  trace.lap("lane tests, plan");
   const uint64_t n_coeffs = (uint64_t)n_ab + npub + 1;
   const FileLayout F(m, npub, n, n_coeffs);
   rep->n_coeffs = n_coeffs;
@@ -483,48 +424,37 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   alloc(&d_odd, (size_t)n * 64);
   alloc(&d_part1, (size_t)cnt.items[0]);
   alloc(&d_part2, (size_t)cnt.items[1]);
-  if (oom) return dev_fail("hipMalloc", hipErrorOutOfMemory);
-  const G1::A *l1 = (const G1::A*)d_blk[0], *al = (const G1::A*)d_blk[2], *bl = (const G1::A*)d_blk[3];
-  const G2::A* l2 = (const G2::A*)d_blk[1];
+  if (oom) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
+  const G1::A *l1 = (const G1::A*)ranges.l1(), *al = (const G1::A*)ranges.alpha_l1(), *bl = (const G1::A*)ranges.beta_l1();
+  const G2::A* l2 = (const G2::A*)ranges.l2();
   // G2 on the second stream, beside the G1 kernels
-  hipLaunchKernelGGL(zn_g2_kernel, dim3((m + 63) / 64), dim3(64), 0, st2, cols, l2, d_p2);
-  if (hipError_t he = hipGetLastError()) return dev_fail("G2 column kernel launch", he);
+  DEV_LAUNCH("G2 column kernel launch", zn_g2_kernel, dim3((m + 63) / 64), dim3(64), st2, cols, l2, d_p2);
   if (cnt.heavy[1]) {
-    hipLaunchKernelGGL(zn_item_g2_kernel, dim3(cnt.items[1]), dim3(ITEM_WG), 0, st2, cols, d_items[1], l2, d_part2);
-    if (hipError_t he = hipGetLastError()) return dev_fail("G2 item kernel launch", he);
-    hipLaunchKernelGGL((zn_combine_kernel<G2, G2L>), dim3(cnt.heavy[1]), dim3(ITEM_WG), 0, st2, d_heavy[1], d_part2, d_p2);
-    if (hipError_t he = hipGetLastError()) return dev_fail("G2 combine kernel launch", he);
+    DEV_LAUNCH("G2 item kernel launch", zn_item_g2_kernel, dim3(cnt.items[1]), dim3(ITEM_WG), st2, cols, d_items[1], l2, d_part2);
+    DEV_LAUNCH("G2 combine kernel launch", (zn_combine_kernel<G2, G2L>), dim3(cnt.heavy[1]), dim3(ITEM_WG), st2, d_heavy[1], d_part2, d_p2);
   }
   const int chunk = 32;
   {
     const uint64_t threads = ((uint64_t)m + chunk - 1) / chunk;
-    hipLaunchKernelGGL((batch_to_affine_kernel<G2, Fq2Ops>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st2, d_p2, (uint64_t)m, chunk, d_a2, d_s2);
-    if (hipError_t he = hipGetLastError()) return dev_fail("batch_to_affine launch", he);
+    DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<G2, Fq2Ops>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st2, d_p2, (uint64_t)m, chunk, d_a2, d_s2);
     const uint64_t ncoord = 4 * (uint64_t)m;
-    hipLaunchKernelGGL((affine_to_mont_kernel<G2::A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), 0, st2, d_a2, ncoord);
-    if (hipError_t he = hipGetLastError()) return dev_fail("affine_to_mont launch", he);
+    DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<G2::A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), st2, d_a2, ncoord);
   }
-  hipLaunchKernelGGL(zn_g1_kernel, dim3((uint32_t)((G1_OUTPUTS * (uint64_t)m + 63) / 64)), dim3(64), 0, st, cols, l1, al, bl, d_p1);
-  if (hipError_t he = hipGetLastError()) return dev_fail("G1 column kernel launch", he);
+  DEV_LAUNCH("G1 column kernel launch", zn_g1_kernel, dim3((uint32_t)((G1_OUTPUTS * (uint64_t)m + 63) / 64)), dim3(64), st, cols, l1, al, bl, d_p1);
   if (cnt.heavy[0]) {
-    hipLaunchKernelGGL(zn_item_g1_kernel, dim3(cnt.items[0]), dim3(ITEM_WG), 0, st, cols, d_items[0], l1, al, bl, d_part1);
-    if (hipError_t he = hipGetLastError()) return dev_fail("G1 item kernel launch", he);
-    hipLaunchKernelGGL((zn_combine_kernel<G1, G1L>), dim3(cnt.heavy[0]), dim3(ITEM_WG), 0, st, d_heavy[0], d_part1, d_p1);
-    if (hipError_t he = hipGetLastError()) return dev_fail("G1 combine kernel launch", he);
+    DEV_LAUNCH("G1 item kernel launch", zn_item_g1_kernel, dim3(cnt.items[0]), dim3(ITEM_WG), st, cols, d_items[0], l1, al, bl, d_part1);
+    DEV_LAUNCH("G1 combine kernel launch", (zn_combine_kernel<G1, G1L>), dim3(cnt.heavy[0]), dim3(ITEM_WG), st, d_heavy[0], d_part1, d_p1);
   }
   {
     const uint64_t pts = G1_OUTPUTS * (uint64_t)m, threads = (pts + chunk - 1) / chunk;
-    hipLaunchKernelGGL((batch_to_affine_kernel<G1, FqOps>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), 0, st, d_p1, pts, chunk, d_a1, d_s1);
-    if (hipError_t he = hipGetLastError()) return dev_fail("batch_to_affine launch", he);
-    hipLaunchKernelGGL((affine_to_mont_kernel<G1::A>), dim3((uint32_t)((2 * pts + 255) / 256)), dim3(256), 0, st, d_a1, 2 * pts);
-    if (hipError_t he = hipGetLastError()) return dev_fail("affine_to_mont launch", he);
+    DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<G1, FqOps>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st, d_p1, pts, chunk, d_a1, d_s1);
+    DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<G1::A>), dim3((uint32_t)((2 * pts + 255) / 256)), dim3(256), st, d_a1, 2 * pts);
   }
-  hipLaunchKernelGGL(odd_gather_kernel, dim3((uint32_t)((4 * (uint64_t)n + 255) / 256)), dim3(256), 0, st, (const uint4*)d_blk[4], (uint64_t)n, (uint4*)d_odd);
-  if (hipError_t he = hipGetLastError()) return dev_fail("gather kernel launch", he);
-  if (hipError_t he = hipStreamSynchronize(st)) return dev_fail("G1 column kernels", he);
-  lap("G1 kernels done");
-  if (hipError_t he = hipStreamSynchronize(st2)) return dev_fail("G2 column kernels", he);
-  lap("G2 kernels done");
+  if (int rc = ranges.gather_odd(st, n, d_odd)) return rc;
+  DEV_TRY("G1 column kernels", hipStreamSynchronize(st));
+  trace.lap("G1 kernels done");
+  DEV_TRY("G2 column kernels", hipStreamSynchronize(st2));
+  trace.lap("G2 kernels done");
   rep->device_ms = pv::ms_since(t_dev);
 
   // ---- the file
@@ -540,7 +470,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
     {out + F.off[8], a1 + OUT_COMB * per + F.len[3], (size_t)F.len[8]},        // comb_s, s > npub
     {out + F.off[9], d_odd, (size_t)n * 64},
   };
-  if (hipError_t he = isnark::staged_copy(shape.dev, jobs, 7, false)) return dev_fail("device to host download", he);
+  DEV_TRY("device to host download", isnark::staged_copy(shape.dev, jobs, 7, false));
   rep->download_ms = pv::ms_since(t_down);
   memcpy(out, "zkey", 4);
   const uint32_t version = 1, n_sections = 10, protocol = 1, n8 = 32, zero = 0, n_coeffs32 = (uint32_t)n_coeffs;
@@ -561,20 +491,8 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   memcpy(hd + 76, &npub, 4);
   memcpy(hd + 80, &n, 4);
   // α₁ β₁ β₂ the ptau's stored words; γ₂ = G₂, δ₁ = G₁, δ₂ = G₂ in Montgomery form
-  bn254_projective_t g1p;
-  bn254_g2_projective_t g2p;
-  bn254_affine_t g1s;
-  bn254_g2_affine_t g2s;
-  bn254_generator(&g1p);
-  bn254_to_affine(&g1p, &g1s);
-  bn254_g2_generator(&g2p);
-  bn254_g2_to_affine(&g2p, &g2s);
-  G1::A g1;
-  G2::A g2;
-  memcpy(&g1, &g1s, sizeof g1);
-  memcpy(&g2, &g2s, sizeof g2);
-  g1 = G1::aff_to_mont(g1);
-  g2 = G2::aff_to_mont(g2);
+  const G1::A g1 = isnark::vb::g1_generator_mont();
+  const G2::A g2 = isnark::vb::g2_generator_mont();
   memcpy(hd + 84, PL.sec[4]->p, 64);
   memcpy(hd + 148, PL.sec[5]->p, 64);
   memcpy(hd + 212, PL.sec[6]->p, 128);
@@ -583,7 +501,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   memcpy(hd + 532, &g2, 128);
   memcpy(out + F.off[4], &n_coeffs32, 4);
   memcpy(out + F.off[10], &zero, 4);
-  lap("download, header");
+  trace.lap("download, header");
   return 0;
 }
 

@@ -10,10 +10,10 @@
 //             a, b, c at each; verify_assemble_kernel — one lane per row j < n — writes the eight scalar vectors of the right sides
 //             with the public-binding rows and the zero tail applied.
 //   ptau      block k of sections 12, 13, 14, 15 and block k + 1 of section 12 go up (nothing else of the file is touched) and
-//             through ptau_g1_kernel / ptau_g2_kernel (ptau_ranges.h: zkey_check29.h's tests, one lane per point); odd_gather_kernel makes
-//             [L'_{2i+1}]₁ contiguous.
+//             through ptau_g1_kernel / ptau_g2_kernel (ptau_ranges.h's PtauRanges: zkey_check29.h's tests, one lane per point);
+//             odd_gather_kernel makes [L'_{2i+1}]₁ contiguous.
 //   sums      six left sides with bitsize = 128 over the key's sections (uploaded here a second time: the key check keeps only 6 and
-//             7 and frees them with its session), ten full-width right sides; bases in slices of MSM_SLICE, partial sums added.
+//             7 and frees them with its session), ten full-width right sides; bases in slices, partial sums added (device_call.h: sliced_msm).
 //   verdict   A, B1, B2 as points; IC, C, H by two host pairings each.
 #include <algorithm>
 #include <chrono>
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../workers.h"
+#include "device_call.h"
 #include "prover_internal.h"
 #include "ptau_ranges.h"
 #include "sha256.h"
@@ -33,15 +34,7 @@ namespace {
 
 namespace pv = isnark::prover;
 
-constexpr uint32_t MSM_SLICE = 1u << 24; // bases per MSM call (partial sums add), as zkey_check.hip
 enum { V_A = 0, V_B, V_A_PUB, V_B_PUB, V_C_PUB, V_A_PRIV, V_B_PRIV, V_C_PRIV, N_VEC };
-
-__device__ __forceinline__ void st(fe* p, const fe& v)
-{
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-  q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
 
 // z^pub = z on the wires 0 … n_public, 0 above; z^priv = z − z^pub.  One lane per wire.
 __global__ __launch_bounds__(256) void verify_split_kernel(const fe* __restrict__ z, uint32_t n_wires, uint32_t n_public, fe* __restrict__ z_pub, fe* __restrict__ z_priv)
@@ -79,53 +72,6 @@ __global__ __launch_bounds__(256) void verify_assemble_kernel(const fe* __restri
   for (int k = 0; k < N_VEC; k++) st(out + (size_t)k * n + j, v[k]);
 }
 
-int dev_fail(const char* what, hipError_t e) { return pv::fail(pv::ERR_DEVICE, "device: %s: %s", what, hipGetErrorString(e)); }
-
-bool words_zero(const void* p, size_t bytes)
-{
-  const uint8_t* b = (const uint8_t*)p;
-  for (size_t i = 0; i < bytes; i++)
-    if (b[i]) return false;
-  return true;
-}
-
-// standard-form affine, (0, 0) = the identity (a projective point with z = 0)
-bn254_affine_t affine_of(const bn254_projective_t& p)
-{
-  bn254_affine_t a;
-  memset(&a, 0, sizeof a);
-  if (!words_zero(&p.z, sizeof p.z)) bn254_to_affine(&p, &a);
-  return a;
-}
-bn254_g2_affine_t affine_of(const bn254_g2_projective_t& p)
-{
-  bn254_g2_affine_t a;
-  memset(&a, 0, sizeof a);
-  if (!words_zero(&p.z, sizeof p.z)) bn254_g2_to_affine(&p, &a);
-  return a;
-}
-template <class P>
-bool same_point(const P& l, const P& r)
-{
-  const auto a = affine_of(l), b = affine_of(r);
-  return memcmp(&a, &b, sizeof a) == 0;
-}
-// e(S, Q) = e(T, G₂), Q a header point (not the identity: the key check has said so): the identity on both sides holds, on one fails
-bool pair_holds(const bn254_projective_t& s, const bn254_g2_affine_t& q, const bn254_projective_t& t)
-{
-  const bn254_affine_t sa = affine_of(s), ta = affine_of(t);
-  const bool zs = words_zero(&sa, sizeof sa), zt = words_zero(&ta, sizeof ta);
-  if (zs || zt) return zs && zt;
-  bn254_g2_projective_t g2p;
-  bn254_g2_affine_t g2;
-  bn254_g2_generator(&g2p);
-  bn254_g2_to_affine(&g2p, &g2);
-  bn254_fq12_t l, r;
-  (void)bn254_pairing(&sa, &q, &l);
-  (void)bn254_pairing(&ta, &g2, &r);
-  return memcmp(&l, &r, sizeof l) == 0;
-}
-
 // the device side of one call
 struct Verify {
   const pv::ZkeyLayout& L;
@@ -133,17 +79,12 @@ struct Verify {
   Groth16R1cs* const h;
   const pv::R1csShape shape;
   const uint32_t n, m, k; // the domain, the wires, log2 n
+  const pv::FileRange zkey_file, ptau_file; // which mapped file the staging workers may pread() for a source pointer (the _file entry)
   isnark::vb::DeviceSession ds;
   double upload_ms = 0;
-  // which mapped file the staging workers may pread() for a source pointer (the _file entry; fd < 0: plain memory)
-  struct Hint {
-    const uint8_t* base = nullptr;
-    size_t len = 0;
-    int fd = -1;
-  } hint[2];
 
-  Verify(const pv::ZkeyLayout& zl, const pv::PtauLayout& pl, Groth16R1cs* handle, uint32_t log_n)
-      : L(zl), PL(pl), h(handle), shape(pv::r1cs_shape(handle)), n(zl.domain), m(zl.n_vars), k(log_n)
+  Verify(const pv::ZkeyLayout& zl, const pv::PtauLayout& pl, Groth16R1cs* handle, uint32_t log_n, const pv::FileRange& zf, const pv::FileRange& pf)
+      : L(zl), PL(pl), h(handle), shape(pv::r1cs_shape(handle)), n(zl.domain), m(zl.n_vars), k(log_n), zkey_file(zf), ptau_file(pf)
   {
   }
 
@@ -151,21 +92,12 @@ struct Verify {
   int alloc(T** p, size_t count)
   {
     *p = ds.buf.alloc<T>(std::max<size_t>(count, 1));
-    return *p ? 0 : dev_fail("hipMalloc", hipErrorOutOfMemory);
+    return *p ? 0 : pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
   }
   int upload(void* dst, const void* src, size_t bytes)
   {
-    if (!bytes) return 0;
-    const Hint* use = nullptr;
-    for (const Hint& f : hint)
-      if (f.fd >= 0 && (const uint8_t*)src >= f.base && (const uint8_t*)src < f.base + f.len) use = &f;
-    isnark::staged_copy_file_hint(use ? use->base : nullptr, use ? use->len : 0, use ? use->fd : -1);
-    const auto t0 = std::chrono::steady_clock::now();
-    const isnark::CopyJob job = {dst, src, bytes};
-    const hipError_t he = isnark::staged_copy(shape.dev, &job, 1, true);
-    upload_ms += pv::ms_since(t0);
-    isnark::staged_copy_file_hint(nullptr, 0, -1);
-    return he ? dev_fail("host to device upload", he) : 0;
+    const pv::FileHint hint(zkey_file.holds(src) ? zkey_file : ptau_file.holds(src) ? ptau_file : pv::FileRange());
+    return pv::timed_upload(shape.dev, dst, src, bytes, &upload_ms);
   }
   template <class T>
   int put(T** d, const void* src, size_t count)
@@ -173,48 +105,11 @@ struct Verify {
     if (int rc = alloc(d, count)) return rc;
     return upload(*d, src, count * sizeof(T));
   }
-
-  MSMConfig config(int bitsize) const
+  // Σ scalars[i]·bases[i] over `count` Montgomery-form affine bases on the device, on the second stream; the group is out's
+  template <class P>
+  int sum(const fe* scalars, const uint8_t* bases, uint64_t count, int bitsize, P* out)
   {
-    MSMConfig mc;
-    memset(&mc, 0, sizeof mc);
-    mc.stream = ds.streams[1];
-    mc.precompute_factor = 1;
-    mc.bitsize = bitsize;
-    mc.batch_size = 1;
-    mc.are_scalars_on_device = true;
-    mc.are_points_on_device = true;
-    mc.are_points_montgomery_form = true;
-    return mc;
-  }
-  // Σ scalars[i]·bases[i] over `count` Montgomery-form affine bases on the device, in slices; count = 0 is the identity
-  int sum(const fe* scalars, const uint8_t* bases, uint64_t count, int bitsize, bn254_projective_t* out)
-  {
-    memset(out, 0, sizeof *out);
-    const MSMConfig mc = config(bitsize);
-    for (uint64_t off = 0; off < count; off += MSM_SLICE) {
-      const int cnt = (int)std::min<uint64_t>(MSM_SLICE, count - off);
-      bn254_projective_t p;
-      if (eIcicleError me = bn254_msm((const bn254_scalar_t*)(scalars + off), (const bn254_affine_t*)(bases + off * 64), cnt, &mc, &p))
-        return pv::fail(pv::ERR_DEVICE, "device: msm (%d): %s", (int)me, icicle_snark_last_error());
-      if (off) bn254_ecadd(out, &p, out);
-      else *out = p;
-    }
-    return 0;
-  }
-  int sum(const fe* scalars, const uint8_t* bases, uint64_t count, int bitsize, bn254_g2_projective_t* out)
-  {
-    memset(out, 0, sizeof *out);
-    const MSMConfig mc = config(bitsize);
-    for (uint64_t off = 0; off < count; off += MSM_SLICE) {
-      const int cnt = (int)std::min<uint64_t>(MSM_SLICE, count - off);
-      bn254_g2_projective_t p;
-      if (eIcicleError me = bn254_g2_msm((const bn254_scalar_t*)(scalars + off), (const bn254_g2_affine_t*)(bases + off * 128), cnt, &mc, &p))
-        return pv::fail(pv::ERR_DEVICE, "device: msm (%d): %s", (int)me, icicle_snark_last_error());
-      if (off) bn254_g2_ecadd(out, &p, out);
-      else *out = p;
-    }
-    return 0;
+    return pv::sliced_msm(pv::device_msm_config(ds.streams[1], bitsize), scalars, bases, count, out);
   }
 };
 
@@ -229,10 +124,9 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   if (int rc = pv::zkey_layout(zkey, zkey_len, zsecs, &L)) return rc;
   if (int rc = pv::ptau_layout(ptau, ptau_len, psecs, &PL)) return rc;
   const pv::R1csShape shape = pv::r1cs_shape(h);
-  // sizes, as groth16_r1cs_match_zkey: the domain is the smallest power of two >= mConstraints + n_public + 1 (snarkjs' rule)
-  uint64_t domain = 1;
-  uint32_t k = 0;
-  while (domain < (uint64_t)shape.m + shape.n_public + 1) domain <<= 1, k++;
+  // sizes, as groth16_r1cs_match_zkey
+  uint32_t k;
+  const uint64_t domain = pv::circuit_domain(shape.m, shape.n_public, &k);
   const bool size_ok[3] = {L.n_vars == shape.n_wires, L.n_public == shape.n_public, L.domain == domain};
   for (int i = 0; i < 3; i++)
     if (!size_ok[i]) {
@@ -242,26 +136,21 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
     }
   if (int rc = pv::ptau_blocks_for_domain(PL, k)) return rc;
   uint8_t seed[32];
-  if (seed32) memcpy(seed, seed32, 32);
-  else if (!isnark::vb::os_random(seed, 32)) return pv::fail(pv::ERR_ARG, "no randomness from the operating system (getrandom, /dev/urandom)");
+  if (int rc = pv::seed_or_random(seed32, seed)) return rc;
 
-  static const bool trace = isnark::env_set("ICICLE_SNARK_TRACE_ZKEY_VERIFY");
-  auto t_prev = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[zkey-verify] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-    t_prev = t;
-  };
+  pv::StageTrace trace("zkey-verify", "ICICLE_SNARK_TRACE_ZKEY_VERIFY");
 
   // the key's own soundness first: the equations below mean nothing over points off their curves
   char device[32];
   snprintf(device, sizeof device, "HIP:%d", shape.dev);
   const Groth16ZkeyCheckOptions opt = {0, seed};
-  if (zkey_fd >= 0) isnark::staged_copy_file_hint(zkey, zkey_len, zkey_fd);
-  const int key_rc = groth16_zkey_check(zkey, zkey_len, device, &opt, &rep->key);
-  isnark::staged_copy_file_hint(nullptr, 0, -1);
-  lap("key check");
+  const pv::FileRange zkey_file = {zkey, zkey_len, zkey_fd}, ptau_file = {ptau, ptau_len, ptau_fd};
+  int key_rc;
+  {
+    const pv::FileHint hint(zkey_file);
+    key_rc = groth16_zkey_check(zkey, zkey_len, device, &opt, &rep->key);
+  }
+  trace.lap("key check");
   if (key_rc < 0) return key_rc;
   // A mismatch of section 6 against 7 as the key's ONLY fault leaves every point where the sums are defined, and B1 and B2 below say
   // which of the two sections is not the circuit's: the equations run.  Any other fault ends the call here.
@@ -288,57 +177,39 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   const uint32_t n = L.domain, m = L.n_vars, npub = L.n_public, nc = shape.m;
   // z_s = coefficient s, y_i = coefficient m + i: one vector, 128 bits each in 32-byte standard form
   std::vector<fe> zy((size_t)m + n);
-  memset(zy.data(), 0, zy.size() * sizeof zy[0]);
-  isnark::run_ranges(zy.size(), 4096, [&](int, size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; i++) isnark::combined_coefficient(seed, (uint64_t)i, (uint8_t*)&zy[i]);
-  });
-  lap("coefficients");
+  pv::fill_coefficients(seed, 0, zy.size(), zy.data());
+  trace.lap("coefficients");
 
   std::lock_guard<std::mutex> lk(pv::r1cs_mutex(h));
   const auto t_dev = std::chrono::steady_clock::now();
-  Verify c(L, PL, h, k);
-  c.hint[0] = {zkey, zkey_len, zkey_fd};
-  c.hint[1] = {ptau, ptau_len, ptau_fd};
+  Verify c(L, PL, h, k, zkey_file, ptau_file);
   if (c.ds.open(shape.dev, 2)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
   const hipStream_t st = c.ds.stream(0);
 
   // rows: z^pub, z^priv, a | b | c at each, the eight scalar vectors
   fe *d_zy, *d_zpub, *d_zpriv, *d_pub, *d_priv, *d_vec;
-  unsigned long long* d_first; // [0 … 4]: the five ptau ranges
+  PtauRanges ranges;
   if (int rc = c.put(&d_zy, zy.data(), zy.size())) return rc;
   if (int rc = c.alloc(&d_zpub, m)) return rc;
   if (int rc = c.alloc(&d_zpriv, m)) return rc;
   if (int rc = c.alloc(&d_pub, 3 * (size_t)nc)) return rc;
   if (int rc = c.alloc(&d_priv, 3 * (size_t)nc)) return rc;
   if (int rc = c.alloc(&d_vec, (size_t)N_VEC * n)) return rc;
-  if (int rc = c.alloc(&d_first, 5)) return rc;
-  if (hipError_t he = hipMemsetAsync(d_first, 0xff, 5 * sizeof *d_first, st)) return dev_fail("hipMemset", he);
-  hipLaunchKernelGGL(verify_split_kernel, dim3((m + 255) / 256), dim3(256), 0, st, d_zy, m, npub, d_zpub, d_zpriv);
-  if (hipError_t he = hipGetLastError()) return dev_fail("split kernel launch", he);
+  if (int rc = ranges.reset(c.ds, st)) return rc;
+  DEV_LAUNCH("split kernel launch", verify_split_kernel, dim3((m + 255) / 256), dim3(256), st, d_zy, m, npub, d_zpub, d_zpriv);
   if (int rc = pv::r1cs_emit_abc(h, d_zpub, d_pub, st)) return rc;
   if (int rc = pv::r1cs_emit_abc(h, d_zpriv, d_priv, st)) return rc;
-  hipLaunchKernelGGL(verify_assemble_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d_pub, d_priv, d_zy, n, nc, npub, d_vec);
-  if (hipError_t he = hipGetLastError()) return dev_fail("assemble kernel launch", he);
+  DEV_LAUNCH("assemble kernel launch", verify_assemble_kernel, dim3((n + 255) / 256), dim3(256), st, d_pub, d_priv, d_zy, n, nc, npub, d_vec);
 
-  // the ptau's ranges: block k of 12, 13, 14, 15 and block k + 1 of 12, each tested where it lands
-  const int blk_sec[5] = {12, 13, 14, 15, 12};
-  const uint32_t blk_pow[5] = {k, k, k, k, k + 1};
-  uint8_t* d_blk[5];
-  for (int i = 0; i < 5; i++) {
-    const size_t elem = blk_sec[i] == 13 ? 128 : 64;
-    const uint64_t cnt = (uint64_t)1 << blk_pow[i];
-    const uint8_t* src;
-    if (int rc = pv::ptau_block(PL, blk_sec[i], blk_pow[i], elem, &src)) return rc;
-    if (int rc = c.put(&d_blk[i], src, cnt * elem)) return rc;
-    if (elem == 64) hipLaunchKernelGGL(ptau_g1_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, st, (const fe*)d_blk[i], (uint32_t)cnt, d_first + i);
-    else hipLaunchKernelGGL(ptau_g2_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, st, (const fe2*)d_blk[i], (uint32_t)cnt, d_first + i);
-    if (hipError_t he = hipGetLastError()) return dev_fail("ptau membership kernel launch", he);
+  // the ptau's ranges, each tested where it lands (both lane tests on this one stream), and [L'_{2i+1}]₁ made contiguous
+  {
+    const pv::FileHint hint(ptau_file);
+    if (int rc = ranges.stage(PL, k, c.ds, shape.dev, st, st, &c.upload_ms)) return rc;
   }
   uint8_t* d_odd;
   if (int rc = c.alloc(&d_odd, (size_t)n * 64)) return rc;
-  hipLaunchKernelGGL(odd_gather_kernel, dim3((uint32_t)((4 * (uint64_t)n + 255) / 256)), dim3(256), 0, st, (const uint4*)d_blk[4], (uint64_t)n, (uint4*)d_odd);
-  if (hipError_t he = hipGetLastError()) return dev_fail("gather kernel launch", he);
-  lap("rows, ptau ranges");
+  if (int rc = ranges.gather_odd(st, n, d_odd)) return rc;
+  trace.lap("rows, ptau ranges");
 
   // the key's sections, a second time (the key check's session has freed them)
   const int key_sec[6] = {5, 6, 7, 8, 9, 3};
@@ -346,15 +217,13 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   uint8_t* d_key[6];
   for (int i = 0; i < 6; i++)
     if (int rc = c.put(&d_key[i], L.sec[key_sec[i]]->p, key_cnt[i] * (key_sec[i] == 7 ? 128 : 64))) return rc;
-  lap("key sections");
+  trace.lap("key sections");
 
-  unsigned long long first[5];
-  if (hipError_t he = hipMemcpyAsync(first, d_first, sizeof first, hipMemcpyDeviceToHost, st)) return dev_fail("download", he);
-  if (hipError_t he = hipStreamSynchronize(st)) return dev_fail("row and ptau kernels", he);
-  for (int i = 0; i < 5; i++)
-    if (first[i] != NO_FAULT)
-      return pv::fail(pv::ERR_FORMAT, "ptau: section %d, block %u, element %llu: %s", blk_sec[i], blk_pow[i], (unsigned long long)(first[i] >> 3), POINT_FAULT[first[i] & 3]);
-  lap("kernels done");
+  unsigned long long first[PtauRanges::N];
+  DEV_TRY("download", hipMemcpyAsync(first, ranges.d_first, sizeof first, hipMemcpyDeviceToHost, st));
+  DEV_TRY("row and ptau kernels", hipStreamSynchronize(st));
+  if (int rc = ranges.verdict(first)) return rc;
+  trace.lap("kernels done");
 
   // left sides over 128-bit scalars, right sides full width
   const fe *d_z = d_zy, *d_y = d_zy + m;
@@ -367,18 +236,18 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   if (!rc) rc = c.sum(d_z + npub + 1, d_key[3], key_cnt[3], 128, &lc);
   if (!rc) rc = c.sum(d_y, d_key[4], n, 128, &lh);
   if (!rc) rc = c.sum(d_z, d_key[5], key_cnt[5], 128, &lic);
-  lap("left sides");
-  if (!rc) rc = c.sum(vec(V_A), d_blk[0], n, 0, &ra);
-  if (!rc) rc = c.sum(vec(V_B), d_blk[0], n, 0, &rb1);
-  if (!rc) rc = c.sum(vec(V_B), d_blk[1], n, 0, &rb2);
+  trace.lap("left sides");
+  if (!rc) rc = c.sum(vec(V_A), ranges.l1(), n, 0, &ra);
+  if (!rc) rc = c.sum(vec(V_B), ranges.l1(), n, 0, &rb1);
+  if (!rc) rc = c.sum(vec(V_B), ranges.l2(), n, 0, &rb2);
   const int pub_vec[3] = {V_A_PUB, V_B_PUB, V_C_PUB}, priv_vec[3] = {V_A_PRIV, V_B_PRIV, V_C_PRIV};
-  const int t_blk[3] = {3, 2, 0}; // a with [β·L]₁ (section 15), b with [α·L]₁ (section 14), c with [L]₁ (section 12)
+  const uint8_t* const t_blk[3] = {ranges.beta_l1(), ranges.alpha_l1(), ranges.l1()}; // a with [β·L]₁ (section 15), b with [α·L]₁ (section 14), c with [L]₁ (section 12)
   for (int i = 0; i < 3 && !rc; i++) {
-    rc = c.sum(vec(pub_vec[i]), d_blk[t_blk[i]], n, 0, &ric[i]);
-    if (!rc) rc = c.sum(vec(priv_vec[i]), d_blk[t_blk[i]], n, 0, &rc3[i]);
+    rc = c.sum(vec(pub_vec[i]), t_blk[i], n, 0, &ric[i]);
+    if (!rc) rc = c.sum(vec(priv_vec[i]), t_blk[i], n, 0, &rc3[i]);
   }
   if (!rc) rc = c.sum(d_y, d_odd, n, 0, &rh);
-  lap("right sides");
+  trace.lap("right sides");
   if (rc) return rc;
   rep->upload_ms = c.upload_ms;
   rep->device_ms = pv::ms_since(t_dev);
@@ -396,6 +265,13 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   bn254_g2_affine_t gamma2, delta2;
   memcpy(&gamma2, &gs, sizeof gamma2);
   memcpy(&delta2, &dls, sizeof delta2);
+  using isnark::vb::affine_or_zero;
+  using isnark::vb::same_point;
+  // e(S, Q) = e(T, G₂), Q a header point (not the identity: the key check has said so): the identity on both sides holds, on one fails
+  const bn254_g2_affine_t g2 = isnark::vb::g2_generator_affine();
+  auto pair_holds = [&](const bn254_projective_t& s, const bn254_g2_affine_t& q, const bn254_projective_t& t) {
+    return isnark::vb::pairing_eq(affine_or_zero(s), q, affine_or_zero(t), g2);
+  };
   if (!same_point(la, ra)) fault(GROTH16_VERIFY_A, 0);
   if (!same_point(lb1, rb1)) fault(GROTH16_VERIFY_B1, 0);
   if (!same_point(lb2, rb2)) fault(GROTH16_VERIFY_B2, 0);
@@ -403,7 +279,7 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   if (!pair_holds(lc, delta2, t_c)) fault(GROTH16_VERIFY_C, 0);
   if (!pair_holds(lh, delta2, rh)) fault(GROTH16_VERIFY_H, 0);
   rep->pairing_ms = pv::ms_since(t_pair);
-  lap("comparisons, pairings");
+  trace.lap("comparisons, pairings");
   if (!first_kind && key_rc == 0) first_kind = GROTH16_VERIFY_KEY; // (the key check's seeded test failed where B1 and B2 held)
   rep->kind = first_kind;
   rep->index = first_index;

@@ -178,6 +178,20 @@ def test_a_ptau_point_off_its_curve_is_a_format_error(world, base):
     assert world.handle(r).verify_zkey(zkey, bytes(bad), seed=SEEDS[0])[0] is True
 
 
+def test_an_early_error_of_the_file_entry_leaves_no_file_hint(world, base, tmp_path):
+    """groth16_zkey_verify_ptau_file returns early from inside its ptau uploads — the staging workers are then reading the mapped
+    ptau by descriptor — and the same thread's next call, a key check from memory, must copy out of memory again"""
+    r, zkey, _ = base
+    bad = bytearray(world.ptau[10])
+    bad[_sections(world.ptau[10])[14][0] + (255 + 7) * 64 + 32] ^= 1   # block 8 of section 14, element 7
+    (tmp_path / "k.zkey").write_bytes(zkey)
+    (tmp_path / "bad.ptau").write_bytes(bytes(bad))
+    with pytest.raises(world.K.ProverError, match=r"\(-2\).*section 14, block 8, element 7: the point is not on the curve"):
+        world.handle(r).verify_zkey(tmp_path / "k.zkey", tmp_path / "bad.ptau", seed=SEEDS[0])
+    ok, rep = world.K.zkey_check(zkey, seed=SEEDS[0])
+    assert ok is True and rep.kind == 0 and list(rep.faults) == [0] * 10
+
+
 def test_sizes(world, base, S):
     r, zkey, _ = base
     other, _ = S.random_circuit(150, 3, 9, seed=11)
