@@ -290,18 +290,20 @@ def test_msm_skewed_scalars(gpu, O, grp):
 def test_msm_degenerate(gpu, O):
     K = gpu
     rng = np.random.default_rng(2)
-    bases = _bases(O, "g1", rng, 8)
-    zero = np.zeros((8, 4), dtype=np.uint64)
-    res = K.msm("g1", zero, bases)
-    assert not K.ec("g1", "to_affine", res).any() and np.array_equal(res, O.ec_zero("g1"))   # (0,1,0)
-    # P − P
-    sc = O.ints_to_arr([5, O.R_MOD - 5])
-    b2 = np.stack([bases[0], bases[0]])
-    assert not K.ec("g1", "to_affine", K.msm("g1", sc, b2)).any()
+    for grp in ("g1", "g2"):
+        bases = _bases(O, grp, rng, 8)
+        zero = np.zeros((8, 4), dtype=np.uint64)
+        res = K.msm(grp, zero, bases)
+        assert not K.ec(grp, "to_affine", res).any() and np.array_equal(res, O.ec_zero(grp))   # (0,1,0)
+        # P − P
+        sc = O.ints_to_arr([5, O.R_MOD - 5])
+        b2 = np.stack([bases[0], bases[0]])
+        assert not K.ec(grp, "to_affine", K.msm(grp, sc, b2)).any()
 
 
 @pytest.mark.parametrize("c", [0, 5, 8, 16])
-def test_msm_edge_scalars(gpu, O, c):
+@pytest.mark.parametrize("grp", ["g1", "g2"])
+def test_msm_edge_scalars(gpu, O, grp, c):
     """recoding limits: scalars around the negation threshold (r − 1)/2, around 2^253, r − 1, all-ones low parts"""
     K = gpu
     R = O.R_MOD
@@ -310,10 +312,10 @@ def test_msm_edge_scalars(gpu, O, c):
             (half >> 230 << 230) - 1, (1 << 240) - 1, ((1 << 253) - 1) ^ (1 << 19)]
     vals = vals + [(R - v) % R for v in vals]
     rng = np.random.default_rng(4)
-    bases = _bases(O, "g1", rng, len(vals))
+    bases = _bases(O, grp, rng, len(vals))
     sc = O.ints_to_arr(vals)
-    got = K.ec("g1", "to_affine", K.msm("g1", sc, bases, c=c))
-    assert np.array_equal(got, O.ec_to_affine("g1", O.msm("g1", sc, bases)))
+    got = K.ec(grp, "to_affine", K.msm(grp, sc, bases, c=c))
+    assert np.array_equal(got, O.ec_to_affine(grp, O.msm(grp, sc, bases)))
 
 
 @pytest.mark.parametrize("grp", ["g1", "g2"])

@@ -237,6 +237,45 @@ def test_edge_scalars_in_the_witness(gpu, cm, O, S):
     cm.evict("edge")
 
 
+@pytest.mark.parametrize("N", [33_000, 262_200])
+def test_edge_scalars_in_the_witness_tables(gpu, cm, O, S, N):
+    """The same on the witness tables of keys large enough for them (witness_table_geometry, csrc/prover/cache.cpp): 33 002 wires
+    run c = 16 / 16 windows, the last two narrowed, on the LDS-staged sort; 262 202 wires run c = 18 / 15 windows with EVERY window
+    one bit narrow (wide = 0: 15 × 17 bits ≥ 254), the width the rule narrows to from 19 because a bucket would hold fewer than 28
+    entries.  Squaring chains whose witness is overwritten in place — wire 0 and the public wires stay — with the edge list of
+    tests/msm_inputs.py for the geometry that runs (each window's digit 1, its negative extreme with the carry, all-ones below,
+    r − v of each, the negation threshold, 2^253): from wire n_public + 1 on, the first wire of the C MSM (its skip_below), whose
+    other side is the public wires; across wires 1023 | 1024, the sort's tile border; and at the last wires.  Not a satisfying
+    witness; proof and publics are the oracle's, and the four witness MSMs report the geometry named here."""
+    import msm_inputs as MI
+    K = gpu
+    O.calibrate_threads()
+    wires = N + 2
+    c, W, wide = MI.WITNESS_GEOMS[wires]
+    zkey, wtns = importlib.import_module("bench").make_inputs(K, S, N)
+    key = f"edge{N}"
+    cm.load(key, zkey)                                              # dense tables built inside the load
+    info = cm.info(key)
+    assert info.n_vars == wires
+    E = MI.ints_to_arr(MI.edge_list((c, W, wide)))
+    n = len(E)
+    wb = np.frombuffer(wtns, dtype=np.uint8).copy()
+    body = wb[len(wb) - 32 * wires:].view(np.uint64).reshape(-1, 4)
+    first = info.n_public + 1
+    starts = [first, 1024 - n // 2, wires - n]
+    assert first + n <= starts[1] and starts[1] + n <= starts[2]
+    for k, s in enumerate(starts):
+        body[s:s + n] = np.roll(E, -k * (n // 3), axis=0)
+    edged = wb.tobytes()
+    pj, qj, _ = cm.prove_mem(key, edged, 7, 11)
+    geoms = [K.msm_profile(back)[1] for back in (4, 3, 2, 1)]       # A, B1, B2, C
+    cm.evict(key)
+    assert [(g["c"], g["W"], g["nbuckets"]) for g in geoms] == [(c, W, 1 << (c - 1))] * 4, geoms
+    assert [g["is_g2"] for g in geoms] == [False, False, True, False]
+    proof, public = O.groth16_prove(zkey, edged, 7, 11)
+    assert json.loads(pj) == proof and json.loads(qj) == public
+
+
 def test_identity_b_bases_and_table_free_layout(gpu, O, S, tmp_path):
     """Wires without a B-side occurrence have the identity as their B1/B2 base (snarkjs writes all-zero bytes): the bucket
     kernels skip them.  Same proof as the oracle's with the fixed-base tables (default) and with the classic layout of a
