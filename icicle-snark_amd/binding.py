@@ -703,6 +703,7 @@ groth16_r1cs_info groth16_r1cs_load groth16_r1cs_load_file groth16_r1cs_get_info
 groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
 groth16_ptau_info groth16_zkey_verify_ptau groth16_zkey_verify_ptau_file
 groth16_zkey_new_size groth16_zkey_new groth16_zkey_new_file
+groth16_zkey_contribute groth16_zkey_contribute_file groth16_zkey_contributions
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1077,6 +1078,77 @@ class R1cs:
             self.close()
         except Exception:
             pass
+
+
+class ZkeyContributeOptions(C.Structure):
+    _fields_ = [("fixed_delta", C.POINTER(C.c_uint8))]
+
+
+class ZkeyContributeReport(C.Structure):
+    """Groth16ZkeyContributeReport: the record's number, the points of sections 8 and 9, the output's size, the first faulty
+    point (section, kind, index) and how many there are, the stage times"""
+    _fields_ = [("contribution", C.c_uint32), ("points_c", C.c_uint64), ("points_h", C.c_uint64), ("zkey_bytes", C.c_uint64),
+                ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64), ("faults", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
+class ContributionsReport(C.Structure):
+    """Groth16ContributionsReport: the record count, kind and index (records count from 1) of the first fault; .records: the
+    (after1 bytes, name bytes) of the records whose bounds hold"""
+    _fields_ = [("count", C.c_uint32), ("kind", C.c_int32), ("index", C.c_uint32)]
+    records = ()
+
+
+class ContributionInfo(C.Structure):
+    _fields_ = [("after1", C.c_uint8 * 64), ("name", C.c_char * 256)]
+
+
+CONTRIB_SECTION, CONTRIB_POINT, CONTRIB_POK, CONTRIB_HEADER, CONTRIB_PAIR = range(1, 6)
+CONTRIB_KIND_NAMES = ["ok", "SECTION", "POINT", "POK", "HEADER", "PAIR"]
+
+
+def zkey_contribute(zkey, secret=None, name="", out=None, device: str = "HIP", delta=None):
+    """groth16_zkey_contribute → (zkey bytes | None, ZkeyContributeReport): one phase-2 contribution applied on the GPU — the
+    header's delta times delta', sections 8 and 9 times its inverse, one record appended to section 10 (this library's own
+    layout: include/groth16_prover.h).  zkey: the image, and the new key comes back as bytes; or a path together with `out`, the
+    path the new key is written to (None comes back).  secret: 32 bytes, None draws from the operating system.  name: str or bytes,
+    at most 255 bytes.  delta: delta' itself as an integer in [1, r), for tests and reproducible runs.  Raises ProverError (−2 a
+    faulty point of section 8 or 9 or a malformed section 10, −3 a name too long or a bad delta)."""
+    if secret is not None and len(secret) != 32:
+        raise ValueError("zkey_contribute: the secret is 32 bytes")
+    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(secret)) if secret is not None else None
+    fd = (C.c_uint8 * 32).from_buffer_copy(int(delta).to_bytes(32, "little")) if delta is not None else None
+    opt, rep = ZkeyContributeOptions(C.cast(fd, C.POINTER(C.c_uint8)) if fd is not None else None), ZkeyContributeReport()
+    nm = name.encode() if isinstance(name, str) else bytes(name)
+    if isinstance(zkey, (str, os.PathLike)):
+        if out is None:
+            raise TypeError("zkey_contribute: a zkey path needs the path to write the new key to")
+        _pcheck(lib().groth16_zkey_contribute_file(os.fsencode(zkey), os.fsencode(out), sd, nm, device.encode(), C.byref(opt), C.byref(rep)), "zkey_contribute_file")
+        return None, rep
+    if out is not None:
+        raise TypeError("zkey_contribute: `out` goes with a zkey path")
+    # sized by the library itself: a first call with no room reports the bytes it needs, before any device work
+    rc = lib().groth16_zkey_contribute(_image(zkey), C.c_size_t(len(zkey)), sd, nm, None, C.c_size_t(0), device.encode(), C.byref(opt), C.byref(rep))
+    if rc != -3 or rep.zkey_bytes == 0:
+        _pcheck(rc, "zkey_contribute")
+    buf = C.create_string_buffer(rep.zkey_bytes)
+    _pcheck(lib().groth16_zkey_contribute(_image(zkey), C.c_size_t(len(zkey)), sd, nm, buf, C.c_size_t(rep.zkey_bytes), device.encode(), C.byref(opt), C.byref(rep)), "zkey_contribute")
+    return buf.raw, rep
+
+
+def zkey_contributions(zkey):
+    """groth16_zkey_contributions → (ok, ContributionsReport with .records): is section 10 a chain of valid contributions from
+    delta = 1 to the header's delta1, and do delta1 and delta2 pair?  Host only: needs no GPU.  It does NOT show that sections 8
+    and 9 follow delta2: that is R1cs.verify_zkey's."""
+    rep = ContributionsReport()
+    cap = min(len(zkey) // 164 + 1, 4096)   # a record is at least 164 bytes; .records holds the first 4096
+    infos = (ContributionInfo * cap)()
+    rc = lib().groth16_zkey_contributions(_image(zkey), C.c_size_t(len(zkey)), C.byref(rep), infos, C.c_size_t(cap))
+    if rc not in (0, 1):
+        _pcheck(rc, "zkey_contributions")
+    held = rep.count if rep.kind != CONTRIB_SECTION else max(int(rep.index) - 1, 0)
+    rep.records = [(bytes(infos[i].after1), infos[i].name) for i in range(min(held, cap))]
+    return rc == 1, rep
 
 
 def sum_commitments(blocks: bytes, count: int) -> bytes:

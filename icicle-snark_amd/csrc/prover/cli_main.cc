@@ -13,6 +13,10 @@
 //   > zkey-verify --r1cs R --zkey Z --ptau P [--device HIP]   r1cs-match, then the point sections against circuit and ceremony (groth16_zkey_verify_ptau)
 //   > zkey-new --r1cs R --ptau P --zkey OUT [--device HIP]    the circuit's key over the ceremony before any contribution, gamma = delta = 1
 //     (groth16_zkey_new_file): one line with sizes and times, then ZKEY_WRITTEN
+//   > zkey-contribute --zkey Z --out OUT [--name N] [--device HIP]    one phase-2 contribution with a secret from the operating system
+//     (groth16_zkey_contribute_file): one summary line, then ZKEY_WRITTEN
+//   > zkey-contributions --zkey Z             section 10's chain and the header's delta pair, on the host (groth16_zkey_contributions):
+//     one line per record, then CHAIN_OK or CHAIN_BAD <kind> <index>.  It does not show that C and H follow delta2: zkey-verify does
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -23,7 +27,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  exit\n";
 }
 
 int main()
@@ -340,6 +344,55 @@ int main()
         std::cout << "ZKEY_WRITTEN" << std::endl;
       }
       groth16_r1cs_free(h);
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-contribute") {
+      // the secret is the operating system's: none is taken from a command line
+      std::string zkey = "circuit_0000.zkey", out = "circuit_0001.zkey", name, device = "HIP", a;
+      while (in >> a) {
+        if (a == "--zkey") in >> zkey;
+        else if (a == "--out") in >> out;
+        else if (a == "--name") in >> name;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16ZkeyContributeReport rep;
+      const int rc = groth16_zkey_contribute_file(zkey.c_str(), out.c_str(), nullptr, name.c_str(), device.c_str(), nullptr, &rep);
+      if (rc < 0) {
+        std::cerr << "zkey-contribute failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        std::cout << "contribution " << rep.contribution << " points C " << rep.points_c << " H " << rep.points_h << " bytes " << rep.zkey_bytes << "; upload " << rep.upload_ms
+                  << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
+        std::cout << "ZKEY_WRITTEN" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-contributions") {
+      // the chain of section 10 and the header's delta pair, on the host; that C and H follow delta2 is zkey-verify's question
+      std::string zkey = "circuit_final.zkey", a;
+      while (in >> a) {
+        if (a == "--zkey") in >> zkey;
+        else print_help();
+      }
+      std::ifstream f(zkey, std::ios::binary);
+      std::ostringstream ss;
+      if (f) ss << f.rdbuf();
+      const std::string image = ss.str();
+      Groth16ContributionsReport rep;
+      std::vector<Groth16ContributionInfo> infos(4096); // the records that are listed; the verdict is over all of them
+      const int rc = f ? groth16_zkey_contributions(image.data(), image.size(), &rep, infos.data(), infos.size()) : -1;
+      if (rc < 0) {
+        std::cerr << "zkey-contributions failed (" << rc << "): " << (f ? groth16_last_error() : "cannot read the zkey") << std::endl;
+      } else {
+        static const char* const kinds[6] = {"", "SECTION", "POINT", "POK", "HEADER", "PAIR"};
+        const uint32_t held = rep.kind == GROTH16_CONTRIB_SECTION ? (rep.index ? rep.index - 1 : 0) : rep.count;
+        for (uint32_t i = 0; i < held && i < infos.size(); i++) {
+          static const char hex[] = "0123456789abcdef";
+          std::string d;
+          for (int k = 0; k < 8; k++) d += {hex[infos[i].after1[k] >> 4], hex[infos[i].after1[k] & 15]};
+          std::cout << "contribution " << i + 1 << " name \"" << infos[i].name << "\" delta1 " << d << "..." << std::endl;
+        }
+        if (rc == 1) std::cout << "CHAIN_OK" << std::endl;
+        else std::cout << "CHAIN_BAD " << kinds[rep.kind >= 1 && rep.kind <= 5 ? rep.kind : 0] << " " << rep.index << std::endl;
+      }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {
       print_help();

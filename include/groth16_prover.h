@@ -407,7 +407,8 @@ int groth16_zkey_verify_ptau_file(Groth16R1cs* h, const char* zkey_path, const c
 /* groth16_zkey_new — the Groth16 proving key of THIS circuit over THIS ceremony, before any phase-2 contribution: what `snarkjs
  * zkey new circuit.r1cs pot.ptau out.zkey` writes, made on the GPU.  Opt-in; nothing else in the library calls it.
  * WHAT IT IS NOT: a key to prove with in production.  Its gamma and delta are 1 (gamma2 = delta2 = G2, delta1 = G1): whoever knows
- * that can forge proofs, until a phase-2 contribution has replaced delta.  The call builds and does not verify — the .ptau is taken
+ * that can forge proofs, until a phase-2 contribution has replaced delta: groth16_zkey_contribute, below, applies one and
+ * groth16_zkey_contributions audits the chain.  The call builds and does not verify — the .ptau is taken
  * as given; groth16_zkey_check, groth16_r1cs_match_zkey and groth16_zkey_verify_ptau are what judge the result.
  * Notation as above: nc constraints, m wires, npub public signals, n = 2^k the smallest power of two >= nc + npub + 1.  For a wire s
  *   A_s  = sum_j A[j,s]*[L_j]1 (+ [L_{nc+s}]1 for s <= npub: the rows snarkjs adds to bind the public signals)
@@ -447,6 +448,83 @@ int groth16_zkey_new(Groth16R1cs* h, const void* ptau, size_t ptau_len, void* zk
                      Groth16ZkeyNewReport* report);
 int groth16_zkey_new_file(Groth16R1cs* h, const char* ptau_path, const char* zkey_path, const Groth16ZkeyNewOptions* opt,
                           Groth16ZkeyNewReport* report);
+
+/* groth16_zkey_contribute — one phase-2 contribution applied to a proving key on the GPU: what makes groth16_zkey_new's key a key
+ * to prove with.  Opt-in; nothing else in the library calls it.  The contributor's secret is delta' in [1, r):
+ *   header   delta1 <- delta'*delta1, delta2 <- delta'*delta2; everything else of section 2 stays byte for byte
+ *   8, 9     every point of C and of H becomes delta'^-1 * P — ONE scalar for |8| + |9| points: zc_scale_g1_kernel, a lane per point
+ *   10       one record appended (the section is created behind the last one when the key has none)
+ *   1, 3, 4, 5, 6, 7 and any other section: copied, in the input's order.
+ * The identity stays all-zero bytes and affine Montgomery bytes are canonical, so the result is a function of (key, delta') alone.
+ * Every point of 8 and 9 passes the key check's lane test (coordinates < q, on the curve) before any arithmetic sees it; a
+ * point that fails is -2 with a text naming section, index and kind, and nothing is written.  The header's delta1 and delta2 get
+ * the same tests on the host (delta2: in the subgroup), and an identity delta is refused (-2).
+ * SECTION 10 — THIS LIBRARY'S OWN LAYOUT.  snarkjs' record needs BLAKE2b, its ChaCha-seeded hash-to-G2 and its circuit hash; what
+ * is written here is instead: u32 count, then count records
+ *   after1   64 B   delta1 after this contribution (affine, Montgomery form, as the header)
+ *   R        64 B   the commitment k*before1, same form
+ *   z        32 B   the response, standard form little-endian, < r
+ *   name_len u32    <= 255
+ *   name     name_len bytes
+ * with TAG = "icicle-snark zkey contribution v1" (ASCII, no terminator); before1 of record 1 = the header's delta1 at the time of
+ * contributing, of record i = record i-1's after1; h_0 = SHA-256(TAG || section 2 bytes [0, 468) || section 3) — everything up to
+ * and including gamma2, and IC: what no contribution changes; e_i = SHA-256(h_{i-1} || before1 || after1 || R || name_len || name),
+ * h_i = e_i; the challenge c_i = the first 16 bytes of e_i, little-endian, 0 replaced by 1; z = k + c*delta' mod r (Schnorr), which
+ * a verifier checks as z*before1 = R + c*after1.  A KEY CONTRIBUTED HERE CONTINUES ITS CEREMONY HERE: snarkjs reads sections 2 to 9
+ * to prove and to export the vk, which are unaffected, but its `zkey verify` and `zkey contribute` do not read this section 10.
+ * SECRETS, from the caller's 32 bytes (secret32 = NULL: the operating system's).  W(x) = SHA-256(x || 0x00) || SHA-256(x || 0x01) read
+ * as a 512-bit big-endian integer, mod r.  delta' = W(secret || TAG) unless opt->fixed_delta (32 bytes, standard form little-endian,
+ * 0 < . < r: for tests and reproducible runs) gives it; k = W(secret || delta' as 32 B LE || h_{i-1} || before1), so one secret used
+ * on two keys does not leak delta'.  A zero delta' or k is -3.  The host copies of secret, delta', delta'^-1, k and the digit masks
+ * are wiped (explicit_bzero) before the call returns — best effort: the masks also travel to the device as kernel arguments, and
+ * the kernel's duration depends on them.
+ * The output's size is known before any device work: the input, plus the record (164 + name bytes), plus 12 when section 10 was
+ * absent; cap is tested first, and a short cap is -3 with report->zkey_bytes set and nothing written.
+ * 0 done; -1 I/O; -2 format: a malformed key, a faulty point of section 8 or 9, a malformed section 10 (or one whose last after1 is
+ * not the header's delta1); -3 argument: a name over 255 bytes, a bad fixed_delta, cap too small, equal paths; -5 device failure
+ * (groth16_last_error).  The _file variant maps the input, writes a temporary beside out_path and renames it: a failed call leaves
+ * nothing.  The calling thread's device is what it was afterwards.  ICICLE_SNARK_TRACE_ZKEY_CONTRIBUTE=1 prints the stage times. */
+typedef struct {
+  const uint8_t* fixed_delta;   /* NULL, or delta' itself: 32 bytes, standard form little-endian, 0 < delta' < r */
+} Groth16ZkeyContributeOptions;
+typedef struct {
+  uint32_t contribution;        /* this record's number: 1 for the first */
+  uint64_t points_c, points_h;  /* points of section 8 and of section 9 */
+  uint64_t zkey_bytes;          /* the output (also when cap was too small) */
+  int32_t  fault_section, fault_kind;   /* after a faulty point: 8 or 9, and GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE */
+  uint64_t fault_index, faults;         /* the first such point's index in its section; how many there are */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the sections' copies up; wall time of the device part up to the last
+                                   kernel; the copies into the buffer or the mapped file; msync and rename (_file) */
+} Groth16ZkeyContributeReport;
+int groth16_zkey_contribute(const void* zkey, size_t len, const uint8_t* secret32 /* NULL = OS randomness */, const char* name,
+                            void* out, size_t cap, const char* device, const Groth16ZkeyContributeOptions* opt,
+                            Groth16ZkeyContributeReport* report);
+int groth16_zkey_contribute_file(const char* zkey_path, const char* out_path, const uint8_t* secret32, const char* name,
+                                 const char* device, const Groth16ZkeyContributeOptions* opt, Groth16ZkeyContributeReport* report);
+
+/* groth16_zkey_contributions — is section 10 a chain of valid contributions that ends in this key's delta?  Host only: never
+ * initialises a GPU.  A key without section 10 counts as zero records.  kinds of fault, in the order of testing: */
+#define GROTH16_CONTRIB_SECTION 1   /* the count or a record does not fit the section (or section 10 is duplicated); index = the record, 0 for the count */
+#define GROTH16_CONTRIB_POINT   2   /* a record's after1 or R has a coordinate >= q or is off the curve, or after1 is the identity */
+#define GROTH16_CONTRIB_POK     3   /* z >= r, or z*before1 != R + c*after1.  Record 1 is checked against before1 = G1: a chain that did
+                                       not start from groth16_zkey_new's delta = 1 fails here at index 1 */
+#define GROTH16_CONTRIB_HEADER  4   /* the last after1 is not the header's delta1; or count = 0 and delta1 != G1 */
+#define GROTH16_CONTRIB_PAIR    5   /* e(delta1, G2) != e(G1, delta2) */
+typedef struct {
+  uint32_t count;            /* records in section 10 (0 after a SECTION fault of the count) */
+  int32_t  kind;             /* 0 = the chain holds, else the kind of the FIRST fault */
+  uint32_t index;            /* the record at fault, 1 for the first; 0 for HEADER, PAIR and the count */
+} Groth16ContributionsReport;
+typedef struct {
+  uint8_t after1[64];        /* as the record holds it */
+  char    name[256];         /* zero-terminated */
+} Groth16ContributionInfo;
+/* infos (may be NULL) receives after1 and the name of the first min(count, infos_cap) records whose bounds hold.
+ * What it does NOT show: that sections 8 and 9 follow delta2 — that C and H really were scaled.  That is
+ * groth16_zkey_verify_ptau's, which pairs both against the header's delta2; run both.
+ * 1 the chain holds, 0 not (report says where), < 0 an error (-2: the key's container or header is malformed). */
+int groth16_zkey_contributions(const void* zkey, size_t len, Groth16ContributionsReport* report, Groth16ContributionInfo* infos,
+                               size_t infos_cap);
 
 #ifdef __cplusplus
 }
