@@ -704,6 +704,7 @@ groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
 groth16_ptau_info groth16_zkey_verify_ptau groth16_zkey_verify_ptau_file
 groth16_zkey_new_size groth16_zkey_new groth16_zkey_new_file
 groth16_zkey_contribute groth16_zkey_contribute_file groth16_zkey_contributions
+groth16_ptau_prepared_size groth16_ptau_prepare groth16_ptau_prepare_file
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1149,6 +1150,46 @@ def zkey_contributions(zkey):
     held = rep.count if rep.kind != CONTRIB_SECTION else max(int(rep.index) - 1, 0)
     rep.records = [(bytes(infos[i].after1), infos[i].name) for i in range(min(held, cap))]
     return rc == 1, rep
+
+
+class PtauPrepareReport(C.Structure):
+    """Groth16PtauPrepareReport: the power, the points of sections 12 to 15, the output's size, the first faulty point (section,
+    kind, element), the stage times"""
+    _fields_ = [("power", C.c_uint32), ("points", C.c_uint64 * 4), ("ptau_bytes", C.c_uint64),
+                ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
+def ptau_prepared_size(ptau: bytes) -> int:
+    """groth16_ptau_prepared_size: the bytes of the file ptau_prepare writes for this UNPREPARED .ptau; host only.  Raises
+    ProverError −2 for a malformed file, with a text of its own for one that is already prepared."""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_ptau_prepared_size(_image(ptau), C.c_size_t(len(ptau)), C.byref(size)), "ptau_prepared_size")
+    return size.value
+
+
+def ptau_prepare(ptau, out=None, device: str = "HIP"):
+    """groth16_ptau_prepare → (ptau bytes | None, PtauPrepareReport): sections 12 to 15 made on the GPU from sections 2 to 5 of an
+    unprepared powers-of-tau file, what `snarkjs powersoftau prepare phase2` makes (include/groth16_prover.h has the definition,
+    and what section 12's last block is).  ptau: the image, and the prepared file comes back as bytes; or a path together with
+    `out`, the path the prepared file is written to (None comes back).  Raises ProverError (−2 a malformed or already prepared
+    file, or a faulty point: section, element and kind in the text)."""
+    rep = PtauPrepareReport()
+    if isinstance(ptau, (str, os.PathLike)):
+        if out is None:
+            raise TypeError("ptau_prepare: a ptau path needs the path to write the prepared file to")
+        rc = lib().groth16_ptau_prepare_file(os.fsencode(ptau), os.fsencode(out), device.encode(), C.byref(rep))
+        if rc != 1:
+            _pcheck(rc, "ptau_prepare_file")
+        return None, rep
+    if out is not None:
+        raise TypeError("ptau_prepare: `out` goes with a ptau path")
+    size = ptau_prepared_size(ptau)
+    buf, got = C.create_string_buffer(size), C.c_uint64()
+    rc = lib().groth16_ptau_prepare(_image(ptau), C.c_size_t(len(ptau)), buf, C.c_size_t(size), C.byref(got), device.encode(), C.byref(rep))
+    if rc != 1:
+        _pcheck(rc, "ptau_prepare")
+    return buf.raw[:got.value], rep
 
 
 def sum_commitments(blocks: bytes, count: int) -> bytes:

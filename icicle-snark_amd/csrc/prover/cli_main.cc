@@ -17,6 +17,8 @@
 //     (groth16_zkey_contribute_file): one summary line, then ZKEY_WRITTEN
 //   > zkey-contributions --zkey Z             section 10's chain and the header's delta pair, on the host (groth16_zkey_contributions):
 //     one line per record, then CHAIN_OK or CHAIN_BAD <kind> <index>.  It does not show that C and H follow delta2: zkey-verify does
+//   > ptau-prepare --ptau IN --out OUT [--device HIP]    sections 12 to 15 of a powers-of-tau file made from its sections 2 to 5
+//     (groth16_ptau_prepare_file, snarkjs' `powersoftau prepare phase2`): one summary line, then PTAU_WRITTEN
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -27,7 +29,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  exit\n";
 }
 
 int main()
@@ -392,6 +394,24 @@ int main()
         }
         if (rc == 1) std::cout << "CHAIN_OK" << std::endl;
         else std::cout << "CHAIN_BAD " << kinds[rep.kind >= 1 && rep.kind <= 5 ? rep.kind : 0] << " " << rep.index << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-prepare") {
+      std::string ptau = "pot.ptau", out = "pot_final.ptau", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--ptau") in >> ptau;
+        else if (a == "--out") in >> out;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16PtauPrepareReport rep;
+      const int rc = groth16_ptau_prepare_file(ptau.c_str(), out.c_str(), device.c_str(), &rep);
+      if (rc < 0) {
+        std::cerr << "ptau-prepare failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        std::cout << "power " << rep.power << " points " << rep.points[0] << " " << rep.points[1] << " " << rep.points[2] << " " << rep.points[3] << " bytes " << rep.ptau_bytes
+                  << "; upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
+        std::cout << "PTAU_WRITTEN" << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

@@ -170,8 +170,8 @@ int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_te
   return 0;
 }
 
-// sections and header of a prepared .ptau (prover_internal.h: PtauLayout)
-int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L)
+// container and section 1 of a .ptau, prepared or not: magic, version, n8, q, power
+static int ptau_header(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L)
 {
   if (!data) return fail(ERR_ARG, "null ptau");
   if (int rc = read_sections(data, len, "ptau", 1, secs)) return rc;
@@ -188,6 +188,13 @@ int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Pta
   memcpy(&L->ceremony_power, h->p + 40, 4);
   if (L->power > 28) return fail(ERR_FORMAT, "ptau: power %u is above the field's two-adicity", L->power);
   L->sec[1] = h;
+  return 0;
+}
+
+// sections and header of a prepared .ptau (prover_internal.h: PtauLayout)
+int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L)
+{
+  if (int rc = ptau_header(data, len, secs, L)) return rc;
   for (int id : {4, 5, 6})
     if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
   if (L->sec[4]->size < 64 || L->sec[5]->size < 64 || L->sec[6]->size < 128) return fail(ERR_FORMAT, "ptau: section 4, 5 or 6 is shorter than one point");
@@ -197,6 +204,30 @@ int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Pta
   for (int id = 12; id < 16; id++)
     if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
   return 0;
+}
+
+// sections and header of an UNPREPARED .ptau, what a ceremony ends with: sections 2 … 7 once each with exactly the element counts
+// of the layout, none of 12 … 15
+int ptau_unprepared_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L)
+{
+  if (int rc = ptau_header(data, len, secs, L)) return rc;
+  for (int id = 12; id < 16; id++) // (read_sections makes room for the ids below 16)
+    if (secs[(size_t)id].count) return fail(ERR_FORMAT, "ptau: section %d is present: the file is already prepared for phase 2", id);
+  for (int id : {2, 3, 4, 5, 6, 7})
+    if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
+  const uint64_t N = (uint64_t)1 << L->power;
+  const uint64_t want[7] = {0, 0, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128};
+  for (int id = 2; id <= 6; id++)
+    if (L->sec[id]->size != want[id])
+      return fail(ERR_FORMAT, "ptau: section %d holds %llu bytes, an unprepared file of power %u has %llu", id, (unsigned long long)L->sec[id]->size, L->power,
+                  (unsigned long long)want[id]);
+  return 0;
+}
+
+uint64_t ptau_prepared_section_bytes(uint32_t power, int sid)
+{
+  const uint64_t N = (uint64_t)1 << power;
+  return sid == 12 ? (4 * N - 1) * 64 : (2 * N - 1) * (sid == 13 ? 128 : 64);
 }
 
 int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out)
@@ -311,5 +342,19 @@ __attribute__((visibility("default"))) int groth16_zkey_new_size(const void* r1c
   const uint64_t payload = 4 + (4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128) + 64 * (npub + 1) + (4 + COEF_RECORD_BYTES * *n_coeffs) + 64 * m + 64 * m + 128 * m +
                            64 * (m - npub - 1) + 64 * n + 4;
   *zkey_bytes = 12 + 10 * 12 + payload;
+  return 0;
+}
+
+// host only: never initialises a GPU.  The size of groth16_ptau_prepare's file (ptau_prepare.hip).
+__attribute__((visibility("default"))) int groth16_ptau_prepared_size(const void* ptau, size_t len, uint64_t* ptau_bytes)
+{
+  if (!ptau_bytes) return fail(ERR_ARG, "null output");
+  *ptau_bytes = 0;
+  std::vector<Section> secs;
+  PtauLayout L;
+  if (int rc = ptau_unprepared_layout((const uint8_t*)ptau, len, secs, &L)) return rc;
+  uint64_t total = len;
+  for (int sid = 12; sid < 16; sid++) total += 12 + ptau_prepared_section_bytes(L.power, sid);
+  *ptau_bytes = total;
   return 0;
 }

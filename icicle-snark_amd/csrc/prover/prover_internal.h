@@ -126,6 +126,11 @@ struct PtauLayout {
   const Section* sec[16] = {};
 };
 int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L);
+// An UNPREPARED .ptau, what groth16_ptau_prepare takes: the same container and section 1; sections 2 … 7 once each — [τ^i]₁ for
+// i < 2^(power+1) − 1, [τ^i]₂, [α·τ^i]₁ and [β·τ^i]₁ for i < 2^power, [β]₂, the contributions — with exactly these element counts; a
+// file that has one of 12 … 15 is refused with a message of its own.  ptau_prepared_section_bytes: what prepare writes for 12 … 15.
+int ptau_unprepared_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L);
+uint64_t ptau_prepared_section_bytes(uint32_t power, int sid);
 // block p of section sid (elements of elem_bytes): its first byte, after checking that it lies inside the section
 int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out);
 // the blocks a verify of a key with domain 2^k reads — block k of 12 … 15 and block k + 1 of 12 — lie inside their sections

@@ -526,6 +526,57 @@ typedef struct {
 int groth16_zkey_contributions(const void* zkey, size_t len, Groth16ContributionsReport* report, Groth16ContributionInfo* infos,
                                size_t infos_cap);
 
+/* groth16_ptau_prepare — sections 12 to 15 of a powers-of-tau file from its sections 2 to 5, on the GPU: what `snarkjs powersoftau
+ * prepare phase2` makes, the first link of ptau-prepare -> zkey-new -> zkey-contribute -> zkey-verify -> prove -> verify.  Opt-in.
+ * THE INPUT is an UNPREPARED file, what a ceremony ends with: magic "ptau", version 1; section 1 = {n8 = 32, q, power <= 28,
+ * ceremonyPower}; section 2 = [tau^i]1 for i < 2^(power+1) - 1; sections 3, 4, 5 = [tau^i]2, [alpha*tau^i]1, [beta*tau^i]1 for
+ * i < 2^power; section 6 = [beta]2; section 7 = the contributions (not read) — each once, with exactly these element counts (-2
+ * naming the section and both sizes otherwise).  A file that has one of 12 to 15 is -2 with a text of its own ("already prepared").
+ * THE OUTPUT is the input byte for byte — sections 1 to 7 and whatever else it holds — with the header's section count four
+ * higher and sections 12, 13, 14, 15 appended in this order.  Points stay uncompressed, affine, Montgomery form, the identity all
+ * zero; affine bytes are canonical, so the output is a function of the input alone.
+ * DEFINITION.  w_p = the root of unity of order 2^p that bn254_get_root_of_unity(2^p) returns.  Block p of a section begins at
+ * element 2^p - 1 and its element j < 2^p is
+ *     (1/2^p) * sum_{i < 2^p} w_p^(-i*j) * S_i
+ * with S_i element i of the source section: 2 -> 12, 3 -> 13, 4 -> 14, 5 -> 15.  Blocks run p = 0 ... power; section 12 has one
+ * more, p = power + 1.  For the sources as above this is [L_j(tau)]1, [L_j(tau)]2, [alpha*L_j(tau)]1, [beta*L_j(tau)]1 of the
+ * size-2^p domain, what groth16_ptau_info describes.
+ * SECTION 12's LAST BLOCK.  Section 2 holds 2^(power+1) - 1 powers, one fewer than that block's transform takes: its last input
+ * S_(2N-1), N = 2^power, is THE IDENTITY — the transform of the zero-extended vector, which is what snarkjs does.  With L'_j the
+ * Lagrange basis of the size-2N domain and w' = w_(power+1) the block therefore holds
+ *     L'_j(tau) - tau^(2N-1) * w'^(-j*(2N-1)) / (2N)      and not L'_j(tau),
+ * which a writer that knows tau (this library's test synthesiser) puts there.  Both give valid keys: the block is only read for a
+ * circuit whose domain is 2^power, as the H basis [L'_(2i+1)]1; the quotient polynomial has degree <= 2N - 2, its coefficient of
+ * x^(2N-1) is zero, and sum_j p(w'^j) * block_j = p(tau) for every p of degree <= 2N - 2.  groth16_zkey_verify_ptau compares H
+ * against whatever block the file holds.  A power of 28 is -3: that block would need a root of order 2^29.
+ * Every point of sections 2 to 5 passes the key check's lane test before any arithmetic sees it (coordinates < q, on the curve,
+ * section 3 in the subgroup; section 6 on the host); a point that fails is -2 with a text naming section, element and kind, the
+ * report says the same, *out_len is 0 and the _file entry leaves no file.  Sections are tested as they are reached: the caller's
+ * buffer may by then hold earlier sections; nothing of it is valid unless the call returns 1.
+ * The transform runs block by block, section by section, decimation in time with affine points between the levels: one lane per
+ * butterfly, T = w*Q by a signed-digit walk with a twiddle per lane, then P + T and P - T; every degenerate case (an identity
+ * input, T = +-P, w = 1) is exact.  One path for every level: there is no switch point between kernels, so no such argument.
+ * groth16_ptau_prepared_size is the host half: the output's size from the input's container alone.  Never initialises a GPU.
+ * What it does NOT do: verify the file's own contribution chain (`powersoftau verify`), apply phase-1 contributions or beacons,
+ * use more than one GPU.  No file written by snarkjs exists offline: reader and writer share the layout stated here.
+ * 1 prepared; -1 I/O; -2 format; -3 argument: cap too small (report->ptau_bytes says what is needed, nothing is written), power 28,
+ * equal paths, a device string that does not name one HIP device; -5 device failure (groth16_last_error).  The _file variant maps
+ * the input, writes a temporary beside out_path and renames it: a failed call leaves nothing.  The calling thread's device is what
+ * it was afterwards.  ICICLE_SNARK_TRACE_PTAU_PREPARE=1 prints the stage times on stderr. */
+typedef struct {
+  uint32_t power;
+  uint64_t points[4];           /* points of sections 12, 13, 14, 15 */
+  uint64_t ptau_bytes;          /* the output (also when cap was too small) */
+  int32_t  fault_section, fault_kind;   /* after a faulty point: 2 to 6, and GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP */
+  uint64_t fault_index;                 /* the lowest faulty element of that section */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the sources' and the twiddles' copies up; wall time of the device part
+                                   without the downloads; the blocks' copies into the buffer or the mapped file; msync and rename (_file) */
+} Groth16PtauPrepareReport;
+int groth16_ptau_prepared_size(const void* ptau, size_t len, uint64_t* ptau_bytes);
+int groth16_ptau_prepare(const void* ptau, size_t len, void* out, size_t cap, uint64_t* out_len, const char* device,
+                         Groth16PtauPrepareReport* report);
+int groth16_ptau_prepare_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPrepareReport* report);
+
 #ifdef __cplusplus
 }
 #endif
