@@ -705,6 +705,8 @@ groth16_ptau_info groth16_zkey_verify_ptau groth16_zkey_verify_ptau_file
 groth16_zkey_new_size groth16_zkey_new groth16_zkey_new_file
 groth16_zkey_contribute groth16_zkey_contribute_file groth16_zkey_contributions
 groth16_ptau_prepared_size groth16_ptau_prepare groth16_ptau_prepare_file
+groth16_ptau_new_size groth16_ptau_new groth16_ptau_new_file
+groth16_ptau_contribute groth16_ptau_contribute_file groth16_ptau_contributions
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1190,6 +1192,95 @@ def ptau_prepare(ptau, out=None, device: str = "HIP"):
     if rc != 1:
         _pcheck(rc, "ptau_prepare")
     return buf.raw[:got.value], rep
+
+
+class PtauContributeOptions(C.Structure):
+    _fields_ = [("fixed_tau", C.POINTER(C.c_uint8)), ("fixed_alpha", C.POINTER(C.c_uint8)), ("fixed_beta", C.POINTER(C.c_uint8))]
+
+
+class PtauContributeReport(C.Structure):
+    """Groth16PtauContributeReport: the record's number, the power, the points of sections 2 to 5, the output's size, the first
+    faulty point (section, kind, element), the stage times"""
+    _fields_ = [("contribution", C.c_uint32), ("power", C.c_uint32), ("points", C.c_uint64 * 4), ("ptau_bytes", C.c_uint64),
+                ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
+class PtauContributionsReport(C.Structure):
+    """Groth16PtauContributionsReport: the record count, kind (CONTRIB_*) and index (records count from 1) of the first fault;
+    .records: (tau1, alpha1, beta1, tau2, beta2, name) bytes of the records whose bounds hold"""
+    _fields_ = [("count", C.c_uint32), ("kind", C.c_int32), ("index", C.c_uint32)]
+    records = ()
+
+
+class PtauContributionInfo(C.Structure):
+    _fields_ = [("tau1", C.c_uint8 * 64), ("alpha1", C.c_uint8 * 64), ("beta1", C.c_uint8 * 64), ("tau2", C.c_uint8 * 128), ("beta2", C.c_uint8 * 128),
+                ("name", C.c_char * 256)]
+
+
+def ptau_new_size(power: int) -> int:
+    """groth16_ptau_new_size: the bytes of ptau_new's file; host only.  Raises ProverError −3 for a power above 27."""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_ptau_new_size(C.c_uint32(power), C.byref(size)), "ptau_new_size")
+    return size.value
+
+
+def ptau_new(power: int, out=None):
+    """groth16_ptau_new → bytes | None: the starting file of a powers-of-tau ceremony, tau = alpha = beta = 1 (every point a
+    generator, section 7 with no record).  Host only: needs no GPU.  out: a path to write the file to (None comes back)."""
+    if out is not None:
+        _pcheck(lib().groth16_ptau_new_file(C.c_uint32(power), os.fsencode(out)), "ptau_new_file")
+        return None
+    size = ptau_new_size(power)
+    buf, got = C.create_string_buffer(size), C.c_uint64()
+    _pcheck(lib().groth16_ptau_new(C.c_uint32(power), buf, C.c_size_t(size), C.byref(got)), "ptau_new")
+    return buf.raw[:got.value]
+
+
+def ptau_contribute(ptau, secret=None, name="", out=None, device: str = "HIP", tau=None, alpha=None, beta=None):
+    """groth16_ptau_contribute → (ptau bytes | None, PtauContributeReport): one participant's secrets applied on the GPU to every
+    point of sections 2 to 6 of an UNPREPARED powers-of-tau file, one record appended to section 7 (this library's own layout:
+    include/groth16_prover.h).  ptau: the image, and the new file comes back as bytes; or a path together with `out`, the path the
+    new file is written to (None comes back).  secret: 32 bytes, None draws from the operating system.  name: str or bytes, at
+    most 255 bytes.  tau, alpha, beta: the secrets themselves as integers in [1, r), for tests and reproducible runs.  Raises
+    ProverError (−2 a faulty point, a prepared file, a malformed or stale section 7; −3 a name too long or a bad fixed secret)."""
+    if secret is not None and len(secret) != 32:
+        raise ValueError("ptau_contribute: the secret is 32 bytes")
+    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(secret)) if secret is not None else None
+    fixed = [(C.c_uint8 * 32).from_buffer_copy(int(v).to_bytes(32, "little")) if v is not None else None for v in (tau, alpha, beta)]
+    opt = PtauContributeOptions(*[C.cast(f, C.POINTER(C.c_uint8)) if f is not None else None for f in fixed])
+    rep = PtauContributeReport()
+    nm = name.encode() if isinstance(name, str) else bytes(name)
+    if isinstance(ptau, (str, os.PathLike)):
+        if out is None:
+            raise TypeError("ptau_contribute: a ptau path needs the path to write the new file to")
+        _pcheck(lib().groth16_ptau_contribute_file(os.fsencode(ptau), os.fsencode(out), sd, nm, device.encode(), C.byref(opt), C.byref(rep)), "ptau_contribute_file")
+        return None, rep
+    if out is not None:
+        raise TypeError("ptau_contribute: `out` goes with a ptau path")
+    # sized by the library itself: a first call with no room reports the bytes it needs, before any device work
+    rc = lib().groth16_ptau_contribute(_image(ptau), C.c_size_t(len(ptau)), sd, nm, None, C.c_size_t(0), device.encode(), C.byref(opt), C.byref(rep))
+    if rc != -3 or rep.ptau_bytes == 0:
+        _pcheck(rc, "ptau_contribute")
+    buf = C.create_string_buffer(rep.ptau_bytes)
+    _pcheck(lib().groth16_ptau_contribute(_image(ptau), C.c_size_t(len(ptau)), sd, nm, buf, C.c_size_t(rep.ptau_bytes), device.encode(), C.byref(opt), C.byref(rep)), "ptau_contribute")
+    return buf.raw, rep
+
+
+def ptau_contributions(ptau):
+    """groth16_ptau_contributions → (ok, PtauContributionsReport with .records): is section 7 a chain of valid contributions from
+    the generators to what sections 2 to 6 hold at their first elements, and do the G1 and G2 sides pair?  Host only: needs no
+    GPU.  It does NOT show that the other powers of the file follow."""
+    rep = PtauContributionsReport()
+    cap = min(len(ptau) // 740 + 1, 4096)   # a record is at least 740 bytes; .records holds the first 4096
+    infos = (PtauContributionInfo * cap)()
+    rc = lib().groth16_ptau_contributions(_image(ptau), C.c_size_t(len(ptau)), C.byref(rep), infos, C.c_size_t(cap))
+    if rc not in (0, 1):
+        _pcheck(rc, "ptau_contributions")
+    held = rep.count if rep.kind != CONTRIB_SECTION else max(int(rep.index) - 1, 0)
+    rep.records = [(bytes(infos[i].tau1), bytes(infos[i].alpha1), bytes(infos[i].beta1), bytes(infos[i].tau2), bytes(infos[i].beta2), infos[i].name)
+                   for i in range(min(held, cap))]
+    return rc == 1, rep
 
 
 def sum_commitments(blocks: bytes, count: int) -> bytes:

@@ -19,6 +19,11 @@
 //     one line per record, then CHAIN_OK or CHAIN_BAD <kind> <index>.  It does not show that C and H follow delta2: zkey-verify does
 //   > ptau-prepare --ptau IN --out OUT [--device HIP]    sections 12 to 15 of a powers-of-tau file made from its sections 2 to 5
 //     (groth16_ptau_prepare_file, snarkjs' `powersoftau prepare phase2`): one summary line, then PTAU_WRITTEN
+//   > ptau-new --power P --out OUT            the starting file of a ceremony, tau = alpha = beta = 1 (groth16_ptau_new_file): PTAU_WRITTEN
+//   > ptau-contribute --ptau IN --out OUT [--name N] [--device HIP]    one phase-1 contribution with secrets from the operating system
+//     (groth16_ptau_contribute_file): one summary line, then PTAU_WRITTEN
+//   > ptau-contributions --ptau P             section 7's chain against the file's first elements, on the host (groth16_ptau_contributions):
+//     one line per record, then CHAIN_OK or CHAIN_BAD <kind> <index>.  It does not show that the other powers follow
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -29,7 +34,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is not shown)\n  exit\n";
 }
 
 int main()
@@ -412,6 +417,68 @@ int main()
         std::cout << "power " << rep.power << " points " << rep.points[0] << " " << rep.points[1] << " " << rep.points[2] << " " << rep.points[3] << " bytes " << rep.ptau_bytes
                   << "; upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
         std::cout << "PTAU_WRITTEN" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-new") {
+      std::string out = "pot_0000.ptau", a;
+      long power = -1;
+      while (in >> a) {
+        if (a == "--power") in >> power;
+        else if (a == "--out") in >> out;
+        else print_help();
+      }
+      const int rc = power < 0 || power > 64 ? -3 : groth16_ptau_new_file((uint32_t)power, out.c_str());
+      if (rc < 0) std::cerr << "ptau-new failed (" << rc << "): " << (power < 0 || power > 64 ? "--power <P> is required, 0 to 27" : groth16_last_error()) << std::endl;
+      else std::cout << "PTAU_WRITTEN" << std::endl;
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-contribute") {
+      // the secrets are the operating system's: none is taken from a command line
+      std::string ptau = "pot_0000.ptau", out = "pot_0001.ptau", name, device = "HIP", a;
+      while (in >> a) {
+        if (a == "--ptau") in >> ptau;
+        else if (a == "--out") in >> out;
+        else if (a == "--name") in >> name;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16PtauContributeReport rep;
+      const int rc = groth16_ptau_contribute_file(ptau.c_str(), out.c_str(), nullptr, name.c_str(), device.c_str(), nullptr, &rep);
+      if (rc < 0) {
+        std::cerr << "ptau-contribute failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        std::cout << "contribution " << rep.contribution << " power " << rep.power << " points " << rep.points[0] << " " << rep.points[1] << " " << rep.points[2] << " " << rep.points[3]
+                  << " bytes " << rep.ptau_bytes << "; upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms
+                  << " ms" << std::endl;
+        std::cout << "PTAU_WRITTEN" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-contributions") {
+      // the chain of section 7 against the file's first elements, on the host; that the other powers follow is another question
+      std::string ptau = "pot_final.ptau", a;
+      while (in >> a) {
+        if (a == "--ptau") in >> ptau;
+        else print_help();
+      }
+      std::ifstream f(ptau, std::ios::binary);
+      std::ostringstream ss;
+      if (f) ss << f.rdbuf();
+      const std::string image = ss.str();
+      Groth16PtauContributionsReport rep;
+      std::vector<Groth16PtauContributionInfo> infos(1024); // the records that are listed; the verdict is over all of them
+      const int rc = f ? groth16_ptau_contributions(image.data(), image.size(), &rep, infos.data(), infos.size()) : -1;
+      if (rc < 0) {
+        std::cerr << "ptau-contributions failed (" << rc << "): " << (f ? groth16_last_error() : "cannot read the ptau") << std::endl;
+      } else {
+        static const char* const kinds[6] = {"", "SECTION", "POINT", "POK", "HEADER", "PAIR"};
+        const uint32_t held = rep.kind == GROTH16_CONTRIB_SECTION ? (rep.index ? rep.index - 1 : 0) : rep.count;
+        for (uint32_t i = 0; i < held && i < infos.size(); i++) {
+          static const char hex[] = "0123456789abcdef";
+          std::string d;
+          for (int k = 0; k < 8; k++) d += {hex[infos[i].tau1[k] >> 4], hex[infos[i].tau1[k] & 15]};
+          std::cout << "contribution " << i + 1 << " name \"" << infos[i].name << "\" tau1 " << d << "..." << std::endl;
+        }
+        if (rc == 1) std::cout << "CHAIN_OK" << std::endl;
+        else std::cout << "CHAIN_BAD " << kinds[rep.kind >= 1 && rep.kind <= 5 ? rep.kind : 0] << " " << rep.index << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

@@ -577,6 +577,110 @@ int groth16_ptau_prepare(const void* ptau, size_t len, void* out, size_t cap, ui
                          Groth16PtauPrepareReport* report);
 int groth16_ptau_prepare_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPrepareReport* report);
 
+/* groth16_ptau_new, groth16_ptau_contribute, groth16_ptau_contributions — start a powers-of-tau ceremony, extend it by one
+ * participant on the GPU, and audit its record chain on the host: the links before groth16_ptau_prepare.  Opt-in.
+ * groth16_ptau_new writes the UNPREPARED file of tau = alpha = beta = 1 (the layout groth16_ptau_prepare states): section 1 with
+ * power = ceremonyPower = `power`, 2^(power+1) - 1 copies of G1 as section 2, 2^power copies of G2 as 3, 2^power copies of G1 as 4
+ * and as 5, G2 as 6, and a zero count as section 7.  Host only: never initialises a GPU.  groth16_ptau_new_size is its size.  A
+ * power above 27 is -3 (groth16_ptau_prepare's own limit); cap is tested before anything is written (-3, *out_len = the bytes needed).
+ * A CONTRIBUTION of the secrets tau', alpha', beta' in [1, r) to an unprepared file of N = 2^power:
+ *   2        P_i <- tau'^i * P_i, i < 2N - 1         3 (G2)   P_i <- tau'^i * P_i, i < N
+ *   4        P_i <- alpha' * tau'^i * P_i, i < N     5        P_i <- beta' * tau'^i * P_i, i < N
+ *   6        beta' * P (on the host)                 7        one record appended
+ * Section 1 and any unknown section stay byte for byte; sections keep the input's order.  Points leave in the file's form — affine,
+ * canonical Montgomery bytes, the identity all zero — so the result is a function of (file, tau', alpha', beta') alone: a file of
+ * (tau, alpha, beta) becomes the file of (tau*tau', alpha*alpha', beta*beta').  A prepared file (one of sections 12 to 15) is -2
+ * with the unprepared reader's text: contribute first, prepare last.
+ * Every point of sections 2 to 5 goes up and through the lane tests (coordinates < q, on the curve, section 3 in the subgroup;
+ * section 6 on the host) and every verdict is read before the first scale kernel is launched: a fault is -2 "ptau: section S,
+ * element E: kind" naming the lowest faulty element of the first faulty section (6 first), the report says the same, nothing is
+ * written.  Then one launch per section, a lane per point: the lane's scalar s = c * tau'^i (c = 1, 1, alpha', beta') is computed
+ * ON THE DEVICE from two small tables the host uploads, lo[j] = tau'^j (j < 2^k) and hi_c[m] = c * tau'^(m * 2^k), k = (power + 2)/2,
+ * as hi_c[i >> k] * lo[i mod 2^k]; then its non-adjacent form and a signed-digit walk of 256 steps.  No table of 2N powers exists.
+ * SECTION 7 — THIS LIBRARY'S OWN LAYOUT, as section 10 of a key contributed here is and for the same reason: snarkjs' record needs
+ * BLAKE2b and its hash-to-G2.  What is written is instead: u32 count, then count records of
+ *   tau1 64 B, alpha1 64 B, beta1 64 B, tau2 128 B, beta2 128 B    [tau]1 [alpha]1 [beta]1 [tau]2 [beta]2 AFTER this contribution
+ *   R_tau 64 B, R_alpha 64 B, R_beta 64 B                          the commitments k_x * before.x1
+ *   z_tau 32 B, z_alpha 32 B, z_beta 32 B                          the responses, standard form little-endian, < r
+ *   name_len u32 <= 255, name
+ * (points affine, Montgomery form) with TAG = "icicle-snark ptau contribution v1" (ASCII, no terminator); `before` of record 1 =
+ * (G1, G1, G1), of record i = record i-1's (tau1, alpha1, beta1); h_0 = SHA-256(TAG || section 1's payload); e_i = SHA-256(h_{i-1}
+ * || before's three points || the five after points || R_tau || R_alpha || R_beta || name_len || name), h_i = e_i; the challenge
+ * c_i = the first 16 bytes of e_i, little-endian, 0 replaced by 1.  One challenge serves three Schnorr proofs with independent
+ * nonces: z_x = k_x + c * x' mod r, checked as z_x * before.x1 = R_x + c * after.x1 for x in {tau, alpha, beta}.  The after points
+ * are x' times what the FILE holds (section 2 element 1, section 3 element 1, section 4 element 0, section 5 element 0, section 6;
+ * at power 0, which holds no power of tau, the last record's tau1 and tau2 or the generators), so a chain over a file that did not
+ * start at groth16_ptau_new's fails the audit at record 1.  A FILE CONTRIBUTED HERE CONTINUES ITS CEREMONY HERE: snarkjs reads
+ * sections 1 to 6 and 12 to 15 to build keys, which are what they would be, but its `powersoftau verify` and `contribute` do not
+ * read this section 7.
+ * SECRETS, from the caller's 32 bytes (secret32 = NULL: the operating system's), with groth16_zkey_contribute's W: x' = W(secret ||
+ * TAG || label_x), one-byte labels 1, 2, 3 for tau, alpha, beta, unless opt->fixed_tau / fixed_alpha / fixed_beta (32 bytes,
+ * standard form little-endian, 0 < . < r: for tests and reproducible runs) gives it; k_x = W(secret || x' as 32 B LE || h_{i-1} ||
+ * before.x1 || label_x).  A zero secret or nonce is -3.  The host copies live in one struct that is wiped (explicit_bzero) on every
+ * way out, and the device tables are overwritten before they are freed — BEST EFFORT: the compiler may keep copies, the lanes'
+ * scalars live in registers and scratch of the device, and a kernel's duration depends on their digits.
+ * The output's size is known before any device work: the input plus the record (740 + name bytes).  cap is tested first; a short
+ * cap is -3 with report->ptau_bytes set and nothing written.  A section 7 that is malformed, or whose last record is not what the
+ * file holds (the HEADER rule below), is -2; earlier proofs are not re-run.
+ * 0 done; -1 I/O; -2 format; -3 argument: a name over 255 bytes, a bad fixed secret, cap too small, equal paths (by name or by
+ * inode), a device string that does not name one HIP device; -5 device failure (groth16_last_error).  The _file variants write a
+ * temporary beside out_path and rename it: a failed call leaves nothing.  The calling thread's device is what it was afterwards.
+ * ICICLE_SNARK_TRACE_PTAU_CONTRIBUTE=1 prints the stage times on stderr.
+ * What none of this does: check that a file's powers are CONSISTENT WITH ONE ANOTHER (`powersoftau verify`'s same-ratio test over
+ * all points) — the audit ties the records to element 1 and element 0 of the sections and to section 6, NOT the other 2N - 2
+ * powers; apply a beacon; read or write snarkjs' record format; use more than one GPU; decompose the scalars (GLV). */
+int groth16_ptau_new_size(uint32_t power, uint64_t* ptau_bytes);
+int groth16_ptau_new(uint32_t power, void* out, size_t cap, uint64_t* out_len);
+int groth16_ptau_new_file(uint32_t power, const char* out_path);
+typedef struct {
+  const uint8_t* fixed_tau;     /* NULL, or tau' itself: 32 bytes, standard form little-endian, 0 < tau' < r */
+  const uint8_t* fixed_alpha;   /* the same for alpha' */
+  const uint8_t* fixed_beta;    /* the same for beta' */
+} Groth16PtauContributeOptions;
+typedef struct {
+  uint32_t contribution;        /* this record's number: 1 for the first */
+  uint32_t power;
+  uint64_t points[4];           /* points of sections 2, 3, 4, 5 */
+  uint64_t ptau_bytes;          /* the output (also when cap was too small) */
+  int32_t  fault_section, fault_kind;   /* after a faulty point: 2 to 6, and GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP */
+  uint64_t fault_index;                 /* the lowest faulty element of that section */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the sections' and the tables' copies up; wall time of the device part up
+                                   to the last kernel; the copies into the buffer or the mapped file; msync and rename (_file) */
+} Groth16PtauContributeReport;
+int groth16_ptau_contribute(const void* ptau, size_t len, const uint8_t* secret32 /* NULL = OS randomness */, const char* name,
+                            void* out, size_t cap, const char* device, const Groth16PtauContributeOptions* opt,
+                            Groth16PtauContributeReport* report);
+int groth16_ptau_contribute_file(const char* in_path, const char* out_path, const uint8_t* secret32, const char* name,
+                                 const char* device, const Groth16PtauContributeOptions* opt, Groth16PtauContributeReport* report);
+
+/* groth16_ptau_contributions — is section 7 of an unprepared file a chain of valid contributions that ends in what the file holds?
+ * Host only: never initialises a GPU.  The kinds are GROTH16_CONTRIB_*, tested in THIS order, the first fault reported:
+ *   SECTION  the count or a record does not fit the section; index = the record, 0 for the count
+ *   then record by record (index = the record, 1 for the first):
+ *   POINT    one of a record's eight points has a coordinate >= q or is off the curve, tau2 or beta2 is outside the subgroup, or
+ *            one of the five after points is the identity
+ *   POK      a z >= r, or one of the three equations fails
+ *   PAIR     e(tau1, G2) != e(G1, tau2), or e(beta1, G2) != e(G1, beta2)
+ *   and at the end
+ *   HEADER   (index 0) the last record's alpha1, beta1, beta2 are not section 4 element 0, section 5 element 0 and section 6, or —
+ *            at power >= 1 — its tau1 and tau2 are not element 1 of sections 2 and 3 (at power 0 the file holds no power of tau:
+ *            only the pairing ties tau1 to tau2); with count = 0 the generators are compared against those same elements.
+ * What it does NOT show: THAT THE OTHER 2N - 2 POWERS FOLLOW — that every point of sections 2 to 5 really was scaled by the power
+ * it should have been.  That is a same-ratio test over all points, a future ptau-verify.
+ * 1 the chain holds, 0 not (report says where), < 0 an error (-2: the container is malformed, or the file is prepared). */
+typedef struct {
+  uint32_t count;            /* records in section 7 (0 after a SECTION fault of the count) */
+  int32_t  kind;             /* 0 = the chain holds, else the kind of the FIRST fault */
+  uint32_t index;            /* the record at fault, 1 for the first; 0 for HEADER and the count */
+} Groth16PtauContributionsReport;
+typedef struct {
+  uint8_t tau1[64], alpha1[64], beta1[64], tau2[128], beta2[128];   /* as the record holds them */
+  char    name[256];                                                /* zero-terminated */
+} Groth16PtauContributionInfo;
+/* infos (may be NULL) receives the points and the name of the first min(count, infos_cap) records whose bounds hold. */
+int groth16_ptau_contributions(const void* ptau, size_t len, Groth16PtauContributionsReport* report,
+                               Groth16PtauContributionInfo* infos, size_t infos_cap);
+
 #ifdef __cplusplus
 }
 #endif
