@@ -707,6 +707,7 @@ groth16_zkey_contribute groth16_zkey_contribute_file groth16_zkey_contributions
 groth16_ptau_prepared_size groth16_ptau_prepare groth16_ptau_prepare_file
 groth16_ptau_new_size groth16_ptau_new groth16_ptau_new_file
 groth16_ptau_contribute groth16_ptau_contribute_file groth16_ptau_contributions
+groth16_ptau_verify groth16_ptau_verify_file
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1280,6 +1281,46 @@ def ptau_contributions(ptau):
     held = rep.count if rep.kind != CONTRIB_SECTION else max(int(rep.index) - 1, 0)
     rep.records = [(bytes(infos[i].tau1), bytes(infos[i].alpha1), bytes(infos[i].beta1), bytes(infos[i].tau2), bytes(infos[i].beta2), infos[i].name)
                    for i in range(min(held, cap))]
+    return rc == 1, rep
+
+
+PTAU_VERIFY_KINDS = ("", "GENERATORS", "TAU_PAIR", "BETA_PAIR", "TAU_G1", "TAU_G2", "ALPHA_TAU", "BETA_TAU", "LAGRANGE_12", "LAGRANGE_13", "LAGRANGE_14",
+                     "LAGRANGE_15", "POINT", "IDENTITY")
+
+
+class PtauVerifyReport(C.Structure):
+    """Groth16PtauVerifyReport: the power, whether sections 12 to 15 were there, the first failing kind, one bit per failing equation
+    (bit kind − 1), the faulty point of POINT / IDENTITY (section, kind, lowest element), the points of sections 2 to 5 and 12 to 15,
+    the stage times.  .kind_name and .failed: the kinds by name"""
+    _fields_ = [("power", C.c_uint32), ("prepared", C.c_int32), ("kind", C.c_int32), ("failed_mask", C.c_uint32),
+                ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64), ("points", C.c_uint64 * 8),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("pairing_ms", C.c_double)]
+
+    @property
+    def kind_name(self):
+        return PTAU_VERIFY_KINDS[self.kind] if 0 <= self.kind < len(PTAU_VERIFY_KINDS) else str(self.kind)
+
+    @property
+    def failed(self):
+        return [PTAU_VERIFY_KINDS[k] for k in range(1, 12) if self.failed_mask >> (k - 1) & 1]
+
+
+def ptau_verify(ptau, seed=None, device: str = "HIP"):
+    """groth16_ptau_verify → (ok, PtauVerifyReport): are sections 2 to 6 of a powers-of-tau file the powers of one (tau, alpha, beta)
+    and, when the file is prepared, sections 12 to 15 the transforms groth16_ptau_prepare writes?  ptau: the image, or a path that
+    is mapped.  seed: 32 bytes for a reproducible run; None draws from the operating system, which is what soundness needs.  A
+    faulty point or an identity in sections 2 to 6 is a verdict (ok False, kind POINT / IDENTITY), not an error.  It does NOT say who
+    contributed: ptau_contributions does.  Raises ProverError (−2 a malformed container, −3 a power above 27)."""
+    if seed is not None and len(seed) != 32:
+        raise ValueError("ptau_verify: the seed is 32 bytes")
+    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+    rep = PtauVerifyReport()
+    if isinstance(ptau, (str, os.PathLike)):
+        rc, what = lib().groth16_ptau_verify_file(os.fsencode(ptau), sd, device.encode(), C.byref(rep)), "ptau_verify_file"
+    else:
+        rc, what = lib().groth16_ptau_verify(_image(ptau), C.c_size_t(len(ptau)), sd, device.encode(), C.byref(rep)), "ptau_verify"
+    if rc not in (0, 1):
+        _pcheck(rc, what)
     return rc == 1, rep
 
 

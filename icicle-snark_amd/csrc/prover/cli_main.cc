@@ -23,7 +23,10 @@
 //   > ptau-contribute --ptau IN --out OUT [--name N] [--device HIP]    one phase-1 contribution with secrets from the operating system
 //     (groth16_ptau_contribute_file): one summary line, then PTAU_WRITTEN
 //   > ptau-contributions --ptau P             section 7's chain against the file's first elements, on the host (groth16_ptau_contributions):
-//     one line per record, then CHAIN_OK or CHAIN_BAD <kind> <index>.  It does not show that the other powers follow
+//     one line per record, then CHAIN_OK or CHAIN_BAD <kind> <index>.  It does not show that the other powers follow: ptau-verify does
+//   > ptau-verify --ptau P [--device HIP]     ptau-contributions (an unprepared file), then the powers of sections 2 to 6 against one
+//     another and sections 12 to 15 against them (groth16_ptau_verify_file): one line per question, then PTAU_OK or
+//     PTAU_BAD <kind> [<section> <element>]
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -34,7 +37,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is not shown)\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  exit\n";
 }
 
 int main()
@@ -479,6 +482,53 @@ int main()
         }
         if (rc == 1) std::cout << "CHAIN_OK" << std::endl;
         else std::cout << "CHAIN_BAD " << kinds[rep.kind >= 1 && rep.kind <= 5 ? rep.kind : 0] << " " << rep.index << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-verify") {
+      // the audit first, as zkey-verify runs r1cs-match: who contributed, then whether the points are what they should be
+      std::string ptau = "pot_final.ptau", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--ptau") in >> ptau;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      static const char* const kinds[14] = {"", "GENERATORS", "TAU_PAIR", "BETA_PAIR", "TAU_G1", "TAU_G2", "ALPHA_TAU", "BETA_TAU", "LAGRANGE_12", "LAGRANGE_13", "LAGRANGE_14",
+                                            "LAGRANGE_15", "POINT", "IDENTITY"};
+      Groth16PtauVerifyReport rep;
+      const int rc = groth16_ptau_verify_file(ptau.c_str(), nullptr, device.c_str(), &rep);
+      if (rc < 0) {
+        std::cerr << "ptau-verify failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        // the chain of section 7: the audit reads an unprepared file; for a prepared one it is said, not skipped silently
+        int chain = -1;
+        if (!rep.prepared) {
+          std::ifstream f(ptau, std::ios::binary);
+          std::ostringstream ss;
+          if (f) ss << f.rdbuf();
+          const std::string image = ss.str();
+          Groth16PtauContributionsReport crep = {};
+          chain = f ? groth16_ptau_contributions(image.data(), image.size(), &crep, nullptr, 0) : -1;
+          std::cout << "contributions: " << (chain == 1 ? "the chain holds" : chain == 0 ? "the chain does NOT hold" : "not read") << ", " << crep.count << " records" << std::endl;
+        } else {
+          std::cout << "contributions: not audited (groth16_ptau_contributions reads the unprepared file)" << std::endl;
+        }
+        const uint32_t powers_mask = rep.failed_mask & 0x7f, lagrange_mask = rep.failed_mask >> 7;
+        const bool point = rep.kind == GROTH16_PTAU_VERIFY_POINT || rep.kind == GROTH16_PTAU_VERIFY_IDENTITY;
+        auto names = [&](uint32_t mask, int first) {
+          std::string out;
+          for (int b = 0; b < 11; b++)
+            if (mask >> b & 1) out += std::string(" ") + kinds[first + b];
+          return out;
+        };
+        std::cout << "power " << rep.power << ", sections 2 to 6 are the powers of one (tau, alpha, beta): "
+                  << (point ? "not decided" : powers_mask ? "NO:" + names(powers_mask, 1) : std::string("yes")) << std::endl;
+        if (rep.prepared)
+          std::cout << "sections 12 to 15 are the transforms of 2 to 5: " << (point ? "not decided" : lagrange_mask ? "NO:" + names(lagrange_mask, 8) : std::string("yes")) << std::endl;
+        std::cout << "upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms pairing " << rep.pairing_ms << " ms" << std::endl;
+        if (rc == 1 && chain != 0) std::cout << "PTAU_OK" << std::endl;
+        else if (rc == 1) std::cout << "PTAU_BAD CHAIN" << std::endl;
+        else if (point) std::cout << "PTAU_BAD " << kinds[rep.kind] << " " << rep.fault_section << " " << rep.fault_index << std::endl;
+        else std::cout << "PTAU_BAD " << kinds[rep.kind >= 1 && rep.kind <= 13 ? rep.kind : 0] << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

@@ -171,7 +171,7 @@ int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_te
 }
 
 // container and section 1 of a .ptau, prepared or not: magic, version, n8, q, power
-static int ptau_header(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L)
+static int ptau_header(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool bound_power = true)
 {
   if (!data) return fail(ERR_ARG, "null ptau");
   if (int rc = read_sections(data, len, "ptau", 1, secs)) return rc;
@@ -186,7 +186,7 @@ static int ptau_header(const uint8_t* data, size_t len, std::vector<Section>& se
   if (!Fq::eq(q, Fq::modulus())) return fail(ERR_FORMAT, "ptau: the prime is not the BN254 base field's");
   memcpy(&L->power, h->p + 36, 4);
   memcpy(&L->ceremony_power, h->p + 40, 4);
-  if (L->power > 28) return fail(ERR_FORMAT, "ptau: power %u is above the field's two-adicity", L->power);
+  if (bound_power && L->power > 28) return fail(ERR_FORMAT, "ptau: power %u is above the field's two-adicity", L->power);
   L->sec[1] = h;
   return 0;
 }
@@ -228,6 +228,30 @@ uint64_t ptau_prepared_section_bytes(uint32_t power, int sid)
 {
   const uint64_t N = (uint64_t)1 << power;
   return sid == 12 ? (4 * N - 1) * 64 : (2 * N - 1) * (sid == 13 ? 128 : 64);
+}
+
+// sections and header of a .ptau in EITHER form, what groth16_ptau_verify takes: sections 2 … 7 once each with the unprepared
+// layout's exact element counts, and of 12 … 15 none, or all four once each with exactly what prepare writes
+int ptau_either_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool* prepared)
+{
+  if (int rc = ptau_header(data, len, secs, L, /*bound_power=*/false)) return rc;
+  if (L->power > 27) return fail(ERR_ARG, "ptau: power %u is above 27, the highest a file with section 12's block for power + 1 can have", L->power);
+  int have = 0;
+  for (int id = 12; id < 16; id++) have += secs[(size_t)id].count != 0; // (read_sections makes room for the ids below 16)
+  if (have != 0 && have != 4) return fail(ERR_FORMAT, "ptau: %d of the sections 12 to 15 are present: a file has none of them or all four", have);
+  *prepared = have == 4;
+  for (int id = 2; id < 16; id++)
+    if (id <= 7 || (id >= 12 && *prepared))
+      if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
+  const uint64_t N = (uint64_t)1 << L->power;
+  const uint64_t want[7] = {0, 0, (2 * N - 1) * 64, N * 128, N * 64, N * 64, 128};
+  for (int id = 2; id < 16; id++) {
+    if (id == 7 || (id > 7 && !(id >= 12 && *prepared))) continue;
+    const uint64_t w = id <= 6 ? want[id] : ptau_prepared_section_bytes(L->power, id);
+    if (L->sec[id]->size != w)
+      return fail(ERR_FORMAT, "ptau: section %d holds %llu bytes, a file of power %u has %llu", id, (unsigned long long)L->sec[id]->size, L->power, (unsigned long long)w);
+  }
+  return 0;
 }
 
 int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out)

@@ -144,13 +144,14 @@ inline int seed_or_random(const uint8_t* seed32, uint8_t out[32])
   else if (!vb::os_random(out, 32)) return fail(ERR_ARG, "no randomness from the operating system (getrandom, /dev/urandom)");
   return 0;
 }
-// out[i] = the combined verifier's coefficient first + i of `seed` (sha256.h): 128 bits in 32-byte standard form, on the worker pool
-inline void fill_coefficients(const uint8_t seed[32], uint64_t first, size_t count, fe* out)
+// out[i] = the combined verifier's coefficient first + i of `seed` (sha256.h): 128 bits in 32-byte standard form, on the worker pool;
+// `meanwhile` (may be empty) runs on the calling thread while the pool works
+inline void fill_coefficients(const uint8_t seed[32], uint64_t first, size_t count, fe* out, const std::function<void()>& meanwhile = nullptr)
 {
   memset(out, 0, count * sizeof out[0]);
   run_ranges(count, 4096, [&](int, size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) combined_coefficient(seed, first + (uint64_t)i, (uint8_t*)&out[i]);
-  });
+  }, meanwhile);
 }
 
 } // namespace prover

@@ -131,6 +131,9 @@ int ptau_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Pta
 // file that has one of 12 … 15 is refused with a message of its own.  ptau_prepared_section_bytes: what prepare writes for 12 … 15.
 int ptau_unprepared_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L);
 uint64_t ptau_prepared_section_bytes(uint32_t power, int sid);
+// A .ptau in EITHER form, what groth16_ptau_verify takes: sections 2 … 7 as ptau_unprepared_layout demands them, and of 12 … 15 none
+// (*prepared = false) or all four, each with exactly ptau_prepared_section_bytes (ERR_FORMAT otherwise).  A power above 27 is ERR_ARG.
+int ptau_either_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool* prepared);
 // block p of section sid (elements of elem_bytes): its first byte, after checking that it lies inside the section
 int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out);
 // the blocks a verify of a key with domain 2^k reads — block k of 12 … 15 and block k + 1 of 12 — lie inside their sections

@@ -391,7 +391,7 @@ typedef struct {
  * mismatch; should both hold nonetheless, the kind is KEY).  The ptau ranges that are
  * read get the same lane tests (coordinates < q, on the curve, section 13 in the subgroup); a ptau point that fails is a format
  * error (-2) naming section and element.  HEADER compares the stored Montgomery words, which the key check has found canonical.
- * What it does NOT show: anything about the .ptau itself, which is taken as given (`powersoftau verify` is another question);
+ * What it does NOT show: anything about the .ptau itself, which is taken as given (groth16_ptau_verify, below, is what judges it);
  * the phase-2 contribution chain of section 10 and snarkjs' circuit hash; WHICH element of a section is wrong (a failing
  * equation is not localised); section 4, which remains groth16_r1cs_match_zkey's.
  * The key's sections go up twice — once inside the key check, once for the MSMs — so that the key check stays what it is.
@@ -557,8 +557,8 @@ int groth16_zkey_contributions(const void* zkey, size_t len, Groth16Contribution
  * butterfly, T = w*Q by a signed-digit walk with a twiddle per lane, then P + T and P - T; every degenerate case (an identity
  * input, T = +-P, w = 1) is exact.  One path for every level: there is no switch point between kernels, so no such argument.
  * groth16_ptau_prepared_size is the host half: the output's size from the input's container alone.  Never initialises a GPU.
- * What it does NOT do: verify the file's own contribution chain (`powersoftau verify`), apply phase-1 contributions or beacons,
- * use more than one GPU.  No file written by snarkjs exists offline: reader and writer share the layout stated here.
+ * What it does NOT do: check its source's powers against one another or its records (groth16_ptau_verify and
+ * groth16_ptau_contributions do: run them first), apply phase-1 contributions or beacons, use more than one GPU.  No file written by snarkjs exists offline: reader and writer share the layout stated here.
  * 1 prepared; -1 I/O; -2 format; -3 argument: cap too small (report->ptau_bytes says what is needed, nothing is written), power 28,
  * equal paths, a device string that does not name one HIP device; -5 device failure (groth16_last_error).  The _file variant maps
  * the input, writes a temporary beside out_path and renames it: a failed call leaves nothing.  The calling thread's device is what
@@ -626,9 +626,9 @@ int groth16_ptau_prepare_file(const char* in_path, const char* out_path, const c
  * inode), a device string that does not name one HIP device; -5 device failure (groth16_last_error).  The _file variants write a
  * temporary beside out_path and rename it: a failed call leaves nothing.  The calling thread's device is what it was afterwards.
  * ICICLE_SNARK_TRACE_PTAU_CONTRIBUTE=1 prints the stage times on stderr.
- * What none of this does: check that a file's powers are CONSISTENT WITH ONE ANOTHER (`powersoftau verify`'s same-ratio test over
- * all points) — the audit ties the records to element 1 and element 0 of the sections and to section 6, NOT the other 2N - 2
- * powers; apply a beacon; read or write snarkjs' record format; use more than one GPU; decompose the scalars (GLV). */
+ * What none of this does: check that a file's powers are CONSISTENT WITH ONE ANOTHER — the audit ties the records to element 1 and
+ * element 0 of the sections and to section 6, NOT the other 2N - 2 powers: that is groth16_ptau_verify's same-ratio test over all
+ * points, below; apply a beacon; read or write snarkjs' record format; use more than one GPU; decompose the scalars (GLV). */
 int groth16_ptau_new_size(uint32_t power, uint64_t* ptau_bytes);
 int groth16_ptau_new(uint32_t power, void* out, size_t cap, uint64_t* out_len);
 int groth16_ptau_new_file(uint32_t power, const char* out_path);
@@ -666,7 +666,7 @@ int groth16_ptau_contribute_file(const char* in_path, const char* out_path, cons
  *            at power >= 1 — its tau1 and tau2 are not element 1 of sections 2 and 3 (at power 0 the file holds no power of tau:
  *            only the pairing ties tau1 to tau2); with count = 0 the generators are compared against those same elements.
  * What it does NOT show: THAT THE OTHER 2N - 2 POWERS FOLLOW — that every point of sections 2 to 5 really was scaled by the power
- * it should have been.  That is a same-ratio test over all points, a future ptau-verify.
+ * it should have been.  That is a same-ratio test over all points: groth16_ptau_verify, below.  Run both.
  * 1 the chain holds, 0 not (report says where), < 0 an error (-2: the container is malformed, or the file is prepared). */
 typedef struct {
   uint32_t count;            /* records in section 7 (0 after a SECTION fault of the count) */
@@ -680,6 +680,90 @@ typedef struct {
 /* infos (may be NULL) receives the points and the name of the first min(count, infos_cap) records whose bounds hold. */
 int groth16_ptau_contributions(const void* ptau, size_t len, Groth16PtauContributionsReport* report,
                                Groth16PtauContributionInfo* infos, size_t infos_cap);
+
+/* groth16_ptau_verify — two questions about one .ptau, UNPREPARED OR PREPARED, answered on the GPU: are sections 2 to 6 the powers of
+ * one (tau, alpha, beta), and — when sections 12 to 15 are present — are they the inverse transforms of 2 to 5 that
+ * groth16_ptau_prepare and snarkjs write?  What `snarkjs powersoftau verify` shows about the points.  Opt-in.
+ * THE CONTAINER: sections 1 to 7 with the unprepared layout's exact element counts (groth16_ptau_prepare states them), and of 12 to 15
+ * none or all four, each with exactly the bytes prepare writes; anything else is -2.  A power above 27 is -3.
+ * POINTS — A VERDICT, NOT AN ERROR.  Every point of 2 to 5 and 12 to 15 goes through the lane tests of the other key tools
+ * (coordinates < q, on the curve, sections 3 and 13 in the subgroup; section 6 on the host).  A point that fails gives 0 with kind
+ * POINT and fault_section, fault_index (the lowest faulty element of that section), fault_kind = GROTH16_ZKEY_NONCANONICAL /
+ * _OFF_CURVE / _OFF_SUBGROUP.  AN IDENTITY IN SECTIONS 2 TO 6 is a fault of its own, kind IDENTITY (fault_kind 0): tau, alpha, beta
+ * are not 0, and e(O, .) = 1 would satisfy every equation below.  Identities in 12 to 15 are legitimate (tau inside a domain).
+ * Sections are tested in the order 6, then pair by pair 2, 12, 3, 13, 4, 14, 5, 15, within a section POINT before IDENTITY; the first
+ * fault ends the call, no sum has read the faulty section, and failed_mask is 0: it then says nothing about the equations.
+ * EQUATIONS ON 2 TO 6, one bit of failed_mask each (bit = kind - 1), all evaluated whatever failed first; kind is the lowest.  N =
+ * 2^power, P_i section 2, Q_i section 3, tau1 = P_1, tau2 = Q_1, rho_i = the 128-bit coefficient i of the seed (SHA-256(seed ||
+ * LE64(i)), first 16 bytes little-endian, 0 -> 1), one vector for the four sections:
+ *   bit 0 GENERATORS  P_0 = G1 and Q_0 = G2, as stored words
+ *   bit 1 TAU_PAIR    e(P_1, G2) = e(G1, Q_1)                                              (power >= 1)
+ *   bit 2 BETA_PAIR   e(section 5 [0], G2) = e(G1, section 6)
+ *   bit 3 TAU_G1      L = sum_{i < 2N-2} rho_i P_i, R = sum rho_i P_(i+1):  e(L, tau2) = e(R, G2)
+ *   bit 4 TAU_G2      L = sum_{i < N-1} rho_i Q_i, R = sum rho_i Q_(i+1):   e(tau1, L) = e(G1, R)
+ *   bit 5 ALPHA_TAU   as bit 3 over section 4 (N points)
+ *   bit 6 BETA_TAU    as bit 3 over section 5
+ * Bit 4 needs tau in G1.  While TAU_PAIR holds that is tau1, as written.  When TAU_PAIR fails, tau1 does not stand for tau2, and bit 4
+ * is evaluated as e(R', L) = e(L', R) with (L', R') the two sums of the first of sections 2, 4, 5 whose own bit holds — that bit IS
+ * R' = tau2 L' — so that a wrong P_1 is named TAU_PAIR + TAU_G1 and not also TAU_G2; when none holds, nothing in the file stands for
+ * tau2 in G1 and bit 4 is set.  Every ratio is thereby measured against tau2 = Q_1, as the tests' exact model does.
+ * At power 0 bits 1 and 3 to 6 have nothing to sum and hold.  What ties element 0 of sections 4 and 5, and tau1 and tau2, to the
+ * contributors is groth16_ptau_contributions' HEADER rule; this call does NOT run that audit (a file written by a model that knows
+ * tau has no records).  Run both.
+ * EQUATIONS ON 12 TO 15, bits 7 to 10, kinds LAGRANGE_12 to LAGRANGE_15, when the sections are present.  Block p of a section starts
+ * at element 2^p - 1 and must be (1/2^p) sum_i w_p^(-ij) S_i over its source S (2 -> 12, 3 -> 13, 4 -> 14, 5 -> 15; section 12's
+ * block power + 1 with the identity as its last input).  The library's NTT is not used — its domain is process-wide state of the
+ * cache manager — but one full-width MSM on each side with scalars every lane computes for itself:
+ *   x     = SHA-256(seed || "icicle-snark ptau verify v1" || LE32(c)) as a big-endian integer mod r, for the first c = 0, 1, ... with
+ *           x != 0 and x^(2^(power+1)) != 1;  y = 1/x
+ *   mu_p  = the 128-bit coefficient 2^32 + p of the seed, p <= power + 1;  W = w_(power+1);  pmax = power + 1 for 12, power for 13 to 15
+ *   left  element e of the prepared section, p = floor(log2(e + 1)), j = e + 1 - 2^p:
+ *           lambda_e = mu_p (x^(2^p) - 1) / (x - W^(j 2^(power+1-p)))
+ *   right element i of the source, q = the least p with 2^p > i:
+ *           d_i = y^(i+1) T[q],  T[q] = sum_{p=q}^{pmax} mu_p x^(2^p)
+ *   sum_e lambda_e B_e = sum_{i < min(|S|, 2^pmax)} d_i S_i, compared as points (section 13 in G2).
+ * It holds because f(X) = sum_i x^(n-1-i) X^i = (x^n - X^n)/(x - X) has f(w^j) = (x^n - 1)/(x - w^j), and a block that is the inverse
+ * transform of S gives sum_j f(w^j) B_j = sum_i x^(n-1-i) S_i.  The mu_p are needed: with equal multipliers an error in one block is
+ * cancelled exactly by chosen errors in the next.  ONLY THE FORM PREPARE AND SNARKJS WRITE IS ACCEPTED: a section 12 whose last block
+ * is the untruncated L'_j(tau) (a writer that knows tau) fails LAGRANGE_12.
+ * SOUNDNESS.  A file that fails an equation in truth is accepted with probability <= 2^-127 per equation of bits 3 to 6 (in rho),
+ * and per Lagrange equation <= 2^(power+1)/r per block (in x) plus 2^-127 (in mu) — IF THE SEED IS SECRET AND FRESH: whoever knows the
+ * seed before writing the file can make a false file pass.  seed32 = NULL draws it from the operating system; a fixed seed is for
+ * tests and reproducible runs.
+ * The file is worked through pair by pair — (2, 12), (3, 13), (4, 14), (5, 15): up, lane tests, sums, freed — so no more than one
+ * pair is resident.  The _file entry maps the file.  No fixed-base table is built, the NTT domain is not touched, the calling thread's
+ * device is what it was afterwards.  ICICLE_SNARK_TRACE_PTAU_VERIFY=1 prints the stage times on stderr.
+ * What it does NOT show: WHO CONTRIBUTED (groth16_ptau_contributions' answer: run both); beacons; snarkjs' section-7 format; a file
+ * with ceremonyPower != power (a truncated file has other counts: -2); more than one GPU; WHICH element of a failing equation is wrong.
+ * 1 both questions hold; 0 not (report says what); -1 I/O; -2 a malformed container; -3 argument: power above 27, a device string
+ * that does not name one HIP device; -5 device failure (groth16_last_error). */
+#define GROTH16_PTAU_VERIFY_GENERATORS  1
+#define GROTH16_PTAU_VERIFY_TAU_PAIR    2
+#define GROTH16_PTAU_VERIFY_BETA_PAIR   3
+#define GROTH16_PTAU_VERIFY_TAU_G1      4
+#define GROTH16_PTAU_VERIFY_TAU_G2      5
+#define GROTH16_PTAU_VERIFY_ALPHA_TAU   6
+#define GROTH16_PTAU_VERIFY_BETA_TAU    7
+#define GROTH16_PTAU_VERIFY_LAGRANGE_12 8   /* 9, 10, 11: LAGRANGE_13, _14, _15 */
+#define GROTH16_PTAU_VERIFY_LAGRANGE_13 9
+#define GROTH16_PTAU_VERIFY_LAGRANGE_14 10
+#define GROTH16_PTAU_VERIFY_LAGRANGE_15 11
+#define GROTH16_PTAU_VERIFY_POINT       12  /* a point failed its lane test: fault_section, fault_index, fault_kind */
+#define GROTH16_PTAU_VERIFY_IDENTITY    13  /* an identity in sections 2 to 6: fault_section, fault_index */
+typedef struct {
+  uint32_t power;
+  int32_t  prepared;            /* 1: sections 12 to 15 are present and were checked */
+  int32_t  kind;                /* 0 = both questions hold, else the FIRST failing kind (the lowest bit of failed_mask, or POINT / IDENTITY) */
+  uint32_t failed_mask;         /* bit (kind - 1) per failing equation; 0 after POINT / IDENTITY */
+  int32_t  fault_section, fault_kind;   /* POINT, IDENTITY: the section; POINT: GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP */
+  uint64_t fault_index;                 /* the lowest faulty element of that section */
+  uint64_t points[8];           /* points of sections 2, 3, 4, 5, 12, 13, 14, 15 (the last four 0 for an unprepared file) */
+  double   upload_ms, device_ms, pairing_ms; /* the sections', coefficients' and tables' copies up; wall time of the device part
+                                   without them; the host's pairings and comparisons */
+} Groth16PtauVerifyReport;
+int groth16_ptau_verify(const void* ptau, size_t len, const uint8_t* seed32 /* NULL = OS randomness */, const char* device,
+                        Groth16PtauVerifyReport* report);
+int groth16_ptau_verify_file(const char* path, const uint8_t* seed32, const char* device, Groth16PtauVerifyReport* report);
 
 #ifdef __cplusplus
 }
