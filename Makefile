@@ -18,7 +18,10 @@ LIB := $(LIBDIR)/libicicle_snark_hip.so
 
 RCCL_LIB := $(LIBDIR)/libicicle_snark_rccl.so
 
-all: $(LIB) links prove dropin $(RCCL_LIB)
+# test-only probes of the lane-level arithmetic (tests/arith_probe.hip); nothing in $(LIB) links or loads it
+PROBE_LIB := $(LIBDIR)/libisnark_arith_probe.so
+
+all: $(LIB) links prove dropin $(RCCL_LIB) $(PROBE_LIB)
 
 $(OBJDIR)/%.o: $(SRC)/% $(HDRS)
 	@mkdir -p $(dir $@)
@@ -37,6 +40,17 @@ links: $(LIB)
 $(RCCL_LIB): $(SRC)/comm/rccl_comm.cpp
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=$(ARCH) -shared -o $@ $< -L/opt/rocm/lib -lrccl
+
+# the Fq2 / G2 probes are built twice, as the product builds Fq2Ops::mul / sqr: out of line, and inlined (msm_g2_acc.hip)
+$(OBJDIR)/arith_probe.o: tests/arith_probe.hip $(HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(CXXFLAGS) -DPROBE_NO_HOST -x hip -c $< -o $@
+$(OBJDIR)/arith_probe_fq2_inline.o: tests/arith_probe.hip $(HDRS)
+	@mkdir -p $(dir $@)
+	$(HIPCC) $(CXXFLAGS) -DPROBE_NO_HOST -DPROBE_FQ2_ONLY -DISNARK_FQ2_INLINE -DPROBE_SUFFIX=_inline -x hip -c $< -o $@
+$(PROBE_LIB): $(OBJDIR)/arith_probe.o $(OBJDIR)/arith_probe_fq2_inline.o
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 prove: $(LIB)
 	@if [ -f $(SRC)/prover/cli_main.cc ]; then \

@@ -6,6 +6,8 @@ uniformly from [0, r) and list the values where limb arithmetic goes wrong.  Arr
 little-endian limbs, standard form — what the C ABI takes."""
 import numpy as np
 
+from field_inputs import common_positions
+
 R_MOD = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 _R_LIMBS = [np.uint64((R_MOD >> (64 * k)) & ((1 << 64) - 1)) for k in range(4)]
 
@@ -37,20 +39,7 @@ def edge_fr() -> list:
     """Python integers in [0, r) at the places where carries, borrows, the final subtraction of r and the signed recodings
     change behaviour: the ends of the field, its middle, 2^253 (the first bit the older generators never set), and the
     boundaries of the three limb widths the kernels use (64-bit host limbs, 32-bit device limbs, 29-bit lazy limbs)."""
-    r = R_MOD
-    half = (r - 1) // 2
-    vals = [0, 1, 2, r - 1, r - 2, half - 1, half, half + 1, (1 << 253) - 1, 1 << 253, (1 << 253) + 1, (1 << 32) - 1]
-    for w in (64, 32, 29):
-        for k in range(1, 254 // w + 1):
-            vals += [(1 << (w * k)) - 1, (1 << (w * k)) + 1]
-    vals += [r - (1 << 64), r - (1 << 64) - 1, r - (1 << 128) + 1, r - (1 << 192) - 1]      # the same borders seen from r
-    vals += [(1 << 253) | ((1 << 192) - 1), (r >> 64 << 64) - 1, r >> 64 << 64]           # all-ones low limbs under the top limb
-    out = []
-    for v in vals:
-        assert 0 <= v < r
-        if v not in out:
-            out.append(v)
-    return out
+    return common_positions(R_MOD)   # the list is pinned by tests/test_fr_inputs.py; other moduli: field_inputs.edge_field
 
 
 def ints_to_arr(xs) -> np.ndarray:

@@ -195,3 +195,139 @@ def test_msm_bitsize_and_precompute_factor_semantics(gpu, O, grp):
             assert np.array_equal(got, w2), (bits, "precompute")
     with pytest.raises(K.IcicleError):
         K.msm(grp, sc, bases, bitsize=300)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The same entry points over the WHOLE field: every generator above stays below 2^253, so the values where limb arithmetic goes
+# wrong (tests/fr_inputs.py, tests/field_inputs.py) never reached div, accumulate, the scalar∘vector ops, the reductions or the
+# Fq conversions of points.  Expected values are Python integers.
+# ------------------------------------------------------------------------------------------------------------------------------
+import ctypes as C   # noqa: E402
+
+from field_inputs import Q_MOD, edge_field, rand_field   # noqa: E402
+from fr_inputs import R_MOD, edge_fr, ints_to_arr, rand_fr_full   # noqa: E402
+
+
+def _edge_cross(rng, extra):
+    """(a, b) as arrays and integer lists: the cross product of the Fr edge list with itself, then `extra` uniform pairs"""
+    e = edge_fr()
+    ra, rb = rand_fr_full(rng, extra), rand_fr_full(rng, extra)
+    a = np.concatenate([ints_to_arr([x for x in e for _ in e]), ra])
+    b = np.concatenate([ints_to_arr([y for _ in e for y in e]), rb])
+    assert len(a) % 256
+    return a, b
+
+
+def test_vec_div_and_accumulate_over_the_whole_field(gpu, O):
+    K, R = gpu, R_MOD
+    a, b = _edge_cross(np.random.default_rng(41), 2000)
+    ai, bi = O.arr_to_ints(a), O.arr_to_ints(b)
+    assert sum(y == 0 for y in bi) >= 48 and any(x == 0 and y == 0 for x, y in zip(ai, bi))       # zero divisors, 0/0 among them
+    want_div = O.ints_to_arr([x * (pow(y, -1, R) if y else 0) % R for x, y in zip(ai, bi)])
+    want_acc = O.ints_to_arr([(x + y) % R for x, y in zip(ai, bi)])
+    assert np.array_equal(K.vec_op2("div", a, b), want_div)
+    da, db = K.DeviceVec.from_host(a), K.DeviceVec.from_host(b)
+    K.vec_op2("div", da, db, out=da)                                                            # device resident, in place
+    assert np.array_equal(da.to_host(a.shape), want_div)
+    host = a.copy()
+    K.accumulate_scalars(host, b)                                                               # host resident, in place
+    assert np.array_equal(host, want_acc)
+    da.copy_from_host(a)
+    K.accumulate_scalars(da, db)
+    assert np.array_equal(da.to_host(a.shape), want_acc)
+    da.free()
+    db.free()
+
+
+@pytest.mark.parametrize("cols", [False, True])
+def test_scalar_vector_ops_over_the_whole_field(gpu, O, cols):
+    """one edge value per batch row as the scalar, the whole edge list and uniform values as its vector: the cross product"""
+    K, R = gpu, R_MOD
+    e = edge_fr()
+    batch, size = len(e), len(e) + 37
+    rows = [e + O.arr_to_ints(rand_fr_full(np.random.default_rng(50 + b), 37)) for b in range(batch)]
+    flat = [rows[k % batch][k // batch] if cols else rows[k // size][k % size] for k in range(batch * size)]
+    v, sc = ints_to_arr(flat), ints_to_arr(e)
+    for name, f in (("add", lambda s, x: (s + x) % R), ("sub", lambda s, x: (s - x) % R), ("mul", lambda s, x: s * x % R)):
+        want = O.ints_to_arr([f(e[(k % batch) if cols else (k // size)], x) for k, x in enumerate(flat)])
+        assert np.array_equal(K.scalar_vec_op(name, sc, v, batch_size=batch, columns_batch=cols), want), name
+        dv, ds = K.DeviceVec.from_host(v), K.DeviceVec.from_host(sc)
+        K.scalar_vec_op(name, ds, dv, batch_size=batch, columns_batch=cols, out=dv)             # device resident, in place
+        assert np.array_equal(dv.to_host(v.shape), want), name + " (device, in place)"
+        dv.free()
+        ds.free()
+
+
+def _reduce_direct(K, name, v, size, batch, cols, on_device):
+    """bn254_vector_{sum,product} called directly: input and RESULT both host resident or both device resident"""
+    cfg = K.VecOpsConfig.default()
+    cfg.is_a_on_device = cfg.is_result_on_device = on_device
+    cfg.batch_size, cfg.columns_batch = batch, cols
+    fn = getattr(K.lib(), "bn254_vector_" + name)
+    if not on_device:
+        out = np.zeros((batch, 4), dtype=np.uint64)
+        K.check(fn(K.ptr_of(v), C.c_uint64(size), C.byref(cfg), K.ptr_of(out)), name)
+        return out
+    dv, dout = K.DeviceVec.from_host(v), K.DeviceVec(32 * batch)
+    K.check(fn(K.ptr_of(dv), C.c_uint64(size), C.byref(cfg), K.ptr_of(dout)), name)
+    out = dout.to_host((batch, 4))
+    dv.free()
+    dout.free()
+    return out
+
+
+@pytest.mark.parametrize("size", [1, 255, 256, 257, 4096, 4097, 4096 * 3 + 5])
+def test_reductions_sizes_layouts_and_residency(gpu, O, size):
+    """Σ and Π at one chunk, the chunk border and several chunks, batch 1 and 3 in both layouts, result on the host and on the
+    device, over uniform values of [0, r) with r − 1 and 0 planted"""
+    K, R = gpu, R_MOD
+    for batch in (1, 3):
+        rows = [O.arr_to_ints(rand_fr_full(np.random.default_rng(1000 * batch + size + b), size)) for b in range(batch)]
+        for r in rows:
+            r[0] = r[-1] = R - 1
+        zrows = [list(r) for r in rows]
+        zrows[-1][size // 2] = 0
+        if size > 2:
+            zrows[0][1] = 0                                                                      # Σ sees a zero in the first row as well
+        want = {}
+        for tag, rr in (("v", rows), ("z", zrows)):
+            prods = []
+            for r in rr:
+                acc = 1
+                for x in r:
+                    acc = acc * x % R
+                prods.append(acc)
+            want[tag] = (O.ints_to_arr([sum(r) % R for r in rr]), O.ints_to_arr(prods))
+        assert all(int(x) for x in O.arr_to_ints(want["v"][1]))                                   # Π of the zero-free rows is not trivially 0
+        for cols in (False, True):
+            for tag, rr in (("v", rows), ("z", zrows)):
+                flat = [rr[k % batch][k // batch] if cols else rr[k // size][k % size] for k in range(batch * size)]
+                v = ints_to_arr(flat)
+                for on_device in (False, True):
+                    where = (size, batch, cols, tag, on_device)
+                    assert np.array_equal(_reduce_direct(K, "sum", v, size, batch, cols, on_device), want[tag][0]), ("sum",) + where
+                    assert np.array_equal(_reduce_direct(K, "product", v, size, batch, cols, on_device), want[tag][1]), ("product",) + where
+
+
+@pytest.mark.parametrize("name,words", [("bn254_affine_convert_montgomery", 2), ("bn254_g2_affine_convert_montgomery", 4),
+                                        ("bn254_projective_convert_montgomery", 3), ("bn254_g2_projective_convert_montgomery", 6)])
+def test_point_montgomery_conversions_are_fq_conversions_over_the_whole_field(gpu, O, name, words):
+    """the point conversions are coordinate-wise Fq conversions: the Fq edge list (with the values of [r, q)) and 4096 uniform
+    values of [0, q) as coordinates, both directions, host resident and device resident in place"""
+    K = gpu
+    vals = edge_field(Q_MOD) + rand_field(np.random.default_rng(61), 4096, Q_MOD)
+    vals += edge_field(Q_MOD)[:-len(vals) % 12]                                                  # whole points for every layout
+    assert len(vals) % words == 0 and any(R_MOD <= v < Q_MOD for v in vals) and Q_MOD - 1 in vals
+    a = ints_to_arr(vals)
+    fn = getattr(K.lib(), name)
+    for to_mont, factor in ((True, 1 << 256), (False, pow(1 << 256, -1, Q_MOD))):
+        want = ints_to_arr([v * factor % Q_MOD for v in vals])
+        cfg = K.VecOpsConfig.default()
+        out = np.zeros_like(a)
+        K.check(fn(K.ptr_of(a), C.c_uint64(len(vals) // words), C.c_bool(to_mont), C.byref(cfg), K.ptr_of(out)), name)
+        assert np.array_equal(out, want), (name, to_mont)
+        d = K.DeviceVec.from_host(a)
+        cfg.is_a_on_device = cfg.is_result_on_device = True
+        K.check(fn(K.ptr_of(d), C.c_uint64(len(vals) // words), C.c_bool(to_mont), C.byref(cfg), K.ptr_of(d)), name)
+        assert np.array_equal(d.to_host(a.shape), want), (name, to_mont, "device, in place")
+        d.free()
