@@ -708,6 +708,8 @@ groth16_ptau_prepared_size groth16_ptau_prepare groth16_ptau_prepare_file
 groth16_ptau_new_size groth16_ptau_new groth16_ptau_new_file
 groth16_ptau_contribute groth16_ptau_contribute_file groth16_ptau_contributions
 groth16_ptau_verify groth16_ptau_verify_file
+groth16_points_pack groth16_points_unpack groth16_ptau_packed_size groth16_ptau_unpacked_size
+groth16_ptau_pack groth16_ptau_pack_file groth16_ptau_unpack groth16_ptau_unpack_file
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1328,3 +1330,102 @@ def sum_commitments(blocks: bytes, count: int) -> bytes:
     out = (C.c_uint8 * COMMITMENTS_BYTES)()
     _pcheck(lib().groth16_sum_commitments(blocks, count, out), "sum_commitments")
     return bytes(out)
+
+
+class PointsPackReport(C.Structure):
+    """Groth16PointsPackReport: the element count, the lowest faulty element with its kind and how many are faulty, the stage times"""
+    _fields_ = [("n", C.c_uint64), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64), ("fault_count", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double)]
+
+
+class PtauPackReport(C.Structure):
+    """Groth16PtauPackReport: power, prepared, the G1 and G2 point counts, the input's and the output's bytes, the first faulty
+    section with its lowest faulty element, its kind and that section's fault count, the stage times"""
+    _fields_ = [("power", C.c_uint32), ("prepared", C.c_int32), ("points", C.c_uint64 * 2), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64),
+                ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64), ("fault_count", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
+class PointFault(ProverError):
+    """a faulty point refused by a pack / unpack call: .report says which"""
+    report = None
+
+
+def _pack_check(rc, what, rep):
+    try:
+        _pcheck(rc, what)
+    except ProverError as e:
+        if rc == -2 and rep.fault_kind:
+            fault = PointFault(str(e))
+            fault.report = rep
+            raise fault from None
+        raise
+
+
+def _points_call(entry, what, buf, in_elem, out_elem, g2, device):
+    if len(buf) % in_elem:
+        raise ValueError(f"{what}: {len(buf)} bytes are no multiple of {in_elem}")
+    n = len(buf) // in_elem
+    out, rep = C.create_string_buffer(max(n * out_elem, 1)), PointsPackReport()
+    rc = entry(_image(buf) if n else None, C.c_uint64(n), C.c_int(1 if g2 else 0), out, device.encode(), C.byref(rep))
+    _pack_check(rc, what, rep)
+    return out.raw[:n * out_elem], rep
+
+
+def points_pack(buf, g2: bool = False, device: str = "HIP"):
+    """groth16_points_pack → (packed bytes, PointsPackReport): file-form points (64 bytes each, g2: 128; affine, Montgomery form, the
+    identity all zero) as x and one bit of y, 32 or 64 bytes each, on the GPU.  Every point passes the key tools' lane test first;
+    a faulty one raises PointFault (−2) whose .report names the lowest faulty element, its kind and the count.  An empty buffer is valid."""
+    return _points_call(lib().groth16_points_pack, "points_pack", buf, 128 if g2 else 64, 64 if g2 else 32, g2, device)
+
+
+def points_unpack(buf, g2: bool = False, device: str = "HIP"):
+    """groth16_points_unpack → (file-form points, PointsPackReport): the inverse of points_pack, a square root per point on the GPU.
+    A word that is no valid packed point raises PointFault (−2): flags, x >= q, no point with this x, outside the subgroup (G2)."""
+    return _points_call(lib().groth16_points_unpack, "points_unpack", buf, 64 if g2 else 32, 128 if g2 else 64, g2, device)
+
+
+def ptau_packed_size(power: int, prepared: bool, ptau_bytes: int) -> int:
+    """groth16_ptau_packed_size: the bytes of ptau_pack's file for a .ptau of this power, form and size; host only.  Raises
+    ProverError −3 for a power above 27 or a size below the form's point sections."""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_ptau_packed_size(C.c_uint32(power), C.c_int(1 if prepared else 0), C.c_uint64(ptau_bytes), C.byref(size)), "ptau_packed_size")
+    return size.value
+
+
+def ptau_unpacked_size(power: int, prepared: bool, packed_bytes: int) -> int:
+    """groth16_ptau_unpacked_size: the bytes of the .ptau that ptau_unpack writes for a packed file of this power, form and size"""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_ptau_unpacked_size(C.c_uint32(power), C.c_int(1 if prepared else 0), C.c_uint64(packed_bytes), C.byref(size)), "ptau_unpacked_size")
+    return size.value
+
+
+def _ptau_transcode(what, buffer_entry, file_entry, src, out, device):
+    rep = PtauPackReport()
+    if isinstance(src, (str, os.PathLike)):
+        if out is None:
+            raise TypeError(f"{what}: an input path needs the path to write to")
+        _pack_check(file_entry(os.fsencode(src), os.fsencode(out), device.encode(), C.byref(rep)), what + "_file", rep)
+        return None, rep
+    if out is not None:
+        raise TypeError(f"{what}: `out` goes with an input path")
+    rc = buffer_entry(_image(src), C.c_size_t(len(src)), None, C.c_size_t(0), device.encode(), C.byref(rep))
+    if rc != -3 or rep.out_bytes == 0:
+        _pack_check(rc, what, rep)
+    buf = C.create_string_buffer(rep.out_bytes)
+    _pack_check(buffer_entry(_image(src), C.c_size_t(len(src)), buf, C.c_size_t(rep.out_bytes), device.encode(), C.byref(rep)), what, rep)
+    return buf.raw[:rep.out_bytes], rep
+
+
+def ptau_pack(ptau, out=None, device: str = "HIP"):
+    """groth16_ptau_pack → (packed bytes | None, PtauPackReport): a .ptau, unprepared or prepared, with every point as x and one bit
+    of y — half the bytes, magic "ptaz" (include/groth16_prover.h has the form).  ptau: the image, and the packed file comes back as
+    bytes; or a path together with `out`, the path the packed file is written to (a temporary, renamed).  Every point passes the
+    lane tests first: PointFault (−2) "ptau: section S, element E: kind", its .report saying the same, and nothing written."""
+    return _ptau_transcode("ptau_pack", lib().groth16_ptau_pack, lib().groth16_ptau_pack_file, ptau, out, device)
+
+
+def ptau_unpack(packed, out=None, device: str = "HIP"):
+    """groth16_ptau_unpack → (ptau bytes | None, PtauPackReport): the .ptau a packed file came from, byte for byte: a square root per
+    point on the GPU, which is also the on-curve test.  Arguments and errors as ptau_pack."""
+    return _ptau_transcode("ptau_unpack", lib().groth16_ptau_unpack, lib().groth16_ptau_unpack_file, packed, out, device)

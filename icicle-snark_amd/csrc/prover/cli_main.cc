@@ -27,6 +27,9 @@
 //   > ptau-verify --ptau P [--device HIP]     ptau-contributions (an unprepared file), then the powers of sections 2 to 6 against one
 //     another and sections 12 to 15 against them (groth16_ptau_verify_file): one line per question, then PTAU_OK or
 //     PTAU_BAD <kind> [<section> <element>]
+//   > ptau-pack --ptau IN --out OUT [--device HIP]       the file with every point as x and one bit of y, half the bytes
+//     (groth16_ptau_pack_file): one summary line, then PTAU_WRITTEN; a faulty point: PTAU_BAD POINT <section> <element>
+//   > ptau-unpack --packed IN --out OUT [--device HIP]   the .ptau back, byte for byte (groth16_ptau_unpack_file): the same lines
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -37,7 +40,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  exit\n";
 }
 
 int main()
@@ -529,6 +532,27 @@ int main()
         else if (rc == 1) std::cout << "PTAU_BAD CHAIN" << std::endl;
         else if (point) std::cout << "PTAU_BAD " << kinds[rep.kind] << " " << rep.fault_section << " " << rep.fault_index << std::endl;
         else std::cout << "PTAU_BAD " << kinds[rep.kind >= 1 && rep.kind <= 13 ? rep.kind : 0] << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-pack" || cmd == "ptau-unpack") {
+      const bool unpack = cmd == "ptau-unpack";
+      std::string inp = unpack ? "pot_final.ptaz" : "pot_final.ptau", out = unpack ? "pot_final.ptau" : "pot_final.ptaz", device = "HIP", a;
+      while (in >> a) {
+        if (a == (unpack ? "--packed" : "--ptau")) in >> inp;
+        else if (a == "--out") in >> out;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16PtauPackReport rep = {};
+      const int rc = unpack ? groth16_ptau_unpack_file(inp.c_str(), out.c_str(), device.c_str(), &rep) : groth16_ptau_pack_file(inp.c_str(), out.c_str(), device.c_str(), &rep);
+      if (rc < 0) {
+        std::cerr << cmd << " failed (" << rc << "): " << groth16_last_error() << std::endl;
+        if (rep.fault_kind) std::cout << "PTAU_BAD POINT " << rep.fault_section << " " << rep.fault_index << std::endl;
+      } else {
+        std::cout << "power " << rep.power << (rep.prepared ? " prepared" : " unprepared") << " points " << rep.points[0] << " " << rep.points[1] << " bytes " << rep.in_bytes << " to "
+                  << rep.out_bytes << "; upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms"
+                  << std::endl;
+        std::cout << "PTAU_WRITTEN" << std::endl;
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {

@@ -171,10 +171,10 @@ int r1cs_walk(const R1csLayout& L, std::vector<uint32_t>& rowptr, uint64_t* n_te
 }
 
 // container and section 1 of a .ptau, prepared or not: magic, version, n8, q, power
-static int ptau_header(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool bound_power = true)
+static int ptau_header(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool bound_power = true, const char* magic = "ptau")
 {
   if (!data) return fail(ERR_ARG, "null ptau");
-  if (int rc = read_sections(data, len, "ptau", 1, secs)) return rc;
+  if (int rc = read_sections(data, len, magic, 1, secs)) return rc;
   const Section* h;
   if (int rc = unique_section(secs, 1, &h)) return rc;
   uint32_t n8 = 0;
@@ -250,6 +250,35 @@ int ptau_either_layout(const uint8_t* data, size_t len, std::vector<Section>& se
     const uint64_t w = id <= 6 ? want[id] : ptau_prepared_section_bytes(L->power, id);
     if (L->sec[id]->size != w)
       return fail(ERR_FORMAT, "ptau: section %d holds %llu bytes, a file of power %u has %llu", id, (unsigned long long)L->sec[id]->size, L->power, (unsigned long long)w);
+  }
+  return 0;
+}
+
+uint64_t ptau_packed_section_bytes(uint32_t power, int sid)
+{
+  const uint64_t N = (uint64_t)1 << power;
+  const uint64_t low[7] = {0, 0, (2 * N - 1) * 32, N * 64, N * 32, N * 32, 64};
+  return sid <= 6 ? low[sid] : ptau_prepared_section_bytes(power, sid) / 2;
+}
+
+// sections and header of a PACKED powers-of-tau file (ptau_pack.hip): a .ptau's section table and section 1 under magic "ptaz",
+// version 1; sections 2 … 7 once each, and of 12 … 15 none or all four, the point sections with exactly the packed element counts
+int ptau_packed_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool* prepared)
+{
+  if (int rc = ptau_header(data, len, secs, L, /*bound_power=*/false, "ptaz")) return rc;
+  if (L->power > 27) return fail(ERR_ARG, "ptau: power %u is above 27, the highest a packed file can have", L->power);
+  int have = 0;
+  for (int id = 12; id < 16; id++) have += secs[(size_t)id].count != 0; // (read_sections makes room for the ids below 16)
+  if (have != 0 && have != 4) return fail(ERR_FORMAT, "ptau: %d of the sections 12 to 15 are present: a file has none of them or all four", have);
+  *prepared = have == 4;
+  for (int id = 2; id < 16; id++)
+    if (id <= 7 || (id >= 12 && *prepared))
+      if (int rc = unique_section(secs, (size_t)id, &L->sec[id])) return rc;
+  for (int id = 2; id < 16; id++) {
+    if (id == 7 || (id > 7 && !(id >= 12 && *prepared))) continue;
+    const uint64_t w = ptau_packed_section_bytes(L->power, id);
+    if (L->sec[id]->size != w)
+      return fail(ERR_FORMAT, "ptau: section %d holds %llu bytes, a packed file of power %u has %llu", id, (unsigned long long)L->sec[id]->size, L->power, (unsigned long long)w);
   }
   return 0;
 }
@@ -381,4 +410,28 @@ __attribute__((visibility("default"))) int groth16_ptau_prepared_size(const void
   for (int sid = 12; sid < 16; sid++) total += 12 + ptau_prepared_section_bytes(L.power, sid);
   *ptau_bytes = total;
   return 0;
+}
+
+// host only: never initialise a GPU.  The sizes of groth16_ptau_pack's and groth16_ptau_unpack's files (ptau_pack.hip): whatever is
+// no point section is carried over as it is, so the other form's size follows from (power, prepared, this form's size).
+static int ptau_pack_sizes(uint32_t power, int prepared, uint64_t in_bytes, bool unpack, uint64_t* out_bytes)
+{
+  if (!out_bytes) return fail(ERR_ARG, "null output");
+  *out_bytes = 0;
+  if (power > 27) return fail(ERR_ARG, "ptau: power %u is above 27", power);
+  uint64_t packed = 0;
+  for (int sid = 2; sid < 16; sid++)
+    if (sid <= 6 || (sid >= 12 && prepared)) packed += ptau_packed_section_bytes(power, sid);
+  const uint64_t points_in = unpack ? packed : 2 * packed, least = 12 + 12 * (prepared ? 11 : 7) + 44 + points_in; // sections 1 to 7 (and 12 to 15)
+  if (in_bytes < least) return fail(ERR_ARG, "ptau: a %s file of power %u has at least %llu bytes, not %llu", unpack ? "packed" : prepared ? "prepared" : "unprepared", power, (unsigned long long)least, (unsigned long long)in_bytes);
+  *out_bytes = unpack ? in_bytes + packed : in_bytes - packed;
+  return 0;
+}
+__attribute__((visibility("default"))) int groth16_ptau_packed_size(uint32_t power, int prepared, uint64_t ptau_bytes, uint64_t* packed_bytes)
+{
+  return ptau_pack_sizes(power, prepared, ptau_bytes, false, packed_bytes);
+}
+__attribute__((visibility("default"))) int groth16_ptau_unpacked_size(uint32_t power, int prepared, uint64_t packed_bytes, uint64_t* ptau_bytes)
+{
+  return ptau_pack_sizes(power, prepared, packed_bytes, true, ptau_bytes);
 }

@@ -1,13 +1,18 @@
 // device_call.h — the host plumbing every key tool wraps its device work in (zkey_check.hip, r1cs_check.hip, zkey_verify.hip,
 // zkey_new.hip; verify_combined.hip takes its MSM configuration from here): one error text and the checked call and launch that
-// return it, stage times, the scoped file hint of the pinned staging, the timed upload, an event that destroys itself, the
-// library's MSMs over device operands in slices, and the seed and coefficients of the randomised checks.  The device session and
-// its buffers are verify_batch.h's; the host point helpers are verify_host.h's; the ptau's ranges are ptau_ranges.h's.
+// return it, stage times, the scoped file hint of the pinned staging, the timed upload, the temporary a _file entry writes and
+// renames (ptau_contribute.hip, ptau_pack.hip), an event that destroys itself, the library's MSMs over device operands in slices,
+// and the seed and coefficients of the randomised checks.  The device session and its buffers are verify_batch.h's; the host point
+// helpers are verify_host.h's; the ptau's ranges are ptau_ranges.h's.
 #pragma once
 #include <algorithm>
 #include <chrono>
+#include <fcntl.h>
 #include <stdio.h>
 #include <string.h>
+#include <string>
+#include <sys/mman.h>
+#include <unistd.h>
 
 #include "../workers.h"
 #include "prover_internal.h"
@@ -77,6 +82,40 @@ inline int timed_upload(int dev, void* dst, const void* src, size_t bytes, doubl
   *ms += ms_since(t0);
   return he ? dev_fail("host to device upload", he) : 0;
 }
+
+// ---- outputs
+// a file written as a temporary beside `path` and renamed over it by finish(0): a failed call leaves nothing there
+struct TempOutput {
+  std::string path, tmp;
+  int fd = -1;
+  uint8_t* map = nullptr;
+  uint64_t map_len = 0;
+  explicit TempOutput(const char* out_path) : path(out_path), tmp(std::string(out_path) + ".tmp." + std::to_string((long)getpid())) {}
+  int open(uint64_t bytes, uint8_t** o)
+  {
+    fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) return fail(ERR_IO, "cannot create %s", tmp.c_str());
+    if (ftruncate(fd, (off_t)bytes) != 0) return fail(ERR_IO, "cannot size %s to %llu bytes", tmp.c_str(), (unsigned long long)bytes);
+    void* p = mmap(nullptr, (size_t)bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
+    if (p == MAP_FAILED) return fail(ERR_IO, "cannot mmap %s", tmp.c_str());
+    map = (uint8_t*)p;
+    map_len = bytes;
+    *o = map;
+    return 0;
+  }
+  // rc: the call's result so far; returns the call's result
+  int finish(int rc)
+  {
+    if (map) {
+      if (rc == 0 && msync(map, (size_t)map_len, MS_SYNC) != 0) rc = fail(ERR_IO, "cannot write %s", tmp.c_str());
+      munmap(map, (size_t)map_len);
+    }
+    if (fd >= 0) close(fd);
+    if (rc == 0 && rename(tmp.c_str(), path.c_str()) != 0) rc = fail(ERR_IO, "cannot rename %s to %s", tmp.c_str(), path.c_str());
+    if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
+    return rc;
+  }
+};
 
 struct Event { // ordering only: no timing
   hipEvent_t e = nullptr;

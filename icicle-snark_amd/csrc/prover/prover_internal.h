@@ -134,6 +134,12 @@ uint64_t ptau_prepared_section_bytes(uint32_t power, int sid);
 // A .ptau in EITHER form, what groth16_ptau_verify takes: sections 2 … 7 as ptau_unprepared_layout demands them, and of 12 … 15 none
 // (*prepared = false) or all four, each with exactly ptau_prepared_section_bytes (ERR_FORMAT otherwise).  A power above 27 is ERR_ARG.
 int ptau_either_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool* prepared);
+// A PACKED powers-of-tau file, what groth16_ptau_unpack takes (ptau_pack.hip; include/groth16_prover.h has the form): a .ptau's
+// section table and section 1 under magic "ptaz", version 1 — a .ptau is refused as any foreign magic is, and no .ptau reader takes
+// this — sections 2 … 7 once each and of 12 … 15 none or all four, every point section with exactly ptau_packed_section_bytes
+// (ERR_FORMAT naming the section and both sizes).  A power above 27 is ERR_ARG.
+int ptau_packed_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, PtauLayout* L, bool* prepared);
+uint64_t ptau_packed_section_bytes(uint32_t power, int sid); // sid 2 … 6, 12 … 15
 // block p of section sid (elements of elem_bytes): its first byte, after checking that it lies inside the section
 int ptau_block(const PtauLayout& L, int sid, uint32_t p, size_t elem_bytes, const uint8_t** out);
 // the blocks a verify of a key with domain 2^k reads — block k of 12 … 15 and block k + 1 of 12 — lie inside their sections

@@ -260,39 +260,7 @@ struct TableWipe {
 };
 
 typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
-
-// a file written as a temporary beside `path` and renamed over it by finish(0): a failed call leaves nothing there
-struct TempOutput {
-  std::string path, tmp;
-  int fd = -1;
-  uint8_t* map = nullptr;
-  uint64_t map_len = 0;
-  explicit TempOutput(const char* out_path) : path(out_path), tmp(std::string(out_path) + ".tmp." + std::to_string((long)getpid())) {}
-  int open(uint64_t bytes, uint8_t** o)
-  {
-    fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return pv::fail(pv::ERR_IO, "cannot create %s", tmp.c_str());
-    if (ftruncate(fd, (off_t)bytes) != 0) return pv::fail(pv::ERR_IO, "cannot size %s to %llu bytes", tmp.c_str(), (unsigned long long)bytes);
-    void* p = mmap(nullptr, (size_t)bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    if (p == MAP_FAILED) return pv::fail(pv::ERR_IO, "cannot mmap %s", tmp.c_str());
-    map = (uint8_t*)p;
-    map_len = bytes;
-    *o = map;
-    return 0;
-  }
-  // rc: the call's result so far; returns the call's result
-  int finish(int rc)
-  {
-    if (map) {
-      if (rc == 0 && msync(map, (size_t)map_len, MS_SYNC) != 0) rc = pv::fail(pv::ERR_IO, "cannot write %s", tmp.c_str());
-      munmap(map, (size_t)map_len);
-    }
-    if (fd >= 0) close(fd);
-    if (rc == 0 && rename(tmp.c_str(), path.c_str()) != 0) rc = pv::fail(pv::ERR_IO, "cannot rename %s to %s", tmp.c_str(), path.c_str());
-    if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
-    return rc;
-  }
-};
+using pv::TempOutput;
 
 // ---- groth16_ptau_new
 int new_size(uint32_t power, uint64_t* bytes)

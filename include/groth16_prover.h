@@ -765,6 +765,75 @@ int groth16_ptau_verify(const void* ptau, size_t len, const uint8_t* seed32 /* N
                         Groth16PtauVerifyReport* report);
 int groth16_ptau_verify_file(const char* path, const uint8_t* seed32, const char* device, Groth16PtauVerifyReport* report);
 
+/* groth16_ptau_pack, groth16_ptau_unpack — a powers-of-tau file in HALF THE BYTES and back, on the GPU: every point stored as x and
+ * one bit of y, what a ceremony's participants download and upload and its coordinator stores.  groth16_points_pack / _unpack are
+ * the same over a plain buffer of points.  Opt-in.
+ * THE PACKED POINT.  A point of a .ptau is affine, canonical Montgomery form (R = 2^256), little-endian, the identity all zero.
+ *   G1, 32 bytes   x exactly as the file holds it.  q < 2^254, so bits 254 and 255 are free: bit 7 of byte 31 = sign(y), bit 6 of
+ *                  byte 31 = the identity flag.  The identity is the flag alone: 00 ... 00 40.
+ *   G2, 64 bytes   x as the file holds it, c0 then c1; the same two flag bits in byte 63.  c0 carries no flags.
+ *   sign(y) in Fq  = 1 iff the STANDARD-form integer of y is above (q - 1)/2 (not defined on the Montgomery representative);
+ *   sign(y) in Fq2 = the sign of y.c1 when y.c1 != 0, else the sign of y.c0.
+ * pack and unpack are inverse bijections between sound file-form points and valid packed words, so both directions are functions of
+ * their input alone.  UNPACKING a word tests, in this order: the flags (an identity flag with any other bit set, the sign bit
+ * included: NONCANONICAL); x < q as an integer (NONCANONICAL); the root of x^3 + 3, on the twist x^3 + 3/xi — none: OFF_CURVE — as
+ * a^((q+1)/4) in Fq and by the complex method in Fq2 (two such exponentiations, no inversion), each ending in a squaring that is
+ * compared with a, so no path can emit a wrong point; a root of 0 with the sign bit set (NONCANONICAL); then negates to match the sign
+ * bit; G2 only, the subgroup test of the other key tools (OFF_SUBGROUP).  The root doubles as the on-curve test.  PACKING runs the
+ * lane test of the other key tools first (coordinates < q, on the curve, G2 in the subgroup), so a file packed here always unpacks.
+ * The kinds are GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP.
+ * THE RAW ENTRIES take n points (64 or 128 bytes each; g2 != 0: G2) or n packed words (32 or 64 bytes) in host memory and write the
+ * other form to `out`; n = 0 is valid.  A faulty element is -2 "points: element E: kind" with fault_index the LOWEST faulty element,
+ * fault_kind its kind and fault_count how many there are; nothing is written.
+ * THE PACKED CONTAINER has the section table of a .ptau under magic "ptaz", version 1: no reader of a .ptau takes it for one (-2,
+ * as any foreign magic), and the packed reader takes no .ptau.  Section 1, section 7 and any unknown section are byte for byte the
+ * .ptau's, the sections keep their order, and the point sections hold exactly (N = 2^power)
+ *   2: (2N - 1) * 32    3: N * 64    4, 5: N * 32    6: 64    and of a prepared file also
+ *   12: (4N - 1) * 32   13: (2N - 1) * 64   14, 15: (2N - 1) * 32
+ * bytes — of 12 to 15 none or all four; anything else is -2 naming the section and both sizes.  groth16_ptau_pack reads a .ptau in
+ * either form as groth16_ptau_verify does (the same container rules, power <= 27).  The host bounds every section before a byte
+ * goes up: no content of a file can make a kernel read outside its buffers.
+ * Section 6 goes through the same lane code on the host; sections 2 to 5 and 12 to 15 go up and through one launch each, a lane per
+ * point.  ALL verdicts are read before anything is written: a faulty point is -2 "ptau: section S, element E: kind" — section 6
+ * first, then the lowest faulty section, its lowest faulty element, fault_count that section's faulty elements — and nothing is
+ * written.  The output's size is known from the container alone: groth16_ptau_packed_size / groth16_ptau_unpacked_size give it from
+ * (power, prepared, the input's bytes) on the host, -3 for a power above 27 or an input shorter than its point sections; cap is
+ * tested before any device work (-3, report->out_bytes says what is needed).
+ * 0 done; -1 I/O; -2 format or a faulty point; -3 argument: cap too small, equal paths (by name or by inode), a power above 27, a
+ * device string that does not name one HIP device; -5 device failure (groth16_last_error).  The _file entries map the input, write a
+ * temporary beside out_path and rename it: a failed call leaves nothing.  The calling thread's device is what it was afterwards.
+ * ICICLE_SNARK_TRACE_PTAU_PACK=1 prints the stage times on stderr.
+ * What it does NOT do: let groth16_ptau_contribute, _verify, _prepare or groth16_zkey_new read a packed file (unpack first; the
+ * device side of unpack leaves file-form points in a device buffer, so a later reader needs no host round trip); .zkey files (the
+ * raw entries take their points); bellman's or snarkjs' challenge / response formats; more than one GPU; a power above 27; judge the
+ * points' RELATIONS (groth16_ptau_verify and groth16_ptau_contributions do, on the unpacked file). */
+typedef struct {
+  uint64_t n;
+  int32_t  fault_kind;          /* after a faulty element: GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP */
+  uint64_t fault_index;         /* the lowest faulty element */
+  uint64_t fault_count;         /* how many elements are faulty */
+  double   upload_ms, device_ms, download_ms;
+} Groth16PointsPackReport;
+int groth16_points_pack(const void* points, uint64_t n, int g2, void* out, const char* device, Groth16PointsPackReport* report);
+int groth16_points_unpack(const void* packed, uint64_t n, int g2, void* out, const char* device, Groth16PointsPackReport* report);
+typedef struct {
+  uint32_t power;
+  int32_t  prepared;            /* 1: sections 12 to 15 are present */
+  uint64_t points[2];           /* G1 points, G2 points (section 6 included) */
+  uint64_t in_bytes, out_bytes; /* the input; the output (also when cap was too small) */
+  int32_t  fault_section, fault_kind;   /* after a faulty point: the section, and GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP */
+  uint64_t fault_index;                 /* the lowest faulty element of that section */
+  uint64_t fault_count;                 /* that section's faulty elements */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the sections' copies up; wall time of the device part without them, up to
+                                   the last kernel; the copies into the buffer or the mapped file; msync and rename (_file) */
+} Groth16PtauPackReport;
+int groth16_ptau_packed_size(uint32_t power, int prepared, uint64_t ptau_bytes, uint64_t* packed_bytes);
+int groth16_ptau_unpacked_size(uint32_t power, int prepared, uint64_t packed_bytes, uint64_t* ptau_bytes);
+int groth16_ptau_pack(const void* ptau, size_t len, void* out, size_t cap, const char* device, Groth16PtauPackReport* report);
+int groth16_ptau_pack_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPackReport* report);
+int groth16_ptau_unpack(const void* packed, size_t len, void* out, size_t cap, const char* device, Groth16PtauPackReport* report);
+int groth16_ptau_unpack_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPackReport* report);
+
 #ifdef __cplusplus
 }
 #endif
