@@ -643,6 +643,24 @@ class CacheManager:
                                              C.c_size_t(len(pj)), qj, C.c_size_t(len(qj)), C.byref(tm)), "prove_resident")
         return pj.value.decode(), qj.value.decode(), tm
 
+    def prove_packed(self, key: str, wtnz: bytes, r: int | None = None, s: int | None = None):
+        """groth16_prove_packed → (proof JSON, public JSON, Timings): prove_mem from a PACKED witness (wtns_pack), decoded on the
+        GPU into the key's resident witness buffer; afterwards prove_mem(resident=True) proves the same witness.  A faulty packed
+        witness raises ProverError (−2 "wtnz: element E: kind") and leaves no witness resident.  Single-device keys only (−3)."""
+        if not hasattr(self, "_bufs"):
+            self._bufs = (C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 20))
+        pj, qj = self._bufs
+        rb = int(r).to_bytes(32, "little") if r is not None else None
+        sb = int(s).to_bytes(32, "little") if s is not None else None
+        tm = Timings()
+        _pcheck(lib().groth16_prove_packed(self._h, key.encode(), _image(wtnz), C.c_size_t(len(wtnz)), rb, sb, pj, C.c_size_t(len(pj)), qj,
+                                           C.c_size_t(len(qj)), C.byref(tm)), "prove_packed")
+        return pj.value.decode(), qj.value.decode(), tm
+
+    def prove_packed_files(self, witness: str, zkey: str, proof: str, public: str, device: str = "HIP"):
+        """groth16_prove_packed_files: prove() with a packed witness file; a key the manager does not hold is loaded first"""
+        _pcheck(lib().groth16_prove_packed_files(witness.encode(), zkey.encode(), proof.encode(), public.encode(), device.encode(), self._h), "prove_packed_files")
+
     # ---- distributed QAP front end (2, 4 or 8 strided shards): see include/groth16_prover.h ----
     def dist_supported(self, key: str) -> bool:
         return bool(lib().groth16_dist_supported(self._h, key.encode()))
@@ -710,6 +728,9 @@ groth16_ptau_contribute groth16_ptau_contribute_file groth16_ptau_contributions
 groth16_ptau_verify groth16_ptau_verify_file
 groth16_points_pack groth16_points_unpack groth16_ptau_packed_size groth16_ptau_unpacked_size
 groth16_ptau_pack groth16_ptau_pack_file groth16_ptau_unpack groth16_ptau_unpack_file
+groth16_wtns_packed_size groth16_wtns_pack groth16_wtns_pack_file groth16_wtns_unpack_host groth16_wtns_unpack_host_file
+groth16_wtns_unpack groth16_wtns_unpack_file groth16_prove_packed groth16_prove_packed_files
+groth16_witness_check_packed groth16_witness_check_packed_file
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1021,6 +1042,14 @@ class R1cs:
         if isinstance(wtns, (str, os.PathLike)):
             return self._verdict(lib().groth16_witness_check_file(self._h, os.fsencode(wtns), C.byref(rep)), rep, "witness_check_file")
         return self._verdict(lib().groth16_witness_check(self._h, _image(wtns), C.c_size_t(len(wtns)), C.byref(rep)), rep, "witness_check")
+
+    def check_packed(self, wtnz):
+        """groth16_witness_check_packed → (ok, WitnessReport): check() of a PACKED witness (wtns_pack; the image, or a path), decoded
+        on the GPU.  A faulty packed witness raises ProverError (−2 "wtnz: element E: kind")."""
+        rep = WitnessReport()
+        if isinstance(wtnz, (str, os.PathLike)):
+            return self._verdict(lib().groth16_witness_check_packed_file(self._h, os.fsencode(wtnz), C.byref(rep)), rep, "witness_check_packed_file")
+        return self._verdict(lib().groth16_witness_check_packed(self._h, _image(wtnz), C.c_size_t(len(wtnz)), C.byref(rep)), rep, "witness_check_packed")
 
     def match_zkey(self, zkey, seed=None):
         """groth16_r1cs_match_zkey → (ok, MatchReport): the key's section 4 against this circuit's A and B.  seed: 32 bytes for a
@@ -1429,3 +1458,73 @@ def ptau_unpack(packed, out=None, device: str = "HIP"):
     """groth16_ptau_unpack → (ptau bytes | None, PtauPackReport): the .ptau a packed file came from, byte for byte: a square root per
     point on the GPU, which is also the on-curve test.  Arguments and errors as ptau_pack."""
     return _ptau_transcode("ptau_unpack", lib().groth16_ptau_unpack, lib().groth16_ptau_unpack_file, packed, out, device)
+
+
+class WtnsPackReport(C.Structure):
+    """Groth16WtnsPackReport: the value count, the input's and the output's bytes, the lowest faulty element with its kind and how
+    many are faulty, the stage times (device entries)"""
+    _fields_ = [("n_witness", C.c_uint32), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64),
+                ("fault_count", C.c_uint64), ("upload_ms", C.c_double), ("kernel_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double),
+                ("write_ms", C.c_double)]
+
+
+WTNZ_KINDS = ("", "CODE", "NONCANONICAL", "RANGE", "DIRECTORY")
+
+
+class WitnessFault(ProverError):
+    """a value refused by wtns_pack / wtns_unpack: .report names the lowest faulty element, its kind and the count"""
+    report = None
+
+
+def _wtns_check(rc, what, rep):
+    try:
+        _pcheck(rc, what)
+    except ProverError as e:
+        if rc == -2 and rep.fault_kind:
+            fault = WitnessFault(str(e))
+            fault.report = rep
+            raise fault from None
+        raise
+
+
+def _wtns_transcode(what, buffer_call, file_call, src, out):
+    rep = WtnsPackReport()
+    if isinstance(src, (str, os.PathLike)):
+        if out is None:
+            raise TypeError(f"{what}: an input path needs the path to write to")
+        _wtns_check(file_call(os.fsencode(src), os.fsencode(out), C.byref(rep)), what + "_file", rep)
+        return None, rep
+    if out is not None:
+        raise TypeError(f"{what}: `out` goes with an input path")
+    # sized by the library itself: a first call with no room reports the bytes it needs
+    rc = buffer_call(_image(src), C.c_size_t(len(src)), None, C.c_size_t(0), C.byref(rep))
+    if rc != -3 or rep.out_bytes == 0:
+        _wtns_check(rc, what, rep)
+    buf = C.create_string_buffer(rep.out_bytes)
+    _wtns_check(buffer_call(_image(src), C.c_size_t(len(src)), buf, C.c_size_t(rep.out_bytes), C.byref(rep)), what, rep)
+    return buf.raw[:rep.out_bytes], rep
+
+
+def wtns_packed_size(wtns) -> int:
+    """groth16_wtns_packed_size: the bytes of wtns_pack's output for this .wtns image; host only"""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_wtns_packed_size(_image(wtns), C.c_size_t(len(wtns)), C.byref(size)), "wtns_packed_size")
+    return size.value
+
+
+def wtns_pack(wtns, out=None):
+    """groth16_wtns_pack → (packed bytes | None, WtnsPackReport): a .wtns with a code byte per value and only the value's significant
+    bytes, magic "wtnz" (include/groth16_prover.h has the form); host only: needs no GPU.  wtns: the image, and the packed witness
+    comes back as bytes; or a path together with `out`, the path it is written to.  A value >= r raises WitnessFault (−2)."""
+    return _wtns_transcode("wtns_pack", lib().groth16_wtns_pack, lib().groth16_wtns_pack_file, wtns, out)
+
+
+def wtns_unpack(packed, out=None, device=None):
+    """groth16_wtns_unpack_host (device=None: on the host, no GPU is initialised) or groth16_wtns_unpack (device="HIP": sections 2 to
+    4 go up, one kernel decodes them) → (.wtns bytes | None, WtnsPackReport).  packed / out as wtns_pack.  A faulty value raises
+    WitnessFault (−2 "wtnz: element E: kind"), its .report naming the lowest faulty element and the count; nothing is written."""
+    if device is None:
+        return _wtns_transcode("wtns_unpack_host", lib().groth16_wtns_unpack_host, lib().groth16_wtns_unpack_host_file, packed, out)
+    dev = device.encode()
+    return _wtns_transcode("wtns_unpack", lambda p, n, o, c, r: lib().groth16_wtns_unpack(p, n, o, c, dev, r),
+                           lambda i, o, r: lib().groth16_wtns_unpack_file(i, o, dev, r), packed, out)

@@ -125,6 +125,11 @@ int assemble_impl(const ZKeyCache* z, const void* wtns, size_t wtns_len, const u
   Wtns w;
   if (int rc = parse_wtns((const uint8_t*)wtns, wtns_len, w)) return rc;
   if (w.n_witness != z->n_vars) return fail(ERR_FORMAT, "Invalid witness length");
+  return assemble_values(z, w.values, points, bl, proof_json, proof_cap, public_json, public_cap, et);
+}
+
+int assemble_values(const ZKeyCache* z, const uint8_t* values, const uint8_t* points, const Blinding& bl, char* proof_json, size_t proof_cap, char* public_json, size_t public_cap, const EarlyTerms* et)
+{
   typedef bn254_projective_t P1;
   typedef bn254_g2_projective_t P2;
   P1 pi_a, pi_b1, pi_c, pi_h, t2;
@@ -192,7 +197,7 @@ int assemble_impl(const ZKeyCache* z, const void* wtns, size_t wtns_len, const u
   // public signals: witness[1..=n_public] as decimal strings — src/proof_helper.rs:297-307
   std::string qj = z->n_public ? "[\n" : "[]";
   for (uint32_t i = 1; i <= z->n_public; i++) {
-    qj += "  \"" + dec(w.values + (size_t)i * 32) + "\"";
+    qj += "  \"" + dec(values + (size_t)i * 32) + "\"";
     qj += i == z->n_public ? "\n]" : ",\n";
   }
   int need = 0;

@@ -26,7 +26,7 @@ ZKeyCache::~ZKeyCache()
       if (t) (void)hipFree(t);
     for (hipStream_t st : streams())
       if (st) (void)hipStreamSynchronize(st);
-    for (void* p : {(void*)d_rowptr, (void*)d_cols, (void*)d_vals, A.d_points, B1.d_points, B2.d_points, C.d_points, H.d_points, (void*)d_witness, (void*)d_vec, (void*)d_fold, (void*)d_skeys, (void*)d_dist_y, (void*)d_dist_recv1, (void*)d_dist_send2, (void*)d_tw1, (void*)d_partials})
+    for (void* p : {(void*)d_rowptr, (void*)d_cols, (void*)d_vals, A.d_points, B1.d_points, B2.d_points, C.d_points, H.d_points, (void*)d_witness, (void*)d_vec, (void*)d_fold, (void*)d_skeys, (void*)d_dist_y, (void*)d_dist_recv1, (void*)d_dist_send2, (void*)d_tw1, (void*)d_partials, (void*)d_wtnz})
       if (p) (void)hipFree(p);
     if (h_partials) (void)hipHostFree(h_partials);
     for (hipStream_t st : streams())

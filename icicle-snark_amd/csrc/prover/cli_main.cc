@@ -30,6 +30,12 @@
 //   > ptau-pack --ptau IN --out OUT [--device HIP]       the file with every point as x and one bit of y, half the bytes
 //     (groth16_ptau_pack_file): one summary line, then PTAU_WRITTEN; a faulty point: PTAU_BAD POINT <section> <element>
 //   > ptau-unpack --packed IN --out OUT [--device HIP]   the .ptau back, byte for byte (groth16_ptau_unpack_file): the same lines
+//   > wtns-pack --wtns W --out Z              the witness with a code byte per value and only its significant bytes, on the host
+//     (groth16_wtns_pack_file): one summary line, then WTNS_WRITTEN; a value >= r: WTNS_BAD VALUE <element> <count>
+//   > wtns-unpack --packed Z --out W [--device HIP]   the .wtns back; on the host, or with --device decoded on the GPU
+//     (groth16_wtns_unpack_host_file / groth16_wtns_unpack_file): the same lines
+//   > prove-packed --witness Z --zkey K --proof P --public Q [--device HIP]   prove from a packed witness (groth16_prove_packed_files)
+//   > wtns-check --r1cs R --wtnz Z [--device HIP]     wtns-check from a packed witness (groth16_witness_check_packed_file)
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -40,7 +46,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -241,10 +247,11 @@ int main()
       }
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else if (cmd == "wtns-check" || cmd == "r1cs-match") {
-      std::string r1cs = "circuit.r1cs", wtns = "witness.wtns", zkey = "circuit_final.zkey", device = "HIP", a;
+      std::string r1cs = "circuit.r1cs", wtns = "witness.wtns", wtnz, zkey = "circuit_final.zkey", device = "HIP", a;
       while (in >> a) {
         if (a == "--r1cs") in >> r1cs;
         else if (a == "--wtns") in >> wtns;
+        else if (a == "--wtnz") in >> wtnz;
         else if (a == "--zkey") in >> zkey;
         else if (a == "--device") in >> device;
         else print_help();
@@ -255,7 +262,7 @@ int main()
         std::cerr << cmd << " failed (" << rc << "): " << groth16_last_error() << std::endl;
       } else if (cmd == "wtns-check") {
         Groth16WitnessReport rep;
-        rc = groth16_witness_check_file(h, wtns.c_str(), &rep);
+        rc = wtnz.empty() ? groth16_witness_check_file(h, wtns.c_str(), &rep) : groth16_witness_check_packed_file(h, wtnz.c_str(), &rep);
         if (rc < 0) {
           std::cerr << "wtns-check failed (" << rc << "): " << groth16_last_error() << std::endl;
         } else {
@@ -554,6 +561,43 @@ int main()
                   << std::endl;
         std::cout << "PTAU_WRITTEN" << std::endl;
       }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "wtns-pack" || cmd == "wtns-unpack") {
+      // pack is the host's; unpack is the host's too unless --device names a GPU
+      const bool unpack = cmd == "wtns-unpack";
+      std::string inp = unpack ? "witness.wtnz" : "witness.wtns", out = unpack ? "witness.wtns" : "witness.wtnz", device, a;
+      while (in >> a) {
+        if (a == (unpack ? "--packed" : "--wtns")) in >> inp;
+        else if (a == "--out") in >> out;
+        else if (a == "--device" && unpack) in >> device;
+        else print_help();
+      }
+      Groth16WtnsPackReport rep = {};
+      const int rc = !unpack          ? groth16_wtns_pack_file(inp.c_str(), out.c_str(), &rep)
+                     : device.empty() ? groth16_wtns_unpack_host_file(inp.c_str(), out.c_str(), &rep)
+                                      : groth16_wtns_unpack_file(inp.c_str(), out.c_str(), device.c_str(), &rep);
+      if (rc < 0) {
+        std::cerr << cmd << " failed (" << rc << "): " << groth16_last_error() << std::endl;
+        if (rep.fault_kind) std::cout << "WTNS_BAD VALUE " << rep.fault_index << " " << rep.fault_count << std::endl;
+      } else {
+        std::cout << "values " << rep.n_witness << " bytes " << rep.in_bytes << " to " << rep.out_bytes;
+        if (!device.empty()) std::cout << "; upload " << rep.upload_ms << " ms kernel " << rep.kernel_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms";
+        std::cout << " write " << rep.write_ms << " ms" << std::endl;
+        std::cout << "WTNS_WRITTEN" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "prove-packed") {
+      std::string witness = "witness.wtnz", zkey = "circuit_final.zkey", proof = "proof.json", pub = "public.json", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--witness") in >> witness;
+        else if (a == "--zkey") in >> zkey;
+        else if (a == "--proof") in >> proof;
+        else if (a == "--public") in >> pub;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      const int rc = groth16_prove_packed_files(witness.c_str(), zkey.c_str(), proof.c_str(), pub.c_str(), device.c_str(), cm);
+      if (rc != 0) std::cerr << "prove-packed failed (" << rc << "): " << groth16_last_error() << std::endl;
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {
       print_help();

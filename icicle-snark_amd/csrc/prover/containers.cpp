@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include "prover_internal.h"
+#include "wtns_pack.h"
 
 using namespace bn254;
 using namespace isnark;
@@ -336,6 +337,48 @@ int parse_wtns(const uint8_t* data, size_t len, Wtns& w)
   if (v->size != (uint64_t)w.n_witness * 32) return fail(ERR_FORMAT, "wtns: section 2 size mismatch");
   w.values = v->p;
   return 0;
+}
+
+// sections, header and directory of a PACKED witness (prover_internal.h: WtnzLayout; wtns_pack.h): everything a decoder — the host's
+// or the kernel — relies on is bounded here, before a byte goes up
+int wtnz_layout(const uint8_t* data, size_t len, WtnzLayout* L)
+{
+  if (!data) return fail(ERR_ARG, "null wtnz");
+  std::vector<Section> s;
+  if (int rc = read_sections(data, len, "wtnz", 1, s)) return rc;
+  const Section* sec[5];
+  for (size_t id = 1; id <= 4; id++)
+    if (int rc = unique_section(s, id, &sec[id])) return rc;
+  if (sec[1]->size >= 4) memcpy(&L->n8, sec[1]->p, 4);
+  if (L->n8 != 32 || sec[1]->size != 4 + 32 + 4) return fail(ERR_FORMAT, "wtnz: unsupported field size %u", L->n8);
+  L->header = sec[1]->p;
+  memcpy(L->q.l, sec[1]->p + 4, 32);
+  memcpy(&L->n_witness, sec[1]->p + 36, 4);
+  L->n_blocks = ((uint64_t)L->n_witness + wz::WZ_BLOCK - 1) / wz::WZ_BLOCK;
+  if (sec[2]->size != L->n_witness)
+    return fail(ERR_FORMAT, "wtnz: section 2 holds %llu bytes, %u values have %u codes", (unsigned long long)sec[2]->size, L->n_witness, L->n_witness);
+  if (sec[3]->size != (L->n_blocks + 1) * 8)
+    return fail(ERR_FORMAT, "wtnz: section 3 holds %llu bytes, the directory of %u values has %llu", (unsigned long long)sec[3]->size, L->n_witness, (unsigned long long)((L->n_blocks + 1) * 8));
+  L->codes = sec[2]->p;
+  L->dir = sec[3]->p;
+  L->payload = sec[4]->p;
+  L->payload_bytes = sec[4]->size;
+  uint64_t at = 0;
+  switch (wz::wz_check_directory(L->dir, L->n_blocks, L->payload_bytes, &at)) {
+  case 0: break;
+  case 1: return fail(ERR_FORMAT, "wtnz: directory entry 0 is %llu, not 0", (unsigned long long)wz::wz_dir_entry(L->dir, 0));
+  case 2: return fail(ERR_FORMAT, "wtnz: directory entry %llu is below entry %llu", (unsigned long long)at, (unsigned long long)(at - 1));
+  case 3:
+    return fail(ERR_FORMAT, "wtnz: block %llu spans %llu bytes, %u is the most", (unsigned long long)at, (unsigned long long)(wz::wz_dir_entry(L->dir, at + 1) - wz::wz_dir_entry(L->dir, at)),
+                wz::WZ_MAX_SPAN);
+  default:
+    return fail(ERR_FORMAT, "wtnz: the directory ends at %llu, section 4 holds %llu bytes", (unsigned long long)wz::wz_dir_entry(L->dir, L->n_blocks), (unsigned long long)L->payload_bytes);
+  }
+  return 0;
+}
+int wtnz_is_bn254(const WtnzLayout& L)
+{
+  return Fr::eq(L.q, Fr::modulus()) ? 0 : fail(ERR_FORMAT, "wtnz: the prime is not the BN254 scalar field's");
 }
 
 } // namespace prover

@@ -27,6 +27,7 @@
 #include <unistd.h>
 
 #include "prover_internal.h"
+#include "wtns_pack.h"
 #include "../workers.h"
 
 using namespace bn254;
@@ -1492,6 +1493,92 @@ __attribute__((visibility("default"))) int groth16_prove(const char* witness_pat
   if (trace_host) fprintf(stderr, "[host] prove: proof assembled        %8.1f us\n", ms_since(t0) * 1e3);
   if (int rc = write_json_pair(proof_path, pj.data(), public_path, qj.data())) return rc;
   if (trace_host) fprintf(stderr, "[host] prove: files written          %8.1f us\n", ms_since(t0) * 1e3);
+  print_proof_took(t0);
+  return 0;
+}
+
+// groth16_prove_mem from a PACKED witness (include/groth16_prover.h; wtns_pack.hip has the decode): sections 2 … 4 go up, one
+// kernel decodes them into the entry's d_witness on the entry's front-end stream, and the resident prove runs — decode and
+// commitments under ONE hold of the manager's mutex.
+__attribute__((visibility("default"))) int groth16_prove_packed(Groth16CacheManager* cm, const char* key, const void* wtnz, size_t len, const uint8_t* r, const uint8_t* s, char* proof_json,
+                                                                size_t proof_cap, char* public_json, size_t public_cap, Groth16Timings* tm)
+{
+  uint8_t pts[GROTH16_COMMITMENTS_BYTES];
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!cm || !wtnz) return fail(ERR_ARG, "null argument");
+  if (find_group(cm, key)) return fail(ERR_ARG, "cache entry '%s' is a device group: groth16_prove_packed takes single-device keys", key ? key : "");
+  const std::shared_ptr<ZKeyCache> zp = find(cm, key);
+  ZKeyCache* z = zp.get();
+  if (!z) return fail(ERR_NOCACHE, "no cache entry '%s'", key ? key : "");
+  if (z->shard_count != 1) return fail(ERR_ARG, "cache entry '%s' is shard %d of %d: groth16_prove_packed takes single-device keys", key ? key : "", z->shard_rank, z->shard_count);
+  WtnzLayout L;
+  if (int rc = wtnz_layout((const uint8_t*)wtnz, len, &L)) return rc;
+  Wtns w;
+  w.n8 = L.n8, w.n_witness = L.n_witness, w.q = L.q;
+  if (int rc = check_witness(z, w)) return rc;
+  Blinding bl;
+  EarlyTerms et;
+  double decode_ms = 0;
+  {
+    std::lock_guard<std::mutex> lk(cm->mu);
+    if (int rc = set_active_device(z->device_id)) return rc;
+    // what a fresh upload resets (receive_witness): nothing of the previous witness counts from here on
+    z->witness_resident = false;
+    z->dist_ready = z->dist_stage2_done = false;
+    z->witness_event_set = false;
+    const size_t need = wtnz_device_bytes(L);
+    if (need > z->wtnz_cap) {
+      if (z->d_wtnz) P_HIP(hipFree(z->d_wtnz));
+      z->d_wtnz = nullptr, z->device_bytes -= z->wtnz_cap, z->wtnz_cap = 0;
+      P_HIP(hipMalloc((void**)&z->d_wtnz, need));
+      z->wtnz_cap = need, z->device_bytes += need;
+    }
+    const auto td = std::chrono::steady_clock::now();
+    WtnzFault f;
+    if (int rc = wtnz_decode_on_device(z->device_id, z->s_qap, L, z->d_wtnz, z->d_witness, &f, nullptr, nullptr)) return rc;
+    if (f.kind) return wtnz_fail(f); // (every verdict is in: nothing is resident, nothing is proved)
+    decode_ms = ms_since(td);
+    z->witness_resident = true;
+    if (int rc = blinded_commitments(cm, nullptr, z, nullptr, 0, r, s, /*take_mu=*/false, nullptr, pts, tm, &bl, &et)) return rc;
+  }
+  // the public signals, decoded on the host (the device has passed every element: no fault is left to find)
+  std::vector<uint8_t> pub(((size_t)z->n_public + 1) * 32);
+  bn254::wz::WzView view;
+  view.n = L.n_witness, view.codes = L.codes, view.dir = L.dir, view.payload = L.payload;
+  uint64_t bad = 0;
+  if (bn254::wz::wz_decode_host(view, 0, (uint64_t)z->n_public + 1, pub.data(), &bad, nullptr)) return fail(ERR_FORMAT, "wtnz: element %llu: the host and the device disagree", (unsigned long long)bad);
+  const int rc = assemble_values(z, pub.data(), pts, bl, proof_json, proof_cap, public_json, public_cap, &et);
+  if (tm) tm->h2d_ms = decode_ms, tm->total_ms = ms_since(t0);
+  return rc;
+}
+
+// groth16_prove with a packed witness, file to file; no cold-path overlap: a key the manager does not hold is loaded first
+__attribute__((visibility("default"))) int groth16_prove_packed_files(const char* witness_path, const char* zkey_path, const char* proof_path, const char* public_path, const char* device,
+                                                                      Groth16CacheManager* cm)
+{
+  if (!witness_path || !zkey_path || !proof_path || !public_path || !device || !cm) return fail(ERR_ARG, "null argument");
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<int> devs;
+  if (int rc = parse_device_string(device, devs)) return rc;
+  if (devs.size() != 1) return fail(ERR_ARG, "device '%s' names %zu devices: groth16_prove_packed_files takes single-device keys", device, devs.size());
+  P_ICICLE(icicle_load_backend_from_env_or_default());
+  if (int rc = set_active_device(devs[0])) return rc;
+  const std::string key = std::string(zkey_path) + "_" + device;
+  if (!groth16_cache_contains(cm, key.c_str()))
+    if (int rc = groth16_cache_load_file(cm, key.c_str(), zkey_path, devs[0], 0, 1)) return rc;
+  MappedFile wf;
+  if (int rc = wf.open_ro(witness_path)) return rc;
+  std::vector<char> pj(4096), qj(256);
+  {
+    Groth16CircuitInfo info;
+    if (int rc = groth16_cache_info(cm, key.c_str(), &info)) return rc;
+    qj.resize(64 + (size_t)info.n_public * 84);
+  }
+  staged_copy_file_hint(wf.data, wf.len, wf.fd);
+  const int prc = groth16_prove_packed(cm, key.c_str(), wf.data, wf.len, nullptr, nullptr, pj.data(), pj.size(), qj.data(), qj.size(), nullptr);
+  staged_copy_file_hint(nullptr, 0, -1);
+  if (prc) return prc;
+  if (int rc = write_json_pair(proof_path, pj.data(), public_path, qj.data())) return rc;
   print_proof_took(t0);
   return 0;
 }

@@ -101,6 +101,34 @@ struct Wtns {
   const uint8_t* values = nullptr; // n_witness × 32 B standard form
 };
 int parse_wtns(const uint8_t* data, size_t len, Wtns& w);
+// A PACKED witness (wtns_pack.h has the value's form; include/groth16_prover.h the container): the section table under magic "wtnz",
+// version 1 — a .wtns is refused as any foreign magic is, and parse_wtns takes none of these — sections 1 … 4 once each; section 1
+// is a .wtns header (n8 = 32, 40 bytes); section 2 holds n_witness codes; section 3 the directory of n_blocks + 1 u64; and the
+// directory begins at 0, never decreases, spans at most 8192 bytes a block and ends at section 4's size (ERR_FORMAT, each with its
+// own text).  The prime is read, not judged: wtnz_is_bn254 / check_witness do that.  Every pointer leads into the caller's `data`.
+struct WtnzLayout {
+  uint32_t n8 = 0, n_witness = 0;
+  fe q;
+  const uint8_t* header = nullptr;  // section 1, 40 bytes
+  const uint8_t* codes = nullptr;   // n_witness bytes
+  const uint8_t* dir = nullptr;     // (n_blocks + 1) × u64, unaligned
+  const uint8_t* payload = nullptr; // payload_bytes
+  uint64_t n_blocks = 0, payload_bytes = 0;
+};
+int wtnz_layout(const uint8_t* data, size_t len, WtnzLayout* L);
+int wtnz_is_bn254(const WtnzLayout& L); // ERR_FORMAT unless the header's prime is r
+// ---- the decode on a device (wtns_pack.hip)
+// The fault of a decode: kind 0 = none, else GROTH16_WTNZ_* of the LOWEST faulty element, and how many there are
+struct WtnzFault {
+  int kind = 0;
+  uint64_t element = 0, count = 0;
+};
+int wtnz_fail(const WtnzFault& f); // ERR_FORMAT "wtnz: element E: kind"
+size_t wtnz_device_bytes(const WtnzLayout& L); // the room wtnz_decode_on_device wants at d_buf (a hipMalloc'd base)
+// Sections 2 … 4 up into d_buf (pinned staging; landed on return), ONE launch on `st` that writes n_witness standard-form values to
+// d_out, the tally down: synchronous.  0 and *fault, or a device error.  upload_ms / kernel_ms (may be null; kernel_ms costs two
+// events) are ADDED to / set.  The caller has made `dev` the active device.
+int wtnz_decode_on_device(int dev, hipStream_t st, const WtnzLayout& L, uint8_t* d_buf, fe* d_out, WtnzFault* fault, double* upload_ms, double* kernel_ms);
 // What an .r1cs says about itself (iden3 binary format): the header's fields and section 2, the constraints —
 // n_constraints × {A, B, C}, each linear combination a u32 count and count × {u32 wire, 32-byte standard-form value}.
 // r1cs_layout checks the container, section 1 and 2 present once, the field; r1cs_walk bounds every record (containers.cpp).
@@ -200,6 +228,8 @@ struct ZKeyCache {
   fe* d_vals = nullptr;         // n_coef, Montgomery form
   Shard A, B1, B2, C, H;
   fe* d_witness = nullptr; // n_vars
+  uint8_t* d_wtnz = nullptr; // sections 2 … 4 of a packed witness on their way into d_witness (groth16_prove_packed): grown on demand
+  size_t wtnz_cap = 0;
   fe* d_vec = nullptr;     // 3n
   fe* d_fold = nullptr;    // 3·n/G: folded rows of a strided H shard (qap_coset_fold3)
   // distributed front end (groth16_dist_stage1/2; strided H shards only): Y rows of stage 1, what exchange 1 delivers,
@@ -305,6 +335,9 @@ void early_pi_b(const ZKeyCache* z, const Blinding& bl, const bn254_g2_projectiv
 int compute_blinding(const ZKeyCache* z, const uint8_t* r_in, const uint8_t* s_in, Blinding* b);
 int assemble_impl(const ZKeyCache* z, const void* wtns, size_t wtns_len, const uint8_t* points, const Blinding& bl, char* proof_json, size_t proof_cap, char* public_json, size_t public_cap,
                   const EarlyTerms* et = nullptr);
+// the same from the witness's first n_public + 1 values (32 bytes each, standard form) instead of a .wtns image
+int assemble_values(const ZKeyCache* z, const uint8_t* values, const uint8_t* points, const Blinding& bl, char* proof_json, size_t proof_cap, char* public_json, size_t public_cap,
+                    const EarlyTerms* et = nullptr);
 
 // ---- one device (prover.cpp)
 struct DeviceGroup; // multi.cpp

@@ -242,6 +242,8 @@ int r1cs_load_impl(const uint8_t* data, size_t len, const char* device, Groth16R
   return 0;
 }
 
+int check_resident_values(Groth16R1cs* h, Groth16WitnessReport* rep, std::chrono::steady_clock::time_point t_dev);
+
 int witness_check_impl(Groth16R1cs* h, const uint8_t* wtns, size_t wtns_len, Groth16WitnessReport* rep)
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
@@ -257,6 +259,12 @@ int witness_check_impl(Groth16R1cs* h, const uint8_t* wtns, size_t wtns_len, Gro
   if (ds.open(h->dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
   if (int rc = reset_tally(h)) return rc;
   if (int rc = pv::timed_upload(h->dev, h->d_w, w.values, (size_t)h->n_wires * 32, &rep->upload_ms)) return rc;
+  return check_resident_values(h, rep, t_dev);
+}
+
+// the witness check over the n_wires values at h->d_w; the caller holds h->mu and the session, and has reset the tally
+int check_resident_values(Groth16R1cs* h, Groth16WitnessReport* rep, std::chrono::steady_clock::time_point t_dev)
+{
   DEV_LAUNCH("range kernel launch", witness_range_kernel, dim3((h->n_wires + 255) / 256), dim3(256), h->st, h->d_w, h->n_wires, h->d_tally);
   Tally t;
   if (int rc = read_tally(h, &t, "range kernel")) return rc;
@@ -272,6 +280,30 @@ int witness_check_impl(Groth16R1cs* h, const uint8_t* wtns, size_t wtns_len, Gro
   else if (t.not_one) rep->kind = GROTH16_WTNS_ONE, rep->index = 0;
   else if (t.failed) rep->kind = GROTH16_WTNS_CONSTRAINT, rep->index = t.first_failed;
   return rep->kind ? 0 : 1;
+}
+
+// the same from a PACKED witness (wtns_pack.hip): sections 2 … 4 up, the decode into h->d_w, then the check as it is
+int witness_check_packed_impl(Groth16R1cs* h, const uint8_t* wtnz, size_t len, Groth16WitnessReport* rep)
+{
+  if (!rep) return pv::fail(pv::ERR_ARG, "null report");
+  memset(rep, 0, sizeof *rep);
+  if (!h) return pv::fail(pv::ERR_ARG, "null r1cs handle");
+  if (!wtnz) return pv::fail(pv::ERR_ARG, "null wtnz");
+  pv::WtnzLayout L;
+  if (int rc = pv::wtnz_layout(wtnz, len, &L)) return rc;
+  if (int rc = pv::wtnz_is_bn254(L)) return rc;
+  if (L.n_witness != h->n_wires) return pv::fail(pv::ERR_ARG, "the witness has %u values, the circuit %u wires", L.n_witness, h->n_wires);
+  std::lock_guard<std::mutex> lk(h->mu);
+  const auto t_dev = std::chrono::steady_clock::now();
+  isnark::vb::DeviceSession ds;
+  if (ds.open(h->dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = reset_tally(h)) return rc;
+  uint8_t* d_buf = ds.buf.alloc<uint8_t>(pv::wtnz_device_bytes(L)); // this call's: freed with the session
+  if (!d_buf) return dev_fail("hipMalloc", hipErrorOutOfMemory);
+  pv::WtnzFault f;
+  if (int rc = pv::wtnz_decode_on_device(h->dev, h->st, L, d_buf, h->d_w, &f, &rep->upload_ms, nullptr)) return rc;
+  if (f.kind) return pv::wtnz_fail(f);
+  return check_resident_values(h, rep, t_dev);
 }
 
 int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8_t* seed32, Groth16R1csMatchReport* rep)
@@ -393,4 +425,18 @@ ISNARK_API int groth16_witness_check_file(Groth16R1cs* h, const char* wtns_path,
   if (int rc = mf.open_ro(wtns_path)) return rc;
   const pv::FileHint hint(mf.data, mf.len, mf.fd);
   return witness_check_impl(h, mf.data, mf.len, report);
+}
+
+ISNARK_API int groth16_witness_check_packed(Groth16R1cs* h, const void* wtnz, size_t len, Groth16WitnessReport* report)
+{
+  return witness_check_packed_impl(h, (const uint8_t*)wtnz, len, report);
+}
+
+ISNARK_API int groth16_witness_check_packed_file(Groth16R1cs* h, const char* wtnz_path, Groth16WitnessReport* report)
+{
+  if (!wtnz_path) return pv::fail(pv::ERR_ARG, "null path");
+  pv::MappedFile mf;
+  if (int rc = mf.open_ro(wtnz_path)) return rc;
+  const pv::FileHint hint(mf.data, mf.len, mf.fd);
+  return witness_check_packed_impl(h, mf.data, mf.len, report);
 }

@@ -1,0 +1,425 @@
+// wtns_pack.hip — a witness PACKED ("wtnz"): groth16_wtns_packed_size / _pack / _unpack_host (host only: they never initialise a
+// GPU), groth16_wtns_unpack (one device) and wtnz_decode_on_device, the decode groth16_prove_packed (prover.cpp) and
+// groth16_witness_check_packed (r1cs_check.hip) put in front of their unchanged device work.  include/groth16_prover.h has the
+// contract and the container; wtns_pack.h the value's form and its lane code; containers.cpp the reader; DESIGN.md §7k.
+//
+//   host, first  wtnz_layout bounds every section and the whole directory before a byte goes up: block b's payload
+//                [dir[b], dir[b + 1]) lies inside section 4 and is at most 8192 bytes, whatever the codes say.
+//   device       sections 2 … 4 go up and through ONE launch: a 256-lane workgroup per block, a lane per value.  The lane's code
+//                gives its length; an exclusive scan of the 256 lengths — wave scans, four wave sums through LDS — gives its
+//                offset, and the block's sum is compared with the directory span BEFORE any payload byte is read (a block whose
+//                sum differs tallies DIRECTORY at its first element, writes zeros and reads nothing).  The block's payload comes
+//                into LDS in aligned 16-byte loads (the buffer is padded and zeroed to the load width: the aligned over-read at
+//                either end stays inside the allocation); each lane assembles its eight words from LDS, runs wz_decode_value and
+//                stores its 32 bytes — consecutive lanes, consecutive rows.  A faulty lane writes zeros and tallies: the lowest
+//                (element << 3 | kind) and a count.
+//   host, last   ALL verdicts are read before the result is used or anything is written.
+#include <chrono>
+#include <functional>
+#include <string>
+#include <sys/stat.h>
+#include <vector>
+
+#include "device_call.h"
+#include "prover_internal.h"
+#include "ptau_ranges.h"
+#include "verify_batch.h"
+#include "wtns_pack.h"
+
+using namespace bn254;
+
+namespace {
+
+namespace pv = isnark::prover;
+namespace vb = isnark::vb;
+
+constexpr int WZ_WG = (int)wz::WZ_BLOCK;
+// the block's payload in LDS: 8192 bytes, up to 15 in front of it (the aligned load begins below the span) and the word behind a
+// lane's last one (the funnel shift reads it): byte 15 + 8192 + 7 at the most
+constexpr int WZ_LDS_VEC = 516;
+
+struct Tally {
+  unsigned long long first, count; // min over the faulty lanes of (element << 3 | kind), NO_FAULT without one; their number
+};
+__device__ __forceinline__ void tally_fault(Tally* t, uint64_t i, int kind)
+{
+  atomicAdd(&t->count, 1ull);
+  atomicMin(&t->first, (unsigned long long)i << 3 | (unsigned long long)kind);
+}
+
+// Block blockIdx.x of a packed witness → out[256·b … 256·b + 255] (standard form), i < n.  `payload` is 16-byte aligned and the
+// allocation reaches the next multiple of 16 behind its last byte; `dir` has passed wz_check_directory.
+__global__ __launch_bounds__(WZ_WG) void wz_unpack_kernel(const uint8_t* __restrict__ codes, const unsigned long long* __restrict__ dir, const uint8_t* __restrict__ payload, uint32_t n,
+                                                          fe* __restrict__ out, Tally* __restrict__ tally)
+{
+  __shared__ uint4 s_pay[WZ_LDS_VEC];
+  __shared__ uint32_t s_wave[WZ_WG / 64];
+  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint64_t i = (uint64_t)blockIdx.x * WZ_WG + t;
+  const bool live = i < n;
+  const uint8_t code = live ? codes[i] : wz::WZ_CODE_ZERO;
+  const int cl = wz::wz_code_len(code);
+  const uint32_t len = cl > 0 ? (uint32_t)cl : 0;
+
+  // exclusive scan of the 256 lengths: inclusive inside each wave, the four wave sums through LDS
+  uint32_t incl = len;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(incl, d, 64);
+    if (lane >= (uint32_t)d) incl += y;
+  }
+  if (lane == 63) s_wave[wv] = incl;
+  __syncthreads();
+  uint32_t base = 0, total = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < WZ_WG / 64; w++) {
+    const uint32_t sw = s_wave[w];
+    if (w < wv) base += sw;
+    total += sw;
+  }
+  const uint32_t off = base + incl - len;
+
+  const unsigned long long lo = dir[blockIdx.x], hi = dir[blockIdx.x + 1];
+  fe row;
+#pragma unroll
+  for (int k = 0; k < 8; k++) row.l[k] = 0;
+  if ((unsigned long long)total != hi - lo) { // the same in every lane of the workgroup: nothing of the payload is read
+    if (t == 0) tally_fault(tally, i, wz::WZ_DIRECTORY);
+    if (live) out[i] = row;
+    return;
+  }
+  // the block's payload, from the 16-byte boundary at or below its first byte to the one at or above its last
+  const uint32_t head = (uint32_t)(lo & 15);
+  if (total) {
+    const uint4* src = (const uint4*)(payload + (lo - head));
+    const uint32_t nvec = (head + total + 15) >> 4; // ≤ 513
+    for (uint32_t v = t; v < nvec; v += WZ_WG) s_pay[v] = src[v];
+  }
+  __syncthreads();
+  if (!live) return;
+  uint32_t pay[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) pay[k] = 0;
+  if (len) {
+    const uint32_t* words = (const uint32_t*)s_pay;
+    const uint32_t p = head + off, w0 = p >> 2, sh = (p & 3) * 8;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; k++)
+      if (4 * k < len) {
+        const uint32_t a = words[w0 + k], b = words[w0 + k + 1];
+        uint32_t w = sh ? (a >> sh) | (b << (32 - sh)) : a;
+        const uint32_t rem = len - 4 * k;
+        if (rem < 4) w &= (1u << (8 * rem)) - 1;
+        pay[k] = w;
+      }
+  }
+  if (const int kind = wz::wz_decode_value(code, pay, row.l)) tally_fault(tally, i, kind);
+  out[i] = row;
+}
+
+inline size_t pad16(size_t x) { return (x + 15) & ~(size_t)15; }
+struct DeviceLayout { // of d_buf
+  size_t tally = 0, dir, codes, payload, total;
+  explicit DeviceLayout(const pv::WtnzLayout& L)
+  {
+    dir = 16;
+    codes = dir + pad16((size_t)(L.n_blocks + 1) * 8);
+    payload = codes + pad16(L.n_witness) + 16;
+    total = payload + pad16((size_t)L.payload_bytes) + 16;
+  }
+};
+
+const char* const WZ_FAULT[5] = {"", "an undefined code byte", "the value's form is not canonical", "32 bytes that are not below r",
+                                 "the block's lengths do not sum to its directory span"};
+
+} // namespace
+
+namespace isnark {
+namespace prover {
+
+int wtnz_fail(const WtnzFault& f) { return fail(ERR_FORMAT, "wtnz: element %llu: %s", (unsigned long long)f.element, WZ_FAULT[f.kind >= 0 && f.kind < 5 ? f.kind : 0]); }
+
+size_t wtnz_device_bytes(const WtnzLayout& L) { return DeviceLayout(L).total; }
+
+int wtnz_decode_on_device(int dev, hipStream_t st, const WtnzLayout& L, uint8_t* d_buf, fe* d_out, WtnzFault* fault, double* upload_ms, double* kernel_ms)
+{
+  *fault = WtnzFault();
+  if (kernel_ms) *kernel_ms = 0;
+  if (!L.n_witness) return 0;
+  const DeviceLayout D(L);
+  Tally t = {NO_FAULT, 0};
+  DEV_TRY("tally upload", hipMemcpyAsync(d_buf + D.tally, &t, sizeof t, hipMemcpyHostToDevice, st));
+  // the padding behind the codes and behind the payload: what an aligned over-read sees is zero
+  DEV_TRY("hipMemsetAsync", hipMemsetAsync(d_buf + D.codes + L.n_witness, 0, D.payload - D.codes - L.n_witness, st));
+  DEV_TRY("hipMemsetAsync", hipMemsetAsync(d_buf + D.payload + L.payload_bytes, 0, D.total - D.payload - (size_t)L.payload_bytes, st));
+  const auto t_up = std::chrono::steady_clock::now();
+  const CopyJob jobs[3] = {{d_buf + D.codes, L.codes, L.n_witness}, {d_buf + D.dir, L.dir, (size_t)(L.n_blocks + 1) * 8}, {d_buf + D.payload, L.payload, (size_t)L.payload_bytes}};
+  if (hipError_t he = staged_copy(dev, jobs, L.payload_bytes ? 3 : 2, true)) return dev_fail("host to device upload", he);
+  if (upload_ms) *upload_ms += ms_since(t_up);
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct DestroyEvents {
+    hipEvent_t* e;
+    ~DestroyEvents()
+    {
+      for (int k = 0; k < 2; k++)
+        if (e[k]) (void)hipEventDestroy(e[k]);
+    }
+  } destroy{ev};
+  if (kernel_ms) {
+    DEV_TRY("hipEventCreate", hipEventCreate(&ev[0]));
+    DEV_TRY("hipEventCreate", hipEventCreate(&ev[1]));
+    DEV_TRY("hipEventRecord", hipEventRecord(ev[0], st));
+  }
+  DEV_LAUNCH("unpack kernel launch", wz_unpack_kernel, dim3((uint32_t)L.n_blocks), dim3(WZ_WG), st, (const uint8_t*)(d_buf + D.codes), (const unsigned long long*)(d_buf + D.dir),
+             (const uint8_t*)(d_buf + D.payload), L.n_witness, d_out, (Tally*)(d_buf + D.tally));
+  if (kernel_ms) DEV_TRY("hipEventRecord", hipEventRecord(ev[1], st));
+  DEV_TRY("download", hipMemcpyAsync(&t, d_buf + D.tally, sizeof t, hipMemcpyDeviceToHost, st));
+  DEV_TRY("unpack kernel", hipStreamSynchronize(st));
+  if (kernel_ms) {
+    float ms = 0;
+    DEV_TRY("hipEventElapsedTime", hipEventElapsedTime(&ms, ev[0], ev[1]));
+    *kernel_ms = ms;
+  }
+  if (t.first != NO_FAULT) fault->kind = (int)(t.first & 7), fault->element = t.first >> 3, fault->count = t.count;
+  return 0;
+}
+
+} // namespace prover
+} // namespace isnark
+
+namespace {
+
+constexpr uint64_t WTNS_HEAD = 12 + (12 + 40) + 12;  // a .wtns of sections 1 and 2 up to its first value
+constexpr uint64_t WTNZ_HEAD = 12 + 4 * 12 + 40;     // a packed witness without its codes, directory and payload
+
+typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+
+void put_section(uint8_t*& w, uint32_t id, uint64_t size)
+{
+  memcpy(w, &id, 4);
+  memcpy(w + 4, &size, 8);
+  w += 12;
+}
+
+// ---- pack (host)
+// the codes, the directory and the payload's size of a .wtns' values; a value >= r is ERR_FORMAT naming the lowest
+int pack_scan(const pv::Wtns& w, std::vector<uint8_t>* codes, std::vector<uint64_t>& dir, Groth16WtnsPackReport* rep)
+{
+  const uint64_t n = w.n_witness, nb = (n + wz::WZ_BLOCK - 1) / wz::WZ_BLOCK;
+  if (!Fr::eq(w.q, Fr::modulus())) return pv::fail(pv::ERR_FORMAT, "wtns: the prime is not the BN254 scalar field's");
+  if (codes) codes->resize((size_t)n);
+  dir.assign((size_t)nb + 1, 0);
+  uint64_t pos = 0, bad = 0, first_bad = 0;
+  for (uint64_t e = 0; e < n; e++) {
+    if (e % wz::WZ_BLOCK == 0) dir[(size_t)(e / wz::WZ_BLOCK)] = pos;
+    uint8_t code = 0, pay[32];
+    const int len = wz::wz_encode_value(w.values + 32 * e, &code, pay);
+    if (len < 0) {
+      if (!bad++) first_bad = e;
+      continue;
+    }
+    if (codes) (*codes)[(size_t)e] = code;
+    pos += (uint64_t)len;
+  }
+  dir[(size_t)nb] = pos;
+  if (bad) {
+    if (rep) rep->fault_kind = GROTH16_WTNZ_RANGE, rep->fault_index = first_bad, rep->fault_count = bad;
+    return pv::fail(pv::ERR_FORMAT, "wtns: element %llu is not below r", (unsigned long long)first_bad);
+  }
+  return 0;
+}
+
+int pack_impl(const uint8_t* data, size_t len, Groth16WtnsPackReport* rep, const Sink& sink)
+{
+  if (!rep) return pv::fail(pv::ERR_ARG, "null report");
+  memset(rep, 0, sizeof *rep);
+  if (!data) return pv::fail(pv::ERR_ARG, "null wtns");
+  pv::Wtns w;
+  if (int rc = pv::parse_wtns(data, len, w)) return rc;
+  rep->n_witness = w.n_witness;
+  rep->in_bytes = len;
+  std::vector<uint8_t> codes;
+  std::vector<uint64_t> dir;
+  if (int rc = pack_scan(w, &codes, dir, rep)) return rc;
+  const uint64_t payload = dir.back();
+  rep->out_bytes = WTNZ_HEAD + codes.size() + 8 * dir.size() + payload;
+  uint8_t* out = nullptr;
+  if (int rc = sink(rep->out_bytes, &out)) return rc;
+  uint8_t* p = out;
+  const uint32_t version = 1, nsec = 4;
+  memcpy(p, "wtnz", 4);
+  memcpy(p + 4, &version, 4);
+  memcpy(p + 8, &nsec, 4);
+  p += 12;
+  put_section(p, 1, 40); // the .wtns header byte for byte (parse_wtns has demanded exactly these 40 bytes)
+  memcpy(p, &w.n8, 4);
+  memcpy(p + 4, w.q.l, 32);
+  memcpy(p + 36, &w.n_witness, 4);
+  p += 40;
+  put_section(p, 2, codes.size());
+  if (!codes.empty()) memcpy(p, codes.data(), codes.size());
+  p += codes.size();
+  put_section(p, 3, 8 * dir.size());
+  memcpy(p, dir.data(), 8 * dir.size());
+  p += 8 * dir.size();
+  put_section(p, 4, payload);
+  for (uint64_t e = 0; e < w.n_witness; e++) {
+    uint8_t code, pay[32];
+    const int l = wz::wz_encode_value(w.values + 32 * e, &code, pay);
+    memcpy(p, pay, (size_t)l);
+    p += l;
+  }
+  return 0;
+}
+
+// ---- unpack: the .wtns a packed witness came from, sections 1 and 2 under version 2
+void put_wtns_head(uint8_t* out, const pv::WtnzLayout& L)
+{
+  const uint32_t version = 2, nsec = 2;
+  memcpy(out, "wtns", 4);
+  memcpy(out + 4, &version, 4);
+  memcpy(out + 8, &nsec, 4);
+  uint8_t* p = out + 12;
+  put_section(p, 1, 40);
+  memcpy(p, L.header, 40);
+  p += 40;
+  put_section(p, 2, (uint64_t)L.n_witness * 32);
+}
+
+int unpack_prologue(const uint8_t* data, size_t len, Groth16WtnsPackReport* rep, pv::WtnzLayout* L)
+{
+  if (!rep) return pv::fail(pv::ERR_ARG, "null report");
+  memset(rep, 0, sizeof *rep);
+  if (int rc = pv::wtnz_layout(data, len, L)) return rc;
+  if (int rc = pv::wtnz_is_bn254(*L)) return rc;
+  rep->n_witness = L->n_witness;
+  rep->in_bytes = len;
+  rep->out_bytes = WTNS_HEAD + (uint64_t)L->n_witness * 32;
+  return 0;
+}
+int report_fault(Groth16WtnsPackReport* rep, const pv::WtnzFault& f)
+{
+  rep->fault_kind = f.kind, rep->fault_index = f.element, rep->fault_count = f.count;
+  return pv::wtnz_fail(f);
+}
+
+int unpack_host_impl(const uint8_t* data, size_t len, Groth16WtnsPackReport* rep, const Sink& sink)
+{
+  pv::WtnzLayout L;
+  if (int rc = unpack_prologue(data, len, rep, &L)) return rc;
+  uint8_t* out = nullptr;
+  if (int rc = sink(rep->out_bytes, &out)) return rc;
+  // (decoded apart: a fault must leave the caller's buffer as it was)
+  std::vector<uint8_t> values((size_t)L.n_witness * 32);
+  wz::WzView view;
+  view.n = L.n_witness, view.codes = L.codes, view.dir = L.dir, view.payload = L.payload;
+  pv::WtnzFault f;
+  f.kind = wz::wz_decode_host(view, 0, L.n_witness, values.data(), &f.element, &f.count);
+  if (f.kind) return report_fault(rep, f);
+  put_wtns_head(out, L);
+  if (!values.empty()) memcpy(out + WTNS_HEAD, values.data(), values.size());
+  return 0;
+}
+
+int unpack_device_impl(const uint8_t* data, size_t len, const char* device, Groth16WtnsPackReport* rep, const Sink& sink)
+{
+  pv::WtnzLayout L;
+  if (int rc = unpack_prologue(data, len, rep, &L)) return rc;
+  if (!device) return pv::fail(pv::ERR_ARG, "null device");
+  const int dev = vb::parse_one_device(device);
+  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  uint8_t* out = nullptr;
+  if (int rc = sink(rep->out_bytes, &out)) return rc;
+  if (L.n_witness) {
+    const auto t_dev = std::chrono::steady_clock::now();
+    vb::DeviceSession ds;
+    if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+    uint8_t* d_buf = ds.buf.alloc<uint8_t>(pv::wtnz_device_bytes(L));
+    fe* d_out = ds.buf.alloc<fe>(L.n_witness);
+    if (!d_buf || !d_out) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
+    pv::WtnzFault f;
+    if (int rc = pv::wtnz_decode_on_device(dev, ds.stream(0), L, d_buf, d_out, &f, &rep->upload_ms, &rep->kernel_ms)) return rc;
+    rep->device_ms = pv::ms_since(t_dev) - rep->upload_ms;
+    // the verdict is in; nothing has been written
+    if (f.kind) return report_fault(rep, f);
+    const auto t_down = std::chrono::steady_clock::now();
+    const isnark::CopyJob job = {out + WTNS_HEAD, d_out, (size_t)L.n_witness * 32};
+    DEV_TRY("device to host download", isnark::staged_copy(dev, &job, 1, false));
+    rep->download_ms = pv::ms_since(t_down);
+  }
+  put_wtns_head(out, L);
+  return 0;
+}
+
+Sink buffer_sink(void* out, size_t cap)
+{
+  return [out, cap](uint64_t bytes, uint8_t** o) {
+    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the file needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
+    *o = (uint8_t*)out;
+    return 0;
+  };
+}
+
+// a _file entry: the input mapped, the output a temporary that is renamed
+int file_entry(const char* in_path, const char* out_path, Groth16WtnsPackReport* report, const std::function<int(const uint8_t*, size_t, const Sink&)>& impl)
+{
+  if (report) memset(report, 0, sizeof *report);
+  if (!in_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
+  if (strcmp(in_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
+  pv::MappedFile mf;
+  if (int rc = mf.open_ro(in_path)) return rc;
+  {
+    struct stat a, b; // the same file under two names
+    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
+  }
+  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
+  pv::TempOutput to(out_path);
+  const Sink sink = [&](uint64_t bytes, uint8_t** o) { return to.open(bytes, o); };
+  int rc = impl(mf.data, mf.len, sink);
+  const auto t_write = std::chrono::steady_clock::now();
+  rc = to.finish(rc);
+  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
+  return rc;
+}
+
+} // namespace
+
+// ---- host only: never initialise a GPU
+ISNARK_API int groth16_wtns_packed_size(const void* wtns, size_t len, uint64_t* packed_bytes)
+{
+  if (!packed_bytes) return pv::fail(pv::ERR_ARG, "null output");
+  *packed_bytes = 0;
+  if (!wtns) return pv::fail(pv::ERR_ARG, "null wtns");
+  pv::Wtns w;
+  if (int rc = pv::parse_wtns((const uint8_t*)wtns, len, w)) return rc;
+  std::vector<uint64_t> dir;
+  if (int rc = pack_scan(w, nullptr, dir, nullptr)) return rc;
+  *packed_bytes = WTNZ_HEAD + w.n_witness + 8 * dir.size() + dir.back();
+  return 0;
+}
+ISNARK_API int groth16_wtns_pack(const void* wtns, size_t len, void* out, size_t cap, Groth16WtnsPackReport* report)
+{
+  return pack_impl((const uint8_t*)wtns, len, report, buffer_sink(out, cap));
+}
+ISNARK_API int groth16_wtns_pack_file(const char* in_path, const char* out_path, Groth16WtnsPackReport* report)
+{
+  return file_entry(in_path, out_path, report, [&](const uint8_t* d, size_t l, const Sink& s) { return pack_impl(d, l, report, s); });
+}
+ISNARK_API int groth16_wtns_unpack_host(const void* packed, size_t len, void* out, size_t cap, Groth16WtnsPackReport* report)
+{
+  return unpack_host_impl((const uint8_t*)packed, len, report, buffer_sink(out, cap));
+}
+ISNARK_API int groth16_wtns_unpack_host_file(const char* in_path, const char* out_path, Groth16WtnsPackReport* report)
+{
+  return file_entry(in_path, out_path, report, [&](const uint8_t* d, size_t l, const Sink& s) { return unpack_host_impl(d, l, report, s); });
+}
+
+// ---- one HIP device
+ISNARK_API int groth16_wtns_unpack(const void* packed, size_t len, void* out, size_t cap, const char* device, Groth16WtnsPackReport* report)
+{
+  return unpack_device_impl((const uint8_t*)packed, len, device, report, buffer_sink(out, cap));
+}
+ISNARK_API int groth16_wtns_unpack_file(const char* in_path, const char* out_path, const char* device, Groth16WtnsPackReport* report)
+{
+  return file_entry(in_path, out_path, report, [&](const uint8_t* d, size_t l, const Sink& s) { return unpack_device_impl(d, l, device, report, s); });
+}

@@ -834,6 +834,79 @@ int groth16_ptau_pack_file(const char* in_path, const char* out_path, const char
 int groth16_ptau_unpack(const void* packed, size_t len, void* out, size_t cap, const char* device, Groth16PtauPackReport* report);
 int groth16_ptau_unpack_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPackReport* report);
 
+/* groth16_wtns_pack, groth16_wtns_unpack, groth16_prove_packed, groth16_witness_check_packed — a witness with a code byte per value
+ * and only the value's significant bytes ("wtnz"), packed on the host of the witness generator and decoded on the GPU straight into
+ * the place the prove reads it from.  A witness is the one file a proving service moves per proof, and most of its 32 bytes a wire
+ * are zero: a bit wire costs 1 byte, a full-width value 33.  Opt-in: nothing that takes a .wtns takes this, and the reverse.
+ * THE VALUE.  v in standard form, 0 <= v < r, as a .wtns holds it; bytes(x) = the significant bytes of x, bytes(0) = 0.  The first
+ * rule that applies:   v = 0: code 0x00, no payload   |   v = 1: code 0x40, no payload   |   m = r - v with bytes(m) < bytes(v): code
+ * 0x80 | bytes(m) (0x81 ... 0x9f), payload m in bytes(m) little-endian bytes   |   else code bytes(v) (0x01 ... 0x20), payload v in
+ * bytes(v) little-endian bytes.  Every other code byte is undefined.  The encoding is unique: pack and unpack are inverse bijections
+ * and both are functions of their input alone.
+ * THE CONTAINER is an iden3 section table under magic "wtnz", version 1, each section once, in any order (pack writes 1, 2, 3, 4):
+ *   1  a .wtns header byte for byte: n8 = 32, q (= r of BN254, 32 bytes), n_witness (u32) — 40 bytes
+ *   2  the codes, one byte per value: n_witness bytes
+ *   3  the directory: ceil(n_witness / 256) + 1 little-endian u64; entry b = the offset in section 4 where the payload of block b
+ *      (values 256 b ... 256 b + 255) begins; entry 0 is 0, the last entry is section 4's size
+ *   4  the payload: the values' significant bytes in order
+ * THE HOST bounds everything before a byte goes up: the section sizes against n_witness; the directory beginning at 0, never
+ * decreasing, ending at section 4's size, no block spanning more than 256 * 32 = 8192 bytes (-2, each with a text of its own).  No
+ * content of a file can then make the kernel read outside its buffers.
+ * A DECODER refuses a value with one of the kinds below (-2 "wtnz: element E: kind"): fault_index is the LOWEST faulty element,
+ * fault_kind its kind, fault_count how many there are, and nothing is written. */
+#define GROTH16_WTNZ_CODE         1   /* an undefined code byte */
+#define GROTH16_WTNZ_NONCANONICAL 2   /* a payload whose top byte is 0; code 0x01 with payload 01; a 32-byte positive form whose negated form is shorter */
+#define GROTH16_WTNZ_RANGE        3   /* 32 bytes that are not below r */
+#define GROTH16_WTNZ_DIRECTORY    4   /* a block's 256 lengths (an undefined code counts 0) do not sum to its directory span: named at the
+                                         block's first element, and the only fault such a block reports */
+typedef struct {
+  uint32_t n_witness;
+  uint64_t in_bytes, out_bytes;  /* the input; the output (also when cap was too small) */
+  int32_t  fault_kind;           /* GROTH16_WTNZ_*; pack: GROTH16_WTNZ_RANGE for a .wtns value >= r */
+  uint64_t fault_index;          /* the lowest faulty element */
+  uint64_t fault_count;          /* how many elements are faulty */
+  double   upload_ms, kernel_ms, device_ms, download_ms, write_ms; /* groth16_wtns_unpack: sections 2 to 4 up; the decode kernel alone
+                                    (events); wall time of the device part without the upload; the values down; msync and rename (_file) */
+} Groth16WtnsPackReport;
+/* HOST ONLY — the five entries below never initialise a GPU: the witness generator's host has none.
+ * groth16_wtns_packed_size: the bytes of the packed form of a .wtns image.  groth16_wtns_pack: a .wtns (as every .wtns reader here
+ * takes it) to its packed form; a value >= r is -2 "wtns: element E is not below r" with report->fault_index = E.
+ * groth16_wtns_unpack_host: the .wtns a packed witness came from, byte for byte when the .wtns had nothing but its sections 1 and 2;
+ * faults as above.  cap is tested before anything is written (-3, report->out_bytes says what is needed).  The _file entries map the
+ * input, write a temporary beside out_path and rename it: a failed call leaves nothing.
+ * What they do NOT do: keep a .wtns' other sections or its version (the output is version 2, sections 1 and 2); check the witness
+ * against a circuit; compress (a dense witness GROWS by one byte a value and the directory). */
+int groth16_wtns_packed_size(const void* wtns, size_t len, uint64_t* packed_bytes);
+int groth16_wtns_pack(const void* wtns, size_t len, void* out, size_t cap, Groth16WtnsPackReport* report);
+int groth16_wtns_pack_file(const char* in_path, const char* out_path, Groth16WtnsPackReport* report);
+int groth16_wtns_unpack_host(const void* packed, size_t len, void* out, size_t cap, Groth16WtnsPackReport* report);
+int groth16_wtns_unpack_host_file(const char* in_path, const char* out_path, Groth16WtnsPackReport* report);
+/* groth16_wtns_unpack — the same on one HIP device: sections 2 to 4 go up, ONE launch decodes them — a 256-lane workgroup per block,
+ * a lane per value — and the values come down.  All verdicts are read before anything is written.  -3 also for a device string that
+ * does not name one HIP device, -5 a device failure.  The calling thread's device is what it was afterwards.
+ * What it does NOT do: pack on the GPU; keep anything resident (groth16_prove_packed does). */
+int groth16_wtns_unpack(const void* packed, size_t len, void* out, size_t cap, const char* device, Groth16WtnsPackReport* report);
+int groth16_wtns_unpack_file(const char* in_path, const char* out_path, const char* device, Groth16WtnsPackReport* report);
+/* groth16_prove_packed — groth16_prove_mem from a packed witness: groth16_prove_mem's two tests of a witness with their messages
+ * (curve, length), sections 2 to 4 up, the decode into the key's resident witness buffer on the key's stream, and on a clean tally
+ * the resident prove (groth16_prove_resident's path) — decode and commitments under one hold of the manager's mutex, so no other
+ * thread's prove lands between them.  The public signals are decoded on the host from the first n_public + 1 values.  Afterwards the
+ * witness is resident as after groth16_prove_mem.  On a fault (-2, as above) NO witness is resident and nothing is proved.
+ * -1 ... -5 as groth16_prove_mem.  What it does NOT do: device groups and shards (-3 with a message: single-device keys only);
+ * overlap the upload with the head of the prove as groth16_prove_mem does for large witnesses; pack on the GPU. */
+int groth16_prove_packed(Groth16CacheManager* cm, const char* key, const void* wtnz, size_t len, const uint8_t* r, const uint8_t* s,
+                         char* proof_json, size_t proof_cap, char* public_json, size_t public_cap, Groth16Timings* timings);
+/* groth16_prove_packed_files — groth16_prove with a packed witness, file to file, the cache key "<zkey_path>_<device>" as there.  A
+ * key the manager does not hold is loaded through groth16_cache_load_file first.  What it does NOT do: groth16_prove's cold-path
+ * overlap — the key's upload and the first proof run one after the other; more than one device (-3). */
+int groth16_prove_packed_files(const char* witness_path, const char* zkey_path, const char* proof_path, const char* public_path,
+                               const char* device, Groth16CacheManager* cm);
+/* groth16_witness_check_packed — groth16_witness_check with the decode in front, on the handle's device: verdict and report are those
+ * of the unpacked witness (upload_ms is the packed sections').  A faulty packed witness is -2 as above: no verdict.
+ * What it does NOT do: anything groth16_witness_check does not. */
+int groth16_witness_check_packed(Groth16R1cs* h, const void* wtnz, size_t len, Groth16WitnessReport* report);
+int groth16_witness_check_packed_file(Groth16R1cs* h, const char* wtnz_path, Groth16WitnessReport* report);
+
 #ifdef __cplusplus
 }
 #endif
