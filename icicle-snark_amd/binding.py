@@ -591,6 +591,22 @@ class CacheManager:
         if wait_tables:
             self.tables_ready(key, wait=True)
 
+    def load_packed(self, key: str, zkez, device_id: int = 0, shard_rank: int = 0, shard_count: int = 1, wait_tables: bool = True):
+        """groth16_cache_load_packed / _file: load() from a PACKED key (zkey_pack) — the image, or a path — decoded on the GPU into
+        the buffers load() fills; the entry is load()'s.  A faulty packed key raises ProverError (−2 "zkez: section S, element E:
+        kind" / "zkez: coefficient E: kind") and nothing is cached.  One device only: anything but shard 0 of 1 is −3."""
+        if isinstance(zkez, (str, os.PathLike)):
+            rc = lib().groth16_cache_load_packed_file(self._h, key.encode(), os.fsencode(zkez), device_id, shard_rank, shard_count)
+        else:
+            rc = lib().groth16_cache_load_packed(self._h, key.encode(), _image(zkez), C.c_size_t(len(zkez)), device_id, shard_rank, shard_count)
+        _pcheck(rc, "cache_load_packed")
+        if wait_tables:
+            self.tables_ready(key, wait=True)
+
+    def prove_zkez_files(self, witness: str, zkez: str, proof: str, public: str, device: str = "HIP"):
+        """groth16_prove_zkez_files: prove() with a packed key file; a key the manager does not hold is loaded packed first"""
+        _pcheck(lib().groth16_prove_zkez_files(witness.encode(), zkez.encode(), proof.encode(), public.encode(), device.encode(), self._h), "prove_zkez_files")
+
     def evict(self, key: str):
         lib().groth16_cache_evict(self._h, key.encode())
 
@@ -731,6 +747,8 @@ groth16_ptau_pack groth16_ptau_pack_file groth16_ptau_unpack groth16_ptau_unpack
 groth16_wtns_packed_size groth16_wtns_pack groth16_wtns_pack_file groth16_wtns_unpack_host groth16_wtns_unpack_host_file
 groth16_wtns_unpack groth16_wtns_unpack_file groth16_prove_packed groth16_prove_packed_files
 groth16_witness_check_packed groth16_witness_check_packed_file
+groth16_zkey_unpacked_size groth16_zkey_packed_bound groth16_zkey_pack groth16_zkey_pack_file groth16_zkey_unpack groth16_zkey_unpack_file
+groth16_zkey_coefs_pack groth16_zkey_coefs_unpack groth16_cache_load_packed groth16_cache_load_packed_file groth16_prove_zkez_files
 """.split()
 # (the int / void / pointer-returning entry points of include/groth16_prover.h; groth16_zkey_export_vk returns int64_t)
 
@@ -1528,3 +1546,102 @@ def wtns_unpack(packed, out=None, device=None):
     dev = device.encode()
     return _wtns_transcode("wtns_unpack", lambda p, n, o, c, r: lib().groth16_wtns_unpack(p, n, o, c, dev, r),
                            lambda i, o, r: lib().groth16_wtns_unpack_file(i, o, dev, r), packed, out)
+
+
+class ZkeyPackReport(C.Structure):
+    """Groth16ZkeyPackReport: the header's counts, the G1 and G2 point counts, the input's and the output's bytes, the packed point
+    sections' and the packed section 4's bytes, the first faulty section with its lowest faulty element, its kind and that section's
+    fault count, the stage times"""
+    _fields_ = [("n_vars", C.c_uint32), ("n_public", C.c_uint32), ("domain", C.c_uint32), ("n_coef", C.c_uint32), ("points", C.c_uint64 * 2),
+                ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("point_bytes", C.c_uint64), ("coef_bytes", C.c_uint64),
+                ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64), ("fault_count", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
+class ZkeyCoefsReport(C.Structure):
+    """Groth16ZkeyCoefsReport: the record count, the input's and the output's bytes, the lowest faulty coefficient with its kind
+    (WTNZ_KINDS) and how many are faulty, the stage times"""
+    _fields_ = [("n", C.c_uint64), ("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64),
+                ("fault_count", C.c_uint64), ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double)]
+
+
+class KeyFault(ProverError):
+    """a point or a coefficient refused by zkey_pack / zkey_unpack / coefs_pack / coefs_unpack: .report says which"""
+    report = None
+
+
+def _key_check(rc, what, rep):
+    try:
+        _pcheck(rc, what)
+    except ProverError as e:
+        if rc == -2 and rep.fault_kind:
+            fault = KeyFault(str(e))
+            fault.report = rep
+            raise fault from None
+        raise
+
+
+def zkey_unpacked_size(zkez) -> int:
+    """groth16_zkey_unpacked_size: the bytes of the .zkey a packed key came from, exact, from the container alone; host only"""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_zkey_unpacked_size(_image(zkez), C.c_size_t(len(zkez)), C.byref(size)), "zkey_unpacked_size")
+    return size.value
+
+
+def zkey_packed_bound(zkey) -> int:
+    """groth16_zkey_packed_bound: an upper bound of zkey_pack's output for this .zkey — every value at 32 bytes; host only"""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_zkey_packed_bound(_image(zkey), C.c_size_t(len(zkey)), C.byref(size)), "zkey_packed_bound")
+    return size.value
+
+
+def _zkey_transcode(what, buffer_entry, file_entry, room, src, out, device):
+    rep = ZkeyPackReport()
+    if isinstance(src, (str, os.PathLike)):
+        if out is None:
+            raise TypeError(f"{what}: an input path needs the path to write to")
+        _key_check(file_entry(os.fsencode(src), os.fsencode(out), device.encode(), C.byref(rep)), what + "_file", rep)
+        return None, rep
+    if out is not None:
+        raise TypeError(f"{what}: `out` goes with an input path")
+    buf = C.create_string_buffer(max(room(src), 1))      # (a refused container raises here, with the reader's message)
+    _key_check(buffer_entry(_image(src), C.c_size_t(len(src)), buf, C.c_size_t(len(buf)), device.encode(), C.byref(rep)), what, rep)
+    return buf.raw[:rep.out_bytes], rep
+
+
+def zkey_pack(zkey, out=None, device: str = "HIP"):
+    """groth16_zkey_pack → (packed bytes | None, ZkeyPackReport): a .zkey with every point as x and one bit of y and every coefficient
+    as a code byte and its significant bytes, magic "zkez" (include/groth16_prover.h has the form).  zkey: the image, and the packed
+    key comes back as bytes; or a path together with `out`, the path the packed key is written to (a temporary, renamed).  Every point
+    passes the lane tests first and every coefficient is below r: KeyFault (−2) "zkey: section S, element E: kind" / "zkey:
+    coefficient E: not below r", its .report saying the same, and nothing written."""
+    return _zkey_transcode("zkey_pack", lib().groth16_zkey_pack, lib().groth16_zkey_pack_file, zkey_packed_bound, zkey, out, device)
+
+
+def zkey_unpack(zkez, out=None, device: str = "HIP"):
+    """groth16_zkey_unpack → (.zkey bytes | None, ZkeyPackReport): the .zkey a packed key came from, byte for byte.  Arguments as
+    zkey_pack; KeyFault (−2) "zkez: section S, element E: kind" / "zkez: coefficient E: kind"."""
+    return _zkey_transcode("zkey_unpack", lib().groth16_zkey_unpack, lib().groth16_zkey_unpack_file, zkey_unpacked_size, zkez, out, device)
+
+
+def coefs_pack(records, device: str = "HIP"):
+    """groth16_zkey_coefs_pack → (the body of a packed section 4, ZkeyCoefsReport): n records of 44 bytes {m, c, s, value·R²} through
+    the two pack kernels; declared_count = n.  A value not below r raises KeyFault (−2).  An empty buffer is valid."""
+    if len(records) % 44:
+        raise ValueError(f"coefs_pack: {len(records)} bytes are no multiple of 44")
+    n = len(records) // 44
+    buf, rep = C.create_string_buffer(24 + 45 * n + 8 * ((n + 255) // 256)), ZkeyCoefsReport()
+    rc = lib().groth16_zkey_coefs_pack(_image(records) if n else None, C.c_uint64(n), buf, C.c_size_t(len(buf)), device.encode(), C.byref(rep))
+    _key_check(rc, "coefs_pack", rep)
+    return buf.raw[:rep.out_bytes], rep
+
+
+def coefs_unpack(body, device: str = "HIP"):
+    """groth16_zkey_coefs_unpack → (n records of 44 bytes, ZkeyCoefsReport): the inverse of coefs_pack.  The body passes the reader's
+    tests of section 4 first (ProverError −2); a faulty value raises KeyFault (−2 "zkez: coefficient E: kind")."""
+    rep = ZkeyCoefsReport()
+    n = int.from_bytes(bytes(body[4:8]), "little") if len(body) >= 8 else 0
+    buf = C.create_string_buffer(max(44 * n, 1))
+    rc = lib().groth16_zkey_coefs_unpack(_image(body), C.c_size_t(len(body)), buf, C.c_size_t(44 * n), device.encode(), C.byref(rep))
+    _key_check(rc, "coefs_unpack", rep)
+    return buf.raw[:rep.out_bytes], rep

@@ -464,6 +464,7 @@ struct LoadCtx {
   uint32_t* d_records = nullptr; // the raw coefficient records the CSR is built from
   size_t rec_bytes = 0;
   void* h_full = nullptr; // strided H: the whole section, from which the residue class is gathered
+  std::vector<void*> packed_tmp; // a packed key (ingest_packed): the packed sections and the tallies on the device
   bool pipeline = false; // decide_layout: the sections arrive behind the caller's prove (the cold uploader task), not in the load
   const bool trace = env_set("ICICLE_SNARK_TRACE_COLD");
   std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
@@ -472,6 +473,7 @@ struct LoadCtx {
   {
     if (h_full) (void)hipFree(h_full);
     if (d_records) (void)hipFree(d_records);
+    for (void* p : packed_tmp) (void)hipFree(p);
   }
   void lap(const char* what)
   {
@@ -620,6 +622,17 @@ int decide_layout(LoadCtx& c)
   return 0;
 }
 
+// the CSR from the file-form records on the device (the range check of the records is part of it)
+int build_csr(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  uint32_t first_bad = 0;
+  P_HIP(qap_build_csr(c.d_records, c.L.n_coef, c.L.domain, z->n_vars, z->d_rowptr, z->d_cols, z->d_vals, &first_bad, nullptr));
+  if (first_bad != 0xffffffffu) return fail(ERR_FORMAT, "zkey: coefficient %u out of range", first_bad);
+  c.lap("device CSR build");
+  return 0;
+}
+
 // the sections over the key's six streams, the strided H gathered, the CSR built (a load that is not pipelined)
 int ingest(LoadCtx& c)
 {
@@ -632,11 +645,53 @@ int ingest(LoadCtx& c)
     c.h_full = nullptr;
   }
   c.lap("staged upload");
-  uint32_t first_bad = 0;
-  P_HIP(qap_build_csr(c.d_records, c.L.n_coef, c.L.domain, z->n_vars, z->d_rowptr, z->d_cols, z->d_vals, &first_bad, nullptr));
-  if (first_bad != 0xffffffffu) return fail(ERR_FORMAT, "zkey: coefficient %u out of range", first_bad);
-  c.lap("device CSR build");
-  return 0;
+  return build_csr(c);
+}
+
+// A packed key (zkez_layout; zkey_pack.hip has the kernels) in ingest's place: the packed point sections and section 4 go up into
+// temporaries, the unpack kernels write file-form points straight into sh.d_points and file-form records into d_records, and every
+// tally is read — a fault is ERR_FORMAT — before the CSR is built from what ingest would have uploaded.  Never sharded, never pipelined.
+int ingest_packed(LoadCtx& c)
+{
+  ZKeyCache* z = c.z.get();
+  const ZkezCoefs& C = c.L.packed->coefs;
+  auto temp = [&](size_t bytes) -> uint8_t* {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    c.packed_tmp.push_back(p);
+    return (uint8_t*)p;
+  };
+  c.jobs.clear(); // (alloc_key_buffers has named the UNPACKED ranges: a packed key has none of them)
+  uint8_t* d_words[5];
+  for (int k = 0; k < 5; k++) {
+    const Shard& sh = BASES[k].of(z);
+    const size_t half = BASES[k].elem() / 2, bytes = (size_t)sh.len() * half;
+    if (!(d_words[k] = temp(bytes))) return fail(ERR_DEVICE, "device: hipMalloc: out of memory");
+    if (bytes) c.jobs.push_back({d_words[k], c.L.sec[BASES[k].section]->p + (size_t)sh.lo * half, bytes});
+  }
+  uint8_t* const d_coefs = temp(zkez_coefs_device_bytes(C));
+  PackTally* const d_tally = (PackTally*)temp(6 * sizeof(PackTally));
+  if (!d_coefs || !d_tally) return fail(ERR_DEVICE, "device: hipMalloc: out of memory");
+  zkez_coefs_jobs(C, d_coefs, c.jobs);
+  if (int rc = staged_upload(c.device_id, c.jobs, z->streams().data(), 6)) return rc;
+  c.lap("staged upload (packed)");
+  PackTally tallies[6];
+  for (PackTally& t : tallies) t = {~0ull, 0};
+  P_HIP(hipMemcpyAsync(d_tally, tallies, sizeof tallies, hipMemcpyHostToDevice, nullptr));
+  for (int k = 0; k < 5; k++)
+    if (int rc = unpack_on_device(nullptr, d_words[k], BASES[k].of(z).len(), BASES[k].g2, (uint8_t*)BASES[k].of(z).d_points, d_tally + k)) return rc;
+  if (int rc = zkez_coefs_decode(nullptr, C, d_coefs, c.d_records, d_tally + 5)) return rc;
+  P_HIP(hipMemcpyAsync(tallies, d_tally, sizeof tallies, hipMemcpyDeviceToHost, nullptr));
+  P_HIP(hipStreamSynchronize(nullptr));
+  c.lap("unpack kernels");
+  // the lowest faulty section, then its lowest faulty element (section 4 lies below the bases' 5 … 9)
+  if (tallies[5].first != ~0ull) return packed_coef_fail("zkez", tallies[5]);
+  for (int id = 5; id <= 9; id++)
+    for (int k = 0; k < 5; k++)
+      if (BASES[k].section == id && tallies[k].first != ~0ull) return packed_point_fail("zkez", id, tallies[k]);
+  for (void* p : c.packed_tmp) (void)hipFree(p);
+  c.packed_tmp.clear();
+  return build_csr(c);
 }
 
 // bases: the file's Montgomery form (R = 2^256) → the bucket kernels' internal encoding (R' = 2^261), once — in place, or as
@@ -739,7 +794,9 @@ int build_cache(const ZkeyLayout& L, int device_id, int rank, int count, std::un
   if (int rc = open_streams(c)) return rc;
   if (int rc = alloc_key_buffers(c)) return rc;
   if (int rc = decide_layout(c)) return rc;
-  if (!c.pipeline)
+  if (L.packed) {
+    if (int rc = ingest_packed(c)) return rc;
+  } else if (!c.pipeline)
     if (int rc = ingest(c)) return rc;
   if (int rc = convert_bases(c)) return rc;
   if (int rc = alloc_work_buffers(c)) return rc;

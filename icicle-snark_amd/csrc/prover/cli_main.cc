@@ -36,6 +36,11 @@
 //     (groth16_wtns_unpack_host_file / groth16_wtns_unpack_file): the same lines
 //   > prove-packed --witness Z --zkey K --proof P --public Q [--device HIP]   prove from a packed witness (groth16_prove_packed_files)
 //   > wtns-check --r1cs R --wtnz Z [--device HIP]     wtns-check from a packed witness (groth16_witness_check_packed_file)
+//   > zkey-pack --zkey IN --out OUT [--device HIP]       the key with every point as x and one bit of y and every coefficient as a code
+//     byte and its significant bytes (groth16_zkey_pack_file): one summary line, then ZKEY_WRITTEN; a fault:
+//     ZKEY_BAD POINT <section> <element> <count> or ZKEY_BAD COEFFICIENT <element> <count>
+//   > zkey-unpack --packed IN --out OUT [--device HIP]   the .zkey back, byte for byte (groth16_zkey_unpack_file): the same lines
+//   > prove-zkez --witness W --zkez Z --proof P --public Q [--device HIP]   prove from a packed key (groth16_prove_zkez_files)
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -46,7 +51,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  zkey-pack --zkey <file> --out <file> [--device HIP]   (points as x and one bit of y, coefficients as a code byte and their significant bytes)\n  zkey-unpack --packed <file> --out <file> [--device HIP]   (the .zkey back, byte for byte)\n  prove-zkez --witness <file> --zkez <packed key> --proof <file> --public <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -598,6 +603,41 @@ int main()
       }
       const int rc = groth16_prove_packed_files(witness.c_str(), zkey.c_str(), proof.c_str(), pub.c_str(), device.c_str(), cm);
       if (rc != 0) std::cerr << "prove-packed failed (" << rc << "): " << groth16_last_error() << std::endl;
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-pack" || cmd == "zkey-unpack") {
+      const bool unpack = cmd == "zkey-unpack";
+      std::string inp = unpack ? "circuit_final.zkez" : "circuit_final.zkey", out = unpack ? "circuit_final.zkey" : "circuit_final.zkez", device = "HIP", a;
+      while (in >> a) {
+        if (a == (unpack ? "--packed" : "--zkey")) in >> inp;
+        else if (a == "--out") in >> out;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16ZkeyPackReport rep = {};
+      const int rc = unpack ? groth16_zkey_unpack_file(inp.c_str(), out.c_str(), device.c_str(), &rep) : groth16_zkey_pack_file(inp.c_str(), out.c_str(), device.c_str(), &rep);
+      if (rc < 0) {
+        std::cerr << cmd << " failed (" << rc << "): " << groth16_last_error() << std::endl;
+        if (rep.fault_kind && rep.fault_section == 4) std::cout << "ZKEY_BAD COEFFICIENT " << rep.fault_index << " " << rep.fault_count << std::endl;
+        else if (rep.fault_kind) std::cout << "ZKEY_BAD POINT " << rep.fault_section << " " << rep.fault_index << " " << rep.fault_count << std::endl;
+      } else {
+        std::cout << "wires " << rep.n_vars << " domain " << rep.domain << " coefficients " << rep.n_coef << " points " << rep.points[0] << " " << rep.points[1] << " bytes " << rep.in_bytes
+                  << " to " << rep.out_bytes << " (packed points " << rep.point_bytes << " section 4 " << rep.coef_bytes << "); upload " << rep.upload_ms << " ms device " << rep.device_ms
+                  << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
+        std::cout << "ZKEY_WRITTEN" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "prove-zkez") {
+      std::string witness = "witness.wtns", zkez = "circuit_final.zkez", proof = "proof.json", pub = "public.json", device = "HIP", a;
+      while (in >> a) {
+        if (a == "--witness") in >> witness;
+        else if (a == "--zkez") in >> zkez;
+        else if (a == "--proof") in >> proof;
+        else if (a == "--public") in >> pub;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      const int rc = groth16_prove_zkez_files(witness.c_str(), zkez.c_str(), proof.c_str(), pub.c_str(), device.c_str(), cm);
+      if (rc != 0) std::cerr << "prove-zkez failed (" << rc << "): " << groth16_last_error() << std::endl;
       std::cout << "COMMAND_COMPLETED" << std::endl;
     } else {
       print_help();

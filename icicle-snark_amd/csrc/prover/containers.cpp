@@ -68,10 +68,35 @@ int unique_section(const std::vector<Section>& s, size_t id, const Section** sec
 }
 
 // sections and header of a zkey (prover_internal.h: ZkeyLayout) — the only code that knows the container's and the header's rules
-int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, bool need_ic)
+// the sections of a container that read_sections has passed, in the file's order
+std::vector<SectionEntry> sections_in_order(const uint8_t* data)
 {
-  if (!data) return fail(ERR_ARG, "null zkey");
-  if (int rc = read_sections(data, len, "zkey", 2, secs)) return rc;
+  uint32_t nsec;
+  memcpy(&nsec, data + 8, 4);
+  std::vector<SectionEntry> out;
+  size_t pos = 12;
+  for (uint32_t i = 0; i < nsec; i++) {
+    SectionEntry e;
+    memcpy(&e.id, data + pos, 4);
+    memcpy(&e.size, data + pos + 4, 8);
+    e.p = data + pos + 12;
+    out.push_back(e);
+    pos += 12 + (size_t)e.size;
+  }
+  return out;
+}
+// where the last of them ends (bytes behind it are no part of the container)
+static uint64_t container_end(const uint8_t* data)
+{
+  uint64_t pos = 12;
+  for (const SectionEntry& e : sections_in_order(data)) pos += 12 + e.size;
+  return pos;
+}
+
+// the container, section 1 and the header (section 2) of a key under `magic`: what a .zkey and a packed key share
+static int zkey_header(const uint8_t* data, size_t len, const char* magic, uint32_t max_version, std::vector<Section>& secs, ZkeyLayout* L, bool need_ic)
+{
+  if (int rc = read_sections(data, len, magic, max_version, secs)) return rc;
   const Section* s1;
   if (int rc = unique_section(secs, 1, &s1)) return rc;
   uint32_t protocol = 0;
@@ -102,6 +127,14 @@ int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Zke
   if (n == 0 || (n & (n - 1))) return fail(ERR_FORMAT, "zkey: domain size %u is not a power of two", n);
   if (L->n_public + 1 > L->n_vars) return fail(ERR_FORMAT, "zkey: n_public exceeds n_vars");
   L->header_points = h + 84;
+  return 0;
+}
+
+int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, bool need_ic)
+{
+  if (!data) return fail(ERR_ARG, "null zkey");
+  if (int rc = zkey_header(data, len, "zkey", 2, secs, L, need_ic)) return rc;
+  const uint32_t n = L->domain;
   // coefficients (section 4): a declared count, then the records — src/cache.rs:126-166
   const Section* s4 = L->sec[4];
   if (s4->size < 4 || (s4->size - 4) % COEF_RECORD_BYTES) return fail(ERR_FORMAT, "zkey: coefficient section size");
@@ -111,6 +144,58 @@ int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, Zke
   if ((need_ic && L->sec[3]->size != np1 * 64) || L->sec[5]->size != nv * 64 || L->sec[6]->size != nv * 64 || L->sec[7]->size != nv * 128 || L->sec[8]->size != (nv - np1) * 64 ||
       L->sec[9]->size != (uint64_t)n * 64)
     return fail(ERR_FORMAT, "zkey: point section size mismatch");
+  return 0;
+}
+
+// section 4 of a packed key, or a raw packed body (prover_internal.h: ZkezCoefs): the size against the sum of its parts, the directory
+int zkez_coefs_layout(const uint8_t* body, uint64_t size, ZkezCoefs* C)
+{
+  if (size < ZKEZ_COEFS_HEAD) return fail(ERR_FORMAT, "zkez: section 4 holds %llu bytes, its three counts alone have %llu", (unsigned long long)size, (unsigned long long)ZKEZ_COEFS_HEAD);
+  memcpy(&C->declared, body, 4);
+  memcpy(&C->n_coef, body + 4, 4);
+  memcpy(&C->payload_bytes, body + 8, 8);
+  C->n_blocks = ((uint64_t)C->n_coef + wz::WZ_BLOCK - 1) / wz::WZ_BLOCK;
+  // (the payload's size is compared first: a hostile one cannot wrap the sum)
+  if (C->payload_bytes > size || zkez_coefs_bytes(C->n_coef, C->payload_bytes) != size)
+    return fail(ERR_FORMAT, "zkez: section 4 holds %llu bytes, %u coefficients with a payload of %llu bytes have %llu", (unsigned long long)size, C->n_coef,
+                (unsigned long long)C->payload_bytes, (unsigned long long)(C->payload_bytes > size ? 0 : zkez_coefs_bytes(C->n_coef, C->payload_bytes)));
+  C->triples = body + ZKEZ_COEFS_HEAD;
+  C->codes = C->triples + 12 * (uint64_t)C->n_coef;
+  C->dir = C->codes + C->n_coef;
+  C->payload = C->dir + 8 * (C->n_blocks + 1);
+  uint64_t at = 0;
+  switch (wz::wz_check_directory(C->dir, C->n_blocks, C->payload_bytes, &at)) {
+  case 0: break;
+  case 1: return fail(ERR_FORMAT, "zkez: directory entry 0 is %llu, not 0", (unsigned long long)wz::wz_dir_entry(C->dir, 0));
+  case 2: return fail(ERR_FORMAT, "zkez: directory entry %llu is below entry %llu", (unsigned long long)at, (unsigned long long)(at - 1));
+  case 3:
+    return fail(ERR_FORMAT, "zkez: block %llu spans %llu bytes, %u is the most", (unsigned long long)at, (unsigned long long)(wz::wz_dir_entry(C->dir, at + 1) - wz::wz_dir_entry(C->dir, at)),
+                wz::WZ_MAX_SPAN);
+  default:
+    return fail(ERR_FORMAT, "zkez: the directory ends at %llu, the payload holds %llu bytes", (unsigned long long)wz::wz_dir_entry(C->dir, C->n_blocks), (unsigned long long)C->payload_bytes);
+  }
+  return 0;
+}
+
+// sections, header and section 4 of a PACKED proving key (prover_internal.h: PackedZkey): everything an unpack kernel relies on
+// is bounded here, before a byte goes up
+int zkez_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, PackedZkey* P)
+{
+  if (!data) return fail(ERR_ARG, "null zkez");
+  if (int rc = zkey_header(data, len, "zkez", 1, secs, L, /*need_ic=*/true)) return rc;
+  const uint64_t nv = L->n_vars, np1 = (uint64_t)L->n_public + 1;
+  const uint64_t want[10] = {0, 0, 0, np1 * 32, 0, nv * 32, nv * 32, nv * 64, (nv - np1) * 32, (uint64_t)L->domain * 32};
+  uint64_t points = 0;
+  for (int id : {3, 5, 6, 7, 8, 9}) {
+    if (L->sec[id]->size != want[id])
+      return fail(ERR_FORMAT, "zkez: section %d holds %llu bytes, a packed key of %u wires, %u public signals and domain %u has %llu", id, (unsigned long long)L->sec[id]->size, L->n_vars,
+                  L->n_public, L->domain, (unsigned long long)want[id]);
+    points += want[id];
+  }
+  if (int rc = zkez_coefs_layout(L->sec[4]->p, L->sec[4]->size, &P->coefs)) return rc;
+  L->n_coef = P->coefs.n_coef;
+  P->unpacked_bytes = container_end(data) + points - L->sec[4]->size + 4 + (uint64_t)L->n_coef * COEF_RECORD_BYTES;
+  L->packed = P;
   return 0;
 }
 
@@ -438,6 +523,32 @@ __attribute__((visibility("default"))) int groth16_zkey_new_size(const void* r1c
   const uint64_t payload = 4 + (4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128) + 64 * (npub + 1) + (4 + COEF_RECORD_BYTES * *n_coeffs) + 64 * m + 64 * m + 128 * m +
                            64 * (m - npub - 1) + 64 * n + 4;
   *zkey_bytes = 12 + 10 * 12 + payload;
+  return 0;
+}
+
+// host only: never initialise a GPU.  The size of groth16_zkey_unpack's file, exact, and an upper bound of groth16_zkey_pack's — every
+// coefficient at 32 payload bytes — both from the container alone (zkey_pack.hip).
+__attribute__((visibility("default"))) int groth16_zkey_unpacked_size(const void* zkez, size_t len, uint64_t* zkey_bytes)
+{
+  if (!zkey_bytes) return fail(ERR_ARG, "null output");
+  *zkey_bytes = 0;
+  std::vector<Section> secs;
+  ZkeyLayout L;
+  PackedZkey P;
+  if (int rc = zkez_layout((const uint8_t*)zkez, len, secs, &L, &P)) return rc;
+  *zkey_bytes = P.unpacked_bytes;
+  return 0;
+}
+__attribute__((visibility("default"))) int groth16_zkey_packed_bound(const void* zkey, size_t len, uint64_t* packed_bytes)
+{
+  if (!packed_bytes) return fail(ERR_ARG, "null output");
+  *packed_bytes = 0;
+  std::vector<Section> secs;
+  ZkeyLayout L;
+  if (int rc = zkey_layout((const uint8_t*)zkey, len, secs, &L, /*need_ic=*/true)) return rc;
+  uint64_t points = 0;
+  for (int id : {3, 5, 6, 7, 8, 9}) points += L.sec[id]->size;
+  *packed_bytes = container_end((const uint8_t*)zkey) - points / 2 - L.sec[4]->size + zkez_coefs_bytes(L.n_coef, 32 * (uint64_t)L.n_coef);
   return 0;
 }
 

@@ -203,6 +203,7 @@ __attribute__((visibility("default"))) void groth16_cache_evict(Groth16CacheMana
 // bytes a single-device entry of this zkey will hold, estimated from the container (for the budget): with tables ≈ 13 × the
 // point sections, else the sections themselves; + the work buffers
 static uint64_t estimate_entry_bytes(size_t zkey_len) { return (uint64_t)zkey_len * 11; }
+static int build_and_insert(Groth16CacheManager* cm, const char* key, const ZkeyLayout& L, int device_id, int shard_rank, int shard_count);
 
 __attribute__((visibility("default"))) int groth16_cache_load(Groth16CacheManager* cm, const char* key, const void* zkey, size_t zkey_len, int device_id, int shard_rank, int shard_count)
 {
@@ -216,6 +217,12 @@ __attribute__((visibility("default"))) int groth16_cache_load(Groth16CacheManage
   std::vector<Section> secs;
   ZkeyLayout L;
   if (int rc = zkey_layout((const uint8_t*)zkey, zkey_len, secs, &L, /*need_ic=*/false)) return rc;
+  return build_and_insert(cm, key, L, device_id, shard_rank, shard_count);
+}
+
+// the entry of a key whose layout has been read, built and put into the manager's map; the caller holds cm->mu
+static int build_and_insert(Groth16CacheManager* cm, const char* key, const ZkeyLayout& L, int device_id, int shard_rank, int shard_count)
+{
   std::unique_ptr<ZKeyCache> z;
   // The NTT domain of the key (twiddle tables of 2·domain_size roots: 9–13 ms at 1.6 M constraints) is set up on a helper
   // thread WHILE the sections cross PCIe — the GPU has nothing else to do then — instead of inside the first prove.
@@ -251,6 +258,37 @@ __attribute__((visibility("default"))) int groth16_cache_load_file(Groth16CacheM
   if (int rc = f.open_ro(zkey_path)) return rc;
   staged_copy_file_hint(f.data, f.len, f.fd); // sections 4-9 are pread() into the pinned staging buffers
   const int rc = groth16_cache_load(cm, key, f.data, f.len, device_id, shard_rank, shard_count);
+  staged_copy_file_hint(nullptr, 0, -1);
+  return rc;
+}
+
+// groth16_cache_load from a PACKED key (include/groth16_prover.h; zkez_layout bounds it, cache.cpp's ingest_packed decodes it on the
+// device): one device, the budget charged the unpacked size
+__attribute__((visibility("default"))) int groth16_cache_load_packed(Groth16CacheManager* cm, const char* key, const void* zkez, size_t len, int device_id, int shard_rank, int shard_count)
+{
+  if (!cm || !key || !zkez) return fail(ERR_ARG, "null argument");
+  if (shard_count != 1 || shard_rank != 0) return fail(ERR_ARG, "shard %d of %d: groth16_cache_load_packed takes single-device keys", shard_rank, shard_count);
+  std::lock_guard<std::mutex> lk(cm->mu);
+  if (find(cm, key) || find_group(cm, key)) return 0;
+  if (cm->warm.joinable()) cm->warm.join();
+  // the container, the header, every section's size and the directory are validated before the device is touched
+  std::vector<Section> secs;
+  ZkeyLayout L;
+  PackedZkey P;
+  if (int rc = zkez_layout((const uint8_t*)zkez, len, secs, &L, &P)) return rc;
+  evict_for_budget(cm, device_id, estimate_entry_bytes(P.unpacked_bytes));
+  return build_and_insert(cm, key, L, device_id, 0, 1);
+}
+
+__attribute__((visibility("default"))) int groth16_cache_load_packed_file(Groth16CacheManager* cm, const char* key, const char* zkez_path, int device_id, int shard_rank, int shard_count)
+{
+  if (!cm || !key || !zkez_path) return fail(ERR_ARG, "null argument");
+  if (shard_count != 1 || shard_rank != 0) return fail(ERR_ARG, "shard %d of %d: groth16_cache_load_packed takes single-device keys", shard_rank, shard_count);
+  if (groth16_cache_contains(cm, key)) return 0;
+  MappedFile f;
+  if (int rc = f.open_ro(zkez_path)) return rc;
+  staged_copy_file_hint(f.data, f.len, f.fd);
+  const int rc = groth16_cache_load_packed(cm, key, f.data, f.len, device_id, 0, 1);
   staged_copy_file_hint(nullptr, 0, -1);
   return rc;
 }
@@ -1550,6 +1588,38 @@ __attribute__((visibility("default"))) int groth16_prove_packed(Groth16CacheMana
   const int rc = assemble_values(z, pub.data(), pts, bl, proof_json, proof_cap, public_json, public_cap, &et);
   if (tm) tm->h2d_ms = decode_ms, tm->total_ms = ms_since(t0);
   return rc;
+}
+
+// groth16_prove with a PACKED key, file to file; no cold-path overlap: a key the manager does not hold is loaded (packed) first, then
+// groth16_prove_mem's path runs
+__attribute__((visibility("default"))) int groth16_prove_zkez_files(const char* witness_path, const char* zkez_path, const char* proof_path, const char* public_path, const char* device,
+                                                                    Groth16CacheManager* cm)
+{
+  if (!witness_path || !zkez_path || !proof_path || !public_path || !device || !cm) return fail(ERR_ARG, "null argument");
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<int> devs;
+  if (int rc = parse_device_string(device, devs)) return rc;
+  if (devs.size() != 1) return fail(ERR_ARG, "device '%s' names %zu devices: groth16_prove_zkez_files takes single-device keys", device, devs.size());
+  P_ICICLE(icicle_load_backend_from_env_or_default());
+  if (int rc = set_active_device(devs[0])) return rc;
+  const std::string key = std::string(zkez_path) + "_" + device;
+  if (!groth16_cache_contains(cm, key.c_str()))
+    if (int rc = groth16_cache_load_packed_file(cm, key.c_str(), zkez_path, devs[0], 0, 1)) return rc;
+  MappedFile wf;
+  if (int rc = wf.open_ro(witness_path)) return rc;
+  std::vector<char> pj(4096), qj(256);
+  {
+    Groth16CircuitInfo info;
+    if (int rc = groth16_cache_info(cm, key.c_str(), &info)) return rc;
+    qj.resize(64 + (size_t)info.n_public * 84);
+  }
+  staged_copy_file_hint(wf.data, wf.len, wf.fd);
+  const int prc = groth16_prove_mem(cm, key.c_str(), wf.data, wf.len, nullptr, nullptr, pj.data(), pj.size(), qj.data(), qj.size(), nullptr);
+  staged_copy_file_hint(nullptr, 0, -1);
+  if (prc) return prc;
+  if (int rc = write_json_pair(proof_path, pj.data(), public_path, qj.data())) return rc;
+  print_proof_took(t0);
+  return 0;
 }
 
 // groth16_prove with a packed witness, file to file; no cold-path overlap: a key the manager does not hold is loaded first

@@ -71,6 +71,12 @@ struct Section {
 };
 int read_sections(const uint8_t* data, size_t len, const char* type, uint32_t max_version, std::vector<Section>& out);
 int unique_section(const std::vector<Section>& s, size_t id, const Section** sec);
+struct SectionEntry { // of a container read_sections has passed, as the file orders them (a writer that keeps the order walks these)
+  uint32_t id;
+  uint64_t size;
+  const uint8_t* p;
+};
+std::vector<SectionEntry> sections_in_order(const uint8_t* data);
 // What a zkey says about itself: the sections 2 … 9 and the header's fields.  zkey_layout is the ONE statement of the container
 // and header rules — the loader (build_cache), the key check and the vk export all read a key through it.  Checked, in this
 // order: section 1 and the protocol; sections 2, (3,) 4 … 9 present once; header length, field sizes, moduli, a power-of-two
@@ -80,14 +86,38 @@ int unique_section(const std::vector<Section>& s, size_t id, const Section** sec
 // loads keys without it (need_ic = false: sec[3] is the section when there is exactly one, else null, and nothing of it is checked).
 // `secs` owns the table L->sec points into; all pointers lead into the caller's `data`.
 constexpr size_t COEF_RECORD_BYTES = 12 + 32;
+struct PackedZkey;
 struct ZkeyLayout {
   uint32_t n8q = 0, n8r = 0, n_vars = 0, n_public = 0, domain = 0, n_coef = 0;
   fe q, r;
   const uint8_t* header_points = nullptr; // α₁ β₁ β₂ γ₂ δ₁ δ₂: 64 / 128 bytes each, Montgomery form
   const Section* sec[10] = {};
   const uint8_t* records() const { return sec[4]->p + 4; } // n_coef × COEF_RECORD_BYTES: {m:u32 c:u32 s:u32 value[32]}, src/cache.rs:126-166
+  const PackedZkey* packed = nullptr; // set by zkez_layout alone: sec[3 … 9] are then the PACKED sections and records() is not to be read
 };
 int zkey_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, bool need_ic = true);
+// A PACKED proving key ("zkez", version 1; include/groth16_prover.h has the container, zkey_pack29.h the coefficient's form).
+// Section 4 of it, and the body groth16_zkey_coefs_pack writes: {u32 declared_count, u32 n_coef, u64 payload_bytes}, n_coef × 12
+// bytes of {m, c, s}, n_coef code bytes, the directory of n_blocks + 1 u64 (blocks of 256 coefficients), the payload.
+// zkez_coefs_layout demands that the size equals the sum of these parts and runs wz_check_directory (ERR_FORMAT, each rule with its
+// text): block b's payload [dir[b], dir[b + 1]) then lies inside the payload and spans at most 8192 bytes whatever the codes say.
+struct ZkezCoefs {
+  uint32_t declared = 0, n_coef = 0;
+  uint64_t n_blocks = 0, payload_bytes = 0;
+  const uint8_t *triples = nullptr, *codes = nullptr, *dir = nullptr, *payload = nullptr; // into the caller's image, unaligned
+};
+int zkez_coefs_layout(const uint8_t* body, uint64_t size, ZkezCoefs* C);
+constexpr uint64_t ZKEZ_COEFS_HEAD = 16;
+inline uint64_t zkez_coefs_bytes(uint64_t n_coef, uint64_t payload_bytes) { return ZKEZ_COEFS_HEAD + 13 * n_coef + 8 * ((n_coef + 255) / 256 + 1) + payload_bytes; }
+// zkez_layout: the section table under magic "zkez", version 1 — a .zkey is refused as any foreign magic is, and zkey_layout takes
+// none of these; zkey_layout's rules for sections 1 and 2 (the same code); sections 3 … 9 once each; every point section with
+// exactly HALF the bytes zkey_layout demands (ERR_FORMAT naming the section and both sizes); section 4 through zkez_coefs_layout.
+// All of it before a byte goes up.  L is filled as zkey_layout fills it, n_coef from section 4's second word, and L->packed = P.
+struct PackedZkey {
+  ZkezCoefs coefs;
+  uint64_t unpacked_bytes = 0; // of the .zkey it came from
+};
+int zkez_layout(const uint8_t* data, size_t len, std::vector<Section>& secs, ZkeyLayout* L, PackedZkey* P);
 struct MappedFile {
   const uint8_t* data = nullptr;
   size_t len = 0;
@@ -283,7 +313,8 @@ int adopt_tables(ZKeyCache* z, bool wait);
 // CacheManager::compute — src/cache.rs:117-241, from a key that zkey_layout has read (a load, every shard of a device group and the
 // cold prove parse once and hand the layout on).  A row of stages over one LoadCtx (cache.cpp): fill_header → open_streams →
 // alloc_key_buffers (shard_ranges.h) → decide_layout → ingest (not when pipelined) → convert_bases → alloc_work_buffers →
-// start_cold_upload / start_table_thread.
+// start_cold_upload / start_table_thread.  A PACKED key (L.packed set by zkez_layout; count = 1, cold = nullptr) runs ingest_packed in
+// ingest's place: the packed sections go up into temporaries of the LoadCtx and the unpack kernels fill the buffers ingest fills.
 // `defer_tables`: return once the key can prove in the classic layout and build
 // the fixed-base tables on a worker thread (single-device keys; ICICLE_SNARK_DEFER_TABLES=0 builds them before returning)
 // `cold` (single-device keys with deferred or no tables): return as soon as the buffers exist and an uploader task has been started —
@@ -306,6 +337,27 @@ void cold_upload_wait(ColdUpload* cu); // blocks until the uploader task has end
 int build_cache(const ZkeyLayout& L, int device_id, int rank, int count, std::unique_ptr<ZKeyCache>& out, bool defer_tables = false, ColdUpload* cold = nullptr);
 typedef CopyJob UploadJob;
 int staged_upload(int device_id, const std::vector<UploadJob>& jobs, const hipStream_t* lanes_in = nullptr, int n_lanes = 0, StagedProgress* progress = nullptr);
+
+// ---- packed points and packed coefficients on a device (ptau_pack.hip, zkey_pack.hip)
+// What a pack / unpack launch leaves behind: min over the faulty lanes of (element << 3 | kind), ~0 without one; their number.
+struct PackTally {
+  unsigned long long first, count;
+};
+// ONE launch, a lane per point, both buffers on the device, the faults into *d_tally (reset by the caller); nothing is synchronised.
+// pack: n file-form points (64 bytes, g2: 128) → n packed words behind zkey_check29.h's lane test (g2: with the subgroup test);
+// unpack: the reverse through point_pack29.h's full pk_unpack_g1 / pk_unpack_g2.  A faulty element leaves zeros.
+int pack_on_device(hipStream_t st, const uint8_t* d_points, uint64_t n, bool g2, uint8_t* d_out, PackTally* d_tally);
+int unpack_on_device(hipStream_t st, const uint8_t* d_words, uint64_t n, bool g2, uint8_t* d_out, PackTally* d_tally);
+// Packed coefficients (a ZkezCoefs that zkez_coefs_layout has passed) → n_coef file-form records of COEF_RECORD_BYTES at d_records:
+// zkez_coefs_device_bytes is the room wanted at d_buf (a hipMalloc'd base), zkez_coefs_jobs appends the four uploads into it, and —
+// once they have landed — zkez_coefs_decode zeroes the paddings and enqueues ONE launch on `st`, a 256-lane workgroup per block.
+// Nothing is synchronised; *d_tally (reset by the caller) holds (coefficient << 3 | GROTH16_WTNZ_*).  A faulty lane writes a zero record.
+size_t zkez_coefs_device_bytes(const ZkezCoefs& C);
+void zkez_coefs_jobs(const ZkezCoefs& C, uint8_t* d_buf, std::vector<UploadJob>& jobs);
+int zkez_coefs_decode(hipStream_t st, const ZkezCoefs& C, uint8_t* d_buf, uint32_t* d_records, PackTally* d_tally);
+// ERR_FORMAT "<form>: section S, element E: <point kind>" / "<form>: coefficient E: <wtnz kind>" for a tally that holds a fault
+int packed_point_fail(const char* form, int section, const PackTally& t);
+int packed_coef_fail(const char* form, const PackTally& t);
 
 // ---- blinding and proof assembly (assemble.cpp)
 // blinding terms that do not depend on the commitments: δ1·r, δ1·s, δ2·s, δ1·r·s (src/proof_helper.rs:280-283);

@@ -35,9 +35,7 @@ namespace vb = isnark::vb;
 constexpr int PK_WG_G1 = 256, PK_WG_G2 = 64;
 constexpr int MAX_SECTIONS = 8; // 2 … 5 and 12 … 15 (section 6 is the host's)
 
-struct Tally {
-  unsigned long long first, count; // min over the faulty lanes of (index << 3 | kind), NO_FAULT without one; their number
-};
+typedef pv::PackTally Tally; // min over the faulty lanes of (index << 3 | kind), NO_FAULT without one; their number
 __device__ __forceinline__ void tally_fault(Tally* t, uint64_t i, int kind)
 {
   atomicAdd(&t->count, 1ull);
@@ -95,7 +93,12 @@ __global__ __launch_bounds__(G2 ? PK_WG_G2 : PK_WG_G1) void pk_unpack_kernel(con
 
 constexpr size_t FILE_BYTES[2] = {64, 128}, PACKED_BYTES[2] = {32, 64}; // [g2]
 
-// n packed words at d_words → n file-form points at d_out, both on the device; the faults into *d_tally (reset by the caller)
+} // namespace
+
+namespace isnark {
+namespace prover {
+// n packed words at d_words → n file-form points at d_out, both on the device; the faults into *d_tally (reset by the caller).
+// (prover_internal.h: the packed proving key, zkey_pack.hip and cache.cpp, runs its point sections through the same two.)
 int unpack_on_device(hipStream_t st, const uint8_t* d_words, uint64_t n, bool g2, uint8_t* d_out, Tally* d_tally)
 {
   if (!n) return 0;
@@ -110,6 +113,12 @@ int pack_on_device(hipStream_t st, const uint8_t* d_points, uint64_t n, bool g2,
   else DEV_LAUNCH("pack kernel launch", pk_pack_kernel<false>, dim3((uint32_t)((n + PK_WG_G1 - 1) / PK_WG_G1)), dim3(PK_WG_G1), st, (const fe*)d_points, n, (fe*)d_out, d_tally);
   return 0;
 }
+} // namespace prover
+} // namespace isnark
+
+namespace {
+using pv::pack_on_device;
+using pv::unpack_on_device;
 
 // one range of points through the device, in either direction
 struct Range {

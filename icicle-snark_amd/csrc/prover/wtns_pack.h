@@ -123,6 +123,11 @@ WZ_HD int wz_decode_value(uint8_t code, const uint32_t pay[8], uint32_t out[8])
 }
 
 // ---- host only from here ------------------------------------------------------------------------------------------------------
+inline const char* wz_fault_text(int kind) // of WZ_CODE … WZ_DIRECTORY, as the messages name them
+{
+  static const char* const text[5] = {"", "an undefined code byte", "the value's form is not canonical", "32 bytes that are not below r", "the block's lengths do not sum to its directory span"};
+  return text[kind >= 0 && kind < 5 ? kind : 0];
+}
 inline void wz_load_words(const uint8_t* bytes, int len, uint32_t w[8]) // len ≤ 32 little-endian bytes, zero-extended
 {
   uint8_t b[32] = {0};

@@ -129,15 +129,12 @@ struct DeviceLayout { // of d_buf
   }
 };
 
-const char* const WZ_FAULT[5] = {"", "an undefined code byte", "the value's form is not canonical", "32 bytes that are not below r",
-                                 "the block's lengths do not sum to its directory span"};
-
 } // namespace
 
 namespace isnark {
 namespace prover {
 
-int wtnz_fail(const WtnzFault& f) { return fail(ERR_FORMAT, "wtnz: element %llu: %s", (unsigned long long)f.element, WZ_FAULT[f.kind >= 0 && f.kind < 5 ? f.kind : 0]); }
+int wtnz_fail(const WtnzFault& f) { return fail(ERR_FORMAT, "wtnz: element %llu: %s", (unsigned long long)f.element, wz::wz_fault_text(f.kind)); }
 
 size_t wtnz_device_bytes(const WtnzLayout& L) { return DeviceLayout(L).total; }
 

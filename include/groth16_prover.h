@@ -907,6 +907,97 @@ int groth16_prove_packed_files(const char* witness_path, const char* zkey_path, 
 int groth16_witness_check_packed(Groth16R1cs* h, const void* wtnz, size_t len, Groth16WitnessReport* report);
 int groth16_witness_check_packed_file(Groth16R1cs* h, const char* wtnz_path, Groth16WitnessReport* report);
 
+/* groth16_zkey_pack, groth16_zkey_unpack, groth16_cache_load_packed, groth16_prove_zkez_files — a proving key PACKED ("zkez") and
+ * back, and a load that takes the packed key and never holds the unpacked one on the host.  The .zkey is the largest file that
+ * reaches a prover: its points are stored as x and one bit of y (the packed point of groth16_ptau_pack above, unchanged: half the
+ * bytes), its coefficients as a code byte and the significant bytes of the value (the value code of groth16_wtns_pack above,
+ * unchanged).  Opt-in: nothing that takes a .zkey takes this, and the reverse.
+ * THE CODED VALUE.  Section 4 of a .zkey holds a coefficient as file_value = v * R^2 mod r, R = 2^256.  The value coded is the
+ * standard-form coefficient v = file_value * R^-2 mod r — in a real key almost always 1 or r - 1, one code byte or two.  Packing
+ * demands file_value < r (a value not below r is the fault RANGE); v -> v * R^2 mod r is a bijection on [0, r) and the value code is
+ * one between [0, r) and its valid (code, payload) pairs, so pack and unpack are inverse byte for byte and both are functions of
+ * their input alone.
+ * THE CONTAINER is the .zkey's section table under magic "zkez", version 1, the sections in the input's order: no reader of a .zkey
+ * takes it for one (-2, as any foreign magic), and the packed reader takes no .zkey.
+ *   1, 2, 10 and any unknown section   byte for byte the .zkey's (the header and its six points are NOT packed)
+ *   3, 5, 6, 8, 9 (G1), 7 (G2)         exactly half the bytes: each point its packed word, the identity 00 ... 00 40
+ *   4   u32 declared_count (the .zkey's first four bytes, verbatim; no loader reads it) | u32 n_coef | u64 payload_bytes |
+ *       n_coef * 12 bytes, the {m, c, s} triples as they stand | n_coef code bytes | the directory, ceil(n_coef / 256) + 1
+ *       little-endian u64: entry b = where the payload of block b (coefficients 256 b ... 256 b + 255) begins, entry 0 = 0, the last
+ *       entry = payload_bytes | the payload: the values' significant bytes in order
+ * THE HOST bounds everything before a byte goes up: sections 1 and 2 by the rules of every .zkey reader here; every point section's
+ * exact packed size (-2 naming the section and both sizes); section 4's size against the sum of its parts; the directory beginning at
+ * 0, never decreasing, no block spanning more than 8192 bytes, ending at payload_bytes (-2, each with a text of its own).  No content
+ * of a file can then make a kernel read outside its buffers.  groth16_zkey_pack reads the key as groth16_zkey_check does (section 3
+ * included): a key that reader refuses is refused with its message.
+ * THE DEVICE runs one launch per point section — packing behind the lane test of the other key tools (section 7 with the subgroup
+ * test), so a file packed here always unpacks; unpacking through the full test of groth16_ptau_unpack, section 7's subgroup test
+ * included — and for section 4 two kernels to pack (code and block sums; then, behind the host's directory, the payload) and one to
+ * unpack, a 256-lane workgroup per block.
+ * FAULTS are -2 and name the lowest faulty section, then its lowest faulty element; fault_count is that section's; nothing is written
+ * and nothing is cached:
+ *   "zkez: section S, element E: <point kind>"   GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE / _OFF_SUBGROUP
+ *   "zkez: coefficient E: <kind>"                fault_section = 4 and GROTH16_WTNZ_CODE / _NONCANONICAL / _RANGE / _DIRECTORY
+ *   packing: "zkey: section S, element E: <point kind>" and "zkey: coefficient E: not below r" (GROTH16_WTNZ_RANGE)
+ * SIZES.  groth16_zkey_unpacked_size is exact from the packed container; groth16_zkey_packed_bound is the upper bound from the .zkey's
+ * container, every value at 32 bytes; both run the reader's tests and need no GPU.  The packed size itself is known only after the
+ * first coefficient kernel: the buffer entry tests cap then (-3, report->out_bytes says what is needed).
+ * 0 done; -1 I/O; -2 format or a fault; -3 argument: cap too small, equal paths (by name or by inode), a device string that does not
+ * name one HIP device; -5 device failure.  The _file entries map the input, write a temporary beside out_path and rename it: a
+ * failed call leaves nothing.  ICICLE_SNARK_TRACE_ZKEY_PACK=1 prints the stage times on stderr.
+ * What it does NOT do: compress the {m, c, s} triples; pack section 2 or section 10; let groth16_zkey_check, _verify_ptau,
+ * _contribute, groth16_r1cs_match_zkey, groth16_cache_load or groth16_prove read a packed key (unpack first, or load it packed);
+ * overlap the packed load with a first proof; skip section 7's subgroup test on load; serve shards or device groups. */
+typedef struct {
+  uint32_t n_vars, n_public, domain, n_coef;
+  uint64_t points[2];             /* G1 points, G2 points of sections 3 and 5 to 9 */
+  uint64_t in_bytes, out_bytes;   /* the input; the output (also when cap was too small) */
+  uint64_t point_bytes, coef_bytes; /* of the PACKED form: the point sections; section 4 */
+  int32_t  fault_section, fault_kind; /* the section; a point's GROTH16_ZKEY_*, in section 4 GROTH16_WTNZ_* */
+  uint64_t fault_index;           /* the lowest faulty element of that section */
+  uint64_t fault_count;           /* that section's faulty elements */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the sections' copies up; wall time of the device part without them, up to
+                                     the last kernel; the copies into the buffer or the mapped file; msync and rename (_file) */
+} Groth16ZkeyPackReport;
+int groth16_zkey_unpacked_size(const void* zkez, size_t len, uint64_t* zkey_bytes);
+int groth16_zkey_packed_bound(const void* zkey, size_t len, uint64_t* packed_bytes);
+int groth16_zkey_pack(const void* zkey, size_t len, void* out, size_t cap, const char* device, Groth16ZkeyPackReport* report);
+int groth16_zkey_pack_file(const char* in_path, const char* out_path, const char* device, Groth16ZkeyPackReport* report);
+int groth16_zkey_unpack(const void* zkez, size_t len, void* out, size_t cap, const char* device, Groth16ZkeyPackReport* report);
+int groth16_zkey_unpack_file(const char* in_path, const char* out_path, const char* device, Groth16ZkeyPackReport* report);
+/* THE RAW CODEC, as groth16_points_pack is to the point sections: n records of 44 bytes {m, c, s, value} in host memory to the body
+ * of a packed section 4 (declared_count = n) and back; n = 0 is valid (a body of 24 bytes).  pack: cap is tested once the size is
+ * known (-3, out_bytes says what is needed; zkez bound: 24 + 45 n + 8 ceil(n / 256) bytes); unpack: the body passes the reader's
+ * tests of section 4 first and `out` takes n * 44 bytes.  Faults as above, "zkey: coefficient E: not below r" / "zkez: coefficient
+ * E: <kind>"; nothing is written. */
+typedef struct {
+  uint64_t n;
+  uint64_t in_bytes, out_bytes;
+  int32_t  fault_kind;          /* GROTH16_WTNZ_* */
+  uint64_t fault_index;         /* the lowest faulty coefficient */
+  uint64_t fault_count;         /* how many are faulty */
+  double   upload_ms, device_ms, download_ms;
+} Groth16ZkeyCoefsReport;
+int groth16_zkey_coefs_pack(const void* records, uint64_t n, void* out, size_t cap, const char* device, Groth16ZkeyCoefsReport* report);
+int groth16_zkey_coefs_unpack(const void* body, size_t len, void* out, size_t cap, const char* device, Groth16ZkeyCoefsReport* report);
+/* groth16_cache_load_packed — groth16_cache_load from a packed key, on ONE device: the packed point sections and section 4 go up, the
+ * unpack kernels write file-form points and records straight into the buffers the loader has always filled, every verdict is read,
+ * and the rest of the load — the CSR build, the bases' conversion, the deferred tables — runs unchanged on what it has always been
+ * given.  The entry is the one groth16_cache_load of the unpacked key builds; the budget is charged the UNPACKED size.  A fault is
+ * -2 as above and nothing is cached.  A key the manager already holds under `key` is 0 at once.  Warm, this load is SLOWER than
+ * groth16_cache_load_file of the same key (the roots cost more than the halved upload saves; README has the figures): what the
+ * format buys is bytes stored and moved.  The arguments are groth16_cache_load's; anything but shard 0 of 1 is -3 with a message.
+ * What it does NOT do: shards and device groups; overlap with a first proof. */
+int groth16_cache_load_packed(Groth16CacheManager* cm, const char* key, const void* zkez, size_t len, int device_id, int shard_rank,
+                              int shard_count);
+int groth16_cache_load_packed_file(Groth16CacheManager* cm, const char* key, const char* zkez_path, int device_id, int shard_rank,
+                                   int shard_count);
+/* groth16_prove_zkez_files — groth16_prove with a packed key, file to file, the cache key "<zkez_path>_<device>".  A key the manager
+ * does not hold is loaded through groth16_cache_load_packed_file first; then groth16_prove_mem's path runs.  What it does NOT do:
+ * groth16_prove's cold-path overlap; more than one device (-3). */
+int groth16_prove_zkez_files(const char* witness_path, const char* zkez_path, const char* proof_path, const char* public_path,
+                             const char* device, Groth16CacheManager* cm);
+
 #ifdef __cplusplus
 }
 #endif
