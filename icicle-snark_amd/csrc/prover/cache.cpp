@@ -676,7 +676,7 @@ int ingest_packed(LoadCtx& c)
   if (int rc = staged_upload(c.device_id, c.jobs, z->streams().data(), 6)) return rc;
   c.lap("staged upload (packed)");
   PackTally tallies[6];
-  for (PackTally& t : tallies) t = {~0ull, 0};
+  for (PackTally& t : tallies) t = {NO_FAULT, 0};
   P_HIP(hipMemcpyAsync(d_tally, tallies, sizeof tallies, hipMemcpyHostToDevice, nullptr));
   for (int k = 0; k < 5; k++)
     if (int rc = unpack_on_device(nullptr, d_words[k], BASES[k].of(z).len(), BASES[k].g2, (uint8_t*)BASES[k].of(z).d_points, d_tally + k)) return rc;
@@ -685,10 +685,10 @@ int ingest_packed(LoadCtx& c)
   P_HIP(hipStreamSynchronize(nullptr));
   c.lap("unpack kernels");
   // the lowest faulty section, then its lowest faulty element (section 4 lies below the bases' 5 … 9)
-  if (tallies[5].first != ~0ull) return packed_coef_fail("zkez", tallies[5]);
+  if (tallies[5].first != NO_FAULT) return packed_coef_fail("zkez", tallies[5]);
   for (int id = 5; id <= 9; id++)
     for (int k = 0; k < 5; k++)
-      if (BASES[k].section == id && tallies[k].first != ~0ull) return packed_point_fail("zkez", id, tallies[k]);
+      if (BASES[k].section == id && tallies[k].first != NO_FAULT) return packed_point_fail("zkez", id, tallies[k]);
   for (void* p : c.packed_tmp) (void)hipFree(p);
   c.packed_tmp.clear();
   return build_csr(c);

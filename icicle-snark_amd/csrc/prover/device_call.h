@@ -1,17 +1,20 @@
-// device_call.h — the host plumbing every key tool wraps its device work in (zkey_check.hip, r1cs_check.hip, zkey_verify.hip,
-// zkey_new.hip; verify_combined.hip takes its MSM configuration from here): one error text and the checked call and launch that
-// return it, stage times, the scoped file hint of the pinned staging, the timed upload, the temporary a _file entry writes and
-// renames (ptau_contribute.hip, ptau_pack.hip), an event that destroys itself, the library's MSMs over device operands in slices,
+// device_call.h — the host plumbing every key, file and pack tool wraps its device work in (the zkey_*.hip, ptau_*.hip, wtns_pack.hip,
+// r1cs_check.hip; verify_combined.hip takes its MSM configuration from here): one error text and the checked call and launch that
+// return it, the device a call names, stage times, the scoped file hint of the pinned staging, the timed upload, where an output
+// goes once its size is known (Sink: the caller's buffer, or the temporary a _file entry writes and renames), the ONE _file entry
+// of a tool that rewrites a file (rewrite_file), an event that destroys itself, the library's MSMs over device operands in slices,
 // and the seed and coefficients of the randomised checks.  The device session and its buffers are verify_batch.h's; the host point
-// helpers are verify_host.h's; the ptau's ranges are ptau_ranges.h's.
+// helpers are verify_host.h's; the ptau's ranges are ptau_ranges.h's; what the packed forms' kernels share is pack_device.h's.
 #pragma once
 #include <algorithm>
 #include <chrono>
 #include <fcntl.h>
+#include <functional>
 #include <stdio.h>
 #include <string.h>
 #include <string>
 #include <sys/mman.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "../workers.h"
@@ -35,6 +38,15 @@ inline int dev_fail(const char* what, hipError_t e) { return fail(ERR_DEVICE, "%
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);      \
     DEV_TRY(what, hipGetLastError());                                     \
   } while (0)
+
+// the one HIP device a call names
+inline int parse_device(const char* device, int* dev)
+{
+  if (!device) return fail(ERR_ARG, "null device");
+  *dev = vb::parse_one_device(device);
+  if (*dev < 0) return fail(ERR_ARG, "device: '%s' does not name one HIP device", device);
+  return 0;
+}
 
 // stage times on stderr when `env` is set (read at every call: common.h's rule for a knob an in-process caller may change), as
 // ICICLE_SNARK_TRACE_COLD for a load
@@ -116,6 +128,38 @@ struct TempOutput {
     return rc;
   }
 };
+
+// where a call's output goes, asked once its size is known and before anything is written
+typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+// the caller's buffer of `cap` bytes; `noun` is what the text calls the output
+inline Sink buffer_sink(const char* noun, void* out, size_t cap)
+{
+  return [noun, out, cap](uint64_t bytes, uint8_t** o) {
+    if (!out || cap < bytes)
+      return fail(ERR_ARG, "the %s needs %llu bytes, the buffer holds %llu", noun, (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
+    *o = (uint8_t*)out;
+    return 0;
+  };
+}
+// A _file entry that rewrites in_path as out_path: the paths are judged (null, the same, the same file under two names), the input
+// is mapped and hinted to the staging workers (they pread() the file instead of copying out of the mapping), `impl` runs over the
+// image with a sink that opens a TempOutput, and the temporary is renamed or unlinked.  *write_ms (may be null): msync and rename.
+inline int rewrite_file(const char* in_path, const char* out_path, double* write_ms, const std::function<int(const uint8_t* data, size_t len, const Sink& sink)>& impl)
+{
+  if (!in_path || !out_path) return fail(ERR_ARG, "null path");
+  if (strcmp(in_path, out_path) == 0) return fail(ERR_ARG, "the output path is the input's");
+  MappedFile mf;
+  if (int rc = mf.open_ro(in_path)) return rc;
+  struct stat a, b;
+  if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return fail(ERR_ARG, "the output path is the input's");
+  const FileHint hint(mf.data, mf.len, mf.fd);
+  TempOutput to(out_path);
+  int rc = impl(mf.data, mf.len, [&](uint64_t bytes, uint8_t** o) { return to.open(bytes, o); });
+  const auto t_write = std::chrono::steady_clock::now();
+  rc = to.finish(rc);
+  if (rc == 0 && write_ms) *write_ms = ms_since(t_write);
+  return rc;
+}
 
 struct Event { // ordering only: no timing
   hipEvent_t e = nullptr;

@@ -32,6 +32,9 @@
 
 namespace isnark {
 const bn254::fe* ntt_domain_table(int* log_n); // ntt.hip
+namespace vb {
+struct DeviceSession; // verify_batch.h
+}
 
 namespace prover {
 using namespace bn254;
@@ -77,6 +80,20 @@ struct SectionEntry { // of a container read_sections has passed, as the file or
   const uint8_t* p;
 };
 std::vector<SectionEntry> sections_in_order(const uint8_t* data);
+// what a writer puts in front: the container's 12 bytes, a section's 12 bytes; w moves behind them
+inline void put_container_head(uint8_t*& w, const char* magic, uint32_t version, uint32_t n_sections)
+{
+  memcpy(w, magic, 4);
+  memcpy(w + 4, &version, 4);
+  memcpy(w + 8, &n_sections, 4);
+  w += 12;
+}
+inline void put_section(uint8_t*& w, uint32_t id, uint64_t size)
+{
+  memcpy(w, &id, 4);
+  memcpy(w + 4, &size, 8);
+  w += 12;
+}
 // What a zkey says about itself: the sections 2 … 9 and the header's fields.  zkey_layout is the ONE statement of the container
 // and header rules — the loader (build_cache), the key check and the vk export all read a key through it.  Checked, in this
 // order: section 1 and the protocol; sections 2, (3,) 4 … 9 present once; header length, field sizes, moduli, a power-of-two
@@ -338,8 +355,12 @@ int build_cache(const ZkeyLayout& L, int device_id, int rank, int count, std::un
 typedef CopyJob UploadJob;
 int staged_upload(int device_id, const std::vector<UploadJob>& jobs, const hipStream_t* lanes_in = nullptr, int n_lanes = 0, StagedProgress* progress = nullptr);
 
-// ---- packed points and packed coefficients on a device (ptau_pack.hip, zkey_pack.hip)
-// What a pack / unpack launch leaves behind: min over the faulty lanes of (element << 3 | kind), ~0 without one; their number.
+// ---- lane tests' verdicts; packed points, packed coefficients and packed witnesses on a device (ptau_pack.hip, zkey_pack.hip,
+// wtns_pack.hip; pack_device.h has what their kernels share)
+// min over the faulty lanes of (element << 3 | kind) without a faulty lane; the text of a point's kind
+constexpr unsigned long long NO_FAULT = ~0ull;
+const char* const POINT_FAULT[4] = {"", "a coordinate is not below q", "the point is not on the curve", "the point is outside the subgroup"};
+// What a pack / unpack launch leaves behind: min over the faulty lanes of (element << 3 | kind), NO_FAULT without one; their number.
 struct PackTally {
   unsigned long long first, count;
 };
@@ -348,6 +369,18 @@ struct PackTally {
 // unpack: the reverse through point_pack29.h's full pk_unpack_g1 / pk_unpack_g2.  A faulty element leaves zeros.
 int pack_on_device(hipStream_t st, const uint8_t* d_points, uint64_t n, bool g2, uint8_t* d_out, PackTally* d_tally);
 int unpack_on_device(hipStream_t st, const uint8_t* d_words, uint64_t n, bool g2, uint8_t* d_out, PackTally* d_tally);
+// one range of points on its way through the device, in either direction
+struct PointRange {
+  int section;
+  bool g2;
+  uint64_t n;
+  const uint8_t* src; // host
+  uint8_t* dst;       // host; set once the output's layout is known
+  uint8_t *d_in, *d_out;
+};
+// every range with points: d_in and d_out from the session, src up (landed on return, its time added to *upload_ms), the ONE launch
+// above on the session's stream 0 with d_tally[k] for range k (reset by the caller).  Nothing is synchronised.
+int enqueue_point_ranges(vb::DeviceSession& ds, int dev, bool unpack, PointRange* ranges, size_t count, PackTally* d_tally, double* upload_ms);
 // Packed coefficients (a ZkezCoefs that zkez_coefs_layout has passed) → n_coef file-form records of COEF_RECORD_BYTES at d_records:
 // zkez_coefs_device_bytes is the room wanted at d_buf (a hipMalloc'd base), zkez_coefs_jobs appends the four uploads into it, and —
 // once they have landed — zkez_coefs_decode zeroes the paddings and enqueues ONE launch on `st`, a 256-lane workgroup per block.

@@ -15,12 +15,8 @@
 //   The device tables are overwritten before they are freed, the host's secrets wiped on every way out: best effort.
 #include <algorithm>
 #include <chrono>
-#include <fcntl.h>
 #include <functional>
 #include <string>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <vector>
 
 #include "../msm_impl.h"
@@ -212,29 +208,6 @@ A point_at(const uint8_t* p)
   return a;
 }
 
-// the input's sections in file order (read_sections has bounded them)
-struct Entry {
-  uint32_t id;
-  uint64_t size;
-  const uint8_t* p;
-};
-std::vector<Entry> file_order(const uint8_t* data)
-{
-  uint32_t nsec;
-  memcpy(&nsec, data + 8, 4);
-  std::vector<Entry> out;
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    Entry e;
-    memcpy(&e.id, data + pos, 4);
-    memcpy(&e.size, data + pos + 4, 8);
-    e.p = data + pos + 12;
-    out.push_back(e);
-    pos += 12 + e.size;
-  }
-  return out;
-}
-
 // everything secret of one call; wiped on every way out (best effort: the compiler may have kept copies in registers or spills)
 struct Secrets {
   uint8_t seed[32];
@@ -259,7 +232,7 @@ struct TableWipe {
   }
 };
 
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+using pv::Sink;
 using pv::TempOutput;
 
 // ---- groth16_ptau_new
@@ -275,11 +248,7 @@ void new_write(uint32_t power, uint8_t* w)
   const uint64_t N = (uint64_t)1 << power;
   const G1::A g1 = vb::g1_generator_mont();
   const G2::A g2 = vb::g2_generator_mont();
-  auto section = [&](uint32_t id, uint64_t size) {
-    memcpy(w, &id, 4);
-    memcpy(w + 4, &size, 8);
-    w += 12;
-  };
+  auto section = [&](uint32_t id, uint64_t size) { pv::put_section(w, id, size); };
   // count copies of one point from w on, on the worker pool
   auto fill = [&](const void* pt, size_t elem, uint64_t count) {
     uint8_t* const base = w;
@@ -288,11 +257,8 @@ void new_write(uint32_t power, uint8_t* w)
     });
     w += count * elem;
   };
-  const uint32_t version = 1, nsec = 7, n8 = 32, zero = 0;
-  memcpy(w, "ptau", 4);
-  memcpy(w + 4, &version, 4);
-  memcpy(w + 8, &nsec, 4);
-  w += 12;
+  const uint32_t n8 = 32, zero = 0;
+  pv::put_container_head(w, "ptau", 1, 7);
   section(1, 44);
   const fe q = Fq::modulus();
   memcpy(w, &n8, 4);
@@ -344,9 +310,8 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   if (!name) name = "";
   const size_t name_len = strlen(name);
   if (name_len > NAME_BYTES_MAX) return pv::fail(pv::ERR_ARG, "the contributor's name has %zu bytes, a record holds %u", name_len, NAME_BYTES_MAX);
@@ -514,11 +479,9 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   uint8_t* out_sec[4] = {nullptr, nullptr, nullptr, nullptr};
   memcpy(w, data, 12);
   w += 12;
-  for (const Entry& e : file_order(data)) {
+  for (const pv::SectionEntry& e : pv::sections_in_order(data)) {
     const uint64_t size = e.id == 7 ? e.size + rec_bytes : e.size;
-    memcpy(w, &e.id, 4);
-    memcpy(w + 4, &size, 8);
-    w += 12;
+    pv::put_section(w, e.id, size);
     if (e.id >= 2 && e.id <= 5) out_sec[e.id - 2] = w;
     else if (e.id == 6) memcpy(w, &beta2_out, 128);
     else memcpy(w, e.p, (size_t)e.size);
@@ -575,8 +538,9 @@ ISNARK_API int groth16_ptau_new(uint32_t power, void* out, size_t cap, uint64_t*
   uint64_t bytes;
   if (int rc = new_size(power, &bytes)) return rc;
   *out_len = bytes;
-  if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the file needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-  new_write(power, (uint8_t*)out);
+  uint8_t* o = nullptr;
+  if (int rc = pv::buffer_sink("file", out, cap)(bytes, &o)) return rc;
+  new_write(power, o);
   return 0;
 }
 
@@ -595,33 +559,15 @@ ISNARK_API int groth16_ptau_new_file(uint32_t power, const char* out_path)
 ISNARK_API int groth16_ptau_contribute(const void* ptau, size_t len, const uint8_t* secret32, const char* name, void* out, size_t cap, const char* device,
                                        const Groth16PtauContributeOptions* opt, Groth16PtauContributeReport* report)
 {
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) {
-    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the file needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-    *o = (uint8_t*)out;
-    return 0;
-  };
-  return contribute_impl((const uint8_t*)ptau, len, secret32, name, device, opt, report, sink);
+  return contribute_impl((const uint8_t*)ptau, len, secret32, name, device, opt, report, pv::buffer_sink("file", out, cap));
 }
 
 ISNARK_API int groth16_ptau_contribute_file(const char* in_path, const char* out_path, const uint8_t* secret32, const char* name, const char* device,
                                             const Groth16PtauContributeOptions* opt, Groth16PtauContributeReport* report)
 {
-  if (!in_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
-  if (strcmp(in_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  pv::MappedFile mf;
-  if (int rc = mf.open_ro(in_path)) return rc;
-  {
-    struct stat a, b; // the same file under two names
-    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  }
-  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
-  TempOutput to(out_path);
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) { return to.open(bytes, o); };
-  int rc = contribute_impl(mf.data, mf.len, secret32, name, device, opt, report, sink);
-  const auto t_write = std::chrono::steady_clock::now();
-  rc = to.finish(rc);
-  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
-  return rc;
+  return pv::rewrite_file(in_path, out_path, report ? &report->write_ms : nullptr, [&](const uint8_t* data, size_t len, const Sink& sink) {
+    return contribute_impl(data, len, secret32, name, device, opt, report, sink);
+  });
 }
 
 ISNARK_API int groth16_ptau_contributions(const void* ptau, size_t len, Groth16PtauContributionsReport* report, Groth16PtauContributionInfo* infos, size_t infos_cap)

@@ -1,6 +1,7 @@
 // ptau_pack.hip — groth16_ptau_pack / groth16_ptau_unpack: a powers-of-tau file with every point as x and one bit of y, half the
 // bytes, and back; groth16_points_pack / groth16_points_unpack: the same over a plain buffer of points.  include/groth16_prover.h
-// has the contract and the packed container; point_pack29.h the packed point and its lane code; DESIGN.md §7j.
+// has the contract and the packed container; point_pack29.h the packed point and its lane code; DESIGN.md §7j.  enqueue_point_ranges
+// (prover_internal.h) is how the ranges of this tool and of the packed proving key (zkey_pack.hip) go up and through their launches.
 //
 //   host, first  the container — a .ptau in either form (ptau_either_layout) for pack, a packed file (ptau_packed_layout) for unpack:
 //                both bound every point section to its exact element count before a byte goes up — the output's size against the
@@ -16,13 +17,12 @@
 #include <chrono>
 #include <functional>
 #include <string>
-#include <sys/stat.h>
 #include <vector>
 
 #include "device_call.h"
+#include "pack_device.h"
 #include "point_pack29.h"
 #include "prover_internal.h"
-#include "ptau_ranges.h"
 #include "verify_batch.h"
 
 using namespace bn254;
@@ -36,11 +36,9 @@ constexpr int PK_WG_G1 = 256, PK_WG_G2 = 64;
 constexpr int MAX_SECTIONS = 8; // 2 … 5 and 12 … 15 (section 6 is the host's)
 
 typedef pv::PackTally Tally; // min over the faulty lanes of (index << 3 | kind), NO_FAULT without one; their number
-__device__ __forceinline__ void tally_fault(Tally* t, uint64_t i, int kind)
-{
-  atomicAdd(&t->count, 1ull);
-  atomicMin(&t->first, (unsigned long long)i << 3 | (unsigned long long)kind);
-}
+using pv::NO_FAULT;
+using pv::POINT_FAULT;
+using pv::tally_fault; // pack_device.h
 
 // One lane per point, pts[i] → out[i], i < n.  A faulty point leaves a zero word (never a valid one: the identity has its flag).
 template <bool G2>
@@ -113,42 +111,36 @@ int pack_on_device(hipStream_t st, const uint8_t* d_points, uint64_t n, bool g2,
   else DEV_LAUNCH("pack kernel launch", pk_pack_kernel<false>, dim3((uint32_t)((n + PK_WG_G1 - 1) / PK_WG_G1)), dim3(PK_WG_G1), st, (const fe*)d_points, n, (fe*)d_out, d_tally);
   return 0;
 }
+int enqueue_point_ranges(vb::DeviceSession& ds, int dev, bool unpack, PointRange* ranges, size_t count, Tally* d_tally, double* upload_ms)
+{
+  const hipStream_t st = ds.stream(0);
+  for (size_t k = 0; k < count; k++) {
+    PointRange& r = ranges[k];
+    const size_t in_elem = (unpack ? PACKED_BYTES : FILE_BYTES)[r.g2], out_elem = (unpack ? FILE_BYTES : PACKED_BYTES)[r.g2];
+    if (!r.n) continue;
+    r.d_in = ds.buf.alloc<uint8_t>((size_t)(r.n * in_elem));
+    r.d_out = ds.buf.alloc<uint8_t>((size_t)(r.n * out_elem));
+    if (!r.d_in || !r.d_out) return dev_fail("hipMalloc", hipErrorOutOfMemory);
+    if (int rc = timed_upload(dev, r.d_in, r.src, (size_t)(r.n * in_elem), upload_ms)) return rc;
+    if (int rc = unpack ? unpack_on_device(st, r.d_in, r.n, r.g2, r.d_out, d_tally + k) : pack_on_device(st, r.d_in, r.n, r.g2, r.d_out, d_tally + k)) return rc;
+  }
+  return 0;
+}
 } // namespace prover
 } // namespace isnark
 
 namespace {
-using pv::pack_on_device;
-using pv::unpack_on_device;
+typedef pv::PointRange Range;
 
-// one range of points through the device, in either direction
-struct Range {
-  int section;
-  bool g2;
-  uint64_t n;
-  const uint8_t* src; // host
-  uint8_t* dst;       // host; set once the output's layout is known
-  uint8_t *d_in, *d_out;
-};
-
-// ranges up and through their kernels; *tallies[k] is range k's.  Every upload has landed and every kernel has run on return.
+// ranges up and through their kernels; tallies[k] is range k's.  Every upload has landed and every kernel has run on return.
 int run_ranges_on_device(vb::DeviceSession& ds, int dev, bool unpack, std::vector<Range>& ranges, Tally* tallies, double* upload_ms)
 {
   const hipStream_t st = ds.stream(0);
   const size_t nr = ranges.size();
   Tally* const d_tally = ds.buf.alloc<Tally>(nr);
   if (!d_tally) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-  for (size_t k = 0; k < nr; k++) tallies[k] = {NO_FAULT, 0};
-  DEV_TRY("tally upload", hipMemcpyAsync(d_tally, tallies, nr * sizeof(Tally), hipMemcpyHostToDevice, st));
-  for (size_t k = 0; k < nr; k++) {
-    Range& r = ranges[k];
-    const size_t in_elem = (unpack ? PACKED_BYTES : FILE_BYTES)[r.g2], out_elem = (unpack ? FILE_BYTES : PACKED_BYTES)[r.g2];
-    if (!r.n) continue;
-    r.d_in = ds.buf.alloc<uint8_t>((size_t)(r.n * in_elem));
-    r.d_out = ds.buf.alloc<uint8_t>((size_t)(r.n * out_elem));
-    if (!r.d_in || !r.d_out) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-    if (int rc = pv::timed_upload(dev, r.d_in, r.src, (size_t)(r.n * in_elem), upload_ms)) return rc;
-    if (int rc = unpack ? unpack_on_device(st, r.d_in, r.n, r.g2, r.d_out, d_tally + k) : pack_on_device(st, r.d_in, r.n, r.g2, r.d_out, d_tally + k)) return rc;
-  }
+  if (int rc = pv::reset_tallies(tallies, d_tally, nr, st)) return rc;
+  if (int rc = pv::enqueue_point_ranges(ds, dev, unpack, ranges.data(), nr, d_tally, upload_ms)) return rc;
   DEV_TRY("download", hipMemcpyAsync(tallies, d_tally, nr * sizeof(Tally), hipMemcpyDeviceToHost, st));
   DEV_TRY("pack kernels", hipStreamSynchronize(st));
   return 0;
@@ -162,13 +154,7 @@ int download_ranges(int dev, bool unpack, const std::vector<Range>& ranges)
   return 0;
 }
 
-int parse_device(const char* device, int* dev)
-{
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  *dev = vb::parse_one_device(device);
-  if (*dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
-  return 0;
-}
+using pv::parse_device;
 
 // ---- groth16_points_pack / groth16_points_unpack
 int points_impl(bool unpack, const void* in, uint64_t n, int g2, void* out, const char* device, Groth16PointsPackReport* rep)
@@ -200,31 +186,10 @@ int points_impl(bool unpack, const void* in, uint64_t n, int g2, void* out, cons
 }
 
 // ---- groth16_ptau_pack / groth16_ptau_unpack
-struct Entry { // the input's sections in file order (read_sections has bounded them)
-  uint32_t id;
-  uint64_t size;
-  const uint8_t* p;
-};
-std::vector<Entry> file_order(const uint8_t* data)
-{
-  uint32_t nsec;
-  memcpy(&nsec, data + 8, 4);
-  std::vector<Entry> out;
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    Entry e;
-    memcpy(&e.id, data + pos, 4);
-    memcpy(&e.size, data + pos + 4, 8);
-    e.p = data + pos + 12;
-    out.push_back(e);
-    pos += 12 + e.size;
-  }
-  return out;
-}
 bool is_point_section(uint32_t id, bool prepared) { return (id >= 2 && id <= 6) || (prepared && id >= 12 && id <= 15); }
 bool is_g2_section(uint32_t id) { return id == 3 || id == 6 || id == 13; }
 
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+using pv::Sink;
 
 int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, Groth16PtauPackReport* rep, const Sink& sink)
 {
@@ -285,17 +250,12 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
 
   // ---- the container: the other magic, the sections in the input's order
   uint8_t* w = out;
-  const uint32_t version = 1;
-  memcpy(w, unpack ? "ptau" : "ptaz", 4);
-  memcpy(w + 4, &version, 4);
-  memcpy(w + 8, data + 8, 4);
-  w += 12;
-  for (const Entry& e : file_order(data)) {
+  const std::vector<pv::SectionEntry> order = pv::sections_in_order(data);
+  pv::put_container_head(w, unpack ? "ptau" : "ptaz", 1, (uint32_t)order.size());
+  for (const pv::SectionEntry& e : order) {
     const bool point = is_point_section(e.id, prepared);
     const uint64_t size = !point ? e.size : unpack ? 2 * e.size : e.size / 2;
-    memcpy(w, &e.id, 4);
-    memcpy(w + 4, &size, 8);
-    w += 12;
+    pv::put_section(w, e.id, size);
     if (!point) memcpy(w, e.p, (size_t)e.size);
     else if (e.id == 6) memcpy(w, beta2_out, (size_t)size);
     else
@@ -313,33 +273,15 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
 
 int buffer_entry(bool unpack, const void* in, size_t len, void* out, size_t cap, const char* device, Groth16PtauPackReport* report)
 {
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) {
-    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the file needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-    *o = (uint8_t*)out;
-    return 0;
-  };
-  return file_impl(unpack, (const uint8_t*)in, len, device, report, sink);
+  return file_impl(unpack, (const uint8_t*)in, len, device, report, pv::buffer_sink("file", out, cap));
 }
 
+// a _file entry: the report zeroed before the paths are judged
 int file_entry(bool unpack, const char* in_path, const char* out_path, const char* device, Groth16PtauPackReport* report)
 {
   if (report) memset(report, 0, sizeof *report);
-  if (!in_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
-  if (strcmp(in_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  pv::MappedFile mf;
-  if (int rc = mf.open_ro(in_path)) return rc;
-  {
-    struct stat a, b; // the same file under two names
-    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  }
-  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
-  pv::TempOutput to(out_path);
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) { return to.open(bytes, o); };
-  int rc = file_impl(unpack, mf.data, mf.len, device, report, sink);
-  const auto t_write = std::chrono::steady_clock::now();
-  rc = to.finish(rc);
-  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
-  return rc;
+  return pv::rewrite_file(in_path, out_path, report ? &report->write_ms : nullptr,
+                          [&](const uint8_t* data, size_t len, const Sink& sink) { return file_impl(unpack, data, len, device, report, sink); });
 }
 
 } // namespace

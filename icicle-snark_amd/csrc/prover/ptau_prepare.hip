@@ -20,12 +20,8 @@
 //   Resident: one source section, the top block's working buffers (affine, projective, the inversion's scratch) and the twiddles.
 #include <algorithm>
 #include <chrono>
-#include <fcntl.h>
 #include <functional>
 #include <string>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <vector>
 
 #include "../msm_impl.h"
@@ -187,15 +183,14 @@ int transform_blocks(hipStream_t st, const Buffers& b, uint64_t avail, uint32_t 
   return 0;
 }
 
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+using pv::Sink;
 
 int prepare_impl(const uint8_t* data, size_t len, const char* device, Groth16PtauPrepareReport* rep, const Sink& sink)
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   std::vector<pv::Section> secs;
   pv::PtauLayout L;
   if (int rc = pv::ptau_unprepared_layout(data, len, secs, &L)) return rc;
@@ -315,52 +310,14 @@ ISNARK_API int groth16_ptau_prepare(const void* ptau, size_t len, void* out, siz
 {
   if (!out_len) return pv::fail(pv::ERR_ARG, "null out_len");
   *out_len = 0;
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) {
-    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the prepared file needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-    *o = (uint8_t*)out;
-    return 0;
-  };
-  if (int rc = prepare_impl((const uint8_t*)ptau, len, device, report, sink)) return rc;
+  if (int rc = prepare_impl((const uint8_t*)ptau, len, device, report, pv::buffer_sink("prepared file", out, cap))) return rc;
   *out_len = report->ptau_bytes;
   return 1;
 }
 
 ISNARK_API int groth16_ptau_prepare_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPrepareReport* report)
 {
-  if (!in_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
-  if (strcmp(in_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  pv::MappedFile mf;
-  if (int rc = mf.open_ro(in_path)) return rc;
-  {
-    struct stat a, b; // the same file under two names
-    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  }
-  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
-  // a temporary beside out_path, renamed over it at the end: a failed call leaves nothing there
-  const std::string tmp = std::string(out_path) + ".tmp." + std::to_string((long)getpid());
-  int fd = -1;
-  uint8_t* map = nullptr;
-  uint64_t map_len = 0;
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) {
-    fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return pv::fail(pv::ERR_IO, "cannot create %s", tmp.c_str());
-    if (ftruncate(fd, (off_t)bytes) != 0) return pv::fail(pv::ERR_IO, "cannot size %s to %llu bytes", tmp.c_str(), (unsigned long long)bytes);
-    void* p = mmap(nullptr, (size_t)bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    if (p == MAP_FAILED) return pv::fail(pv::ERR_IO, "cannot mmap %s", tmp.c_str());
-    map = (uint8_t*)p;
-    map_len = bytes;
-    *o = map;
-    return 0;
-  };
-  int rc = prepare_impl(mf.data, mf.len, device, report, sink);
-  const auto t_write = std::chrono::steady_clock::now();
-  if (map) {
-    if (rc == 0 && msync(map, (size_t)map_len, MS_SYNC) != 0) rc = pv::fail(pv::ERR_IO, "cannot write %s", tmp.c_str());
-    munmap(map, (size_t)map_len);
-  }
-  if (fd >= 0) close(fd);
-  if (rc == 0 && rename(tmp.c_str(), out_path) != 0) rc = pv::fail(pv::ERR_IO, "cannot rename %s to %s", tmp.c_str(), out_path);
-  if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
-  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
+  const int rc = pv::rewrite_file(in_path, out_path, report ? &report->write_ms : nullptr,
+                                  [&](const uint8_t* data, size_t len, const Sink& sink) { return prepare_impl(data, len, device, report, sink); });
   return rc ? rc : 1;
 }

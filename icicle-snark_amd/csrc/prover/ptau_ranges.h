@@ -1,8 +1,9 @@
 // ptau_ranges.h — reading a prepared .ptau's blocks on the device, shared by groth16_zkey_verify_ptau (zkey_verify.hip) and
 // groth16_zkey_new (zkey_new.hip): which five ranges a circuit of domain 2^k needs, the procedure that stages them (PtauRanges:
 // bound, allocate, upload, lane test where each lands), the lane tests every uploaded range goes through before anything else reads
-// it, the gather of the odd elements of section 12's block k + 1, and the one error text of a faulting element.  The kernels are in
-// an unnamed namespace, so each of the two translation units compiles its own copy of them; the host procedure is one text.
+// it, and the gather of the odd elements of section 12's block k + 1 (NO_FAULT and the text of a faulting element are
+// prover_internal.h's).  The kernels are in an unnamed namespace, so every translation unit that includes this compiles its own copy
+// of them — include it where they are launched, nowhere else; the host procedure is one text.
 #pragma once
 #include "device_call.h"
 #include "prover_internal.h"
@@ -41,8 +42,8 @@ __global__ __launch_bounds__(64) void ptau_g2_kernel(const fe2* __restrict__ pts
 }
 #endif
 
-constexpr unsigned long long NO_FAULT = ~0ull;
-const char* const POINT_FAULT[4] = {"", "a coordinate is not below q", "the point is not on the curve", "the point is outside the subgroup"};
+using isnark::prover::NO_FAULT; // prover_internal.h
+using isnark::prover::POINT_FAULT;
 
 // The five ranges of a circuit with domain 2^k: block k of sections 12 [L]₁, 13 [L]₂, 14 [αL]₁, 15 [βL]₁ and block k + 1 of section
 // 12.  The caller decides the streams, and downloads d_first (sizeof first[N]) at a synchronisation point of its own — behind both

@@ -113,9 +113,8 @@ int verify_impl(const uint8_t* data, size_t len, const uint8_t* seed32, const ch
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   std::vector<pv::Section> secs;
   pv::PtauLayout L;
   bool prepared = false;

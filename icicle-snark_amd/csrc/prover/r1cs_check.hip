@@ -171,9 +171,8 @@ int r1cs_load_impl(const uint8_t* data, size_t len, const char* device, Groth16R
 {
   if (!out) return pv::fail(pv::ERR_ARG, "null handle pointer");
   *out = nullptr;
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = isnark::vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   pv::R1csLayout L;
   if (int rc = pv::r1cs_layout(data, len, &L)) return rc;
   std::vector<uint32_t> rowptr;

@@ -1,7 +1,8 @@
 // wtns_pack.hip — a witness PACKED ("wtnz"): groth16_wtns_packed_size / _pack / _unpack_host (host only: they never initialise a
 // GPU), groth16_wtns_unpack (one device) and wtnz_decode_on_device, the decode groth16_prove_packed (prover.cpp) and
 // groth16_witness_check_packed (r1cs_check.hip) put in front of their unchanged device work.  include/groth16_prover.h has the
-// contract and the container; wtns_pack.h the value's form and its lane code; containers.cpp the reader; DESIGN.md §7k.
+// contract and the container; wtns_pack.h the value's form and its lane code; containers.cpp the reader; pack_device.h the block
+// codec's pieces (scan, span test, aligned load, word read), which zkey_pack.hip's kernels share; DESIGN.md §7k.
 //
 //   host, first  wtnz_layout bounds every section and the whole directory before a byte goes up: block b's payload
 //                [dir[b], dir[b + 1]) lies inside section 4 and is at most 8192 bytes, whatever the codes say.
@@ -17,12 +18,11 @@
 #include <chrono>
 #include <functional>
 #include <string>
-#include <sys/stat.h>
 #include <vector>
 
 #include "device_call.h"
+#include "pack_device.h"
 #include "prover_internal.h"
-#include "ptau_ranges.h"
 #include "verify_batch.h"
 #include "wtns_pack.h"
 
@@ -34,90 +34,45 @@ namespace pv = isnark::prover;
 namespace vb = isnark::vb;
 
 constexpr int WZ_WG = (int)wz::WZ_BLOCK;
-// the block's payload in LDS: 8192 bytes, up to 15 in front of it (the aligned load begins below the span) and the word behind a
-// lane's last one (the funnel shift reads it): byte 15 + 8192 + 7 at the most
-constexpr int WZ_LDS_VEC = 516;
-
-struct Tally {
-  unsigned long long first, count; // min over the faulty lanes of (element << 3 | kind), NO_FAULT without one; their number
-};
-__device__ __forceinline__ void tally_fault(Tally* t, uint64_t i, int kind)
-{
-  atomicAdd(&t->count, 1ull);
-  atomicMin(&t->first, (unsigned long long)i << 3 | (unsigned long long)kind);
-}
+static_assert(WZ_WG == pv::PACK_WG, "pack_device.h's block codec is a 256-lane workgroup's");
+typedef pv::PackTally Tally;
+using pv::pad16;
 
 // Block blockIdx.x of a packed witness → out[256·b … 256·b + 255] (standard form), i < n.  `payload` is 16-byte aligned and the
 // allocation reaches the next multiple of 16 behind its last byte; `dir` has passed wz_check_directory.
 __global__ __launch_bounds__(WZ_WG) void wz_unpack_kernel(const uint8_t* __restrict__ codes, const unsigned long long* __restrict__ dir, const uint8_t* __restrict__ payload, uint32_t n,
                                                           fe* __restrict__ out, Tally* __restrict__ tally)
 {
-  __shared__ uint4 s_pay[WZ_LDS_VEC];
+  __shared__ uint4 s_pay[pv::PACK_LDS_VEC];
   __shared__ uint32_t s_wave[WZ_WG / 64];
-  const uint32_t t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const uint32_t t = threadIdx.x;
   const uint64_t i = (uint64_t)blockIdx.x * WZ_WG + t;
   const bool live = i < n;
   const uint8_t code = live ? codes[i] : wz::WZ_CODE_ZERO;
   const int cl = wz::wz_code_len(code);
   const uint32_t len = cl > 0 ? (uint32_t)cl : 0;
+  uint32_t off, total;
+  pv::block_scan(len, s_wave, &off, &total);
 
-  // exclusive scan of the 256 lengths: inclusive inside each wave, the four wave sums through LDS
-  uint32_t incl = len;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += y;
-  }
-  if (lane == 63) s_wave[wv] = incl;
-  __syncthreads();
-  uint32_t base = 0, total = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < WZ_WG / 64; w++) {
-    const uint32_t sw = s_wave[w];
-    if (w < wv) base += sw;
-    total += sw;
-  }
-  const uint32_t off = base + incl - len;
-
-  const unsigned long long lo = dir[blockIdx.x], hi = dir[blockIdx.x + 1];
+  unsigned long long lo;
+  uint32_t head;
   fe row;
 #pragma unroll
   for (int k = 0; k < 8; k++) row.l[k] = 0;
-  if ((unsigned long long)total != hi - lo) { // the same in every lane of the workgroup: nothing of the payload is read
-    if (t == 0) tally_fault(tally, i, wz::WZ_DIRECTORY);
+  if (!pv::block_span(dir, total, &lo, &head)) { // nothing of the payload is read
+    if (t == 0) pv::tally_fault(tally, i, wz::WZ_DIRECTORY);
     if (live) out[i] = row;
     return;
   }
-  // the block's payload, from the 16-byte boundary at or below its first byte to the one at or above its last
-  const uint32_t head = (uint32_t)(lo & 15);
-  if (total) {
-    const uint4* src = (const uint4*)(payload + (lo - head));
-    const uint32_t nvec = (head + total + 15) >> 4; // ≤ 513
-    for (uint32_t v = t; v < nvec; v += WZ_WG) s_pay[v] = src[v];
-  }
+  pv::block_payload_to_lds(payload, lo, head, total, s_pay);
   __syncthreads();
   if (!live) return;
-  uint32_t pay[8];
-#pragma unroll
-  for (int k = 0; k < 8; k++) pay[k] = 0;
-  if (len) {
-    const uint32_t* words = (const uint32_t*)s_pay;
-    const uint32_t p = head + off, w0 = p >> 2, sh = (p & 3) * 8;
-#pragma unroll
-    for (uint32_t k = 0; k < 8; k++)
-      if (4 * k < len) {
-        const uint32_t a = words[w0 + k], b = words[w0 + k + 1];
-        uint32_t w = sh ? (a >> sh) | (b << (32 - sh)) : a;
-        const uint32_t rem = len - 4 * k;
-        if (rem < 4) w &= (1u << (8 * rem)) - 1;
-        pay[k] = w;
-      }
-  }
-  if (const int kind = wz::wz_decode_value(code, pay, row.l)) tally_fault(tally, i, kind);
+  uint32_t pay[8] = {};
+  pv::lane_payload_words(s_pay, head + off, len, pay);
+  if (const int kind = wz::wz_decode_value(code, pay, row.l)) pv::tally_fault(tally, i, kind);
   out[i] = row;
 }
 
-inline size_t pad16(size_t x) { return (x + 15) & ~(size_t)15; }
 struct DeviceLayout { // of d_buf
   size_t tally = 0, dir, codes, payload, total;
   explicit DeviceLayout(const pv::WtnzLayout& L)
@@ -144,8 +99,8 @@ int wtnz_decode_on_device(int dev, hipStream_t st, const WtnzLayout& L, uint8_t*
   if (kernel_ms) *kernel_ms = 0;
   if (!L.n_witness) return 0;
   const DeviceLayout D(L);
-  Tally t = {NO_FAULT, 0};
-  DEV_TRY("tally upload", hipMemcpyAsync(d_buf + D.tally, &t, sizeof t, hipMemcpyHostToDevice, st));
+  Tally t;
+  if (int rc = reset_tallies(&t, (Tally*)(d_buf + D.tally), 1, st)) return rc;
   // the padding behind the codes and behind the payload: what an aligned over-read sees is zero
   DEV_TRY("hipMemsetAsync", hipMemsetAsync(d_buf + D.codes + L.n_witness, 0, D.payload - D.codes - L.n_witness, st));
   DEV_TRY("hipMemsetAsync", hipMemsetAsync(d_buf + D.payload + L.payload_bytes, 0, D.total - D.payload - (size_t)L.payload_bytes, st));
@@ -189,14 +144,8 @@ namespace {
 constexpr uint64_t WTNS_HEAD = 12 + (12 + 40) + 12;  // a .wtns of sections 1 and 2 up to its first value
 constexpr uint64_t WTNZ_HEAD = 12 + 4 * 12 + 40;     // a packed witness without its codes, directory and payload
 
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
-
-void put_section(uint8_t*& w, uint32_t id, uint64_t size)
-{
-  memcpy(w, &id, 4);
-  memcpy(w + 4, &size, 8);
-  w += 12;
-}
+using pv::put_section;
+using pv::Sink;
 
 // ---- pack (host)
 // the codes, the directory and the payload's size of a .wtns' values; a value >= r is ERR_FORMAT naming the lowest
@@ -243,11 +192,7 @@ int pack_impl(const uint8_t* data, size_t len, Groth16WtnsPackReport* rep, const
   uint8_t* out = nullptr;
   if (int rc = sink(rep->out_bytes, &out)) return rc;
   uint8_t* p = out;
-  const uint32_t version = 1, nsec = 4;
-  memcpy(p, "wtnz", 4);
-  memcpy(p + 4, &version, 4);
-  memcpy(p + 8, &nsec, 4);
-  p += 12;
+  pv::put_container_head(p, "wtnz", 1, 4);
   put_section(p, 1, 40); // the .wtns header byte for byte (parse_wtns has demanded exactly these 40 bytes)
   memcpy(p, &w.n8, 4);
   memcpy(p + 4, w.q.l, 32);
@@ -270,13 +215,9 @@ int pack_impl(const uint8_t* data, size_t len, Groth16WtnsPackReport* rep, const
 }
 
 // ---- unpack: the .wtns a packed witness came from, sections 1 and 2 under version 2
-void put_wtns_head(uint8_t* out, const pv::WtnzLayout& L)
+void put_wtns_head(uint8_t* p, const pv::WtnzLayout& L)
 {
-  const uint32_t version = 2, nsec = 2;
-  memcpy(out, "wtns", 4);
-  memcpy(out + 4, &version, 4);
-  memcpy(out + 8, &nsec, 4);
-  uint8_t* p = out + 12;
+  pv::put_container_head(p, "wtns", 2, 2);
   put_section(p, 1, 40);
   memcpy(p, L.header, 40);
   p += 40;
@@ -322,9 +263,8 @@ int unpack_device_impl(const uint8_t* data, size_t len, const char* device, Grot
 {
   pv::WtnzLayout L;
   if (int rc = unpack_prologue(data, len, rep, &L)) return rc;
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   uint8_t* out = nullptr;
   if (int rc = sink(rep->out_bytes, &out)) return rc;
   if (L.n_witness) {
@@ -348,35 +288,13 @@ int unpack_device_impl(const uint8_t* data, size_t len, const char* device, Grot
   return 0;
 }
 
-Sink buffer_sink(void* out, size_t cap)
-{
-  return [out, cap](uint64_t bytes, uint8_t** o) {
-    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the file needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-    *o = (uint8_t*)out;
-    return 0;
-  };
-}
+Sink buffer_sink(void* out, size_t cap) { return pv::buffer_sink("file", out, cap); }
 
-// a _file entry: the input mapped, the output a temporary that is renamed
+// a _file entry: the report zeroed before the paths are judged
 int file_entry(const char* in_path, const char* out_path, Groth16WtnsPackReport* report, const std::function<int(const uint8_t*, size_t, const Sink&)>& impl)
 {
   if (report) memset(report, 0, sizeof *report);
-  if (!in_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
-  if (strcmp(in_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  pv::MappedFile mf;
-  if (int rc = mf.open_ro(in_path)) return rc;
-  {
-    struct stat a, b; // the same file under two names
-    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  }
-  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
-  pv::TempOutput to(out_path);
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) { return to.open(bytes, o); };
-  int rc = impl(mf.data, mf.len, sink);
-  const auto t_write = std::chrono::steady_clock::now();
-  rc = to.finish(rc);
-  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
-  return rc;
+  return pv::rewrite_file(in_path, out_path, report ? &report->write_ms : nullptr, impl);
 }
 
 } // namespace

@@ -34,7 +34,7 @@ namespace pv = isnark::prover;
 constexpr int G1_WG = 256;                      // points per block of zkey_g1_kernel (its LDS tile: 256 rows of 64 + 16 B)
 constexpr int G2_WG = 64;
 constexpr uint32_t DEFAULT_SLICE = 1u << 20;    // points per upload slice: 64 MB of G1 rows, 128 MB of G2 rows
-constexpr unsigned long long NO_FAULT = ~0ull;
+using pv::NO_FAULT;
 
 // per zkey section id: how many elements are at fault, and min over them of (index << 3 | kind)
 struct Tally {
@@ -218,9 +218,8 @@ int zkey_check_impl(const uint8_t* data, size_t len, const char* device, const G
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = isnark::vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   std::vector<pv::Section> secs;
   ZkeyLayout L;
   if (int rc = pv::zkey_layout(data, len, secs, &L)) return rc;

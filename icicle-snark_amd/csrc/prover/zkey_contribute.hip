@@ -13,12 +13,8 @@
 //                that no point was at fault (the _file entry unlinks its temporary otherwise).
 #include <algorithm>
 #include <chrono>
-#include <fcntl.h>
 #include <functional>
 #include <string>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <vector>
 
 #include "../msm_impl.h"
@@ -39,7 +35,7 @@ namespace pv = isnark::prover;
 namespace vb = isnark::vb;
 
 constexpr int SCALE_WG = 64;
-constexpr unsigned long long NO_FAULT = ~0ull;
+using pv::NO_FAULT;
 const char TAG[] = "icicle-snark zkey contribution v1";
 constexpr size_t TAG_LEN = sizeof TAG - 1;
 constexpr size_t HEADER_FIXED = 468;                       // section 2 up to and including γ₂
@@ -161,29 +157,6 @@ void chain_step(uint8_t h[32], const uint8_t* before1, const Record& r, fe* c)
   memcpy(c->l, c16, 16);
 }
 
-// the input's sections in file order (read_sections has bounded them)
-struct Entry {
-  uint32_t id;
-  uint64_t size;
-  const uint8_t* p;
-};
-std::vector<Entry> file_order(const uint8_t* data)
-{
-  uint32_t nsec;
-  memcpy(&nsec, data + 8, 4);
-  std::vector<Entry> out;
-  size_t pos = 12;
-  for (uint32_t i = 0; i < nsec; i++) {
-    Entry e;
-    memcpy(&e.id, data + pos, 4);
-    memcpy(&e.size, data + pos + 4, 8);
-    e.p = data + pos + 12;
-    out.push_back(e);
-    pos += 12 + e.size;
-  }
-  return out;
-}
-
 // everything secret of one call; wiped on every way out (best effort: the compiler may have kept copies in registers or spills)
 struct Secrets {
   uint8_t seed[32];
@@ -192,16 +165,15 @@ struct Secrets {
   ~Secrets() { explicit_bzero(this, sizeof *this); }
 };
 
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+using pv::Sink;
 
 int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, const char* name, const char* device, const Groth16ZkeyContributeOptions* opt,
                     Groth16ZkeyContributeReport* rep, const Sink& sink)
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  const int dev = vb::parse_one_device(device);
-  if (dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
+  int dev;
+  if (int rc = pv::parse_device(device, &dev)) return rc;
   if (!name) name = "";
   const size_t name_len = strlen(name);
   if (name_len > NAME_BYTES_MAX) return pv::fail(pv::ERR_ARG, "the contributor's name has %zu bytes, a record holds %u", name_len, NAME_BYTES_MAX);
@@ -217,10 +189,10 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   if (count && memcmp(recs.back().after1, hdr + DELTA1_OFF, 64) != 0) return pv::fail(pv::ERR_FORMAT, "zkey: section 10's last record is not the header's delta1");
 
   // the output's size, before anything else is done
-  const std::vector<Entry> order = file_order(data);
+  const std::vector<pv::SectionEntry> order = pv::sections_in_order(data);
   const uint64_t rec_bytes = RECORD_FIXED + name_len;
   uint64_t total = 12 + rec_bytes + (s10 ? 0 : 12 + 4);
-  for (const Entry& e : order) total += 12 + e.size;
+  for (const pv::SectionEntry& e : order) total += 12 + e.size;
   const uint64_t n8 = L.sec[8]->size / 64, n9 = L.sec[9]->size / 64, n = n8 + n9;
   rep->contribution = count + 1;
   rep->points_c = n8, rep->points_h = n9;
@@ -324,30 +296,24 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   // ---- meanwhile: the container, and every section that is copied
   uint8_t* w = out;
   uint8_t *out8 = nullptr, *out9 = nullptr;
-  auto section = [&](uint32_t id, uint64_t size) {
-    memcpy(w, &id, 4);
-    memcpy(w + 4, &size, 8);
-    w += 12;
-  };
   auto section10 = [&] {
     const uint64_t old = s10 ? s10->size : 4;
     const uint32_t now = count + 1;
-    section(10, old + rec_bytes);
+    pv::put_section(w, 10, old + rec_bytes);
     memcpy(w, &now, 4);
     if (s10) memcpy(w + 4, s10->p + 4, (size_t)old - 4);
     memcpy(w + old, record.data(), (size_t)rec_bytes);
     w += old + rec_bytes;
   };
-  memcpy(w, data, 8);
-  const uint32_t nsec = (uint32_t)order.size() + (s10 ? 0 : 1);
-  memcpy(w + 8, &nsec, 4);
-  w += 12;
-  for (const Entry& e : order) {
+  uint32_t version;
+  memcpy(&version, data + 4, 4);
+  pv::put_container_head(w, "zkey", version, (uint32_t)order.size() + (s10 ? 0 : 1));
+  for (const pv::SectionEntry& e : order) {
     if (e.id == 10) {
       section10();
       continue;
     }
-    section(e.id, e.size);
+    pv::put_section(w, e.id, e.size);
     if (e.id == 8) out8 = w;
     else if (e.id == 9) out9 = w;
     else memcpy(w, e.p, (size_t)e.size); // (in ranges on the worker pool this took 230–253 ms instead of 155–160 at benchmark/1600k: not kept)
@@ -401,53 +367,15 @@ bn254_g2_affine_t std_affine(const G2::A& a)
 ISNARK_API int groth16_zkey_contribute(const void* zkey, size_t len, const uint8_t* secret32, const char* name, void* out, size_t cap, const char* device,
                                        const Groth16ZkeyContributeOptions* opt, Groth16ZkeyContributeReport* report)
 {
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) {
-    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the key needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-    *o = (uint8_t*)out;
-    return 0;
-  };
-  return contribute_impl((const uint8_t*)zkey, len, secret32, name, device, opt, report, sink);
+  return contribute_impl((const uint8_t*)zkey, len, secret32, name, device, opt, report, pv::buffer_sink("key", out, cap));
 }
 
 ISNARK_API int groth16_zkey_contribute_file(const char* zkey_path, const char* out_path, const uint8_t* secret32, const char* name, const char* device,
                                             const Groth16ZkeyContributeOptions* opt, Groth16ZkeyContributeReport* report)
 {
-  if (!zkey_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
-  if (strcmp(zkey_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  pv::MappedFile mf;
-  if (int rc = mf.open_ro(zkey_path)) return rc;
-  {
-    struct stat a, b; // the same file under two names
-    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  }
-  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
-  // a temporary beside out_path, renamed over it at the end: a failed call leaves nothing there
-  const std::string tmp = std::string(out_path) + ".tmp." + std::to_string((long)getpid());
-  int fd = -1;
-  uint8_t* map = nullptr;
-  uint64_t map_len = 0;
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) {
-    fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return pv::fail(pv::ERR_IO, "cannot create %s", tmp.c_str());
-    if (ftruncate(fd, (off_t)bytes) != 0) return pv::fail(pv::ERR_IO, "cannot size %s to %llu bytes", tmp.c_str(), (unsigned long long)bytes);
-    void* p = mmap(nullptr, (size_t)bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    if (p == MAP_FAILED) return pv::fail(pv::ERR_IO, "cannot mmap %s", tmp.c_str());
-    map = (uint8_t*)p;
-    map_len = bytes;
-    *o = map;
-    return 0;
-  };
-  int rc = contribute_impl(mf.data, mf.len, secret32, name, device, opt, report, sink);
-  const auto t_write = std::chrono::steady_clock::now();
-  if (map) {
-    if (rc == 0 && msync(map, (size_t)map_len, MS_SYNC) != 0) rc = pv::fail(pv::ERR_IO, "cannot write %s", tmp.c_str());
-    munmap(map, (size_t)map_len);
-  }
-  if (fd >= 0) close(fd);
-  if (rc == 0 && rename(tmp.c_str(), out_path) != 0) rc = pv::fail(pv::ERR_IO, "cannot rename %s to %s", tmp.c_str(), out_path);
-  if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
-  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
-  return rc;
+  return pv::rewrite_file(zkey_path, out_path, report ? &report->write_ms : nullptr, [&](const uint8_t* data, size_t len, const Sink& sink) {
+    return contribute_impl(data, len, secret32, name, device, opt, report, sink);
+  });
 }
 
 ISNARK_API int groth16_zkey_contributions(const void* zkey, size_t len, Groth16ContributionsReport* report, Groth16ContributionInfo* infos, size_t infos_cap)

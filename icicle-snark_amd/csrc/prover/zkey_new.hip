@@ -18,13 +18,9 @@
 //               down into the caller's buffer or the mapped output file through the pinned staging.
 #include <algorithm>
 #include <chrono>
-#include <fcntl.h>
 #include <functional>
 #include <mutex>
 #include <string>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 #include <vector>
 
 #include "../msm_impl.h"
@@ -274,7 +270,7 @@ struct FileLayout {
 };
 
 // where the key goes, once its size is known: the caller's buffer, or the mapped temporary of the _file entry
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
+using pv::Sink;
 
 int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau_fd, const Groth16ZkeyNewOptions* opt, Groth16ZkeyNewReport* rep, const Sink& sink)
 {
@@ -509,12 +505,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
 
 ISNARK_API int groth16_zkey_new(Groth16R1cs* h, const void* ptau, size_t ptau_len, void* zkey_out, size_t cap, const Groth16ZkeyNewOptions* opt, Groth16ZkeyNewReport* report)
 {
-  const Sink sink = [&](uint64_t bytes, uint8_t** out) {
-    if (!zkey_out || cap < bytes) return pv::fail(pv::ERR_ARG, "the key needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(zkey_out ? cap : 0));
-    *out = (uint8_t*)zkey_out;
-    return 0;
-  };
-  return zkey_new_impl(h, (const uint8_t*)ptau, ptau_len, -1, opt, report, sink);
+  return zkey_new_impl(h, (const uint8_t*)ptau, ptau_len, -1, opt, report, pv::buffer_sink("key", zkey_out, cap));
 }
 
 ISNARK_API int groth16_zkey_new_file(Groth16R1cs* h, const char* ptau_path, const char* zkey_path, const Groth16ZkeyNewOptions* opt, Groth16ZkeyNewReport* report)
@@ -522,31 +513,10 @@ ISNARK_API int groth16_zkey_new_file(Groth16R1cs* h, const char* ptau_path, cons
   if (!ptau_path || !zkey_path) return pv::fail(pv::ERR_ARG, "null path");
   pv::MappedFile pf;
   if (int rc = pf.open_ro(ptau_path, /*read_ahead=*/false)) return rc; // only the ranges that are read are touched
-  // a temporary beside zkey_path, renamed over it at the end: a failed call leaves nothing there
-  const std::string tmp = std::string(zkey_path) + ".tmp." + std::to_string((long)getpid());
-  int fd = -1;
-  uint8_t* map = nullptr;
-  uint64_t map_len = 0;
-  const Sink sink = [&](uint64_t bytes, uint8_t** out) {
-    fd = ::open(tmp.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);
-    if (fd < 0) return pv::fail(pv::ERR_IO, "cannot create %s", tmp.c_str());
-    if (ftruncate(fd, (off_t)bytes) != 0) return pv::fail(pv::ERR_IO, "cannot size %s to %llu bytes", tmp.c_str(), (unsigned long long)bytes);
-    void* p = mmap(nullptr, (size_t)bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-    if (p == MAP_FAILED) return pv::fail(pv::ERR_IO, "cannot mmap %s", tmp.c_str());
-    map = (uint8_t*)p;
-    map_len = bytes;
-    *out = map;
-    return 0;
-  };
-  int rc = zkey_new_impl(h, pf.data, pf.len, pf.fd, opt, report, sink);
+  pv::TempOutput to(zkey_path); // a failed call leaves nothing there
+  int rc = zkey_new_impl(h, pf.data, pf.len, pf.fd, opt, report, [&](uint64_t bytes, uint8_t** out) { return to.open(bytes, out); });
   const auto t_write = std::chrono::steady_clock::now();
-  if (map) {
-    if (rc == 0 && msync(map, (size_t)map_len, MS_SYNC) != 0) rc = pv::fail(pv::ERR_IO, "cannot write %s", tmp.c_str());
-    munmap(map, (size_t)map_len);
-  }
-  if (fd >= 0) close(fd);
-  if (rc == 0 && rename(tmp.c_str(), zkey_path) != 0) rc = pv::fail(pv::ERR_IO, "cannot rename %s to %s", tmp.c_str(), zkey_path);
-  if (rc != 0 && fd >= 0) (void)unlink(tmp.c_str());
+  rc = to.finish(rc);
   if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
   return rc;
 }

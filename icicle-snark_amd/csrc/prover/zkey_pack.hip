@@ -2,12 +2,13 @@
 // coefficient as a code byte and its significant bytes ("zkez"), and back; groth16_zkey_coefs_pack / _unpack: the coefficient codec
 // over a plain buffer of records; and the decode the packed load (cache.cpp: ingest_packed) puts in front of its unchanged device
 // work.  include/groth16_prover.h has the contract and the container; zkey_pack29.h the coefficient's form and its lane code;
-// point_pack29.h the packed point; containers.cpp the reader (zkez_layout); DESIGN.md §7l.
+// point_pack29.h the packed point; containers.cpp the reader (zkez_layout); pack_device.h the block codec's pieces, which
+// wz_unpack_kernel shares; DESIGN.md §7l.
 //
 //   host, first  the container — a .zkey through zkey_layout(need_ic) for pack, a packed key through zkez_layout for unpack: every
 //                point section is tied to its element count, section 4 to the sum of its parts and the whole directory is bounded
 //                before a byte goes up.
-//   device       points: ONE launch per section through ptau_pack.hip's pack_on_device / unpack_on_device.
+//   device       points: ONE launch per section through ptau_pack.hip's enqueue_point_ranges (pack_on_device / unpack_on_device).
 //                coefficients, pack: kernel 1 (a 256-lane workgroup per block of 256 records, a lane per record) tests the value
 //                below r, takes it through from_mont twice, writes the code, copies the triple and writes the block's length sum;
 //                the HOST turns the sums into the directory; kernel 2 derives the value again, scans the block's lengths (wave
@@ -24,12 +25,11 @@
 #include <chrono>
 #include <functional>
 #include <string>
-#include <sys/stat.h>
 #include <vector>
 
 #include "device_call.h"
+#include "pack_device.h"
 #include "prover_internal.h"
-#include "ptau_ranges.h"
 #include "verify_batch.h"
 #include "zkey_pack29.h"
 
@@ -40,41 +40,14 @@ namespace {
 namespace pv = isnark::prover;
 namespace vb = isnark::vb;
 typedef pv::PackTally Tally;
+using pv::block_scan; // pack_device.h: the block codec's pieces
+using pv::NO_FAULT;
+using pv::pad16;
+using pv::tally_fault;
 
 constexpr int ZP_WG = (int)zp::ZP_BLOCK;
-// a block's payload in LDS: 8192 bytes, up to 15 in front of it (its position mod 16) and, for the unpack kernel, the word behind a
-// lane's last one (the funnel shift reads it): byte 15 + 8192 + 7 at the most
-constexpr int ZP_LDS_VEC = 516;
+static_assert(ZP_WG == pv::PACK_WG, "pack_device.h's block codec is a 256-lane workgroup's");
 constexpr int ZP_REC_VEC = (int)(zp::ZP_BLOCK_BYTES / 16); // 704
-
-__device__ __forceinline__ void tally_fault(Tally* t, uint64_t i, int kind)
-{
-  atomicAdd(&t->count, 1ull);
-  atomicMin(&t->first, (unsigned long long)i << 3 | (unsigned long long)kind);
-}
-
-// exclusive scan of the workgroup's 256 lengths: inclusive inside each wave, the four wave sums through LDS.  EVERY lane calls it.
-__device__ __forceinline__ void block_scan(uint32_t len, uint32_t* s_wave, uint32_t* off, uint32_t* total)
-{
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = len;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += y;
-  }
-  if (lane == 63) s_wave[wv] = incl;
-  __syncthreads();
-  uint32_t base = 0, sum = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < ZP_WG / 64; w++) {
-    const uint32_t sw = s_wave[w];
-    if (w < wv) base += sw;
-    sum += sw;
-  }
-  *off = base + incl - len;
-  *total = sum;
-}
 
 // record i of `rec` (11 words each): its value through zp_encode.  The payload's length, 0 for a value not below r (*bad set).
 __device__ __forceinline__ uint32_t encode_record(const uint32_t* __restrict__ rec, uint64_t i, uint8_t* code, uint32_t pay[8], bool* bad)
@@ -115,7 +88,7 @@ __global__ __launch_bounds__(ZP_WG) void zp_scan_kernel(const uint32_t* __restri
 // vector store never covers a byte outside [dir[block], dir[block + 1]): the neighbours' payloads abut at any byte.
 __global__ __launch_bounds__(ZP_WG) void zp_emit_kernel(const uint32_t* __restrict__ rec, uint32_t n, const unsigned long long* __restrict__ dir, uint8_t* __restrict__ payload)
 {
-  __shared__ uint4 s_pay[ZP_LDS_VEC];
+  __shared__ uint4 s_pay[pv::PACK_LDS_VEC];
   __shared__ uint32_t s_wave[ZP_WG / 64];
   const uint32_t t = threadIdx.x;
   const uint64_t i = (uint64_t)blockIdx.x * ZP_WG + t;
@@ -127,9 +100,9 @@ __global__ __launch_bounds__(ZP_WG) void zp_emit_kernel(const uint32_t* __restri
   }
   uint32_t off, total;
   block_scan(len, s_wave, &off, &total);
-  const unsigned long long lo = dir[blockIdx.x], hi = dir[blockIdx.x + 1];
-  if ((unsigned long long)total != hi - lo || !total) return; // (the host made the directory from kernel 1's sums: they agree)
-  const uint32_t head = (uint32_t)(lo & 15);
+  unsigned long long lo;
+  uint32_t head;
+  if (!pv::block_span(dir, total, &lo, &head) || !total) return; // (the host made the directory from kernel 1's sums: they agree)
   uint8_t* const s_bytes = (uint8_t*)s_pay;
   if (len) {
     const uint32_t p = head + off;
@@ -158,7 +131,7 @@ __global__ __launch_bounds__(ZP_WG) void zp_emit_kernel(const uint32_t* __restri
 __global__ __launch_bounds__(ZP_WG) void zp_unpack_kernel(const uint8_t* __restrict__ codes, const uint32_t* __restrict__ triples, const unsigned long long* __restrict__ dir,
                                                           const uint8_t* __restrict__ payload, uint32_t n, uint32_t* __restrict__ out, Tally* __restrict__ tally)
 {
-  __shared__ uint4 s_pay[ZP_LDS_VEC];
+  __shared__ uint4 s_pay[pv::PACK_LDS_VEC];
   __shared__ uint4 s_rec[ZP_REC_VEC];
   __shared__ uint32_t s_wave[ZP_WG / 64];
   const uint32_t t = threadIdx.x;
@@ -170,36 +143,17 @@ __global__ __launch_bounds__(ZP_WG) void zp_unpack_kernel(const uint8_t* __restr
   uint32_t off, total;
   block_scan(len, s_wave, &off, &total);
 
-  const unsigned long long lo = dir[blockIdx.x], hi = dir[blockIdx.x + 1];
-  const bool dir_ok = (unsigned long long)total == hi - lo; // the same in every lane of the workgroup
-  const uint32_t head = (uint32_t)(lo & 15);
+  unsigned long long lo;
+  uint32_t head;
+  const bool dir_ok = pv::block_span(dir, total, &lo, &head);
   if (!dir_ok && t == 0) tally_fault(tally, i, wz::WZ_DIRECTORY);
-  // the block's payload, from the 16-byte boundary at or below its first byte to the one at or above its last; nothing of it is
-  // read when the lengths do not sum to the span
-  if (dir_ok && total) {
-    const uint4* src = (const uint4*)(payload + (lo - head));
-    const uint32_t nvec = (head + total + 15) >> 4; // ≤ 513
-    for (uint32_t v = t; v < nvec; v += ZP_WG) s_pay[v] = src[v];
-  }
+  // nothing of the payload is read when the lengths do not sum to the span
+  if (dir_ok) pv::block_payload_to_lds(payload, lo, head, total, s_pay);
   __syncthreads();
   uint32_t* const s_words = (uint32_t*)s_rec;
   if (live) {
-    uint32_t pay[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) pay[k] = 0;
-    if (dir_ok && len) {
-      const uint32_t* words = (const uint32_t*)s_pay;
-      const uint32_t p = head + off, w0 = p >> 2, sh = (p & 3) * 8;
-#pragma unroll
-      for (uint32_t k = 0; k < 8; k++)
-        if (4 * k < len) {
-          const uint32_t a = words[w0 + k], b = words[w0 + k + 1];
-          uint32_t w = sh ? (a >> sh) | (b << (32 - sh)) : a;
-          const uint32_t rem = len - 4 * k;
-          if (rem < 4) w &= (1u << (8 * rem)) - 1;
-          pay[k] = w;
-        }
-    }
+    uint32_t pay[8] = {};
+    if (dir_ok) pv::lane_payload_words(s_pay, head + off, len, pay);
     fe f;
 #pragma unroll
     for (int k = 0; k < 8; k++) f.l[k] = 0;
@@ -222,7 +176,6 @@ __global__ __launch_bounds__(ZP_WG) void zp_unpack_kernel(const uint8_t* __restr
   if (t < (n_words & 3)) g[(n_words & ~3u) + t] = s_words[(n_words & ~3u) + t];
 }
 
-inline size_t pad16(size_t x) { return (x + 15) & ~(size_t)15; }
 struct DeviceLayout { // of zkez_coefs_decode's d_buf
   size_t dir = 0, triples, codes, payload, total;
   explicit DeviceLayout(const pv::ZkezCoefs& C)
@@ -277,13 +230,9 @@ int packed_coef_fail(const char* form, const PackTally& t)
 
 namespace {
 
-int parse_device(const char* device, int* dev)
-{
-  if (!device) return pv::fail(pv::ERR_ARG, "null device");
-  *dev = vb::parse_one_device(device);
-  if (*dev < 0) return pv::fail(pv::ERR_ARG, "device: '%s' does not name one HIP device", device);
-  return 0;
-}
+using pv::parse_device;
+using pv::reset_tallies;
+using pv::Sink;
 
 // ---- the coefficients of a pack, on their way through the two kernels
 struct CoefPack {
@@ -346,24 +295,6 @@ void coef_pack_body(const CoefPack& cp, uint32_t declared, uint8_t* w, std::vect
   if (payload) down.push_back({dir + cp.dir.size() * 8, cp.d_payload, (size_t)payload});
 }
 
-int reset_tallies(Tally* d_tally, size_t count, hipStream_t st)
-{
-  std::vector<Tally> t(count, Tally{NO_FAULT, 0});
-  DEV_TRY("tally upload", hipMemcpyAsync(d_tally, t.data(), count * sizeof(Tally), hipMemcpyHostToDevice, st));
-  DEV_TRY("tally upload", hipStreamSynchronize(st)); // (t leaves scope)
-  return 0;
-}
-
-typedef std::function<int(uint64_t bytes, uint8_t** out)> Sink;
-Sink buffer_sink(void* out, size_t cap)
-{
-  return [out, cap](uint64_t bytes, uint8_t** o) {
-    if (!out || cap < bytes) return pv::fail(pv::ERR_ARG, "the output needs %llu bytes, the buffer holds %llu", (unsigned long long)bytes, (unsigned long long)(out ? cap : 0));
-    *o = (uint8_t*)out;
-    return 0;
-  };
-}
-
 // ---- groth16_zkey_coefs_pack / groth16_zkey_coefs_unpack
 int coefs_fault(Groth16ZkeyCoefsReport* rep, const char* form, const Tally& t)
 {
@@ -387,17 +318,17 @@ int coefs_pack_impl(const void* records, uint64_t n, void* out, size_t cap, cons
   const hipStream_t st = ds.stream(0);
   Tally* const d_tally = ds.buf.alloc<Tally>(1);
   if (!d_tally) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-  if (int rc = reset_tallies(d_tally, 1, st)) return rc;
+  Tally t;
+  if (int rc = reset_tallies(&t, d_tally, 1, st)) return rc;
   CoefPack cp;
   if (int rc = coef_pack_scan(ds, dev, st, (const uint8_t*)records, (uint32_t)n, cp, d_tally, &rep->upload_ms)) return rc;
-  Tally t;
   DEV_TRY("download", hipMemcpyAsync(&t, d_tally, sizeof t, hipMemcpyDeviceToHost, st));
   DEV_TRY("coefficient scan kernel", hipStreamSynchronize(st));
   if (t.first != NO_FAULT) return coefs_fault(rep, "zkey", t);
   make_directory(cp);
   rep->out_bytes = pv::zkez_coefs_bytes(n, cp.payload_bytes());
   uint8_t* w = nullptr;
-  if (int rc = buffer_sink(out, cap)(rep->out_bytes, &w)) return rc;
+  if (int rc = pv::buffer_sink("output", out, cap)(rep->out_bytes, &w)) return rc;
   if (int rc = coef_pack_emit(ds, st, cp)) return rc;
   rep->device_ms = pv::ms_since(t_dev) - rep->upload_ms;
   const auto t_down = std::chrono::steady_clock::now();
@@ -422,7 +353,7 @@ int coefs_unpack_impl(const void* body, size_t len, void* out, size_t cap, const
   rep->out_bytes = (uint64_t)C.n_coef * zp::ZP_RECORD_BYTES;
   uint8_t* w = nullptr;
   if (C.n_coef)
-    if (int rc = buffer_sink(out, cap)(rep->out_bytes, &w)) return rc;
+    if (int rc = pv::buffer_sink("output", out, cap)(rep->out_bytes, &w)) return rc;
   if (!C.n_coef) return 0;
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
@@ -432,14 +363,14 @@ int coefs_unpack_impl(const void* body, size_t len, void* out, size_t cap, const
   uint8_t* const d_buf = ds.buf.alloc<uint8_t>(pv::zkez_coefs_device_bytes(C));
   uint32_t* const d_records = ds.buf.alloc<uint32_t>((size_t)C.n_coef * zp::ZP_RECORD_WORDS);
   if (!d_tally || !d_buf || !d_records) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-  if (int rc = reset_tallies(d_tally, 1, st)) return rc;
+  Tally t;
+  if (int rc = reset_tallies(&t, d_tally, 1, st)) return rc;
   std::vector<pv::UploadJob> jobs;
   pv::zkez_coefs_jobs(C, d_buf, jobs);
   const auto t_up = std::chrono::steady_clock::now();
   DEV_TRY("host to device upload", isnark::staged_copy(dev, jobs.data(), jobs.size(), true));
   rep->upload_ms = pv::ms_since(t_up);
   if (int rc = pv::zkez_coefs_decode(st, C, d_buf, d_records, d_tally)) return rc;
-  Tally t;
   DEV_TRY("download", hipMemcpyAsync(&t, d_tally, sizeof t, hipMemcpyDeviceToHost, st));
   DEV_TRY("coefficient unpack kernel", hipStreamSynchronize(st));
   rep->device_ms = pv::ms_since(t_dev) - rep->upload_ms;
@@ -456,15 +387,6 @@ int coefs_unpack_impl(const void* body, size_t len, void* out, size_t cap, const
 constexpr int POINT_SECTIONS[6] = {3, 5, 6, 7, 8, 9};
 constexpr int COEF_TALLY = 6; // the tallies: one per point section, then section 4's
 bool is_point_section(uint32_t id) { return id == 3 || (id >= 5 && id <= 9); }
-
-struct PointRange {
-  int section;
-  bool g2;
-  uint64_t n;
-  const uint8_t* src;
-  uint8_t* dst; // host; set once the output's layout is known
-  uint8_t* d_out;
-};
 
 int file_fault(Groth16ZkeyPackReport* rep, const char* form, int section, const Tally& t)
 {
@@ -496,13 +418,13 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   rep->n_vars = L.n_vars, rep->n_public = L.n_public, rep->domain = L.domain, rep->n_coef = L.n_coef;
   rep->in_bytes = len;
   const char* const form = unpack ? "zkez" : "zkey";
-  const size_t in_elem[2] = {unpack ? 32u : 64u, unpack ? 64u : 128u}, out_elem[2] = {unpack ? 64u : 32u, unpack ? 128u : 64u}; // [g2]
-  PointRange ranges[6];
+  pv::PointRange ranges[6];
   uint64_t packed_points = 0;
   for (int k = 0; k < 6; k++) {
     const int id = POINT_SECTIONS[k];
     const bool g2 = id == 7;
-    ranges[k] = {id, g2, L.sec[id]->size / in_elem[g2], L.sec[id]->p, nullptr, nullptr};
+    const size_t in_elem = (unpack ? 32u : 64u) * (g2 ? 2u : 1u);
+    ranges[k] = {id, g2, L.sec[id]->size / in_elem, L.sec[id]->p, nullptr, nullptr, nullptr};
     rep->points[g2] += ranges[k].n;
     packed_points += ranges[k].n * (g2 ? 64 : 32);
   }
@@ -523,17 +445,9 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   Tally tallies[COEF_TALLY + 1];
   Tally* const d_tally = ds.buf.alloc<Tally>(COEF_TALLY + 1);
   if (!d_tally) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-  if (int rc = reset_tallies(d_tally, COEF_TALLY + 1, st)) return rc;
+  if (int rc = reset_tallies(tallies, d_tally, COEF_TALLY + 1, st)) return rc;
   // the point sections: up, one launch each
-  for (int k = 0; k < 6; k++) {
-    PointRange& r = ranges[k];
-    if (!r.n) continue;
-    uint8_t* const d_in = ds.buf.alloc<uint8_t>((size_t)(r.n * in_elem[r.g2]));
-    r.d_out = ds.buf.alloc<uint8_t>((size_t)(r.n * out_elem[r.g2]));
-    if (!d_in || !r.d_out) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-    if (int rc = pv::timed_upload(dev, d_in, r.src, (size_t)(r.n * in_elem[r.g2]), &rep->upload_ms)) return rc;
-    if (int rc = unpack ? pv::unpack_on_device(st, d_in, r.n, r.g2, r.d_out, d_tally + k) : pv::pack_on_device(st, d_in, r.n, r.g2, r.d_out, d_tally + k)) return rc;
-  }
+  if (int rc = pv::enqueue_point_ranges(ds, dev, unpack, ranges, 6, d_tally, &rep->upload_ms)) return rc;
   // section 4
   CoefPack cp;
   uint32_t* d_records = nullptr;
@@ -572,17 +486,12 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   // ---- the container: the other magic, the sections in the input's order
   std::vector<isnark::CopyJob> down;
   uint8_t* w = out;
-  const uint32_t version = 1;
-  memcpy(w, unpack ? "zkey" : "zkez", 4);
-  memcpy(w + 4, &version, 4);
-  memcpy(w + 8, data + 8, 4);
-  w += 12;
-  for (const pv::SectionEntry& e : pv::sections_in_order(data)) {
+  const std::vector<pv::SectionEntry> order = pv::sections_in_order(data);
+  pv::put_container_head(w, unpack ? "zkey" : "zkez", 1, (uint32_t)order.size());
+  for (const pv::SectionEntry& e : order) {
     const bool point = is_point_section(e.id);
     const uint64_t size = e.id == 4 ? (unpack ? 4 + (uint64_t)L.n_coef * zp::ZP_RECORD_BYTES : rep->coef_bytes) : !point ? e.size : unpack ? 2 * e.size : e.size / 2;
-    memcpy(w, &e.id, 4);
-    memcpy(w + 4, &size, 8);
-    w += 12;
+    pv::put_section(w, e.id, size);
     if (e.id == 4 && unpack) {
       memcpy(w, &P.coefs.declared, 4);
       if (L.n_coef) down.push_back({w + 4, d_records, (size_t)L.n_coef * zp::ZP_RECORD_BYTES});
@@ -593,7 +502,7 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
     } else if (!point) {
       memcpy(w, e.p, (size_t)e.size);
     } else {
-      for (PointRange& r : ranges)
+      for (pv::PointRange& r : ranges)
         if (r.section == (int)e.id && r.n) down.push_back({w, r.d_out, (size_t)size});
     }
     w += size;
@@ -606,25 +515,12 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   return 0;
 }
 
+// a _file entry: the report zeroed before the paths are judged
 int file_entry(bool unpack, const char* in_path, const char* out_path, const char* device, Groth16ZkeyPackReport* report)
 {
   if (report) memset(report, 0, sizeof *report);
-  if (!in_path || !out_path) return pv::fail(pv::ERR_ARG, "null path");
-  if (strcmp(in_path, out_path) == 0) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  pv::MappedFile mf;
-  if (int rc = mf.open_ro(in_path)) return rc;
-  {
-    struct stat a, b; // the same file under two names
-    if (stat(out_path, &b) == 0 && fstat(mf.fd, &a) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino) return pv::fail(pv::ERR_ARG, "the output path is the input's");
-  }
-  const pv::FileHint hint(mf.data, mf.len, mf.fd); // (the staging workers pread() the file instead of copying out of the mapping)
-  pv::TempOutput to(out_path);
-  const Sink sink = [&](uint64_t bytes, uint8_t** o) { return to.open(bytes, o); };
-  int rc = file_impl(unpack, mf.data, mf.len, device, report, sink);
-  const auto t_write = std::chrono::steady_clock::now();
-  rc = to.finish(rc);
-  if (rc == 0 && report) report->write_ms = pv::ms_since(t_write);
-  return rc;
+  return pv::rewrite_file(in_path, out_path, report ? &report->write_ms : nullptr,
+                          [&](const uint8_t* data, size_t len, const Sink& sink) { return file_impl(unpack, data, len, device, report, sink); });
 }
 
 } // namespace
@@ -639,11 +535,11 @@ ISNARK_API int groth16_zkey_coefs_unpack(const void* body, size_t len, void* out
 }
 ISNARK_API int groth16_zkey_pack(const void* zkey, size_t len, void* out, size_t cap, const char* device, Groth16ZkeyPackReport* report)
 {
-  return file_impl(false, (const uint8_t*)zkey, len, device, report, buffer_sink(out, cap));
+  return file_impl(false, (const uint8_t*)zkey, len, device, report, pv::buffer_sink("output", out, cap));
 }
 ISNARK_API int groth16_zkey_unpack(const void* zkez, size_t len, void* out, size_t cap, const char* device, Groth16ZkeyPackReport* report)
 {
-  return file_impl(true, (const uint8_t*)zkez, len, device, report, buffer_sink(out, cap));
+  return file_impl(true, (const uint8_t*)zkez, len, device, report, pv::buffer_sink("output", out, cap));
 }
 ISNARK_API int groth16_zkey_pack_file(const char* in_path, const char* out_path, const char* device, Groth16ZkeyPackReport* report)
 {

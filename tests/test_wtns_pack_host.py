@@ -81,6 +81,23 @@ def test_file_entries(K, tmp_path):
     assert sorted(p.name for p in tmp_path.iterdir()) == ["back.wtns", "bad.wtnz", "w.wtns", "w.wtnz"]
 
 
+def test_a_hard_link_of_the_input_is_refused_and_no_refusal_leaves_a_temporary(K, tmp_path):
+    """the shared _file entry: the same file under two names, and the temporary of a call that fails behind its sink"""
+    w, link, bad = tmp_path / "w.wtns", tmp_path / "link.wtns", tmp_path / "bad.wtnz"
+    w.write_bytes(M.write_wtns(mixed(300, seed=6)))
+    os.link(w, link)
+    before = w.read_bytes()
+    with pytest.raises(K.ProverError, match="the output path is the input's"):
+        K.wtns_pack(str(w), out=str(link))
+    assert w.read_bytes() == before and link.read_bytes() == before
+    assert not list(tmp_path.glob("*.tmp.*"))
+    bad.write_bytes(M.container(1, b"\x41", [0, 0], b""))  # an undefined code: the fault is found after the output was sized
+    with pytest.raises(K.WitnessFault):
+        K.wtns_unpack(str(bad), out=str(tmp_path / "never.wtns"))
+    assert not list(tmp_path.glob("*.tmp.*"))
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["bad.wtnz", "link.wtns", "w.wtns"]
+
+
 def with_faults(values, faults):
     """the packed parts of `values` with element e's (code, payload) replaced: faults = {e: (code, payload)}"""
     codes, payload, directory = bytearray(), bytearray(), []
