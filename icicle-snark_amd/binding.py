@@ -744,6 +744,7 @@ groth16_ptau_contribute groth16_ptau_contribute_file groth16_ptau_contributions
 groth16_ptau_verify groth16_ptau_verify_file
 groth16_points_pack groth16_points_unpack groth16_ptau_packed_size groth16_ptau_unpacked_size
 groth16_ptau_pack groth16_ptau_pack_file groth16_ptau_unpack groth16_ptau_unpack_file
+groth16_ptau_truncated_size groth16_ptau_truncate groth16_ptau_truncate_file
 groth16_wtns_packed_size groth16_wtns_pack groth16_wtns_pack_file groth16_wtns_unpack_host groth16_wtns_unpack_host_file
 groth16_wtns_unpack groth16_wtns_unpack_file groth16_prove_packed groth16_prove_packed_files
 groth16_witness_check_packed groth16_witness_check_packed_file
@@ -1476,6 +1477,44 @@ def ptau_unpack(packed, out=None, device: str = "HIP"):
     """groth16_ptau_unpack → (ptau bytes | None, PtauPackReport): the .ptau a packed file came from, byte for byte: a square root per
     point on the GPU, which is also the on-curve test.  Arguments and errors as ptau_pack."""
     return _ptau_transcode("ptau_unpack", lib().groth16_ptau_unpack, lib().groth16_ptau_unpack_file, packed, out, device)
+
+
+class PtauTruncateReport(C.Structure):
+    """Groth16PtauTruncateReport: the input's and the output's power, prepared, the elements of section 12's block power_out + 1 that
+    were fixed up, the input's and the output's bytes, the faulty section with its lowest faulty element, its kind and the count,
+    the stage times"""
+    _fields_ = [("power_in", C.c_uint32), ("power_out", C.c_uint32), ("prepared", C.c_int32), ("points_fixed", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("fault_section", C.c_int32), ("fault_kind", C.c_int32), ("fault_index", C.c_uint64), ("fault_count", C.c_uint64),
+                ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
+
+
+def ptau_truncated_size(ptau, power: int) -> int:
+    """groth16_ptau_truncated_size: the bytes of ptau_truncate's file for this .ptau (unprepared or prepared) and power; host only.
+    Raises ProverError −3 for a power above the file's, −2 for a malformed container."""
+    size = C.c_uint64()
+    _pcheck(lib().groth16_ptau_truncated_size(_image(ptau), C.c_size_t(len(ptau)), C.c_uint32(power), C.byref(size)), "ptau_truncated_size")
+    return size.value
+
+
+def ptau_truncate(ptau, power: int, out=None, device: str = "HIP"):
+    """groth16_ptau_truncate → (ptau bytes | None, PtauTruncateReport): the file of power `power` <= the input's — prefixes of the
+    sections, section 1 with the new power, and for a prepared input section 12's block power + 1 fixed up on the GPU so that the
+    result is what ptau_prepare writes for the truncated unprepared file (include/groth16_prover.h).  ptau: the image, and the file
+    comes back as bytes; or a path together with `out`, the path the file is written to (a temporary, renamed).  An unprepared
+    input, or power equal to the file's, opens no GPU.  A faulty point of the block or of the one point of section 2 that is read
+    raises PointFault (−2) with .report, and nothing is written; the copied prefixes are not tested (ptau_verify judges a file)."""
+    rep = PtauTruncateReport()
+    if isinstance(ptau, (str, os.PathLike)):
+        if out is None:
+            raise TypeError("ptau_truncate: an input path needs the path to write to")
+        _pack_check(lib().groth16_ptau_truncate_file(os.fsencode(ptau), os.fsencode(out), C.c_uint32(power), device.encode(), C.byref(rep)), "ptau_truncate_file", rep)
+        return None, rep
+    if out is not None:
+        raise TypeError("ptau_truncate: `out` goes with an input path")
+    size = ptau_truncated_size(ptau, power)
+    buf = C.create_string_buffer(size)
+    _pack_check(lib().groth16_ptau_truncate(_image(ptau), C.c_size_t(len(ptau)), C.c_uint32(power), buf, C.c_size_t(size), device.encode(), C.byref(rep)), "ptau_truncate", rep)
+    return buf.raw[:rep.out_bytes], rep
 
 
 class WtnsPackReport(C.Structure):

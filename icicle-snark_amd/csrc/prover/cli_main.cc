@@ -30,6 +30,9 @@
 //   > ptau-pack --ptau IN --out OUT [--device HIP]       the file with every point as x and one bit of y, half the bytes
 //     (groth16_ptau_pack_file): one summary line, then PTAU_WRITTEN; a faulty point: PTAU_BAD POINT <section> <element>
 //   > ptau-unpack --packed IN --out OUT [--device HIP]   the .ptau back, byte for byte (groth16_ptau_unpack_file): the same lines
+//   > ptau-truncate --ptau IN --power p --out OUT [--device HIP]   the file of power p <= the input's: prefixes of the sections, and
+//     section 12's block p + 1 fixed up on the GPU (groth16_ptau_truncate_file; an unprepared input opens no GPU): one summary line,
+//     then PTAU_WRITTEN; a faulty point: PTAU_BAD POINT <section> <element> <count>
 //   > wtns-pack --wtns W --out Z              the witness with a code byte per value and only its significant bytes, on the host
 //     (groth16_wtns_pack_file): one summary line, then WTNS_WRITTEN; a value >= r: WTNS_BAD VALUE <element> <count>
 //   > wtns-unpack --packed Z --out W [--device HIP]   the .wtns back; on the host, or with --device decoded on the GPU
@@ -51,7 +54,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  zkey-pack --zkey <file> --out <file> [--device HIP]   (points as x and one bit of y, coefficients as a code byte and their significant bytes)\n  zkey-unpack --packed <file> --out <file> [--device HIP]   (the .zkey back, byte for byte)\n  prove-zkez --witness <file> --zkez <packed key> --proof <file> --public <file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  ptau-truncate --ptau <file> --power <p> --out <file> [--device HIP]   (the file of a lower power; section 12's last block fixed up)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  zkey-pack --zkey <file> --out <file> [--device HIP]   (points as x and one bit of y, coefficients as a code byte and their significant bytes)\n  zkey-unpack --packed <file> --out <file> [--device HIP]   (the .zkey back, byte for byte)\n  prove-zkez --witness <file> --zkez <packed key> --proof <file> --public <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -562,6 +565,29 @@ int main()
         if (rep.fault_kind) std::cout << "PTAU_BAD POINT " << rep.fault_section << " " << rep.fault_index << std::endl;
       } else {
         std::cout << "power " << rep.power << (rep.prepared ? " prepared" : " unprepared") << " points " << rep.points[0] << " " << rep.points[1] << " bytes " << rep.in_bytes << " to "
+                  << rep.out_bytes << "; upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms"
+                  << std::endl;
+        std::cout << "PTAU_WRITTEN" << std::endl;
+      }
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "ptau-truncate") {
+      std::string inp = "pot_final.ptau", out = "pot_cut.ptau", device = "HIP", a;
+      long power = -1;
+      while (in >> a) {
+        if (a == "--ptau") in >> inp;
+        else if (a == "--power") in >> power;
+        else if (a == "--out") in >> out;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16PtauTruncateReport rep = {};
+      const bool bad_power = power < 0 || power > 64;
+      const int rc = bad_power ? -3 : groth16_ptau_truncate_file(inp.c_str(), out.c_str(), (uint32_t)power, device.c_str(), &rep);
+      if (rc < 0) {
+        std::cerr << "ptau-truncate failed (" << rc << "): " << (bad_power ? "--power <p> is required, 0 to the file's power" : groth16_last_error()) << std::endl;
+        if (rep.fault_kind) std::cout << "PTAU_BAD POINT " << rep.fault_section << " " << rep.fault_index << " " << rep.fault_count << std::endl;
+      } else {
+        std::cout << "power " << rep.power_in << " to " << rep.power_out << (rep.prepared ? " prepared" : " unprepared") << " fixed " << rep.points_fixed << " bytes " << rep.in_bytes << " to "
                   << rep.out_bytes << "; upload " << rep.upload_ms << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms"
                   << std::endl;
         std::cout << "PTAU_WRITTEN" << std::endl;

@@ -132,12 +132,14 @@ int walk_records(const pv::Section* s7, std::vector<Record>& recs, uint32_t* cou
   *bad = n;
   return pos == s7->size ? 0 : 1; // bytes behind the last record
 }
-// h₀: what no contribution changes
+// h₀: what no contribution changes.  A file with power < ceremonyPower (groth16_ptau_truncate's) hashes section 1 as the file the
+// records were made for held it: the power field replaced by ceremonyPower.  Every other file hashes its own bytes.
 void chain_start(const pv::PtauLayout& L, uint8_t h[32])
 {
   std::vector<uint8_t> m;
   append(m, TAG, TAG_LEN);
   append(m, L.sec[1]->p, (size_t)L.sec[1]->size);
+  if (L.power < L.ceremony_power) memcpy(m.data() + TAG_LEN + 36, &L.ceremony_power, 4); // (ptau_header: the payload has 44 bytes)
   isnark::sha256(m.data(), m.size(), h);
 }
 // e_i = SHA-256(h_{i−1} ‖ before ‖ the five after points ‖ R_tau ‖ R_alpha ‖ R_beta ‖ name_len ‖ name) → h (in place); c: its first
@@ -319,6 +321,8 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   pv::PtauLayout L;
   if (int rc = pv::ptau_unprepared_layout(data, len, secs, &L)) return rc;
   const uint32_t power = L.power;
+  if (power < L.ceremony_power)
+    return pv::fail(pv::ERR_FORMAT, "ptau: power %u is below the ceremony's %u: the file is a truncation; contribute to the full file, then truncate", power, L.ceremony_power);
   const uint64_t N = (uint64_t)1 << power;
   const uint64_t counts[4] = {2 * N - 1, N, N, N};
   std::vector<Record> recs;

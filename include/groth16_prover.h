@@ -734,7 +734,8 @@ int groth16_ptau_contributions(const void* ptau, size_t len, Groth16PtauContribu
  * pair is resident.  The _file entry maps the file.  No fixed-base table is built, the NTT domain is not touched, the calling thread's
  * device is what it was afterwards.  ICICLE_SNARK_TRACE_PTAU_VERIFY=1 prints the stage times on stderr.
  * What it does NOT show: WHO CONTRIBUTED (groth16_ptau_contributions' answer: run both); beacons; snarkjs' section-7 format; a file
- * with ceremonyPower != power (a truncated file has other counts: -2); more than one GPU; WHICH element of a failing equation is wrong.
+ * truncated by a prefix copy (other counts: -2, or LAGRANGE_12; groth16_ptau_truncate's files have this layout and are judged as
+ * any other); more than one GPU; WHICH element of a failing equation is wrong.
  * 1 both questions hold; 0 not (report says what); -1 I/O; -2 a malformed container; -3 argument: power above 27, a device string
  * that does not name one HIP device; -5 device failure (groth16_last_error). */
 #define GROTH16_PTAU_VERIFY_GENERATORS  1
@@ -833,6 +834,67 @@ int groth16_ptau_pack(const void* ptau, size_t len, void* out, size_t cap, const
 int groth16_ptau_pack_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPackReport* report);
 int groth16_ptau_unpack(const void* packed, size_t len, void* out, size_t cap, const char* device, Groth16PtauPackReport* report);
 int groth16_ptau_unpack_file(const char* in_path, const char* out_path, const char* device, Groth16PtauPackReport* report);
+
+/* groth16_ptau_truncate — a powers-of-tau file of power P cut down to the file of power p <= P, what `snarkjs powersoftau truncate`
+ * is for: a ceremony is run once at a large power and each circuit is served the file of its own.  Opt-in.
+ * truncate(F, p) is defined for a .ptau F of power P <= 27, UNPREPARED (sections 1 to 7) or PREPARED (1 to 7 and 12 to 15, the
+ * container rules of groth16_ptau_verify), and 0 <= p <= P.  Sections keep F's order; any section this library does not know is
+ * copied byte for byte.  With n' = 2^p:
+ *   1            power <- p, ceremonyPower unchanged           (p = P: the output is F byte for byte)
+ *   2            the first 2n' - 1 points                      3, 4, 5      the first n' points
+ *   6, 7         byte for byte
+ *   13, 14, 15   the first 2n' - 1 points: blocks 0 to p       12           blocks 0 to p byte for byte, then block p + 1 FIXED UP
+ * THE FIX-UP.  Block p + 1 of F's section 12 (p < P) is the full transform of size 2n' — all 2n' powers exist in F — while a file of
+ * power p defines it over the zero-extended vector, section 2 holding only 2n' - 1 powers, and groth16_ptau_verify accepts only that
+ * form (LAGRANGE_12).  A prefix copy would fail this library's own verifier.  With Q = element 2n' - 1 of F's section 2, the one
+ * input the small file no longer holds, and w' the root of order 2n':
+ *   B'_j = B_j - (w'^j / 2n') * Q,   j < 2n'        (the scalar of input 2n' - 1 is w'^(-j(2n' - 1)) / 2n' = w'^j / 2n')
+ * so that truncate(prepare(U), p) = prepare(truncate(U, p)) BYTE FOR BYTE for every unprepared U.  No fix-up when p = P.
+ * ON THE GPU: 2n' lanes, each with a full-width scalar of its own — computed in the lane from two small public tables, lo[i] = w'^i
+ * and hi[m] = w'^(m 2^k) / 2n', k = (p + 2) / 2 — times THE SAME point Q.  A common base needs no doublings: the host builds 816
+ * signed-window multiples d * 32^w * Q (d = 1 to 16, w < 51; width 5) as affine points, a workgroup of 256 lanes stages them in
+ * 52 224 bytes of LDS (three workgroups a CU), and a lane recodes its scalar into 51 signed digits and adds one row per non-zero
+ * digit, y negated for a negative one: AT MOST 51 MIXED ADDITIONS A LANE for the product and one for B_j - T, against the 256
+ * doublings and 85 additions of the per-lane-base walk.  Exact in every degenerate case: B_j the identity, T = B_j (the all-zero
+ * identity), T = -B_j (a doubling), a partial sum that meets a row or its negative.  Q the identity: nothing to subtract, the block
+ * is copied and no device is opened.
+ * LANE TESTS FIRST: Q (on the host) and every point of block p + 1 (on the device) go through the lane test of the other tools
+ * (coordinates < q, on the curve) before any arithmetic: a fault is -2 "ptau: section S, element E: kind" — Q first, then the lowest
+ * faulty element of the block, fault_count how many of the block are faulty — and nothing is written.  THE COPIED PREFIXES ARE NOT
+ * TESTED: they are the input's bytes, and groth16_ptau_verify judges a file.  Only block p + 1 and the tables go up.  AN UNPREPARED
+ * INPUT, OR p = P, NEVER INITIALISES A GPU (the device string is still parsed).
+ * THE CHAIN.  h_0 of section 7's chain hashes section 1's payload, which holds `power`.  For a file with power < ceremonyPower —
+ * only a truncation makes one — h_0 is computed over the payload with the power field REPLACED BY ceremonyPower: the payload of the
+ * file the records were made for.  For power >= ceremonyPower the hashed bytes are what they were.  groth16_ptau_contributions
+ * therefore audits a truncated unprepared file with the records and the verdict of the full one: the HEADER rule's elements
+ * (element 1 of sections 2 and 3, element 0 of 4 and 5, section 6) survive, and at p = 0 the power-0 rule applies.  It does NOT
+ * show that power was not lowered by hand: a file cut by other means with the same bytes IS this file.  groth16_ptau_contribute
+ * refuses a file with power < ceremonyPower (-2: contribute to the full file, then truncate), before any device work.
+ * groth16_ptau_truncated_size gives the output's size on the host.  cap is tested before any device work (-3, report->out_bytes says
+ * what is needed).  0 done; -1 I/O; -2 format (a packed "ptaz" file: the reader's text; unpack first) or a faulty point; -3 argument:
+ * power above the file's, cap too small, equal paths (by name or by inode), a device string that does not name one HIP device; -5
+ * device failure (groth16_last_error).  The _file entry maps the input, writes a temporary beside out_path and renames it: a failed
+ * call leaves nothing.  The calling thread's device is what it was afterwards.  ICICLE_SNARK_TRACE_PTAU_TRUNCATE=1 prints the stage
+ * times on stderr.
+ * What it does NOT do: read a packed (ptaz) file; RAISE a power; apply or check beacons; read or write snarkjs' section-7 format; use
+ * more than one GPU; test the copied prefixes. */
+typedef struct {
+  uint32_t power_in, power_out;
+  int32_t  prepared;            /* 1: sections 12 to 15 are present */
+  uint64_t points_fixed;        /* elements of section 12's block power_out + 1 that went through the fix-up (0: none needed) */
+  uint64_t in_bytes, out_bytes; /* the input; the output (also when cap was too small) */
+  int32_t  fault_section, fault_kind;   /* after a faulty point: 2 or 12, and GROTH16_ZKEY_NONCANONICAL / _OFF_CURVE */
+  uint64_t fault_index;                 /* the lowest faulty element of that section */
+  uint64_t fault_count;                 /* the block's faulty elements (1 for Q) */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the block's and the tables' copies up; wall time of the device part
+                                   without them and without the host's copy of the container, which runs beside the kernels: what
+                                   the device adds to the call; the block's copy down; msync and rename (_file) */
+} Groth16PtauTruncateReport;
+int groth16_ptau_truncated_size(const void* ptau, size_t len, uint32_t power, uint64_t* bytes);
+int groth16_ptau_truncate(const void* ptau, size_t len, uint32_t power, void* out, size_t cap, const char* device,
+                          Groth16PtauTruncateReport* report);
+int groth16_ptau_truncate_file(const char* in_path, const char* out_path, uint32_t power, const char* device,
+                               Groth16PtauTruncateReport* report);
 
 /* groth16_wtns_pack, groth16_wtns_unpack, groth16_prove_packed, groth16_witness_check_packed — a witness with a code byte per value
  * and only the value's significant bytes ("wtnz"), packed on the host of the witness generator and decoded on the GPU straight into
