@@ -1,10 +1,13 @@
 // device_call.h — the host plumbing every key, file and pack tool wraps its device work in (the zkey_*.hip, ptau_*.hip, wtns_pack.hip,
 // r1cs_check.hip; verify_combined.hip takes its MSM configuration from here): one error text and the checked call and launch that
-// return it, the device a call names, stage times, the scoped file hint of the pinned staging, the timed upload, where an output
-// goes once its size is known (Sink: the caller's buffer, or the temporary a _file entry writes and renames), the ONE _file entry
-// of a tool that rewrites a file (rewrite_file), an event that destroys itself, the library's MSMs over device operands in slices,
-// and the seed and coefficients of the randomised checks.  The device session and its buffers are verify_batch.h's; the host point
-// helpers are verify_host.h's; the ptau's ranges are ptau_ranges.h's; what the packed forms' kernels share is pack_device.h's.
+// return it, the device a call names and the session it opens (open_session), stage times, the scoped file hint of the pinned
+// staging, the timed upload, where an output goes once its size is known (Sink: the caller's buffer, or the temporary a _file entry
+// writes and renames), the ONE _file entry of a tool that rewrites a file (rewrite_file), an event that destroys itself, the
+// library's MSMs over device operands in slices, the seed and coefficients of the randomised checks, and the scalar tables of the
+// ptau tools (root_of_unity, split_power_tables over ptau_contribute29.h's fill).  The device session and its buffers are
+// verify_batch.h's; the host point helpers are verify_host.h's; a contribution's transcript is transcript.h's; the ptau's ranges and
+// the lane test of an uploaded range are ptau_ranges.h's; the way back to the file's form is point_form.h's; what the packed forms'
+// kernels share is pack_device.h's.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -19,6 +22,7 @@
 
 #include "../workers.h"
 #include "prover_internal.h"
+#include "ptau_contribute29.h"
 #include "sha256.h"
 #include "verify_batch.h"
 
@@ -47,6 +51,8 @@ inline int parse_device(const char* device, int* dev)
   if (*dev < 0) return fail(ERR_ARG, "device: '%s' does not name one HIP device", device);
   return 0;
 }
+// the session of a call: `dev` made active, `streams` streams
+inline int open_session(vb::DeviceSession& ds, int dev, int streams) { return ds.open(dev, streams) ? fail(ERR_DEVICE, "%s", groth16_verify_last_error()) : 0; }
 
 // stage times on stderr when `env` is set (read at every call: common.h's rule for a knob an in-process caller may change), as
 // ICICLE_SNARK_TRACE_COLD for a load
@@ -235,6 +241,30 @@ inline void fill_coefficients(const uint8_t seed[32], uint64_t first, size_t cou
   run_ranges(count, 4096, [&](int, size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) combined_coefficient(seed, first + (uint64_t)i, (uint8_t*)&out[i]);
   }, meanwhile);
+}
+
+
+// ---- the ptau tools' scalar tables
+// the root of unity of order 2^order_log2, standard form
+inline int root_of_unity(uint32_t order_log2, fe* w_std)
+{
+  bn254_scalar_t rou;
+  if (bn254_get_root_of_unity((uint64_t)1 << order_log2, &rou) != ICICLE_SUCCESS) return fail(ERR_ARG, "ptau: no root of unity of order 2^%u", order_log2);
+  memcpy(w_std->l, &rou, 32);
+  return 0;
+}
+// The two-table split of a power sequence (ptau_contribute29.h: index i = m·2^kbits + j), into the caller's 2^kbits + n_starts·n_hi
+// entries at `out`: lo[j] = base^j for j < 2^kbits, then for each start c hi_c[m] = start_c·base^(m·2^kbits) for m < n_hi.
+// Montgomery form in and out, filled on the worker pool; nothing is allocated, so a caller's secrets stay in its own storage.
+inline void split_power_tables(const fe& base_m, uint32_t kbits, size_t n_hi, const fe* starts_m, int n_starts, fe* out)
+{
+  const size_t n_lo = (size_t)1 << kbits;
+  const fe one_m = Fr::to_mont(Fr::one_std()), step_m = bn254::pc29::pc_pow(base_m, n_lo);
+  run_ranges(n_lo, 1024, [&](int, size_t lo, size_t hi) { bn254::pc29::pc_fill_powers(base_m, one_m, lo, hi, out); });
+  for (int c = 0; c < n_starts; c++) {
+    fe* const hi_c = out + n_lo + (size_t)c * n_hi;
+    run_ranges(n_hi, 1024, [&](int, size_t lo, size_t hi) { bn254::pc29::pc_fill_powers(step_m, starts_m[c], lo, hi, hi_c); });
+  }
 }
 
 } // namespace prover

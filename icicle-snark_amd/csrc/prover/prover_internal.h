@@ -391,6 +391,17 @@ int zkez_coefs_decode(hipStream_t st, const ZkezCoefs& C, uint8_t* d_buf, uint32
 // ERR_FORMAT "<form>: section S, element E: <point kind>" / "<form>: coefficient E: <wtnz kind>" for a tally that holds a fault
 int packed_point_fail(const char* form, int section, const PackTally& t);
 int packed_coef_fail(const char* form, const PackTally& t);
+// ERR_FORMAT "ptau: section S, element E: <point kind>": a faulty point of a .ptau, whichever tool met it
+inline int ptau_point_fail(int section, uint64_t element, int kind)
+{
+  return fail(ERR_FORMAT, "ptau: section %d, element %llu: %s", section, (unsigned long long)element, POINT_FAULT[kind & 3]);
+}
+// where a faulty point lies, into whichever report it is: the reports share these names (fault_count is set where a report has it)
+template <class Report>
+void set_point_fault(Report* rep, int section, uint64_t element, int kind)
+{
+  rep->fault_section = section, rep->fault_index = element, rep->fault_kind = kind;
+}
 
 // ---- blinding and proof assembly (assemble.cpp)
 // blinding terms that do not depend on the commitments: δ1·r, δ1·s, δ2·s, δ1·r·s (src/proof_helper.rs:280-283);

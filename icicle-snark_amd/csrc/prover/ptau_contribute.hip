@@ -3,13 +3,15 @@
 // 7 records.  include/groth16_prover.h has the contract and section 7's layout; DESIGN.md §7h.
 //
 //   host, first  the container (ptau_unprepared_layout), section 7's bounds and its last record against the file, the output's size
-//                against the room, section 6 through the lane test; τ′, α′, β′ and the three nonces; the tables lo[j] = τ′^j and
-//                hi_c[m] = c·τ′^(m·2^k) for c ∈ {1, α′, β′} (ptau_contribute29.h), Montgomery form, on the worker pool.
+//                against the room, section 6 through the lane test; τ′, α′, β′ and the three nonces (transcript.h has the hashes, the
+//                record walk and the proof of knowledge, one text with groth16_zkey_contribute's); the tables lo[j] = τ′^j and
+//                hi_c[m] = c·τ′^(m·2^k) for c ∈ {1, α′, β′} (device_call.h's split_power_tables over ptau_contribute29.h), Montgomery
+//                form, on the worker pool.
 //   device       sections 2 … 5 go up and stay; each through ptau_ranges.h's lane test (section 3 with the subgroup test), and all four
 //                verdicts are read before any arithmetic sees a point.  Then per section ONE launch of pc_scale_kernel, a lane per
 //                point: s = from_mont(hi_c[i ≫ k]·lo[i mod 2^k]) = c·τ′^i, its non-adjacent form, pp29::pp_scale's walk — a full-width
-//                scalar per lane that no table of 2N entries holds.  batch_to_affine_kernel and affine_to_mont_kernel (msm_impl.h's)
-//                write the section back over its source in the file's form, the identity all zero.
+//                scalar per lane that no table of 2N entries holds.  point_form.h's to_file_form writes the section back over its
+//                source in the file's form, the identity all zero.
 //   host, beside the record — eight G1 and two G2 multiplications by zc_mul_affine, on points the verdicts have passed — section 6 and
 //                the sections that are copied, while the kernels run.  Nothing is written before the verdicts are in.
 //   The device tables are overwritten before they are freed, the host's secrets wiped on every way out: best effort.
@@ -19,45 +21,31 @@
 #include <string>
 #include <vector>
 
-#include "../msm_impl.h"
 #include "../workers.h"
 #include "device_call.h"
+#include "point_form.h"
 #include "prover_internal.h"
 #include "ptau_contribute29.h"
 #include "ptau_ranges.h"
-#include "sha256.h"
+#include "transcript.h"
 #include "verify_batch.h"
-#include "zkey_check29.h"
 
 using namespace bn254;
-using bn254::zc29::ZcDigits;
+using namespace isnark::transcript;
 
 namespace {
 
 namespace pv = isnark::prover;
 namespace vb = isnark::vb;
+using pv::Group;
 
 constexpr int PC_WG = 64;
 const char TAG[] = "icicle-snark ptau contribution v1";
 constexpr size_t TAG_LEN = sizeof TAG - 1;
-constexpr uint32_t NAME_BYTES_MAX = 255;
 constexpr uint32_t NEW_POWER_MAX = 27; // groth16_ptau_prepare's limit
 // a record: the five `after` points, the three commitments, the three responses, the name
 constexpr size_t TAU1 = 0, ALPHA1 = 64, BETA1 = 128, TAU2 = 192, BETA2 = 320, AFTER_BYTES = 448, R_TAU = 448, Z_TAU = 640, NAME_LEN = 736, RECORD_FIXED = 740;
 constexpr size_t BEFORE_BYTES = 192; // (tau1, alpha1, beta1): the first three points of a record
-
-template <class C>
-struct Group;
-template <>
-struct Group<G1> {
-  typedef Fq29 F;
-  typedef FqOps Fo;
-};
-template <>
-struct Group<G2> {
-  typedef Fq2_29 F;
-  typedef Fq2Ops Fo;
-};
 
 // One lane per point of a section (pts[i], i < n): (c·τ′^i)·P as Montgomery projective, the identity (0, 1, 0).  lo[j] = τ′^j for
 // j < 2^k and hi[m] = c·τ′^(m·2^k) for m ≤ (n − 1) ≫ k, Montgomery form: the host sizes hi for 2^(power+1) indices, n is at most
@@ -73,65 +61,7 @@ __global__ __launch_bounds__(PC_WG) void pc_scale_kernel(const typename C::A* __
   out[i] = C::x_to_projective(CL::x_store(pc29::pc_lane<typename Group<C>::F>(p, ld(hi + (i >> k)), ld(lo + (i & (((uint64_t)1 << k) - 1))))));
 }
 
-// ---- scalars on the host: standard form, below r
-fe fr_mul(const fe& a, const fe& b) { return Fr::mul(Fr::to_mont(a), b); }
-// a big-endian integer of `len` bytes mod r, by Horner's rule in additions
-fe fr_from_be(const uint8_t* b, size_t len)
-{
-  fe acc = Fr::zero();
-  for (size_t i = 0; i < len; i++) {
-    for (int k = 0; k < 8; k++) acc = Fr::dbl(acc);
-    fe d = Fr::zero();
-    d.l[0] = b[i];
-    acc = Fr::add(acc, d);
-  }
-  return acc;
-}
-// W(x) = SHA-256(x ‖ 0x00) ‖ SHA-256(x ‖ 0x01) as a 512-bit big-endian integer, mod r (groth16_zkey_contribute's).  x is wiped.
-fe wide_hash(std::vector<uint8_t>& x)
-{
-  uint8_t d[64];
-  x.push_back(0);
-  isnark::sha256(x.data(), x.size(), d);
-  x.back() = 1;
-  isnark::sha256(x.data(), x.size(), d + 32);
-  const fe v = fr_from_be(d, 64);
-  explicit_bzero(d, sizeof d);
-  explicit_bzero(x.data(), x.size());
-  return v;
-}
-void append(std::vector<uint8_t>& v, const void* p, size_t n) { v.insert(v.end(), (const uint8_t*)p, (const uint8_t*)p + n); }
-
-// ---- section 7
-struct Record {
-  const uint8_t* p;
-  uint32_t name_len;
-  size_t bytes() const { return RECORD_FIXED + name_len; }
-};
-// the records of section 7.  0, or 1 with *bad = the record that does not fit (0: the count); recs holds the records before it.
-int walk_records(const pv::Section* s7, std::vector<Record>& recs, uint32_t* count, uint32_t* bad)
-{
-  recs.clear();
-  *count = 0, *bad = 0;
-  if (s7->size < 4) return 1;
-  uint32_t n;
-  memcpy(&n, s7->p, 4);
-  if ((uint64_t)n * RECORD_FIXED > s7->size - 4) return 1; // (a hostile count sizes nothing)
-  *count = n;
-  uint64_t pos = 4;
-  for (uint32_t i = 0; i < n; i++) {
-    *bad = i + 1;
-    if (s7->size - pos < RECORD_FIXED) return 1;
-    Record r;
-    r.p = s7->p + pos;
-    memcpy(&r.name_len, r.p + NAME_LEN, 4);
-    if (r.name_len > NAME_BYTES_MAX || s7->size - pos - RECORD_FIXED < r.name_len) return 1;
-    recs.push_back(r);
-    pos += r.bytes();
-  }
-  *bad = n;
-  return pos == s7->size ? 0 : 1; // bytes behind the last record
-}
+// ---- section 7 (the scalars, the record walk and the proof of knowledge are transcript.h's)
 // h₀: what no contribution changes.  A file with power < ceremonyPower (groth16_ptau_truncate's) hashes section 1 as the file the
 // records were made for held it: the power field replaced by ceremonyPower.  Every other file hashes its own bytes.
 void chain_start(const pv::PtauLayout& L, uint8_t h[32])
@@ -151,11 +81,7 @@ void chain_step(uint8_t h[32], const uint8_t* before, const Record& r, fe* c)
   append(m, before, BEFORE_BYTES);
   append(m, r.p, Z_TAU);
   append(m, r.p + NAME_LEN, 4 + r.name_len);
-  isnark::sha256(m.data(), m.size(), h);
-  uint8_t c16[16];
-  isnark::combined_coefficient_from_digest(h, c16);
-  *c = Fr::zero();
-  memcpy(c->l, c16, 16);
+  hash_step(m, h, c);
 }
 
 // the five points a record must end in, as the file holds them now: [τ]₁ [α]₁ [β]₁ [τ]₂ [β]₂ in a record's order.  At power 0 the
@@ -191,23 +117,6 @@ void generators(uint8_t out[AFTER_BYTES])
   const G2::A g2 = vb::g2_generator_mont();
   for (size_t off : {TAU1, ALPHA1, BETA1}) memcpy(out + off, &g1, 64);
   for (size_t off : {TAU2, BETA2}) memcpy(out + off, &g2, 128);
-}
-int classify(const G1::A& a)
-{
-  const fe w[2] = {a.x, a.y};
-  return p29::classify_g1(w);
-}
-int classify(const G2::A& a)
-{
-  const fe2 w[2] = {a.x, a.y};
-  return p29::classify_g2(w);
-}
-template <class A>
-A point_at(const uint8_t* p)
-{
-  A a;
-  memcpy(&a, p, sizeof a);
-  return a;
 }
 
 // everything secret of one call; wiped on every way out (best effort: the compiler may have kept copies in registers or spills)
@@ -293,18 +202,12 @@ struct Buffers {
 template <class C>
 int scale_section(hipStream_t st, const Buffers& b, int k4, uint64_t n, const fe* d_lo, const fe* d_hi, uint32_t kbits)
 {
-  typedef typename Group<C>::Fo Fo;
   typedef typename C::A A;
   typedef typename C::P P;
   A* const d_a = (A*)b.sec[k4];
   P* const d_p = (P*)b.proj;
-  typename Fo::T* const d_s = (typename Fo::T*)b.scratch;
-  const int chunk = 32;
-  const uint64_t threads = (n + chunk - 1) / chunk, ncoord = n * (sizeof(A) / sizeof(fe));
   DEV_LAUNCH("scale kernel launch", (pc_scale_kernel<C>), dim3((uint32_t)((n + PC_WG - 1) / PC_WG)), dim3(PC_WG), st, (const A*)d_a, n, d_lo, d_hi, kbits, d_p);
-  DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<C, Fo>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st, d_p, n, chunk, d_a, d_s);
-  DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), st, d_a, ncoord);
-  return 0;
+  return pv::to_file_form<C>(st, d_p, n, d_a, (typename Group<C>::Fo::T*)b.scratch);
 }
 
 int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, const char* name, const char* device, const Groth16PtauContributeOptions* opt,
@@ -327,7 +230,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   const uint64_t counts[4] = {2 * N - 1, N, N, N};
   std::vector<Record> recs;
   uint32_t count, bad;
-  if (walk_records(L.sec[7], recs, &count, &bad)) return pv::fail(pv::ERR_FORMAT, "ptau: section 7 is malformed at record %u of %u", bad, count);
+  if (walk_records(L.sec[7], RECORD_FIXED, NAME_LEN, recs, &count, &bad)) return pv::fail(pv::ERR_FORMAT, "ptau: section 7 is malformed at record %u of %u", bad, count);
   const Held held = held_points(L);
   if (count && !header_holds(held, recs.back().p)) return pv::fail(pv::ERR_FORMAT, "ptau: section 7's last record is not what sections 2 to 6 hold");
 
@@ -340,8 +243,8 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   uint8_t* out = nullptr;
   if (int rc = sink(total, &out)) return rc;
   auto fault = [&](int section, uint64_t element, int kind) {
-    rep->fault_section = section, rep->fault_index = element, rep->fault_kind = kind;
-    return pv::fail(pv::ERR_FORMAT, "ptau: section %d, element %llu: %s", section, (unsigned long long)element, POINT_FAULT[kind & 3]);
+    pv::set_point_fault(rep, section, element, kind);
+    return pv::ptau_point_fail(section, element, kind);
   };
   const G2::A beta2_in = point_at<G2::A>(L.sec[6]->p);
   if (const int kind = classify(beta2_in)) return fault(6, 0, kind);
@@ -404,21 +307,16 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   const size_t n_lo = (size_t)1 << kbits, n_hi = (size_t)1 << (power + 1 - kbits);
   S.tables.resize(n_lo + 3 * n_hi);
   {
-    const fe one_m = Fr::to_mont(Fr::one_std()), tau_m = Fr::to_mont(S.x[0]), step_m = pc29::pc_pow(tau_m, n_lo);
-    fe* const t = S.tables.data();
-    isnark::run_ranges(n_lo, 1024, [&](int, size_t lo, size_t hi) { pc29::pc_fill_powers(tau_m, one_m, lo, hi, t); });
-    for (int c = 0; c < 3; c++) {
-      const fe start_m = c ? Fr::to_mont(S.x[c]) : one_m;
-      fe* const tc = t + n_lo + c * n_hi;
-      isnark::run_ranges(n_hi, 1024, [&](int, size_t lo, size_t hi) { pc29::pc_fill_powers(step_m, start_m, lo, hi, tc); });
-    }
+    fe starts_m[3] = {Fr::to_mont(Fr::one_std()), Fr::to_mont(S.x[1]), Fr::to_mont(S.x[2])};
+    pv::split_power_tables(Fr::to_mont(S.x[0]), kbits, n_hi, starts_m, 3, S.tables.data());
+    explicit_bzero(starts_m, sizeof starts_m);
   }
   trace.lap("layout, secrets, tables");
 
   // ---- sections 2 … 5 up, and through the lane tests before anything else reads them
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   Buffers b;
   static_assert(sizeof(G2::A) == 2 * sizeof(G1::A) && sizeof(G2::P) == 2 * sizeof(G1::P), "a G2 section of 2^power points fills the buffers of a G1 section of 2^(power+1)");
@@ -434,9 +332,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   DEV_TRY("hipMemset", hipMemsetAsync(b.first, 0xff, 4 * sizeof *b.first, st));
   for (int k4 = 0; k4 < 4; k4++) {
     if (int rc = pv::timed_upload(dev, b.sec[k4], L.sec[2 + k4]->p, (size_t)L.sec[2 + k4]->size, &rep->upload_ms)) return rc;
-    const uint64_t n = counts[k4];
-    if (k4 == 1) DEV_LAUNCH("ptau membership kernel launch", ptau_g2_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), st, (const fe2*)b.sec[k4], (uint32_t)n, b.first + k4);
-    else DEV_LAUNCH("ptau membership kernel launch", ptau_g1_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), st, (const fe*)b.sec[k4], (uint32_t)n, b.first + k4);
+    if (int rc = enqueue_lane_test(st, k4 == 1, b.sec[k4], counts[k4], b.first + k4)) return rc;
   }
   if (int rc = pv::timed_upload(dev, b.tables, S.tables.data(), S.tables.size() * sizeof(fe), &rep->upload_ms)) return rc;
   unsigned long long first[4] = {NO_FAULT, NO_FAULT, NO_FAULT, NO_FAULT};
@@ -475,7 +371,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
     fe c;
     chain_step(h, before, rec, &c);
     for (int x = 0; x < 3; x++) {
-      const fe z = Fr::add(S.k[x], fr_mul(c, S.x[x]));
+      const fe z = schnorr_response(S.k[x], c, S.x[x]);
       memcpy(r + Z_TAU + 32 * x, z.l, 32);
     }
   }
@@ -508,22 +404,6 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   rep->download_ms = pv::ms_since(t_down);
   trace.lap("sections downloaded");
   return 0;
-}
-
-// a Montgomery-form point as the host pairing takes it
-bn254_affine_t std_affine(const G1::A& a)
-{
-  const G1::A s = {Fq::from_mont(a.x), Fq::from_mont(a.y)};
-  bn254_affine_t p;
-  memcpy(&p, &s, sizeof p);
-  return p;
-}
-bn254_g2_affine_t std_affine(const G2::A& a)
-{
-  const G2::A s = {Fq2Ops::from_mont(a.x), Fq2Ops::from_mont(a.y)};
-  bn254_g2_affine_t p;
-  memcpy(&p, &s, sizeof p);
-  return p;
 }
 
 } // namespace
@@ -587,7 +467,7 @@ ISNARK_API int groth16_ptau_contributions(const void* ptau, size_t len, Groth16P
   };
   std::vector<Record> recs;
   uint32_t bad;
-  const int malformed = walk_records(L.sec[7], recs, &report->count, &bad);
+  const int malformed = walk_records(L.sec[7], RECORD_FIXED, NAME_LEN, recs, &report->count, &bad);
   for (size_t i = 0; infos && i < recs.size() && i < infos_cap; i++) {
     const uint8_t* const p = recs[i].p;
     memcpy(infos[i].tau1, p + TAU1, 64);
@@ -623,12 +503,7 @@ ISNARK_API int groth16_ptau_contributions(const void* ptau, size_t len, Groth16P
     for (int x = 0; x < 3; x++) {
       fe z;
       memcpy(z.l, r.p + Z_TAU + 32 * x, 32);
-      if (!Fr::is_canonical(z)) return fault(GROTH16_CONTRIB_POK, i + 1);
-      const G1::A lhs = zc29::zc_mul_affine<G1, G1L>(point_at<G1::A>(before + 64 * x), z);
-      G1L::X acc = zc29::zc_scale<G1L>(after[x], cd);
-      if (!G1::aff_is_zero(commitment[x])) G1L::x_madd(acc, G1L::load_affine(commitment[x], G1L::MONT256, false));
-      const G1::A rhs = G1::p_to_affine(G1::x_to_projective(G1L::x_store(acc)));
-      if (memcmp(&lhs, &rhs, sizeof lhs) != 0) return fault(GROTH16_CONTRIB_POK, i + 1);
+      if (!pok_holds(point_at<G1::A>(before + 64 * x), after[x], commitment[x], z, cd)) return fault(GROTH16_CONTRIB_POK, i + 1);
     }
     // PAIR: e(tau1, G₂) = e(G₁, tau2) and e(beta1, G₂) = e(G₁, beta2)
     if (!vb::pairing_eq(std_affine(after[0]), g2, g1, std_affine(tau2)) || !vb::pairing_eq(std_affine(after[2]), g2, g1, std_affine(beta2))) return fault(GROTH16_CONTRIB_PAIR, i + 1);

@@ -169,7 +169,7 @@ int points_impl(bool unpack, const void* in, uint64_t n, int g2, void* out, cons
   if (!n) return 0;
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   std::vector<Range> ranges(1);
   ranges[0] = {0, g2 != 0, n, (const uint8_t*)in, (uint8_t*)out, nullptr, nullptr};
   Tally t;
@@ -221,8 +221,8 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   uint8_t* out = nullptr;
   if (int rc = sink(total, &out)) return rc;
   auto fault = [&](int section, uint64_t element, int kind, uint64_t count) {
-    rep->fault_section = section, rep->fault_index = element, rep->fault_kind = kind, rep->fault_count = count;
-    return pv::fail(pv::ERR_FORMAT, "ptau: section %d, element %llu: %s", section, (unsigned long long)element, POINT_FAULT[kind & 3]);
+    pv::set_point_fault(rep, section, element, kind), rep->fault_count = count;
+    return pv::ptau_point_fail(section, element, kind);
   };
   // section 6 on the host, through the same lane code
   fe2 beta2_in[2], beta2_out[2];
@@ -239,7 +239,7 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   trace.lap("layout, section 6");
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   Tally tallies[MAX_SECTIONS];
   if (int rc = run_ranges_on_device(ds, dev, unpack, ranges, tallies, &rep->upload_ms)) return rc;
   rep->device_ms = pv::ms_since(t_dev) - rep->upload_ms;

@@ -15,8 +15,8 @@
 //                              end is the identity: the zero-extended vector of section 12's block power + 1.
 //             pp_level_kernel  level s, a lane per butterfly of every block p > s: a[i0], a[i0 + 2^s] with the twiddle ω_(s+1)^(−j) =
 //                              tw[j·2^(power−s)], a scalar per lane (ptau_prepare29.h: pp_twiddled, pp_side).  Level 0 multiplies nothing.
-//           each followed by batch_to_affine_kernel and affine_to_mont_kernel (msm_impl.h's): the block is in the file's form after
-//           every level, the identity all zero.  The finished blocks go down into the output at element 2^p − 1 of their section.
+//           each followed by point_form.h's to_file_form: the block is in the file's form after every level, the identity all
+//           zero.  The finished blocks go down into the output at element 2^p − 1 of their section.
 //   Resident: one source section, the top block's working buffers (affine, projective, the inversion's scratch) and the twiddles.
 #include <algorithm>
 #include <chrono>
@@ -24,9 +24,9 @@
 #include <string>
 #include <vector>
 
-#include "../msm_impl.h"
 #include "../workers.h"
 #include "device_call.h"
+#include "point_form.h"
 #include "prover_internal.h"
 #include "ptau_prepare29.h"
 #include "ptau_ranges.h"
@@ -40,21 +40,9 @@ namespace {
 
 namespace pv = isnark::prover;
 namespace vb = isnark::vb;
+using pv::Group;
 
 constexpr int PP_WG = 64;
-
-template <class C>
-struct Group;
-template <>
-struct Group<G1> {
-  typedef Fq29 F;
-  typedef FqOps Fo;
-};
-template <>
-struct Group<G2> {
-  typedef Fq2_29 F;
-  typedef Fq2Ops Fo;
-};
 
 // Blocks p_lo … p_hi of a section side by side in the working buffers, as they lie in the section: block p begins at element
 // 2^p − 2^p_lo of the buffers (2^p − 1 of the section), so the blocks 0 … p − 1 together are one element shorter than block p alone.
@@ -109,27 +97,16 @@ __global__ __launch_bounds__(PP_WG) void pp_level_kernel(const typename C::A* __
 }
 
 // ---- scalars on the host
-fe fr_pow(fe base_mont, uint64_t e)
-{
-  fe acc = Fr::to_mont(Fr::one_std());
-  for (; e; e >>= 1) {
-    if (e & 1) acc = Fr::mul(acc, base_mont);
-    base_mont = Fr::sqr(base_mont);
-  }
-  return acc;
-}
 // tw[i] = w^(−i), i < count, standard form; w the root of order 2·count (count = 1: the table is {1})
 int twiddle_table(uint32_t power, std::vector<fe>& tw)
 {
   const size_t count = (size_t)1 << power;
-  bn254_scalar_t rou;
-  if (bn254_get_root_of_unity((uint64_t)2 << power, &rou) != ICICLE_SUCCESS) return pv::fail(pv::ERR_ARG, "ptau: no root of unity of order 2^%u", power + 1);
   fe w;
-  memcpy(w.l, &rou, 32);
+  if (int rc = pv::root_of_unity(power + 1, &w)) return rc;
   const fe winv = Fr::inv(Fr::to_mont(w));
   tw.resize(count);
   isnark::run_ranges(count, 1 << 14, [&](int, size_t lo, size_t hi) {
-    fe x = fr_pow(winv, lo);
+    fe x = pc29::pc_pow(winv, lo);
     for (size_t i = lo; i < hi; i++) {
       tw[i] = Fr::from_mont(x);
       x = Fr::mul(x, winv);
@@ -141,7 +118,7 @@ fe inverse_of_two_to(uint32_t p)
 {
   fe two = Fr::zero();
   two.l[0] = 2;
-  return Fr::from_mont(Fr::inv(fr_pow(Fr::to_mont(two), p)));
+  return Fr::from_mont(Fr::inv(pc29::pc_pow(Fr::to_mont(two), p)));
 }
 
 struct Buffers {
@@ -156,20 +133,12 @@ constexpr uint32_t INV_COUNT = 29;
 template <class C>
 int transform_blocks(hipStream_t st, const Buffers& b, uint64_t avail, uint32_t p_lo, uint32_t p_hi, uint32_t power)
 {
-  typedef typename Group<C>::Fo Fo;
   typedef typename C::A A;
   typedef typename C::P P;
   const uint64_t n = ((uint64_t)2 << p_hi) - ((uint64_t)1 << p_lo);
   A* const d_a = (A*)b.aff;
   P* const d_p = (P*)b.proj;
-  typename Fo::T* const d_s = (typename Fo::T*)b.scratch;
-  const int chunk = 32;
-  const uint64_t threads = (n + chunk - 1) / chunk, ncoord = n * (sizeof(A) / sizeof(fe));
-  auto to_file_form = [&]() -> int {
-    DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<C, Fo>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st, d_p, n, chunk, d_a, d_s);
-    DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), st, d_a, ncoord);
-    return 0;
-  };
+  auto to_file_form = [&] { return pv::to_file_form<C>(st, d_p, n, d_a, (typename Group<C>::Fo::T*)b.scratch); };
   DEV_LAUNCH("load kernel launch", (pp_load_kernel<C>), dim3((uint32_t)((n + PP_WG - 1) / PP_WG)), dim3(PP_WG), st, (const A*)b.src, avail, p_lo, n, (const ZcDigits*)b.inv, d_p);
   if (int rc = to_file_form()) return rc;
   for (uint32_t s = 0; s < p_hi; s++) {
@@ -209,8 +178,8 @@ int prepare_impl(const uint8_t* data, size_t len, const char* device, Groth16Pta
   uint8_t* out = nullptr;
   if (int rc = sink(total, &out)) return rc;
   auto fault = [&](int section, uint64_t element, int kind) {
-    rep->fault_section = section, rep->fault_index = element, rep->fault_kind = kind;
-    return pv::fail(pv::ERR_FORMAT, "ptau: section %d, element %llu: %s", section, (unsigned long long)element, POINT_FAULT[kind & 3]);
+    pv::set_point_fault(rep, section, element, kind);
+    return pv::ptau_point_fail(section, element, kind);
   };
   {
     fe2 beta2[2];
@@ -235,7 +204,7 @@ int prepare_impl(const uint8_t* data, size_t len, const char* device, Groth16Pta
 
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   // every section's largest block has 2^(power+1) G1 points or 2^power G2 points: the same bytes
   const size_t top = (size_t)(2 * N);
@@ -273,8 +242,7 @@ int prepare_impl(const uint8_t* data, size_t len, const char* device, Groth16Pta
     // up, and through the lane tests before anything else reads it
     if (int rc = pv::timed_upload(dev, b.src, L.sec[src_id]->p, (size_t)(avail * elem), &rep->upload_ms)) return rc;
     DEV_TRY("hipMemset", hipMemsetAsync(b.first, 0xff, sizeof *b.first, st));
-    if (g2) DEV_LAUNCH("ptau membership kernel launch", ptau_g2_kernel, dim3((uint32_t)((avail + 63) / 64)), dim3(64), st, (const fe2*)b.src, (uint32_t)avail, b.first);
-    else DEV_LAUNCH("ptau membership kernel launch", ptau_g1_kernel, dim3((uint32_t)((avail + 255) / 256)), dim3(256), st, (const fe*)b.src, (uint32_t)avail, b.first);
+    if (int rc = enqueue_lane_test(st, g2, b.src, avail, b.first)) return rc;
     unsigned long long first = NO_FAULT;
     DEV_TRY("download", hipMemcpyAsync(&first, b.first, sizeof first, hipMemcpyDeviceToHost, st));
     DEV_TRY("lane tests", hipStreamSynchronize(st));

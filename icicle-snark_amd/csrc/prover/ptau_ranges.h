@@ -1,7 +1,8 @@
 // ptau_ranges.h — reading a prepared .ptau's blocks on the device, shared by groth16_zkey_verify_ptau (zkey_verify.hip) and
 // groth16_zkey_new (zkey_new.hip): which five ranges a circuit of domain 2^k needs, the procedure that stages them (PtauRanges:
 // bound, allocate, upload, lane test where each lands), the lane tests every uploaded range goes through before anything else reads
-// it, and the gather of the odd elements of section 12's block k + 1 (NO_FAULT and the text of a faulting element are
+// it and their launch (enqueue_lane_test: ptau_prepare.hip and ptau_contribute.hip send their sections through it too;
+// ptau_verify.hip still launches the two kernels from a lambda of its own), and the gather of the odd elements of section 12's block k + 1 (NO_FAULT and the text of a faulting element are
 // prover_internal.h's).  The kernels are in an unnamed namespace, so every translation unit that includes this compiles its own copy
 // of them — include it where they are launched, nowhere else; the host procedure is one text.
 #pragma once
@@ -39,6 +40,13 @@ __global__ __launch_bounds__(64) void ptau_g2_kernel(const fe2* __restrict__ pts
   const fe2 p[2] = {pts[2 * (size_t)i], pts[2 * (size_t)i + 1]};
   const int kind = p29::classify_g2(p);
   if (kind) atomicMin(first, (unsigned long long)i << 3 | (unsigned long long)kind);
+}
+// the lane test of n uploaded points (g2: 128-byte points, with the subgroup test) enqueued on `stream`; *d_first was set to NO_FAULT
+inline int enqueue_lane_test(hipStream_t stream, bool g2, const uint8_t* d_pts, uint64_t n, unsigned long long* d_first)
+{
+  if (g2) DEV_LAUNCH("ptau membership kernel launch", ptau_g2_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), stream, (const fe2*)d_pts, (uint32_t)n, d_first);
+  else DEV_LAUNCH("ptau membership kernel launch", ptau_g1_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), stream, (const fe*)d_pts, (uint32_t)n, d_first);
+  return 0;
 }
 #endif
 
@@ -101,10 +109,7 @@ inline int PtauRanges::stage(const isnark::prover::PtauLayout& PL, uint32_t log_
     d_blk[i] = session.buf.alloc<uint8_t>((size_t)(cnt * elem));
     if (!d_blk[i]) return isnark::prover::dev_fail("hipMalloc", hipErrorOutOfMemory);
     if (int rc = isnark::prover::timed_upload(dev, d_blk[i], src, (size_t)(cnt * elem), upload_ms)) return rc;
-    if (elem == 64)
-      DEV_LAUNCH("ptau membership kernel launch", ptau_g1_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), stream_g1, (const fe*)d_blk[i], (uint32_t)cnt, d_first + i);
-    else
-      DEV_LAUNCH("ptau membership kernel launch", ptau_g2_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), stream_g2, (const fe2*)d_blk[i], (uint32_t)cnt, d_first + i);
+    if (int rc = enqueue_lane_test(elem == 64 ? stream_g1 : stream_g2, elem == 128, d_blk[i], cnt, d_first + i)) return rc;
   }
   return 0;
 }

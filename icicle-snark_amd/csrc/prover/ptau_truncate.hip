@@ -8,10 +8,10 @@
 //   device       (prepared, p < P) Q = element 2^(p+1) − 1 of section 2 goes through classify_g1 on the host, which builds its table;
 //                section 12's block p + 1 and the tables go up — nothing else does — and the block through the same lane test
 //                (ptau_g1_kernel's, with a tally): the verdict is read before any arithmetic and before anything is written.  Then ONE launch of pt_fix_kernel, a lane per element j of the block:
-//                  B′_j = B_j − s_j·Q,  s_j = ω′^j/2^(p+1) from two small tables (ptau_contribute29.h's split),
-//                Q's table of 816 signed-window multiples staged in LDS (52 224 bytes a workgroup of 256 lanes: three a CU), at most
-//                51 mixed additions for s_j·Q and one for B_j, no doubling.  batch_to_affine_kernel and affine_to_mont_kernel
-//                (msm_impl.h's) put the block back in the file's form, the identity all zero.
+//                  B′_j = B_j − s_j·Q,  s_j = ω′^j/2^(p+1) from two small tables (ptau_contribute29.h's split, built by device_call.h's
+//                split_power_tables), Q's table of 816 signed-window multiples staged in LDS (52 224 bytes a workgroup of 256 lanes:
+//                three a CU), at most 51 mixed additions for s_j·Q and one for B_j, no doubling.  point_form.h's to_file_form puts
+//                the block back in the file's form, the identity all zero.
 //   host, last   the container in the input's order, the block down into its place.
 //   The COPIED PREFIXES ARE NOT TESTED: they are bytes of the input, and groth16_ptau_verify judges a file.  Q the identity (no
 //   honest file has one): nothing to subtract, the block is copied and no device is opened.
@@ -20,10 +20,10 @@
 #include <string>
 #include <vector>
 
-#include "../msm_impl.h"
 #include "../workers.h"
 #include "device_call.h"
 #include "pack_device.h"
+#include "point_form.h"
 #include "prover_internal.h"
 #include "ptau_truncate29.h"
 #include "verify_batch.h"
@@ -41,9 +41,10 @@ constexpr uint32_t PT_GRID_MAX = 3072; // 256 CUs × 3 resident workgroups × 4:
 
 typedef pv::PackTally Tally;
 using pv::NO_FAULT;
-using pv::POINT_FAULT;
 
-// the lane test of the ranges that went up: pts[i], i < cnt, through classify_g1; the lowest faulty element and their number
+// the lane test of the ranges that went up: pts[i], i < cnt, through classify_g1; the lowest faulty element and their number.
+// This is ptau_ranges.h's ptau_g1_kernel plus the count the report's fault_count needs: that kernel is compiled into five objects
+// and is not to change for one caller's count, so the test with a tally stays a kernel of this file.
 __global__ __launch_bounds__(PT_WG) void pt_test_kernel(const fe* __restrict__ pts, uint64_t cnt, Tally* __restrict__ tally)
 {
   const uint64_t i = (uint64_t)blockIdx.x * PT_WG + threadIdx.x;
@@ -123,15 +124,11 @@ int fix_on_device(int dev, uint32_t p, Fix& fx, Groth16PtauTruncateReport* rep, 
   const size_t n_lo = (size_t)1 << kbits, n_hi = (size_t)1 << (p + 1 - kbits);
   std::vector<fe> tables(n_lo + n_hi);
   {
-    bn254_scalar_t rou;
-    if (bn254_get_root_of_unity(n, &rou) != ICICLE_SUCCESS) return pv::fail(pv::ERR_ARG, "ptau: no root of unity of order 2^%u", p + 1);
     fe w, order = Fr::zero();
-    memcpy(w.l, &rou, 32);
+    if (int rc = pv::root_of_unity(p + 1, &w)) return rc;
     order.l[0] = (uint32_t)n; // n ≤ 2^27
-    const fe one_m = Fr::to_mont(Fr::one_std()), w_m = Fr::to_mont(w), step_m = pc29::pc_pow(w_m, n_lo), ninv_m = Fr::inv(Fr::to_mont(order));
-    fe* const t = tables.data();
-    isnark::run_ranges(n_lo, 1024, [&](int, size_t lo, size_t hi) { pc29::pc_fill_powers(w_m, one_m, lo, hi, t); });
-    isnark::run_ranges(n_hi, 1024, [&](int, size_t lo, size_t hi) { pc29::pc_fill_powers(step_m, ninv_m, lo, hi, t + n_lo); });
+    const fe ninv_m = Fr::inv(Fr::to_mont(order));
+    pv::split_power_tables(Fr::to_mont(w), kbits, n_hi, &ninv_m, 1, tables.data());
   }
   std::vector<G1::A> qtab(pt29::PT_TABLE_POINTS);
   G1::A q;
@@ -140,8 +137,8 @@ int fix_on_device(int dev, uint32_t p, Fix& fx, Groth16PtauTruncateReport* rep, 
     // Q through the same lane test on the host, before the host's own arithmetic reads it: a faulty Q is reported before the block
     const fe w[2] = {q.x, q.y};
     if (const int kind = p29::classify_g1(w)) {
-      rep->fault_section = 2, rep->fault_index = n - 1, rep->fault_kind = kind, rep->fault_count = 1;
-      return pv::fail(pv::ERR_FORMAT, "ptau: section 2, element %llu: %s", (unsigned long long)(n - 1), POINT_FAULT[kind & 3]);
+      pv::set_point_fault(rep, 2, n - 1, kind), rep->fault_count = 1;
+      return pv::ptau_point_fail(2, n - 1, kind);
     }
   }
   {
@@ -153,7 +150,7 @@ int fix_on_device(int dev, uint32_t p, Fix& fx, Groth16PtauTruncateReport* rep, 
 
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   uint8_t* const d_blk = ds.buf.alloc<uint8_t>((size_t)(n * sizeof(G1::A))); // the block, then the result
   uint8_t* const d_proj = ds.buf.alloc<uint8_t>((size_t)(n * sizeof(G1::P)));
@@ -173,21 +170,16 @@ int fix_on_device(int dev, uint32_t p, Fix& fx, Groth16PtauTruncateReport* rep, 
   DEV_TRY("lane tests", hipStreamSynchronize(st));
   trace.lap("block up, lane tests");
   if (tally.first != NO_FAULT) {
-    const uint64_t e = tally.first >> 3;
+    const uint64_t e = n - 1 + (tally.first >> 3); // block p + 1 begins at element 2^(p+1) − 1 of section 12
     const int kind = (int)(tally.first & 7);
-    rep->fault_section = 12;
-    rep->fault_index = n - 1 + e; // block p + 1 begins at element 2^(p+1) − 1 of section 12
-    rep->fault_kind = kind, rep->fault_count = tally.count;
-    return pv::fail(pv::ERR_FORMAT, "ptau: section %d, element %llu: %s", rep->fault_section, (unsigned long long)rep->fault_index, POINT_FAULT[kind & 3]);
+    pv::set_point_fault(rep, 12, e, kind), rep->fault_count = tally.count;
+    return pv::ptau_point_fail(12, e, kind);
   }
 
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + PT_WG - 1) / PT_WG, PT_GRID_MAX);
   DEV_LAUNCH("fix kernel launch", pt_fix_kernel, dim3(grid), dim3(PT_WG), st, (const G1::A*)d_blk, n, (const uint4*)d_qtab, (const fe*)d_tables, (const fe*)(d_tables + n_lo), kbits,
              (G1::P*)d_proj);
-  const int chunk = 32;
-  const uint64_t threads = (n + chunk - 1) / chunk, ncoord = 2 * n;
-  DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<G1, FqOps>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st, (const G1::P*)d_proj, n, chunk, (G1::A*)d_blk, d_scratch);
-  DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<G1::A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), st, (G1::A*)d_blk, ncoord);
+  if (int rc = pv::to_file_form<G1>(st, (const G1::P*)d_proj, n, (G1::A*)d_blk, d_scratch)) return rc;
   const auto t_place = std::chrono::steady_clock::now();
   place();
   const double place_ms = pv::ms_since(t_place);

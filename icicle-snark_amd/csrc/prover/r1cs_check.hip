@@ -183,7 +183,7 @@ int r1cs_load_impl(const uint8_t* data, size_t len, const char* device, Groth16R
 
   const auto t_dev = std::chrono::steady_clock::now();
   isnark::vb::DeviceSession ds;
-  if (ds.open(dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 0)) return rc;
   std::unique_ptr<Groth16R1cs> h(new Groth16R1cs); // (destroyed before the session: declared after it)
   h->dev = dev;
   h->n_wires = L.n_wires;
@@ -255,7 +255,7 @@ int witness_check_impl(Groth16R1cs* h, const uint8_t* wtns, size_t wtns_len, Gro
   std::lock_guard<std::mutex> lk(h->mu);
   const auto t_dev = std::chrono::steady_clock::now();
   isnark::vb::DeviceSession ds;
-  if (ds.open(h->dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, h->dev, 0)) return rc;
   if (int rc = reset_tally(h)) return rc;
   if (int rc = pv::timed_upload(h->dev, h->d_w, w.values, (size_t)h->n_wires * 32, &rep->upload_ms)) return rc;
   return check_resident_values(h, rep, t_dev);
@@ -295,7 +295,7 @@ int witness_check_packed_impl(Groth16R1cs* h, const uint8_t* wtnz, size_t len, G
   std::lock_guard<std::mutex> lk(h->mu);
   const auto t_dev = std::chrono::steady_clock::now();
   isnark::vb::DeviceSession ds;
-  if (ds.open(h->dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, h->dev, 0)) return rc;
   if (int rc = reset_tally(h)) return rc;
   uint8_t* d_buf = ds.buf.alloc<uint8_t>(pv::wtnz_device_bytes(L)); // this call's: freed with the session
   if (!d_buf) return dev_fail("hipMalloc", hipErrorOutOfMemory);
@@ -331,7 +331,7 @@ int match_zkey_impl(Groth16R1cs* h, const uint8_t* zkey, size_t len, const uint8
   std::lock_guard<std::mutex> lk(h->mu);
   const auto t_dev = std::chrono::steady_clock::now();
   isnark::vb::DeviceSession ds;
-  if (ds.open(h->dev, 0)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, h->dev, 0)) return rc;
   const uint32_t n = L.domain, m = h->m;
   uint32_t* d_rec = ds.buf.alloc<uint32_t>((size_t)L.n_coef * 11);
   uint32_t* k_rowptr = ds.buf.alloc<uint32_t>(2 * (size_t)n + 1);

@@ -270,7 +270,7 @@ int unpack_device_impl(const uint8_t* data, size_t len, const char* device, Grot
   if (L.n_witness) {
     const auto t_dev = std::chrono::steady_clock::now();
     vb::DeviceSession ds;
-    if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+    if (int rc = pv::open_session(ds, dev, 1)) return rc;
     uint8_t* d_buf = ds.buf.alloc<uint8_t>(pv::wtnz_device_bytes(L));
     fe* d_out = ds.buf.alloc<fe>(L.n_witness);
     if (!d_buf || !d_out) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);

@@ -117,7 +117,7 @@ struct Check {
 
   int open()
   {
-    if (ds.open(dev, 2)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+    if (int rc = pv::open_session(ds, dev, 2)) return rc;
     const uint64_t longest = std::max<uint64_t>(std::max<uint64_t>(L.n_vars, L.domain), L.n_coef);
     const size_t ring_bytes = (size_t)std::min<uint64_t>(slice, longest) * 64;
     d_tally = ds.buf.alloc<Tally>(1);

@@ -3,12 +3,13 @@
 //
 //   host, first  the container (zkey_layout), section 10's bounds and hash chain, the output's size against the room, the header's δ₁
 //                and δ₂ through the key check's lane tests; δ′, the nonce k and the record — three G1 and one G2 scalar
-//                multiplications by zkey_contribute29.h's zc_mul_affine, the text the kernel runs.
+//                multiplications by zkey_contribute29.h's zc_mul_affine, the text the kernel runs.  transcript.h has the hashes,
+//                the record walk and the proof of knowledge, one text with groth16_ptau_contribute's.
 //   device       sections 8 and 9 go up into one array; zc_scale_g1_kernel, one lane per point: the lane test (classify_g1: a hostile
 //                file does not reach the lazy arithmetic), then δ′⁻¹·P by zc_scale with the digit masks of δ′⁻¹ in the kernel's
 //                argument struct — the same scalar in every lane: no divergence, nothing per lane but the point.  A faulty point is the
-//                rare branch: its lane alone counts itself and takes the minimum of (index, kind).  Then batch_to_affine_kernel and
-//                affine_to_mont_kernel (msm_impl.h's), the identity kept as zeros, and down into the output's sections 8 and 9.
+//                rare branch: its lane alone counts itself and takes the minimum of (index, kind) (pack_device.h's tally).  Then
+//                point_form.h's to_file_form, the identity kept as zeros, and down into the output's sections 8 and 9.
 //   host, beside the sections no contribution changes are copied while the kernels run; nothing of the output is final before the tally says
 //                that no point was at fault (the _file entry unlinks its temporary otherwise).
 #include <algorithm>
@@ -17,17 +18,16 @@
 #include <string>
 #include <vector>
 
-#include "../msm_impl.h"
 #include "../workers.h"
 #include "device_call.h"
+#include "pack_device.h"
+#include "point_form.h"
 #include "prover_internal.h"
-#include "sha256.h"
+#include "transcript.h"
 #include "verify_batch.h"
-#include "zkey_check29.h"
-#include "zkey_contribute29.h"
 
 using namespace bn254;
-using bn254::zc29::ZcDigits;
+using namespace isnark::transcript;
 
 namespace {
 
@@ -36,31 +36,24 @@ namespace vb = isnark::vb;
 
 constexpr int SCALE_WG = 64;
 using pv::NO_FAULT;
+using pv::POINT_FAULT;
 const char TAG[] = "icicle-snark zkey contribution v1";
 constexpr size_t TAG_LEN = sizeof TAG - 1;
 constexpr size_t HEADER_FIXED = 468;                       // section 2 up to and including γ₂
 constexpr size_t DELTA1_OFF = 468, DELTA2_OFF = 532;       // in section 2's payload
-constexpr size_t RECORD_FIXED = 64 + 64 + 32 + 4;
-constexpr uint32_t NAME_BYTES_MAX = 255;
-const char* const FAULT_TEXT[4] = {"", "a coordinate is not below q", "the point is not on the curve", "the point is outside the subgroup"};
-
-struct Tally {
-  unsigned long long count, first; // faulty points; min over them of (index << 3 | kind), index over sections 8 | 9
-};
+// a record: after1, the commitment, the response, the name
+constexpr size_t AFTER1 = 0, COMMITMENT = 64, RESPONSE = 128, NAME_LEN = 160, RECORD_FIXED = 164;
 
 // One lane per point of sections 8 | 9 (pts[i], i < n): δ′⁻¹·P as Montgomery projective, the identity (0, 1, 0).  A lane whose point
-// fails the lane test writes the identity and tallies itself: nothing of such a run is used.
-__global__ __launch_bounds__(SCALE_WG) void zc_scale_g1_kernel(const G1::A* __restrict__ pts, uint64_t n, ZcDigits digits, G1::P* __restrict__ out, Tally* __restrict__ t)
+// fails the lane test writes the identity and tallies itself (t->first: index over sections 8 | 9): nothing of such a run is used.
+__global__ __launch_bounds__(SCALE_WG) void zc_scale_g1_kernel(const G1::A* __restrict__ pts, uint64_t n, ZcDigits digits, G1::P* __restrict__ out, pv::PackTally* __restrict__ t)
 {
   const uint64_t i = (uint64_t)blockIdx.x * SCALE_WG + threadIdx.x;
   if (i >= n) return;
   const G1::A p = pts[i];
   const fe words[2] = {p.x, p.y};
   const int kind = p29::classify_g1(words);
-  if (kind) {
-    atomicAdd(&t->count, 1ull);
-    atomicMin(&t->first, (unsigned long long)i << 3 | (unsigned long long)kind);
-  }
+  if (kind) pv::tally_fault(t, i, kind);
   if (kind || G1::aff_is_zero(p)) {
     out[i] = G1::p_zero();
     return;
@@ -68,69 +61,7 @@ __global__ __launch_bounds__(SCALE_WG) void zc_scale_g1_kernel(const G1::A* __re
   out[i] = G1::x_to_projective(G1L::x_store(zc29::zc_scale<G1L>(p, digits)));
 }
 
-// ---- scalars on the host: standard form, below r
-fe fr_mul(const fe& a, const fe& b) { return Fr::mul(Fr::to_mont(a), b); }
-fe fr_inv(const fe& a) { return Fr::from_mont(Fr::inv(Fr::to_mont(a))); }
-// a big-endian integer of `len` bytes mod r, by Horner's rule in additions
-fe fr_from_be(const uint8_t* b, size_t len)
-{
-  fe acc = Fr::zero();
-  for (size_t i = 0; i < len; i++) {
-    for (int k = 0; k < 8; k++) acc = Fr::dbl(acc);
-    fe d = Fr::zero();
-    d.l[0] = b[i];
-    acc = Fr::add(acc, d);
-  }
-  return acc;
-}
-// W(x) = SHA-256(x ‖ 0x00) ‖ SHA-256(x ‖ 0x01) as a 512-bit big-endian integer, mod r.  x is wiped: it holds the secret.
-fe wide_hash(std::vector<uint8_t>& x)
-{
-  uint8_t d[64];
-  x.push_back(0);
-  isnark::sha256(x.data(), x.size(), d);
-  x.back() = 1;
-  isnark::sha256(x.data(), x.size(), d + 32);
-  const fe v = fr_from_be(d, 64);
-  explicit_bzero(d, sizeof d);
-  explicit_bzero(x.data(), x.size());
-  return v;
-}
-void append(std::vector<uint8_t>& v, const void* p, size_t n) { v.insert(v.end(), (const uint8_t*)p, (const uint8_t*)p + n); }
-
-// ---- section 10
-struct Record {
-  const uint8_t *after1, *commitment, *z, *name;
-  uint32_t name_len;
-  size_t bytes() const { return RECORD_FIXED + name_len; }
-};
-// the records of section 10 (s10 null: no section, no records).  0, or 1 with *bad = the record that does not fit (0: the count);
-// recs holds the records before it.
-int walk_records(const pv::Section* s10, std::vector<Record>& recs, uint32_t* count, uint32_t* bad)
-{
-  recs.clear();
-  *count = 0, *bad = 0;
-  if (!s10) return 0;
-  if (s10->size < 4) return 1;
-  uint32_t n;
-  memcpy(&n, s10->p, 4);
-  if ((uint64_t)n * RECORD_FIXED > s10->size - 4) return 1; // (a hostile count sizes nothing)
-  *count = n;
-  uint64_t pos = 4;
-  for (uint32_t i = 0; i < n; i++) {
-    *bad = i + 1;
-    if (s10->size - pos < RECORD_FIXED) return 1;
-    Record r;
-    r.after1 = s10->p + pos, r.commitment = r.after1 + 64, r.z = r.after1 + 128;
-    memcpy(&r.name_len, r.after1 + 160, 4);
-    r.name = r.after1 + RECORD_FIXED;
-    if (r.name_len > NAME_BYTES_MAX || s10->size - pos - RECORD_FIXED < r.name_len) return 1;
-    recs.push_back(r);
-    pos += r.bytes();
-  }
-  *bad = n;
-  return pos == s10->size ? 0 : 1; // bytes behind the last record
-}
+// ---- section 10 (the scalars, the record walk and the proof of knowledge are transcript.h's; no section 10: no records)
 // h₀: what no contribution changes
 void chain_start(const pv::ZkeyLayout& L, uint8_t h[32])
 {
@@ -146,15 +77,10 @@ void chain_step(uint8_t h[32], const uint8_t* before1, const Record& r, fe* c)
   std::vector<uint8_t> m;
   append(m, h, 32);
   append(m, before1, 64);
-  append(m, r.after1, 64);
-  append(m, r.commitment, 64);
-  append(m, &r.name_len, 4);
-  append(m, r.name, r.name_len);
-  isnark::sha256(m.data(), m.size(), h);
-  uint8_t c16[16];
-  isnark::combined_coefficient_from_digest(h, c16);
-  *c = Fr::zero();
-  memcpy(c->l, c16, 16);
+  append(m, r.p + AFTER1, 64);
+  append(m, r.p + COMMITMENT, 64);
+  append(m, r.p + NAME_LEN, 4 + r.name_len);
+  hash_step(m, h, c);
 }
 
 // everything secret of one call; wiped on every way out (best effort: the compiler may have kept copies in registers or spills)
@@ -184,9 +110,9 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   const pv::Section* s10 = secs[10].count ? &secs[10] : nullptr;
   std::vector<Record> recs;
   uint32_t count, bad;
-  if (walk_records(s10, recs, &count, &bad)) return pv::fail(pv::ERR_FORMAT, "zkey: section 10 is malformed at record %u of %u", bad, count);
+  if (walk_records(s10, RECORD_FIXED, NAME_LEN, recs, &count, &bad)) return pv::fail(pv::ERR_FORMAT, "zkey: section 10 is malformed at record %u of %u", bad, count);
   const uint8_t* const hdr = L.sec[2]->p;
-  if (count && memcmp(recs.back().after1, hdr + DELTA1_OFF, 64) != 0) return pv::fail(pv::ERR_FORMAT, "zkey: section 10's last record is not the header's delta1");
+  if (count && memcmp(recs.back().p + AFTER1, hdr + DELTA1_OFF, 64) != 0) return pv::fail(pv::ERR_FORMAT, "zkey: section 10's last record is not the header's delta1");
 
   // the output's size, before anything else is done
   const std::vector<pv::SectionEntry> order = pv::sections_in_order(data);
@@ -201,17 +127,11 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   if (int rc = sink(total, &out)) return rc;
 
   // the header's δ₁ and δ₂: the lane tests, and neither the identity
-  G1::A d1;
-  G2::A d2;
-  memcpy(&d1, hdr + DELTA1_OFF, 64);
-  memcpy(&d2, hdr + DELTA2_OFF, 128);
-  {
-    const fe w1[2] = {d1.x, d1.y};
-    const fe2 w2[2] = {d2.x, d2.y};
-    if (const int kind = p29::classify_g1(w1)) return pv::fail(pv::ERR_FORMAT, "zkey: the header's delta1: %s", FAULT_TEXT[kind & 3]);
-    if (const int kind = p29::classify_g2(w2)) return pv::fail(pv::ERR_FORMAT, "zkey: the header's delta2: %s", FAULT_TEXT[kind & 3]);
-    if (G1::aff_is_zero(d1) || G2::aff_is_zero(d2)) return pv::fail(pv::ERR_FORMAT, "zkey: the header's delta is the identity");
-  }
+  const G1::A d1 = point_at<G1::A>(hdr + DELTA1_OFF);
+  const G2::A d2 = point_at<G2::A>(hdr + DELTA2_OFF);
+  if (const int kind = classify(d1)) return pv::fail(pv::ERR_FORMAT, "zkey: the header's delta1: %s", POINT_FAULT[kind & 3]);
+  if (const int kind = classify(d2)) return pv::fail(pv::ERR_FORMAT, "zkey: the header's delta2: %s", POINT_FAULT[kind & 3]);
+  if (G1::aff_is_zero(d1) || G2::aff_is_zero(d2)) return pv::fail(pv::ERR_FORMAT, "zkey: the header's delta is the identity");
 
   // ---- δ′, the nonce, the record
   Secrets S;
@@ -234,7 +154,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   const G1::A g1 = vb::g1_generator_mont();
   for (uint32_t i = 0; i < count; i++) {
     fe c;
-    chain_step(h, i ? recs[i - 1].after1 : (const uint8_t*)&g1, recs[i], &c);
+    chain_step(h, i ? recs[i - 1].p + AFTER1 : (const uint8_t*)&g1, recs[i], &c);
   }
   {
     std::vector<uint8_t> m;
@@ -251,15 +171,15 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   {
     const uint32_t nl = (uint32_t)name_len;
     uint8_t* const b = record.data();
-    memcpy(b, &after1, 64);
-    memcpy(b + 64, &commitment, 64);
-    memcpy(b + 160, &nl, 4);
+    memcpy(b + AFTER1, &after1, 64);
+    memcpy(b + COMMITMENT, &commitment, 64);
+    memcpy(b + NAME_LEN, &nl, 4);
     memcpy(b + RECORD_FIXED, name, name_len);
-    const Record r = {b, b + 64, b + 128, b + RECORD_FIXED, nl};
+    const Record r = {b, nl};
     fe c;
     chain_step(h, hdr + DELTA1_OFF, r, &c);
-    const fe z = Fr::add(S.k, fr_mul(c, S.delta));
-    memcpy(b + 128, z.l, 32);
+    const fe z = schnorr_response(S.k, c, S.delta);
+    memcpy(b + RESPONSE, z.l, 32);
   }
 
   pv::StageTrace trace("zkey-contribute", "ICICLE_SNARK_TRACE_ZKEY_CONTRIBUTE");
@@ -269,27 +189,23 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   if (n > 0xffffffffull) return pv::fail(pv::ERR_ARG, "sections 8 and 9 hold more than 2^32 points");
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   const size_t cnt = (size_t)std::max<uint64_t>(n, 1);
   G1::A* d_in = ds.buf.alloc<G1::A>(cnt);
   G1::P* d_p = ds.buf.alloc<G1::P>(cnt);
   G1::A* d_a = ds.buf.alloc<G1::A>(cnt);
   fe* d_s = ds.buf.alloc<fe>(cnt);
-  Tally* d_tally = ds.buf.alloc<Tally>(1);
+  pv::PackTally* d_tally = ds.buf.alloc<pv::PackTally>(1);
   if (!d_in || !d_p || !d_a || !d_s || !d_tally) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-  Tally tally = {0, NO_FAULT};
-  DEV_TRY("upload", hipMemcpyAsync(d_tally, &tally, sizeof tally, hipMemcpyHostToDevice, st));
-  DEV_TRY("upload", hipStreamSynchronize(st)); // (`tally` is pageable: the copy has read it)
+  pv::PackTally tally; // (lives until the call's own synchronisation)
+  if (int rc = pv::reset_tallies(&tally, d_tally, 1, st)) return rc;
   if (int rc = pv::timed_upload(dev, d_in, L.sec[8]->p, (size_t)n8 * 64, &rep->upload_ms)) return rc;
   if (int rc = pv::timed_upload(dev, d_in + n8, L.sec[9]->p, (size_t)n9 * 64, &rep->upload_ms)) return rc;
   trace.lap("sections 8, 9 uploaded");
   if (n) {
-    const int chunk = 32;
-    const uint64_t threads = (n + chunk - 1) / chunk;
     DEV_LAUNCH("scale kernel launch", zc_scale_g1_kernel, dim3((uint32_t)((n + SCALE_WG - 1) / SCALE_WG)), dim3(SCALE_WG), st, d_in, n, S.digits, d_p, d_tally);
-    DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<G1, FqOps>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st, d_p, n, chunk, d_a, d_s);
-    DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<G1::A>), dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), st, d_a, 2 * n);
+    if (int rc = pv::to_file_form<G1>(st, d_p, n, d_a, d_s)) return rc;
   }
   DEV_TRY("download", hipMemcpyAsync(&tally, d_tally, sizeof tally, hipMemcpyDeviceToHost, st));
 
@@ -332,10 +248,8 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   rep->faults = tally.count;
   if (tally.first != NO_FAULT) {
     const uint64_t i = tally.first >> 3;
-    rep->fault_kind = (int32_t)(tally.first & 7);
-    rep->fault_section = i < n8 ? 8 : 9;
-    rep->fault_index = i < n8 ? i : i - n8;
-    return pv::fail(pv::ERR_FORMAT, "zkey: section %d, element %llu: %s (%llu points at fault)", rep->fault_section, (unsigned long long)rep->fault_index, FAULT_TEXT[rep->fault_kind & 3],
+    pv::set_point_fault(rep, i < n8 ? 8 : 9, i < n8 ? i : i - n8, (int)(tally.first & 7));
+    return pv::fail(pv::ERR_FORMAT, "zkey: section %d, element %llu: %s (%llu points at fault)", rep->fault_section, (unsigned long long)rep->fault_index, POINT_FAULT[rep->fault_kind & 3],
                     (unsigned long long)tally.count);
   }
   const auto t_down = std::chrono::steady_clock::now();
@@ -344,22 +258,6 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   rep->download_ms = pv::ms_since(t_down);
   trace.lap("sections 8, 9 downloaded");
   return 0;
-}
-
-// a Montgomery-form header point as the host pairing takes it
-bn254_affine_t std_affine(const G1::A& a)
-{
-  const G1::A s = {Fq::from_mont(a.x), Fq::from_mont(a.y)};
-  bn254_affine_t p;
-  memcpy(&p, &s, sizeof p);
-  return p;
-}
-bn254_g2_affine_t std_affine(const G2::A& a)
-{
-  const G2::A s = {Fq2Ops::from_mont(a.x), Fq2Ops::from_mont(a.y)};
-  bn254_g2_affine_t p;
-  memcpy(&p, &s, sizeof p);
-  return p;
 }
 
 } // namespace
@@ -392,11 +290,11 @@ ISNARK_API int groth16_zkey_contributions(const void* zkey, size_t len, Groth16C
   if (secs[10].count > 1) return fault(GROTH16_CONTRIB_SECTION, 0);
   std::vector<Record> recs;
   uint32_t bad;
-  const int malformed = walk_records(secs[10].count ? &secs[10] : nullptr, recs, &report->count, &bad);
+  const int malformed = walk_records(secs[10].count ? &secs[10] : nullptr, RECORD_FIXED, NAME_LEN, recs, &report->count, &bad);
   for (size_t i = 0; infos && i < recs.size() && i < infos_cap; i++) {
-    memcpy(infos[i].after1, recs[i].after1, 64);
+    memcpy(infos[i].after1, recs[i].p + AFTER1, 64);
     memset(infos[i].name, 0, sizeof infos[i].name);
-    memcpy(infos[i].name, recs[i].name, recs[i].name_len);
+    memcpy(infos[i].name, recs[i].p + RECORD_FIXED, recs[i].name_len);
   }
   if (malformed) return fault(GROTH16_CONTRIB_SECTION, bad);
 
@@ -407,30 +305,19 @@ ISNARK_API int groth16_zkey_contributions(const void* zkey, size_t len, Groth16C
   G1::A before = g1;
   for (uint32_t i = 0; i < report->count; i++) {
     const Record& r = recs[i];
-    G1::A after, commitment;
+    const G1::A after = point_at<G1::A>(r.p + AFTER1), commitment = point_at<G1::A>(r.p + COMMITMENT);
     fe z;
-    memcpy(&after, r.after1, 64);
-    memcpy(&commitment, r.commitment, 64);
-    memcpy(z.l, r.z, 32);
-    const fe wa[2] = {after.x, after.y}, wc[2] = {commitment.x, commitment.y};
-    if (p29::classify_g1(wa) || p29::classify_g1(wc) || G1::aff_is_zero(after)) return fault(GROTH16_CONTRIB_POINT, i + 1);
+    memcpy(z.l, r.p + RESPONSE, 32);
+    if (classify(after) || classify(commitment) || G1::aff_is_zero(after)) return fault(GROTH16_CONTRIB_POINT, i + 1);
     fe c;
     chain_step(h, (const uint8_t*)&before, r, &c);
-    if (!Fr::is_canonical(z)) return fault(GROTH16_CONTRIB_POK, i + 1);
-    // z·before1 = R + c·after1, compared in the file's canonical affine form
-    const G1::A lhs = zc29::zc_mul_affine<G1, G1L>(before, z);
-    G1L::X acc = zc29::zc_scale<G1L>(after, zc29::zc_recode(c));
-    if (!G1::aff_is_zero(commitment)) G1L::x_madd(acc, G1L::load_affine(commitment, G1L::MONT256, false));
-    const G1::A rhs = G1::p_to_affine(G1::x_to_projective(G1L::x_store(acc)));
-    if (memcmp(&lhs, &rhs, sizeof lhs) != 0) return fault(GROTH16_CONTRIB_POK, i + 1);
+    if (!pok_holds(before, after, commitment, z, zc29::zc_recode(c))) return fault(GROTH16_CONTRIB_POK, i + 1);
     before = after;
   }
   if (memcmp(&before, hdr + DELTA1_OFF, 64) != 0) return fault(GROTH16_CONTRIB_HEADER, 0);
   // e(δ₁, G₂) = e(G₁, δ₂); δ₁ is a point that has passed the lane test (or G₁), δ₂ gets its own
-  G2::A d2;
-  memcpy(&d2, hdr + DELTA2_OFF, 128);
-  const fe2 w2[2] = {d2.x, d2.y};
-  if (p29::classify_g2(w2) || G2::aff_is_zero(d2)) return fault(GROTH16_CONTRIB_PAIR, 0);
+  const G2::A d2 = point_at<G2::A>(hdr + DELTA2_OFF);
+  if (classify(d2) || G2::aff_is_zero(d2)) return fault(GROTH16_CONTRIB_PAIR, 0);
   if (!vb::pairing_eq(std_affine(before), vb::g2_generator_affine(), vb::g1_generator_affine(), std_affine(d2))) return fault(GROTH16_CONTRIB_PAIR, 0);
   return 1;
 }

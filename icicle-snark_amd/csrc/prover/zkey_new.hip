@@ -14,8 +14,8 @@
 //               zkey_new29.h's zn_walk in lazy XYZZ registers.  A column of more than heavy_column_terms terms is left out: the
 //               plan kernel has cut it into items of that many terms, zn_item_kernel sums an item with one workgroup (each lane a
 //               slice, then an LDS tree of x_add), and zn_combine_kernel adds a column's items the same way.
-//   output      projective sums → batch_to_affine_kernel → affine_to_mont_kernel (msm_impl.h's), the identity kept as zeros, and
-//               down into the caller's buffer or the mapped output file through the pinned staging.
+//   output      projective sums → point_form.h's to_file_form (G2's on the second stream), the identity kept as zeros, and down
+//               into the caller's buffer or the mapped output file through the pinned staging.
 #include <algorithm>
 #include <chrono>
 #include <functional>
@@ -23,9 +23,9 @@
 #include <string>
 #include <vector>
 
-#include "../msm_impl.h"
 #include "../workers.h"
 #include "device_call.h"
+#include "point_form.h"
 #include "prover_internal.h"
 #include "ptau_ranges.h"
 #include "verify_batch.h"
@@ -299,10 +299,10 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
     const int hdr_sec[2] = {4, 5};
     for (int sid : hdr_sec) {
       memcpy(p1, PL.sec[sid]->p, 64);
-      if (const int kind = p29::classify_g1(p1)) return pv::fail(pv::ERR_FORMAT, "ptau: section %d, element 0: %s", sid, POINT_FAULT[kind & 3]);
+      if (const int kind = p29::classify_g1(p1)) return pv::ptau_point_fail(sid, 0, kind);
     }
     memcpy(p2, PL.sec[6]->p, 128);
-    if (const int kind = p29::classify_g2(p2)) return pv::fail(pv::ERR_FORMAT, "ptau: section 6, element 0: %s", POINT_FAULT[kind & 3]);
+    if (const int kind = p29::classify_g2(p2)) return pv::ptau_point_fail(6, 0, kind);
   }
 
   pv::StageTrace trace("zkey-new", "ICICLE_SNARK_TRACE_ZKEY_NEW");
@@ -313,7 +313,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   std::lock_guard<std::mutex> lk(pv::r1cs_mutex(h));
   const auto t_dev = std::chrono::steady_clock::now();
   isnark::vb::DeviceSession ds;
-  if (ds.open(shape.dev, 2)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, shape.dev, 2)) return rc;
   const hipStream_t st = ds.stream(0), st2 = ds.stream(1);
   pv::Event ev_cols, ev_g2;
   if (int rc = ev_cols.create()) return rc;
@@ -429,23 +429,13 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
     DEV_LAUNCH("G2 item kernel launch", zn_item_g2_kernel, dim3(cnt.items[1]), dim3(ITEM_WG), st2, cols, d_items[1], l2, d_part2);
     DEV_LAUNCH("G2 combine kernel launch", (zn_combine_kernel<G2, G2L>), dim3(cnt.heavy[1]), dim3(ITEM_WG), st2, d_heavy[1], d_part2, d_p2);
   }
-  const int chunk = 32;
-  {
-    const uint64_t threads = ((uint64_t)m + chunk - 1) / chunk;
-    DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<G2, Fq2Ops>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st2, d_p2, (uint64_t)m, chunk, d_a2, d_s2);
-    const uint64_t ncoord = 4 * (uint64_t)m;
-    DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<G2::A>), dim3((uint32_t)((ncoord + 255) / 256)), dim3(256), st2, d_a2, ncoord);
-  }
+  if (int rc = pv::to_file_form<G2>(st2, d_p2, m, d_a2, d_s2)) return rc;
   DEV_LAUNCH("G1 column kernel launch", zn_g1_kernel, dim3((uint32_t)((G1_OUTPUTS * (uint64_t)m + 63) / 64)), dim3(64), st, cols, l1, al, bl, d_p1);
   if (cnt.heavy[0]) {
     DEV_LAUNCH("G1 item kernel launch", zn_item_g1_kernel, dim3(cnt.items[0]), dim3(ITEM_WG), st, cols, d_items[0], l1, al, bl, d_part1);
     DEV_LAUNCH("G1 combine kernel launch", (zn_combine_kernel<G1, G1L>), dim3(cnt.heavy[0]), dim3(ITEM_WG), st, d_heavy[0], d_part1, d_p1);
   }
-  {
-    const uint64_t pts = G1_OUTPUTS * (uint64_t)m, threads = (pts + chunk - 1) / chunk;
-    DEV_LAUNCH("batch_to_affine launch", (batch_to_affine_kernel<G1, FqOps>), dim3((uint32_t)((threads + 63) / 64)), dim3(64), st, d_p1, pts, chunk, d_a1, d_s1);
-    DEV_LAUNCH("affine_to_mont launch", (affine_to_mont_kernel<G1::A>), dim3((uint32_t)((2 * pts + 255) / 256)), dim3(256), st, d_a1, 2 * pts);
-  }
+  if (int rc = pv::to_file_form<G1>(st, d_p1, G1_OUTPUTS * (uint64_t)m, d_a1, d_s1)) return rc;
   if (int rc = ranges.gather_odd(st, n, d_odd)) return rc;
   DEV_TRY("G1 column kernels", hipStreamSynchronize(st));
   trace.lap("G1 kernels done");

@@ -314,7 +314,7 @@ int coefs_pack_impl(const void* records, uint64_t n, void* out, size_t cap, cons
   if (n > 0xffffffffull) return pv::fail(pv::ERR_ARG, "coefficients: %llu records in one call, 2^32 - 1 is the most", (unsigned long long)n);
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   Tally* const d_tally = ds.buf.alloc<Tally>(1);
   if (!d_tally) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
@@ -357,7 +357,7 @@ int coefs_unpack_impl(const void* body, size_t len, void* out, size_t cap, const
   if (!C.n_coef) return 0;
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   Tally* const d_tally = ds.buf.alloc<Tally>(1);
   uint8_t* const d_buf = ds.buf.alloc<uint8_t>(pv::zkez_coefs_device_bytes(C));
@@ -440,7 +440,7 @@ int file_impl(bool unpack, const uint8_t* data, size_t len, const char* device, 
   trace.lap("layout");
   const auto t_dev = std::chrono::steady_clock::now();
   vb::DeviceSession ds;
-  if (ds.open(dev, 1)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(ds, dev, 1)) return rc;
   const hipStream_t st = ds.stream(0);
   Tally tallies[COEF_TALLY + 1];
   Tally* const d_tally = ds.buf.alloc<Tally>(COEF_TALLY + 1);

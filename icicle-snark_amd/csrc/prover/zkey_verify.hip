@@ -183,7 +183,7 @@ int verify_impl(Groth16R1cs* h, const uint8_t* zkey, size_t zkey_len, const uint
   std::lock_guard<std::mutex> lk(pv::r1cs_mutex(h));
   const auto t_dev = std::chrono::steady_clock::now();
   Verify c(L, PL, h, k, zkey_file, ptau_file);
-  if (c.ds.open(shape.dev, 2)) return pv::fail(pv::ERR_DEVICE, "%s", groth16_verify_last_error());
+  if (int rc = pv::open_session(c.ds, shape.dev, 2)) return rc;
   const hipStream_t st = c.ds.stream(0);
 
   // rows: z^pub, z^priv, a | b | c at each, the eight scalar vectors
