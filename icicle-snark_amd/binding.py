@@ -737,6 +737,7 @@ groth16_r1cs_info groth16_r1cs_load groth16_r1cs_load_file groth16_r1cs_get_info
 groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
 groth16_ptau_info groth16_zkey_verify_ptau groth16_zkey_verify_ptau_file
 groth16_zkey_new_size groth16_zkey_new groth16_zkey_new_file
+groth16_setup_toxic_check groth16_setup groth16_setup_file
 groth16_zkey_contribute groth16_zkey_contribute_file groth16_zkey_contributions
 groth16_ptau_prepared_size groth16_ptau_prepare groth16_ptau_prepare_file
 groth16_ptau_new_size groth16_ptau_new groth16_ptau_new_file
@@ -1002,6 +1003,35 @@ class ZkeyNewReport(C.Structure):
                 ("upload_ms", C.c_double), ("device_ms", C.c_double), ("download_ms", C.c_double), ("write_ms", C.c_double)]
 
 
+class SetupOptions(C.Structure):
+    _fields_ = [("heavy_column_terms", C.c_uint32)]
+
+
+class SetupReport(C.Structure):
+    """Groth16SetupReport: ZkeyNewReport's fields, then the device time by stage"""
+    _fields_ = ZkeyNewReport._fields_ + [("lagrange_ms", C.c_double), ("columns_ms", C.c_double), ("g1_ms", C.c_double), ("g2_ms", C.c_double)]
+
+
+TOXIC_RANGE, TOXIC_ZERO, TOXIC_DOMAIN = 1, 2, 3
+R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+
+def toxic160(toxic):
+    """(τ, α, β, γ, δ) as ints → the 160 bytes groth16_setup takes (any value below 2^256 is representable: the library judges it)"""
+    toxic = tuple(toxic)
+    if len(toxic) != 5:
+        raise ValueError("toxic waste is (tau, alpha, beta, gamma, delta)")
+    return (C.c_uint8 * 160).from_buffer_copy(b"".join(int(x).to_bytes(32, "little") for x in toxic))
+
+
+def setup_toxic_check(toxic, domain_power: int) -> int:
+    """groth16_setup_toxic_check → 0, or TOXIC_RANGE / TOXIC_ZERO / TOXIC_DOMAIN; host only"""
+    rc = lib().groth16_setup_toxic_check(toxic160(toxic), C.c_uint32(domain_power))
+    if rc < 0:
+        _pcheck(rc, "setup_toxic_check")
+    return rc
+
+
 def _image(data):
     return data.ctypes.data_as(C.c_void_p) if isinstance(data, np.ndarray) else C.c_char_p(data) if isinstance(data, bytes) else (C.c_char * len(data)).from_buffer(data)
 
@@ -1114,6 +1144,24 @@ class R1cs:
             _pcheck(rc, "zkey_new")
         buf = C.create_string_buffer(rep.zkey_bytes)
         _pcheck(lib().groth16_zkey_new(self._h, _image(ptau), C.c_size_t(len(ptau)), buf, C.c_size_t(rep.zkey_bytes), C.byref(opt), C.byref(rep)), "zkey_new")
+        return buf.raw, rep
+
+    def setup(self, out=None, toxic=None, heavy_column_terms: int = 0):
+        """groth16_setup → (zkey bytes | None, SetupReport): this circuit's proving key made directly from toxic waste, no .ptau.
+        WHOEVER RAN THIS CALL CAN FORGE PROOFS FOR THE KEY: for development, CI, benchmarks and single-party deployments.  toxic:
+        (τ, α, β, γ, δ) as ints, for tests and reproducible benchmarks; None = the operating system's randomness.  out: a path the
+        key is written to (None comes back); None: the key comes back as bytes.  Raises ProverError (−2 faulty toxic waste)."""
+        opt, rep = SetupOptions(int(heavy_column_terms)), SetupReport()
+        tx = toxic160(toxic) if toxic is not None else None
+        if out is not None:
+            _pcheck(lib().groth16_setup_file(self._h, tx, os.fsencode(out), C.byref(opt), C.byref(rep)), "setup_file")
+            return None, rep
+        # sized by the library itself: a first call with no room reports the bytes it needs
+        rc = lib().groth16_setup(self._h, tx, None, C.c_size_t(0), C.byref(opt), C.byref(rep))
+        if rc != -3 or rep.zkey_bytes == 0:
+            _pcheck(rc, "setup")
+        buf = C.create_string_buffer(rep.zkey_bytes)
+        _pcheck(lib().groth16_setup(self._h, tx, buf, C.c_size_t(rep.zkey_bytes), C.byref(opt), C.byref(rep)), "setup")
         return buf.raw, rep
 
     def close(self):

@@ -13,6 +13,9 @@
 //   > zkey-verify --r1cs R --zkey Z --ptau P [--device HIP]   r1cs-match, then the point sections against circuit and ceremony (groth16_zkey_verify_ptau)
 //   > zkey-new --r1cs R --ptau P --zkey OUT [--device HIP]    the circuit's key over the ceremony before any contribution, gamma = delta = 1
 //     (groth16_zkey_new_file): one line with sizes and times, then ZKEY_WRITTEN
+//   > zkey-setup --r1cs R --zkey OUT [--vk VK] [--device HIP]    the circuit's key directly from fresh toxic waste of the operating
+//     system's (groth16_setup_file): one summary line, a line saying that this is a single-party key, then ZKEY_WRITTEN; --vk also
+//     writes the key's verification_key.json
 //   > zkey-contribute --zkey Z --out OUT [--name N] [--device HIP]    one phase-2 contribution with a secret from the operating system
 //     (groth16_zkey_contribute_file): one summary line, then ZKEY_WRITTEN
 //   > zkey-contributions --zkey Z             section 10's chain and the header's delta pair, on the host (groth16_zkey_contributions):
@@ -54,7 +57,7 @@
 
 static void print_help()
 {
-  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  ptau-truncate --ptau <file> --power <p> --out <file> [--device HIP]   (the file of a lower power; section 12's last block fixed up)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  zkey-pack --zkey <file> --out <file> [--device HIP]   (points as x and one bit of y, coefficients as a code byte and their significant bytes)\n  zkey-unpack --packed <file> --out <file> [--device HIP]   (the .zkey back, byte for byte)\n  prove-zkez --witness <file> --zkez <packed key> --proof <file> --public <file> [--device HIP]\n  exit\n";
+  std::cout << "Usage:\n  prove [--system groth16] --witness <file> --zkey <file> --proof <file> --public <file> --device <HIP>\n  verify [--system groth16] --proof <file> --public <file> --vk <file>\n  verify-batch --list <file> --vk <file> [--device HIP] [--combined]\n  zkey-check --zkey <file> [--device HIP]\n  zkey-export-vk --zkey <file> --vk <file>\n  wtns-check --r1cs <file> --wtns <file> [--device HIP]\n  r1cs-match --r1cs <file> --zkey <file> [--device HIP]\n  zkey-verify --r1cs <file> --zkey <file> --ptau <file> [--device HIP]\n  zkey-new --r1cs <file> --ptau <file> --zkey <file> [--device HIP]\n  zkey-setup --r1cs <file> --zkey <file> [--vk <file>] [--device HIP]   (a single-party key from the operating system's randomness: whoever runs it can forge proofs)\n  zkey-contribute --zkey <file> --out <file> [--name <text>] [--device HIP]   (the secret is the operating system's)\n  zkey-contributions --zkey <file>   (section 10's chain and the header's delta; that C and H follow delta2 is zkey-verify's)\n  ptau-prepare --ptau <file> --out <file> [--device HIP]   (sections 12 to 15 from 2 to 5: powersoftau prepare phase2)\n  ptau-new --power <P> --out <file>   (the starting file of a ceremony: tau = alpha = beta = 1)\n  ptau-contribute --ptau <file> --out <file> [--name <text>] [--device HIP]   (the secrets are the operating system's)\n  ptau-contributions --ptau <file>   (section 7's chain and the file's first elements; that the other powers follow is ptau-verify's)\n  ptau-verify --ptau <file> [--device HIP]   (the contributions, then every power against the others and sections 12 to 15 against 2 to 5)\n  ptau-pack --ptau <file> --out <file> [--device HIP]   (every point as x and one bit of y: half the bytes)\n  ptau-unpack --packed <file> --out <file> [--device HIP]   (the .ptau back, byte for byte; a root per point)\n  ptau-truncate --ptau <file> --power <p> --out <file> [--device HIP]   (the file of a lower power; section 12's last block fixed up)\n  wtns-pack --wtns <file> --out <file>   (a code byte per value and only its significant bytes; on the host)\n  wtns-unpack --packed <file> --out <file> [--device HIP]   (the .wtns back; without --device on the host)\n  prove-packed --witness <packed file> --zkey <file> --proof <file> --public <file> [--device HIP]\n  wtns-check --r1cs <file> --wtnz <packed file> [--device HIP]\n  zkey-pack --zkey <file> --out <file> [--device HIP]   (points as x and one bit of y, coefficients as a code byte and their significant bytes)\n  zkey-unpack --packed <file> --out <file> [--device HIP]   (the .zkey back, byte for byte)\n  prove-zkez --witness <file> --zkez <packed key> --proof <file> --public <file> [--device HIP]\n  exit\n";
 }
 
 int main()
@@ -370,6 +373,51 @@ int main()
                   << " longest column " << rep.longest_column << " heavy columns " << rep.heavy_columns << " in " << rep.heavy_items << " items; upload " << rep.upload_ms
                   << " ms device " << rep.device_ms << " ms download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
         std::cout << "ZKEY_WRITTEN" << std::endl;
+      }
+      groth16_r1cs_free(h);
+      std::cout << "COMMAND_COMPLETED" << std::endl;
+    } else if (cmd == "zkey-setup") {
+      // the toxic waste is the operating system's: none is taken from a command line
+      std::string r1cs = "circuit.r1cs", zkey = "circuit_final.zkey", vk, device = "HIP", a;
+      while (in >> a) {
+        if (a == "--r1cs") in >> r1cs;
+        else if (a == "--zkey") in >> zkey;
+        else if (a == "--vk") in >> vk;
+        else if (a == "--device") in >> device;
+        else print_help();
+      }
+      Groth16R1cs* h = nullptr;
+      int rc = groth16_r1cs_load_file(r1cs.c_str(), device.c_str(), &h);
+      Groth16SetupReport rep;
+      if (rc == 0) rc = groth16_setup_file(h, nullptr, zkey.c_str(), nullptr, &rep);
+      if (rc < 0) {
+        std::cerr << "zkey-setup failed (" << rc << "): " << groth16_last_error() << std::endl;
+      } else {
+        std::cout << "wires " << rep.n_vars << " public " << rep.n_public << " domain " << rep.domain << " coefficients " << rep.n_coeffs << " bytes " << rep.zkey_bytes
+                  << " longest column " << rep.longest_column << " heavy columns " << rep.heavy_columns << " in " << rep.heavy_items << " items; upload " << rep.upload_ms
+                  << " ms device " << rep.device_ms << " ms (lagrange " << rep.lagrange_ms << " columns " << rep.columns_ms << " G1 " << rep.g1_ms << " G2 " << rep.g2_ms
+                  << ") download " << rep.download_ms << " ms write " << rep.write_ms << " ms" << std::endl;
+        std::cout << "single-party key: whoever ran this command can forge proofs for it; a key for third parties comes from the ceremony chain" << std::endl;
+        bool vk_ok = true;
+        if (!vk.empty()) {
+          std::ifstream f(zkey, std::ios::binary);
+          std::ostringstream ss;
+          if (f) ss << f.rdbuf();
+          const std::string image = ss.str();
+          const int64_t need = f ? groth16_zkey_export_vk(image.data(), image.size(), nullptr, 0) : -1;
+          vk_ok = need >= 0;
+          if (vk_ok) {
+            std::string text((size_t)need, '\0');
+            (void)groth16_zkey_export_vk(image.data(), image.size(), &text[0], text.size());
+            text.resize((size_t)need - 1);
+            std::ofstream o(vk, std::ios::binary);
+            o << text;
+            vk_ok = (bool)o;
+          }
+          if (!vk_ok) std::cerr << "zkey-setup: cannot write " << vk << ": " << (need < 0 ? groth16_last_error() : "I/O") << std::endl;
+        }
+        std::cout << "ZKEY_WRITTEN" << std::endl;
+        if (!vk.empty() && vk_ok) std::cout << "VK_WRITTEN" << std::endl;
       }
       groth16_r1cs_free(h);
       std::cout << "COMMAND_COMPLETED" << std::endl;

@@ -2,11 +2,9 @@
 // (γ = δ = 1; what `snarkjs zkey new` writes, without its circuit hash).  include/groth16_prover.h has the contract and the file's
 // layout; DESIGN.md §7e.
 //
-//   transpose   the handle's rows become column lists, one per (matrix, wire): zn_count_kernel (one lane per row: an atomic per
-//               term on its column's counter; the public-binding rows nc … nc + npub count as terms of A), msm_sort.hip's scan, and
-//               zn_scatter_kernel with an atomic cursor per column.  The order inside a column is whatever the atomics gave: the
-//               sums do not depend on it, and the affine bytes that leave are canonical.  The same pass counts A's and B's terms
-//               per constraint; their scan places section 4's records, which zn_records_kernel writes.
+//   transpose   zkey_columns.h's transpose_rows (shared with groth16_setup): the handle's rows become column lists, one per
+//               (matrix, wire), and section 4's records are written.  The order inside a column is whatever the atomics gave: the
+//               sums do not depend on it, and the affine bytes that leave are canonical.
 //   ptau        block k of sections 12, 13, 14, 15 and block k + 1 of section 12 go up and through ptau_g1_kernel / ptau_g2_kernel
 //               (ptau_ranges.h's PtauRanges), as groth16_zkey_verify_ptau stages them; odd_gather_kernel makes section 9.
 //   columns     zn_g1_kernel: one lane per (output, wire) for A_s, B1_s and comb_s; zn_g2_kernel: one lane per wire for B2_s — a
@@ -29,40 +27,18 @@
 #include "prover_internal.h"
 #include "ptau_ranges.h"
 #include "verify_batch.h"
+#include "zkey_columns.h"
 #include "zkey_new29.h"
 
 using namespace bn254;
-using bn254::zn29::ZnEntry;
 using bn254::zn29::ZnList;
 
 namespace {
 
 namespace pv = isnark::prover;
 
-constexpr uint32_t DEFAULT_HEAVY_COLUMN_TERMS = 64; // the large-bucket rule's floor (msm_sort.hip): a starting point, not yet swept
-constexpr uint32_t MIN_HEAVY_COLUMN_TERMS = 8;
-constexpr int ITEM_WG = 64;                          // lanes of an item's / a heavy column's workgroup: one wave
-
-// what the kernels know of the transposed circuit: column (mat, s) is entries[colptr[mat·m + s] … colptr[mat·m + s + 1])
-struct Columns {
-  const uint32_t* colptr; // 3m + 1
-  const ZnEntry* entries;
-  const fe* vals;
-  uint32_t m, thr;
-};
 // G1 job o·m + s: o = 0 A_s, 1 B1_s, 2 comb_s; the G2 job s: B2_s
 enum { OUT_A = 0, OUT_B1 = 1, OUT_COMB = 2, G1_OUTPUTS = 3 };
-struct Counters {
-  uint32_t heavy[2], items[2]; // [0] G1, [1] G2
-  uint32_t longest;
-};
-struct Heavy {
-  uint32_t job, first, n_items;
-};
-struct Item {
-  uint32_t job, lo, hi;
-};
-
 __device__ __forceinline__ ZnList<G1L> list_of(const Columns& c, int mat, uint32_t s, const G1::A* bases)
 {
   const uint32_t lo = c.colptr[(size_t)mat * c.m + s];
@@ -94,65 +70,6 @@ __device__ __forceinline__ ZnList<G2L> g2_job(const Columns& c, uint32_t s, cons
 {
   const uint32_t lo = c.colptr[(size_t)c.m + s];
   return {c.entries + lo, c.colptr[(size_t)c.m + s + 1] - lo, l2};
-}
-
-// one lane per row ρ < 3·nc of the handle (ρ = 3j + matrix), then one per public-binding row
-__global__ __launch_bounds__(256) void zn_count_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, uint32_t nc, uint32_t m, uint32_t npub,
-                                                        uint32_t* __restrict__ counts, uint32_t* __restrict__ ab_terms)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint64_t rows = 3 * (uint64_t)nc;
-  if (i < rows) {
-    const uint32_t mat = (uint32_t)(i % 3);
-    for (uint32_t t = rowptr[i]; t < rowptr[i + 1]; t++) atomicAdd(&counts[(size_t)mat * m + cols[t]], 1u);
-    if (mat == 0) ab_terms[i / 3] = rowptr[i + 2] - rowptr[i];
-  } else if (i - rows <= npub) {
-    atomicAdd(&counts[i - rows], 1u);
-  }
-}
-__global__ __launch_bounds__(256) void zn_scatter_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, uint32_t nc, uint32_t m, uint32_t npub,
-                                                          const uint32_t* __restrict__ colptr, uint32_t* __restrict__ cursor, ZnEntry* __restrict__ entries)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint64_t rows = 3 * (uint64_t)nc;
-  if (i < rows) {
-    const uint32_t mat = (uint32_t)(i % 3), j = (uint32_t)(i / 3);
-    for (uint32_t t = rowptr[i]; t < rowptr[i + 1]; t++) {
-      const size_t col = (size_t)mat * m + cols[t];
-      entries[colptr[col] + atomicAdd(&cursor[col], 1u)] = {j, t};
-    }
-  } else if (i - rows <= npub) {
-    const uint32_t s = (uint32_t)(i - rows);
-    entries[colptr[s] + atomicAdd(&cursor[s], 1u)] = {nc + s, zn29::ZN_BINDING};
-  }
-}
-// section 4: record {matrix, row, wire, value·R² mod r} of A's and B's terms, constraint by constraint in the file's order
-// (rec_off[j] = the records before constraint j, rec_off[nc] = all of them), then the binding records (0, nc + s, s, 1)
-__global__ __launch_bounds__(256) void zn_records_kernel(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ cols, const fe* __restrict__ vals, uint32_t nc, uint32_t npub,
-                                                          const uint32_t* __restrict__ rec_off, uint32_t* __restrict__ rec)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  const uint64_t rows = 3 * (uint64_t)nc;
-  if (i < rows) {
-    const uint32_t mat = (uint32_t)(i % 3), j = (uint32_t)(i / 3);
-    if (mat == 2) return;
-    const uint32_t t0 = rowptr[i];
-    const size_t base = (size_t)rec_off[j] + (mat ? t0 - rowptr[i - 1] : 0u);
-    for (uint32_t t = t0; t < rowptr[i + 1]; t++) {
-      uint32_t* e = rec + (base + (t - t0)) * 11;
-      const fe v = Fr::to_mont(ld(vals + t)); // value·R in the handle, value·R² in the file
-      e[0] = mat, e[1] = j, e[2] = cols[t];
-#pragma unroll
-      for (int k = 0; k < 8; k++) e[3 + k] = v.l[k];
-    }
-  } else if (i - rows <= npub) {
-    const uint32_t s = (uint32_t)(i - rows);
-    uint32_t* e = rec + ((size_t)rec_off[nc] + s) * 11;
-    const fe v = Fr::r2();
-    e[0] = 0, e[1] = nc + s, e[2] = s;
-#pragma unroll
-    for (int k = 0; k < 8; k++) e[3 + k] = v.l[k];
-  }
 }
 
 // one lane per job: a job of more than thr terms is cut into items of thr terms.  heavy / items have room for every job that can
@@ -253,22 +170,6 @@ __global__ __launch_bounds__(ITEM_WG) void zn_combine_kernel(const Heavy* __rest
   if (threadIdx.x == 0) store_sum<C, CL>(out + h.job, sh[0]);
 }
 
-// byte offsets of the payloads in the file: sections 1 … 10 in this order, each behind its 12-byte {id, length}
-struct FileLayout {
-  uint64_t off[11], len[11], total;
-  FileLayout(uint64_t m, uint64_t npub, uint64_t n, uint64_t n_coeffs)
-  {
-    const uint64_t l[11] = {0, 4, 4 + 32 + 4 + 32 + 12 + 3 * 64 + 3 * 128, 64 * (npub + 1), 4 + pv::COEF_RECORD_BYTES * n_coeffs, 64 * m, 64 * m, 128 * m, 64 * (m - npub - 1), 64 * n, 4};
-    uint64_t pos = 12;
-    for (int s = 1; s <= 10; s++) {
-      len[s] = l[s];
-      off[s] = pos + 12;
-      pos += 12 + l[s];
-    }
-    total = pos;
-  }
-};
-
 // where the key goes, once its size is known: the caller's buffer, or the mapped temporary of the _file entry
 using pv::Sink;
 
@@ -307,8 +208,7 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
 
   pv::StageTrace trace("zkey-new", "ICICLE_SNARK_TRACE_ZKEY_NEW");
 
-  uint32_t thr = opt && opt->heavy_column_terms ? opt->heavy_column_terms : DEFAULT_HEAVY_COLUMN_TERMS;
-  thr = std::max(thr, MIN_HEAVY_COLUMN_TERMS);
+  const uint32_t thr = heavy_threshold(opt ? opt->heavy_column_terms : 0);
 
   std::lock_guard<std::mutex> lk(pv::r1cs_mutex(h));
   const auto t_dev = std::chrono::steady_clock::now();
@@ -326,42 +226,26 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   };
 
   // ---- transpose: column lists, and section 4's records
-  const uint32_t n_cols = 3 * m + 1;
   // a heavy job has more than thr terms and the jobs of a group share at most 2·n_entries (G1) / n_entries (G2) of them
   const uint64_t cap_heavy[2] = {2 * n_entries / thr + 1, n_entries / thr + 1};
   const uint64_t cap_items[2] = {2 * cap_heavy[0] + 1, 2 * cap_heavy[1] + 1};
-  uint32_t *d_counts, *d_colptr, *d_ab, *d_recoff, *d_scan, *d_rec;
-  ZnEntry* d_entries;
+  Transposed T;
   Counters* d_cnt;
   PtauRanges ranges;
   Heavy* d_heavy[2];
   Item* d_items[2];
-  alloc(&d_counts, n_cols);
-  alloc(&d_colptr, n_cols);
-  alloc(&d_ab, (size_t)nc + 1);
-  alloc(&d_recoff, (size_t)nc + 1);
-  alloc(&d_scan, std::max(isnark::exclusive_scan_u32_scratch_words(n_cols), isnark::exclusive_scan_u32_scratch_words(nc + 1)));
-  alloc(&d_rec, (size_t)n_entries * 11);
-  alloc(&d_entries, (size_t)n_entries);
   alloc(&d_cnt, 1);
   for (int g = 0; g < 2; g++) {
     alloc(&d_heavy[g], (size_t)cap_heavy[g]);
     alloc(&d_items[g], (size_t)cap_items[g]);
   }
   if (oom) return pv::dev_fail("hipMalloc", hipErrorOutOfMemory);
-  DEV_TRY("hipMemset", hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st));
-  DEV_TRY("hipMemset", hipMemsetAsync(d_ab, 0, ((size_t)nc + 1) * 4, st));
   DEV_TRY("hipMemset", hipMemsetAsync(d_cnt, 0, sizeof(Counters), st));
   if (int rc = ranges.reset(ds, st)) return rc;
-  const uint64_t row_lanes = 3 * (uint64_t)nc + npub + 1;
-  const dim3 row_grid((uint32_t)((row_lanes + 255) / 256));
-  DEV_LAUNCH("count kernel launch", zn_count_kernel, row_grid, dim3(256), st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_counts, d_ab);
-  DEV_TRY("column scan", isnark::exclusive_scan_u32(d_counts, n_cols, d_colptr, d_scan, st));
-  DEV_TRY("record scan", isnark::exclusive_scan_u32(d_ab, nc + 1, d_recoff, d_scan, st));
-  DEV_TRY("hipMemset", hipMemsetAsync(d_counts, 0, (size_t)n_cols * 4, st)); // now the cursors
-  DEV_LAUNCH("scatter kernel launch", zn_scatter_kernel, row_grid, dim3(256), st, rows.d_rowptr, rows.d_cols, nc, m, npub, d_colptr, d_counts, d_entries);
-  DEV_LAUNCH("records kernel launch", zn_records_kernel, row_grid, dim3(256), st, rows.d_rowptr, rows.d_cols, rows.d_vals, nc, npub, d_recoff, d_rec);
-  const Columns cols = {d_colptr, d_entries, rows.d_vals, m, thr};
+  if (int rc = transpose_rows(ds, st, rows, nc, m, npub, &T)) return rc;
+  uint32_t* const d_recoff = T.d_recoff;
+  uint32_t* const d_rec = T.d_rec;
+  const Columns cols = T.columns(rows.d_vals, m, thr);
   DEV_LAUNCH("plan kernel launch", zn_plan_kernel<false>, dim3((uint32_t)((3 * (uint64_t)m + 255) / 256)), dim3(256), st, cols, d_cnt, d_heavy[0], d_items[0]);
   DEV_LAUNCH("plan kernel launch", zn_plan_kernel<true>, dim3((m + 255) / 256), dim3(256), st, cols, d_cnt, d_heavy[1], d_items[1]);
   // (the second stream's first kernel writes the ranges' d_first: behind the memsets)
@@ -458,35 +342,10 @@ int zkey_new_impl(Groth16R1cs* h, const uint8_t* ptau, size_t ptau_len, int ptau
   };
   DEV_TRY("device to host download", isnark::staged_copy(shape.dev, jobs, 7, false));
   rep->download_ms = pv::ms_since(t_down);
-  memcpy(out, "zkey", 4);
-  const uint32_t version = 1, n_sections = 10, protocol = 1, n8 = 32, zero = 0, n_coeffs32 = (uint32_t)n_coeffs;
-  memcpy(out + 4, &version, 4);
-  memcpy(out + 8, &n_sections, 4);
-  for (uint32_t s = 1; s <= 10; s++) {
-    memcpy(out + F.off[s] - 12, &s, 4);
-    memcpy(out + F.off[s] - 8, &F.len[s], 8);
-  }
-  memcpy(out + F.off[1], &protocol, 4);
-  uint8_t* hd = out + F.off[2];
-  const fe q = Fq::modulus(), r = Fr::modulus();
-  memcpy(hd, &n8, 4);
-  memcpy(hd + 4, q.l, 32);
-  memcpy(hd + 36, &n8, 4);
-  memcpy(hd + 40, r.l, 32);
-  memcpy(hd + 72, &m, 4);
-  memcpy(hd + 76, &npub, 4);
-  memcpy(hd + 80, &n, 4);
   // α₁ β₁ β₂ the ptau's stored words; γ₂ = G₂, δ₁ = G₁, δ₂ = G₂ in Montgomery form
   const G1::A g1 = isnark::vb::g1_generator_mont();
   const G2::A g2 = isnark::vb::g2_generator_mont();
-  memcpy(hd + 84, PL.sec[4]->p, 64);
-  memcpy(hd + 148, PL.sec[5]->p, 64);
-  memcpy(hd + 212, PL.sec[6]->p, 128);
-  memcpy(hd + 340, &g2, 128);
-  memcpy(hd + 468, &g1, 64);
-  memcpy(hd + 532, &g2, 128);
-  memcpy(out + F.off[4], &n_coeffs32, 4);
-  memcpy(out + F.off[10], &zero, 4);
+  write_key_frame(out, F, m, npub, n, n_coeffs, {PL.sec[4]->p, PL.sec[5]->p, PL.sec[6]->p, &g2, &g1, &g2});
   trace.lap("download, header");
   return 0;
 }

@@ -449,6 +449,56 @@ int groth16_zkey_new(Groth16R1cs* h, const void* ptau, size_t ptau_len, void* zk
 int groth16_zkey_new_file(Groth16R1cs* h, const char* ptau_path, const char* zkey_path, const Groth16ZkeyNewOptions* opt,
                           Groth16ZkeyNewReport* report);
 
+/* groth16_setup — the Groth16 proving key of a loaded circuit made DIRECTLY from toxic waste (tau, alpha, beta, gamma, delta) on
+ * one GPU, without any .ptau: what arkworks' generate_random_parameters, gnark's groth16.Setup, bellman and `snarkjs groth16 setup`
+ * offer.  Opt-in; nothing else in the library calls it.  For development, CI, benchmarks on one's own circuit, and deployments where
+ * prover and verifier are one party.
+ * WHAT IT IS NOT: **whoever ran the call can forge proofs for the key.**  The five scalars existed in that process's memory; they
+ * are wiped on the host (explicit_bzero) and every device buffer that held a scalar derived from them is overwritten before it is
+ * freed, which is best effort — registers, spills and the operating system's copies are out of reach.  groth16_zkey_contribute
+ * afterwards protects only delta; tau, alpha and beta stay known to the runner.  A key for third parties comes from the ceremony
+ * chain (ptau-new -> ptau-contribute -> ptau-prepare -> zkey-new -> zkey-contribute).
+ * THE KEY: the layout, the sizes and section 4 are groth16_zkey_new's (groth16_zkey_new_size gives the size), byte for byte what
+ * synth.setup writes for the same five scalars; with gamma = delta = 1 it is groth16_zkey_new's key over a .ptau of the same tau,
+ * alpha, beta.  With n the domain, w its root of unity, g the root of order 2n and L_j(x) = w^j (x^n - 1) / (n (x - w^j)):
+ *   a_s = sum_j A[j,s]*L_j(tau) (+ L_{nc+s}(tau) for s <= npub), b_s, c_s likewise from B and C;  A_s = [a_s]1, B1_s = [b_s]1,
+ *   B2_s = [b_s]2;  comb_s = beta*a_s + alpha*b_s + c_s;  IC_s = [comb_s/gamma]1 (s <= npub), C_s = [comb_s/delta]1 (s > npub);
+ *   H_j = [L_j(tau/g) * (tau^n - 1) / (-2 delta)]1;  the header holds [alpha]1 [beta]1 [beta]2 [gamma]2 [delta]1 [delta]2.
+ * A wire in no matrix, or whose column cancels, is the identity: all-zero bytes.  Section 10 has a zero count, so
+ * groth16_zkey_contributions answers as it does for any key with delta != 1 and no record.
+ * toxic160: tau, alpha, beta, gamma, delta as five 32-byte little-endian standard-form scalars — for tests and reproducible
+ * benchmarks.  NULL: the operating system's randomness, redrawn until valid.  groth16_setup_toxic_check (host only, never
+ * initialises a GPU) returns 0, or the kind of the first fault: GROTH16_TOXIC_RANGE a scalar >= r, GROTH16_TOXIC_ZERO a zero among
+ * the five, GROTH16_TOXIC_DOMAIN tau^(2n) = 1 for n = 2^domain_power — tau in the domain or in its coset g*domain, where a Lagrange
+ * denominator vanishes (-3: a null pointer or domain_power > 27).  groth16_setup runs it before any device work: a fault is -2 with
+ * a message naming the scalar and the kind, nothing is written and the caller's buffer is untouched.
+ * A column of more than heavy_column_terms terms is cut into items that a workgroup each sums in Fr; field addition is exact, so no
+ * byte depends on the threshold.
+ * WHAT IT DOES NOT DO: read a zkez or any packed input; use more than one GPU; write a .ptau; write snarkjs' circuit hash. */
+enum { GROTH16_TOXIC_RANGE = 1, GROTH16_TOXIC_ZERO = 2, GROTH16_TOXIC_DOMAIN = 3 };
+typedef struct {
+  uint32_t heavy_column_terms;   /* 0 = the default */
+} Groth16SetupOptions;
+typedef struct {
+  uint32_t n_vars, n_public, domain;
+  uint64_t n_coeffs, zkey_bytes;           /* section 4's records; the file (also when cap was too small) */
+  uint32_t longest_column;                  /* terms of the longest (matrix, wire) column, binding rows included */
+  uint32_t heavy_columns, heavy_items;      /* columns that were cut, and the items they were cut into */
+  double   upload_ms, device_ms, download_ms, write_ms; /* the tables' copies; wall time of the device part up to the last
+                                               kernel; the copies into the buffer or the mapped file; msync and rename (_file) */
+  double   lagrange_ms, columns_ms, g1_ms, g2_ms;       /* device time by stage: the Lagrange rows; the column sums and outputs;
+                                               the fixed-base multiplications of the G1 array; of the G2 array (beside G1's) */
+} Groth16SetupReport;
+/* 0 built; -1 I/O; -2 the toxic waste (above); -3 argument: a null handle or report, a domain above 2^27, or cap too small
+ * (report->zkey_bytes still says what is needed); -5 device failure (groth16_last_error).  The _file variant writes to a temporary
+ * beside zkey_path and renames it: a failed call leaves no file there.  The calling thread's device is what it was afterwards;
+ * calls on one handle are serialised.  ICICLE_SNARK_TRACE_ZKEY_SETUP=1 prints the stage times on stderr. */
+int groth16_setup_toxic_check(const uint8_t toxic160[160], uint32_t domain_power);
+int groth16_setup(Groth16R1cs* h, const uint8_t* toxic160, void* zkey_out, size_t cap, const Groth16SetupOptions* opt,
+                  Groth16SetupReport* report);
+int groth16_setup_file(Groth16R1cs* h, const uint8_t* toxic160, const char* zkey_path, const Groth16SetupOptions* opt,
+                       Groth16SetupReport* report);
+
 /* groth16_zkey_contribute — one phase-2 contribution applied to a proving key on the GPU: what makes groth16_zkey_new's key a key
  * to prove with.  Opt-in; nothing else in the library calls it.  The contributor's secret is delta' in [1, r):
  *   header   delta1 <- delta'*delta1, delta2 <- delta'*delta2; everything else of section 2 stays byte for byte
