@@ -117,6 +117,10 @@ def lib():
                               "this package has no CPU fallback")
         _lib = C.CDLL(LIB_PATH)
         _lib.icicle_snark_last_error.restype = C.c_char_p
+        _lib.groth16_last_error.restype = _lib.groth16_verify_last_error.restype = C.c_char_p
+        _lib.groth16_cache_manager_new.restype = C.c_void_p
+        _lib.groth16_zkey_export_vk.restype = C.c_int64
+        _lib.groth16_verify_combined_coefficients.restype = None
         for n in ("bn254_eq", "bn254_g2_eq", "bn254_is_on_curve", "bn254_g2_is_on_curve"):
             getattr(_lib, n).restype = C.c_bool
     return _lib
@@ -225,11 +229,17 @@ class DeviceVec:
 
 
 # --------------------------------------------------------------------------------------------- vec ops
-def _vec_op(name, a, b, out, n, stream, is_async):
+def _vec_cfg(a, b, out, stream, is_async, batch_size=1, columns_batch=False):
+    """the VecOpsConfig of one call: where a, b and out live (None: the host), the stream, the batch"""
     cfg = VecOpsConfig.default()
     cfg.is_a_on_device, cfg.is_b_on_device, cfg.is_result_on_device = _on_dev(a), _on_dev(b), _on_dev(out)
-    cfg.is_async = is_async
+    cfg.is_async, cfg.batch_size, cfg.columns_batch = is_async, batch_size, columns_batch
     cfg.stream = stream.handle if stream else None
+    return cfg
+
+
+def _vec_op(name, a, b, out, n, stream, is_async):
+    cfg = _vec_cfg(a, b, out, stream, is_async)
     check(getattr(lib(), name)(ptr_of(a), ptr_of(b), C.c_uint64(n), C.byref(cfg), ptr_of(out)), name)
 
 
@@ -263,10 +273,7 @@ def vec_op2(name: str, a, b, n=None, batch_size=1, columns_batch=False, out=None
     total = _n_of(a)
     if out is None:
         out = np.empty((total, 4), dtype=np.uint64)
-    cfg = VecOpsConfig.default()
-    cfg.is_a_on_device, cfg.is_b_on_device, cfg.is_result_on_device = _on_dev(a), _on_dev(b), _on_dev(out)
-    cfg.is_async, cfg.batch_size, cfg.columns_batch = is_async, batch_size, columns_batch
-    cfg.stream = stream.handle if stream else None
+    cfg = _vec_cfg(a, b, out, stream, is_async, batch_size, columns_batch)
     n = total // batch_size if n is None else n
     check(getattr(lib(), "bn254_vector_" + name)(ptr_of(a), ptr_of(b), C.c_uint64(n), C.byref(cfg), ptr_of(out)), name)
     return out
@@ -274,10 +281,7 @@ def vec_op2(name: str, a, b, n=None, batch_size=1, columns_batch=False, out=None
 
 def accumulate_scalars(a, b, stream=None, is_async=False):
     """a += b in place — vector_accumulate"""
-    cfg = VecOpsConfig.default()
-    cfg.is_a_on_device, cfg.is_b_on_device, cfg.is_result_on_device = _on_dev(a), _on_dev(b), _on_dev(a)
-    cfg.is_async = is_async
-    cfg.stream = stream.handle if stream else None
+    cfg = _vec_cfg(a, b, a, stream, is_async)
     check(lib().bn254_vector_accumulate(ptr_of(a), ptr_of(b), C.c_uint64(_n_of(a)), C.byref(cfg)), "vector_accumulate")
     return a
 
@@ -287,10 +291,7 @@ def scalar_vec_op(name: str, scalars, v, batch_size=1, columns_batch=False, out=
     total = _n_of(v)
     if out is None:
         out = np.empty((total, 4), dtype=np.uint64)
-    cfg = VecOpsConfig.default()
-    cfg.is_a_on_device, cfg.is_b_on_device, cfg.is_result_on_device = _on_dev(scalars), _on_dev(v), _on_dev(out)
-    cfg.is_async, cfg.batch_size, cfg.columns_batch = is_async, batch_size, columns_batch
-    cfg.stream = stream.handle if stream else None
+    cfg = _vec_cfg(scalars, v, out, stream, is_async, batch_size, columns_batch)
     check(getattr(lib(), f"bn254_scalar_{name}_vec")(ptr_of(scalars), ptr_of(v), C.c_uint64(total // batch_size), C.byref(cfg), ptr_of(out)), name)
     return out
 
@@ -298,10 +299,7 @@ def scalar_vec_op(name: str, scalars, v, batch_size=1, columns_batch=False, out=
 def reduce_scalars(name: str, v, batch_size=1, columns_batch=False, stream=None, is_async=False):
     """Σ / Π of every batch vector, name in sum/product → (batch_size, 4) array"""
     out = np.empty((batch_size, 4), dtype=np.uint64)
-    cfg = VecOpsConfig.default()
-    cfg.is_a_on_device, cfg.is_result_on_device = _on_dev(v), False
-    cfg.is_async, cfg.batch_size, cfg.columns_batch = is_async, batch_size, columns_batch
-    cfg.stream = stream.handle if stream else None
+    cfg = _vec_cfg(v, None, None, stream, is_async, batch_size, columns_batch)
     check(getattr(lib(), "bn254_vector_" + name)(ptr_of(v), C.c_uint64(_n_of(v) // batch_size), C.byref(cfg), ptr_of(out)), name)
     return out
 
@@ -309,7 +307,7 @@ def reduce_scalars(name: str, v, batch_size=1, columns_batch=False, stream=None,
 def projective_convert_montgomery(group: str, a: np.ndarray, to_mont: bool) -> np.ndarray:
     per = 96 if group == "g1" else 192
     out = np.empty_like(a)
-    cfg = VecOpsConfig.default()
+    cfg = _vec_cfg(a, None, out, None, False)
     name = "bn254_projective_convert_montgomery" if group == "g1" else "bn254_g2_projective_convert_montgomery"
     check(getattr(lib(), name)(ptr_of(a), C.c_size_t(a.nbytes // per), C.c_bool(to_mont), C.byref(cfg), ptr_of(out)), name)
     return out
@@ -318,10 +316,7 @@ def projective_convert_montgomery(group: str, a: np.ndarray, to_mont: bool) -> n
 def scalar_convert_montgomery(a, to_mont: bool, out=None, stream=None, is_async=False):
     if out is None:
         out = np.empty_like(a) if isinstance(a, np.ndarray) else a
-    cfg = VecOpsConfig.default()
-    cfg.is_a_on_device, cfg.is_result_on_device = _on_dev(a), _on_dev(out)
-    cfg.is_async = is_async
-    cfg.stream = stream.handle if stream else None
+    cfg = _vec_cfg(a, None, out, stream, is_async)
     check(lib().bn254_scalar_convert_montgomery(ptr_of(a), C.c_uint64(_n_of(a)), C.c_bool(to_mont), C.byref(cfg), ptr_of(out)), "scalar_convert_montgomery")
     return out
 
@@ -331,10 +326,7 @@ def affine_convert_montgomery(group: str, a, to_mont: bool, out=None, stream=Non
     n = (a.nbytes if isinstance(a, (np.ndarray, DeviceVec)) else 0) // per
     if out is None:
         out = np.empty_like(a) if isinstance(a, np.ndarray) else a
-    cfg = VecOpsConfig.default()
-    cfg.is_a_on_device, cfg.is_result_on_device = _on_dev(a), _on_dev(out)
-    cfg.is_async = is_async
-    cfg.stream = stream.handle if stream else None
+    cfg = _vec_cfg(a, None, out, stream, is_async)
     name = "bn254_affine_convert_montgomery" if group == "g1" else "bn254_g2_affine_convert_montgomery"
     check(getattr(lib(), name)(ptr_of(a), C.c_uint64(n), C.c_bool(to_mont), C.byref(cfg), ptr_of(out)), name)
     return out
@@ -541,16 +533,63 @@ class ProverError(RuntimeError):
 
 def _pcheck(rc, what):
     if rc != 0:
-        lib().groth16_last_error.restype = C.c_char_p
         msg = lib().groth16_last_error()
         raise ProverError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+
+
+def _verify_fail(rc, what):
+    raise ProverError(f"{what}: {lib().groth16_verify_last_error().decode()} (code {rc})")
+
+
+def _image(data):
+    """zero-copy pointer to the caller's ndarray, bytes or writable buffer (a 0.8 GB zkey must not be duplicated on the way in)"""
+    return data.ctypes.data_as(C.c_void_p) if isinstance(data, np.ndarray) else C.c_char_p(data) if isinstance(data, bytes) else (C.c_char * len(data)).from_buffer(data)
+
+
+def _is_path(x):
+    return isinstance(x, (str, os.PathLike))
+
+
+def _path_or_image(what, src, out):
+    """True: src is a path and `out` the path to write to; False: src is an image, which takes no `out`"""
+    if _is_path(src):
+        if out is None:
+            raise TypeError(f"{what}: an input path needs the path to write to")
+        return True
+    if out is not None:
+        raise TypeError(f"{what}: `out` goes with an input path")
+    return False
+
+
+def _le32(value):
+    return int(value).to_bytes(32, "little") if value is not None else None
+
+
+def _seed32(seed, what, noun="seed"):
+    """32 caller-chosen bytes as the array the C entry points take; None stays None (the library draws its own)"""
+    if seed is None:
+        return None
+    if len(seed) != 32:
+        raise ValueError(f"{what}: the {noun} is 32 bytes")
+    return (C.c_uint8 * 32).from_buffer_copy(bytes(seed))
+
+
+def _sized_twice(call, rep, size_field, what, check=lambda rc, what, rep: _pcheck(rc, what)):
+    """call(buffer, room) sized by the library itself: a first call with no room is −3 and reports the bytes it needs, before any
+    device work; the second fills a buffer of that size, which comes back"""
+    rc = call(None, C.c_size_t(0))
+    if rc != -3 or getattr(rep, size_field) == 0:
+        check(rc, what, rep)
+    size = getattr(rep, size_field)
+    buf = C.create_string_buffer(size)
+    check(call(buf, C.c_size_t(size)), what, rep)
+    return buf
 
 
 class CacheManager:
     """CacheManager — src/cache.rs:110-262 (include/groth16_prover.h)."""
 
     def __init__(self):
-        lib().groth16_cache_manager_new.restype = C.c_void_p
         self._h = C.c_void_p(lib().groth16_cache_manager_new())
 
     def close(self):
@@ -565,14 +604,7 @@ class CacheManager:
         """groth16_cache_load.  A single-device key is usable before its fixed-base tables exist (they are built behind the
         first proofs); wait_tables=True (the default of this binding: tests and timings want the final layout) blocks until
         they are adopted, wait_tables=False returns like the C entry point does."""
-        # zero-copy views of the caller's buffer (a 0.8 GB zkey must not be duplicated on the way in)
-        if isinstance(zkey, np.ndarray):
-            p = zkey.ctypes.data_as(C.c_void_p)
-        elif isinstance(zkey, bytes):
-            p = C.c_char_p(zkey)
-        else:
-            p = (C.c_char * len(zkey)).from_buffer(zkey)   # bytearray / writable memoryview
-        _pcheck(lib().groth16_cache_load(self._h, key.encode(), p, C.c_size_t(len(zkey)), device_id, shard_rank, shard_count), "cache_load")
+        _pcheck(lib().groth16_cache_load(self._h, key.encode(), _image(zkey), C.c_size_t(len(zkey)), device_id, shard_rank, shard_count), "cache_load")
         if wait_tables:
             self.tables_ready(key, wait=True)
 
@@ -580,8 +612,7 @@ class CacheManager:
         """one key over a GROUP of devices in this process (what groth16_prove builds for "HIP:0-7"): shard k lives on
         device_ids[k]; a device may be named several times (several shards on one GPU)."""
         ids = (C.c_int * len(device_ids))(*device_ids)
-        p = zkey.ctypes.data_as(C.c_void_p) if isinstance(zkey, np.ndarray) else C.c_char_p(zkey) if isinstance(zkey, bytes) else (C.c_char * len(zkey)).from_buffer(zkey)
-        _pcheck(lib().groth16_cache_load_devices(self._h, key.encode(), p, C.c_size_t(len(zkey)), ids, len(device_ids)), "cache_load_devices")
+        _pcheck(lib().groth16_cache_load_devices(self._h, key.encode(), _image(zkey), C.c_size_t(len(zkey)), ids, len(device_ids)), "cache_load_devices")
 
     def set_budget(self, bytes_per_device: int):
         lib().groth16_cache_set_budget(self._h, C.c_uint64(bytes_per_device))
@@ -595,7 +626,7 @@ class CacheManager:
         """groth16_cache_load_packed / _file: load() from a PACKED key (zkey_pack) — the image, or a path — decoded on the GPU into
         the buffers load() fills; the entry is load()'s.  A faulty packed key raises ProverError (−2 "zkez: section S, element E:
         kind" / "zkez: coefficient E: kind") and nothing is cached.  One device only: anything but shard 0 of 1 is −3."""
-        if isinstance(zkez, (str, os.PathLike)):
+        if _is_path(zkez):
             rc = lib().groth16_cache_load_packed_file(self._h, key.encode(), os.fsencode(zkez), device_id, shard_rank, shard_count)
         else:
             rc = lib().groth16_cache_load_packed(self._h, key.encode(), _image(zkez), C.c_size_t(len(zkez)), device_id, shard_rank, shard_count)
@@ -640,20 +671,22 @@ class CacheManager:
 
     def assemble(self, key: str, wtns: bytes, points: bytes, r: int | None = None, s: int | None = None):
         pj, qj = C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 20)
-        rb = int(r).to_bytes(32, "little") if r is not None else None
-        sb = int(s).to_bytes(32, "little") if s is not None else None
+        rb, sb = _le32(r), _le32(s)
         _pcheck(lib().groth16_assemble_proof(self._h, key.encode(), wtns, C.c_size_t(len(wtns)), points, rb, sb,
                                              pj, C.c_size_t(len(pj)), qj, C.c_size_t(len(qj))), "assemble_proof")
         return pj.value.decode(), qj.value.decode()
 
+    def _json_bufs(self):
+        """the proof and public JSON buffers of prove_mem / prove_packed, made once"""
+        if not hasattr(self, "_bufs"):
+            self._bufs = (C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 20))
+        return self._bufs
+
     def prove_mem(self, key: str, wtns: bytes, r: int | None = None, s: int | None = None, resident: bool = False):
         """commitments + blinding + JSON in one call (the blinding terms are computed on a host thread while the GPU
         works).  resident=True re-uses the witness already uploaded by an earlier call."""
-        if not hasattr(self, "_bufs"):
-            self._bufs = (C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 20))
-        pj, qj = self._bufs
-        rb = int(r).to_bytes(32, "little") if r is not None else None
-        sb = int(s).to_bytes(32, "little") if s is not None else None
+        pj, qj = self._json_bufs()
+        rb, sb = _le32(r), _le32(s)
         tm = Timings()
         _pcheck(lib().groth16_prove_resident(self._h, key.encode(), wtns, C.c_size_t(len(wtns)), int(resident), rb, sb, pj,
                                              C.c_size_t(len(pj)), qj, C.c_size_t(len(qj)), C.byref(tm)), "prove_resident")
@@ -663,11 +696,8 @@ class CacheManager:
         """groth16_prove_packed → (proof JSON, public JSON, Timings): prove_mem from a PACKED witness (wtns_pack), decoded on the
         GPU into the key's resident witness buffer; afterwards prove_mem(resident=True) proves the same witness.  A faulty packed
         witness raises ProverError (−2 "wtnz: element E: kind") and leaves no witness resident.  Single-device keys only (−3)."""
-        if not hasattr(self, "_bufs"):
-            self._bufs = (C.create_string_buffer(1 << 14), C.create_string_buffer(1 << 20))
-        pj, qj = self._bufs
-        rb = int(r).to_bytes(32, "little") if r is not None else None
-        sb = int(s).to_bytes(32, "little") if s is not None else None
+        pj, qj = self._json_bufs()
+        rb, sb = _le32(r), _le32(s)
         tm = Timings()
         _pcheck(lib().groth16_prove_packed(self._h, key.encode(), _image(wtnz), C.c_size_t(len(wtnz)), rb, sb, pj, C.c_size_t(len(pj)), qj,
                                            C.c_size_t(len(qj)), C.byref(tm)), "prove_packed")
@@ -790,8 +820,7 @@ def groth16_verify_json(proof_json: str, public_json: str, vk_json: str) -> bool
     """groth16_verify_helper — src/proof_helper.rs:319-372 on JSON texts."""
     rc = lib().groth16_verify_json(proof_json.encode(), public_json.encode(), vk_json.encode())
     if rc < 0:
-        lib().groth16_verify_last_error.restype = C.c_char_p
-        raise ProverError(f"groth16_verify: {lib().groth16_verify_last_error().decode()} (code {rc})")
+        _verify_fail(rc, "groth16_verify")
     return rc == 1
 
 
@@ -829,8 +858,7 @@ def groth16_verify_batch(proofs, publics, vk: str, device: str = "HIP") -> list:
     out = (C.c_int32 * max(n, 1))()
     rc = lib().groth16_verify_batch(pa, qa, C.c_int(n), vk.encode(), device.encode(), out)
     if rc != 0:
-        lib().groth16_verify_last_error.restype = C.c_char_p
-        raise ProverError(f"groth16_verify_batch: {lib().groth16_verify_last_error().decode()} (code {rc})")
+        _verify_fail(rc, "groth16_verify_batch")
     return [int(out[i]) for i in range(n)]
 
 
@@ -842,27 +870,22 @@ def groth16_verify_batch_combined(proofs, publics, vk: str, device: str = "HIP",
     n = len(proofs)
     if len(publics) != n:
         raise ValueError("groth16_verify_batch_combined: proofs and publics differ in length")
-    if seed is not None and len(seed) != 32:
-        raise ValueError("groth16_verify_batch_combined: the seed is 32 bytes")
+    sd = _seed32(seed, "groth16_verify_batch_combined")
     pa = (C.c_char_p * max(n, 1))(*[p.encode() if isinstance(p, str) else p for p in proofs])
     qa = (C.c_char_p * max(n, 1))(*[q.encode() if isinstance(q, str) else q for q in publics])
     out = (C.c_int32 * max(n, 1))()
     path = C.c_int32(0)
-    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
     rc = lib().groth16_verify_batch_combined(pa, qa, C.c_int(n), vk.encode(), device.encode(), sd, out, C.byref(path))
     if rc != 0:
-        lib().groth16_verify_last_error.restype = C.c_char_p
-        raise ProverError(f"groth16_verify_batch_combined: {lib().groth16_verify_last_error().decode()} (code {rc})")
+        _verify_fail(rc, "groth16_verify_batch_combined")
     return [int(out[i]) for i in range(n)], int(path.value)
 
 
 def verify_combined_coefficients(seed: bytes, first: int, count: int) -> list:
     """the combined verifier's coefficients z_first … z_{first+count−1} for a 32-byte seed, as integers (no GPU)"""
-    if len(seed) != 32:
-        raise ValueError("verify_combined_coefficients: the seed is 32 bytes")
+    sd = _seed32(bytes(seed), "verify_combined_coefficients")   # not optional here
     out = (C.c_uint8 * (16 * max(count, 1)))()
-    lib().groth16_verify_combined_coefficients.restype = None
-    lib().groth16_verify_combined_coefficients((C.c_uint8 * 32).from_buffer_copy(bytes(seed)), C.c_uint64(first), C.c_uint64(count), out)
+    lib().groth16_verify_combined_coefficients(sd, C.c_uint64(first), C.c_uint64(count), out)
     raw = bytes(out)
     return [int.from_bytes(raw[16 * k:16 * k + 16], "little") for k in range(count)]
 
@@ -901,8 +924,7 @@ def groth16_verify(proof: str, public: str, vk: str):
     """groth16_verify — src/lib.rs:63-82 (paths in; raises on a rejected proof like the reference's assert)."""
     rc = lib().groth16_verify(proof.encode(), public.encode(), vk.encode())
     if rc != 0:
-        lib().groth16_verify_last_error.restype = C.c_char_p
-        raise ProverError(f"groth16_verify: {lib().groth16_verify_last_error().decode()} (code {rc})")
+        _verify_fail(rc, "groth16_verify")
 
 
 class ZkeyReport(C.Structure):
@@ -919,9 +941,7 @@ ZKEY_NONCANONICAL, ZKEY_OFF_CURVE, ZKEY_OFF_SUBGROUP, ZKEY_IDENTITY, ZKEY_PAIR_M
 
 
 def _zkey_check(call, what, device, slice_points, seed):
-    if seed is not None and len(seed) != 32:
-        raise ValueError(f"{what}: the seed is 32 bytes")
-    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+    sd = _seed32(seed, what)
     opt = ZkeyCheckOptions(int(slice_points), C.cast(sd, C.c_char_p) if sd is not None else None)
     rep = ZkeyReport()
     rc = call(device.encode(), C.byref(opt), C.byref(rep))
@@ -934,7 +954,7 @@ def zkey_check(zkey: bytes, device: str = "HIP", slice_points: int = 0, seed=Non
     """groth16_zkey_check: every point of the key on its curve (B2: in the subgroup), the coefficient records in range, the
     header pairs and B1 against B2 consistent.  Returns (ok, ZkeyReport); raises ProverError for a malformed file or a device
     error.  seed: 32 bytes for a reproducible test — leave it None otherwise (a secret, fresh seed is drawn)."""
-    p = zkey.ctypes.data_as(C.c_void_p) if isinstance(zkey, np.ndarray) else C.c_char_p(zkey) if isinstance(zkey, bytes) else (C.c_char * len(zkey)).from_buffer(zkey)
+    p = _image(zkey)
     return _zkey_check(lambda d, o, r: lib().groth16_zkey_check(p, C.c_size_t(len(zkey)), d, o, r), "zkey_check", device, slice_points, seed)
 
 
@@ -946,7 +966,6 @@ def zkey_check_file(path: str, device: str = "HIP", slice_points: int = 0, seed=
 def zkey_export_vk(zkey: bytes) -> str:
     """groth16_zkey_export_vk: the key's verification_key.json text (host only: needs no GPU)"""
     f = lib().groth16_zkey_export_vk
-    f.restype = C.c_int64
     need = f(C.c_char_p(bytes(zkey)), C.c_size_t(len(zkey)), None, C.c_size_t(0))
     if need < 0:
         _pcheck(int(need), "zkey_export_vk")
@@ -1032,10 +1051,6 @@ def setup_toxic_check(toxic, domain_power: int) -> int:
     return rc
 
 
-def _image(data):
-    return data.ctypes.data_as(C.c_void_p) if isinstance(data, np.ndarray) else C.c_char_p(data) if isinstance(data, bytes) else (C.c_char * len(data)).from_buffer(data)
-
-
 def r1cs_info(r1cs: bytes) -> R1csInfo:
     """groth16_r1cs_info: the counts of an .r1cs after the host walk that bounds every record (host only: needs no GPU)"""
     info = R1csInfo()
@@ -1054,7 +1069,7 @@ def ptau_info(ptau, domain_power: int = -1) -> PtauInfo:
     """groth16_ptau_info: power and sections of a prepared .ptau (bytes, or a path that is mapped; host only: needs no GPU).
     domain_power >= 0 also asks whether the file serves a key of that domain (ProverError −3 / −2 when not)."""
     info = PtauInfo()
-    if isinstance(ptau, (str, os.PathLike)):
+    if _is_path(ptau):
         import mmap
         with open(ptau, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
             view = np.frombuffer(mm, dtype=np.uint8)
@@ -1072,7 +1087,7 @@ class R1cs:
 
     def __init__(self, r1cs, device: str = "HIP"):
         self._h = C.c_void_p()
-        if isinstance(r1cs, (str, os.PathLike)):
+        if _is_path(r1cs):
             _pcheck(lib().groth16_r1cs_load_file(os.fsencode(r1cs), device.encode(), C.byref(self._h)), "r1cs_load_file")
         else:
             _pcheck(lib().groth16_r1cs_load(_image(r1cs), C.c_size_t(len(r1cs)), device.encode(), C.byref(self._h)), "r1cs_load")
@@ -1088,7 +1103,7 @@ class R1cs:
         """groth16_witness_check → (ok, WitnessReport); wtns: the .wtns image, or a path.  Raises ProverError for a malformed
         file, a witness of another size or a device error."""
         rep = WitnessReport()
-        if isinstance(wtns, (str, os.PathLike)):
+        if _is_path(wtns):
             return self._verdict(lib().groth16_witness_check_file(self._h, os.fsencode(wtns), C.byref(rep)), rep, "witness_check_file")
         return self._verdict(lib().groth16_witness_check(self._h, _image(wtns), C.c_size_t(len(wtns)), C.byref(rep)), rep, "witness_check")
 
@@ -1096,16 +1111,14 @@ class R1cs:
         """groth16_witness_check_packed → (ok, WitnessReport): check() of a PACKED witness (wtns_pack; the image, or a path), decoded
         on the GPU.  A faulty packed witness raises ProverError (−2 "wtnz: element E: kind")."""
         rep = WitnessReport()
-        if isinstance(wtnz, (str, os.PathLike)):
+        if _is_path(wtnz):
             return self._verdict(lib().groth16_witness_check_packed_file(self._h, os.fsencode(wtnz), C.byref(rep)), rep, "witness_check_packed_file")
         return self._verdict(lib().groth16_witness_check_packed(self._h, _image(wtnz), C.c_size_t(len(wtnz)), C.byref(rep)), rep, "witness_check_packed")
 
     def match_zkey(self, zkey, seed=None):
         """groth16_r1cs_match_zkey → (ok, MatchReport): the key's section 4 against this circuit's A and B.  seed: 32 bytes for a
         reproducible test — leave it None otherwise (a secret, fresh seed is drawn)."""
-        if seed is not None and len(seed) != 32:
-            raise ValueError("match_zkey: the seed is 32 bytes")
-        sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+        sd = _seed32(seed, "match_zkey")
         rep = MatchReport()
         return self._verdict(lib().groth16_r1cs_match_zkey(self._h, _image(zkey), C.c_size_t(len(zkey)), sd, C.byref(rep)), rep, "r1cs_match_zkey")
 
@@ -1113,11 +1126,9 @@ class R1cs:
         """groth16_zkey_verify_ptau → (ok, VerifyReport): is the key this circuit's Groth16 key over this prepared .ptau?  zkey
         and ptau: both images, or both paths (mapped; only the ptau ranges that are read are touched).  seed: 32 bytes for a
         reproducible test — leave it None otherwise (a secret, fresh seed is drawn)."""
-        if seed is not None and len(seed) != 32:
-            raise ValueError("verify_zkey: the seed is 32 bytes")
-        sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+        sd = _seed32(seed, "verify_zkey")
         rep = VerifyReport()
-        paths = [isinstance(x, (str, os.PathLike)) for x in (zkey, ptau)]
+        paths = [_is_path(x) for x in (zkey, ptau)]
         if all(paths):
             return self._verdict(lib().groth16_zkey_verify_ptau_file(self._h, os.fsencode(zkey), os.fsencode(ptau), sd, C.byref(rep)), rep, "zkey_verify_ptau_file")
         if any(paths):
@@ -1131,19 +1142,11 @@ class R1cs:
         as bytes; or a path together with `out`, the path the key is written to (None comes back).  heavy_column_terms: 0 = the
         default.  Raises ProverError (−2 an unprepared ptau or a ptau point failing its lane test, −3 a ptau of too low a power)."""
         opt, rep = ZkeyNewOptions(int(heavy_column_terms)), ZkeyNewReport()
-        if isinstance(ptau, (str, os.PathLike)):
-            if out is None:
-                raise TypeError("new_zkey: a ptau path needs the path to write the key to")
+        if _path_or_image("new_zkey", ptau, out):
             _pcheck(lib().groth16_zkey_new_file(self._h, os.fsencode(ptau), os.fsencode(out), C.byref(opt), C.byref(rep)), "zkey_new_file")
             return None, rep
-        if out is not None:
-            raise TypeError("new_zkey: `out` goes with a ptau path")
-        # sized by the library itself: a first call with no room reports the bytes it needs
-        rc = lib().groth16_zkey_new(self._h, _image(ptau), C.c_size_t(len(ptau)), None, C.c_size_t(0), C.byref(opt), C.byref(rep))
-        if rc != -3 or rep.zkey_bytes == 0:
-            _pcheck(rc, "zkey_new")
-        buf = C.create_string_buffer(rep.zkey_bytes)
-        _pcheck(lib().groth16_zkey_new(self._h, _image(ptau), C.c_size_t(len(ptau)), buf, C.c_size_t(rep.zkey_bytes), C.byref(opt), C.byref(rep)), "zkey_new")
+        buf = _sized_twice(lambda buf, room: lib().groth16_zkey_new(self._h, _image(ptau), C.c_size_t(len(ptau)), buf, room, C.byref(opt), C.byref(rep)),
+                           rep, "zkey_bytes", "zkey_new")
         return buf.raw, rep
 
     def setup(self, out=None, toxic=None, heavy_column_terms: int = 0):
@@ -1156,12 +1159,7 @@ class R1cs:
         if out is not None:
             _pcheck(lib().groth16_setup_file(self._h, tx, os.fsencode(out), C.byref(opt), C.byref(rep)), "setup_file")
             return None, rep
-        # sized by the library itself: a first call with no room reports the bytes it needs
-        rc = lib().groth16_setup(self._h, tx, None, C.c_size_t(0), C.byref(opt), C.byref(rep))
-        if rc != -3 or rep.zkey_bytes == 0:
-            _pcheck(rc, "setup")
-        buf = C.create_string_buffer(rep.zkey_bytes)
-        _pcheck(lib().groth16_setup(self._h, tx, buf, C.c_size_t(rep.zkey_bytes), C.byref(opt), C.byref(rep)), "setup")
+        buf = _sized_twice(lambda buf, room: lib().groth16_setup(self._h, tx, buf, room, C.byref(opt), C.byref(rep)), rep, "zkey_bytes", "setup")
         return buf.raw, rep
 
     def close(self):
@@ -1216,25 +1214,15 @@ def zkey_contribute(zkey, secret=None, name="", out=None, device: str = "HIP", d
     path the new key is written to (None comes back).  secret: 32 bytes, None draws from the operating system.  name: str or bytes,
     at most 255 bytes.  delta: delta' itself as an integer in [1, r), for tests and reproducible runs.  Raises ProverError (−2 a
     faulty point of section 8 or 9 or a malformed section 10, −3 a name too long or a bad delta)."""
-    if secret is not None and len(secret) != 32:
-        raise ValueError("zkey_contribute: the secret is 32 bytes")
-    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(secret)) if secret is not None else None
-    fd = (C.c_uint8 * 32).from_buffer_copy(int(delta).to_bytes(32, "little")) if delta is not None else None
+    sd = _seed32(secret, "zkey_contribute", "secret")
+    fd = _seed32(_le32(delta), "zkey_contribute")
     opt, rep = ZkeyContributeOptions(C.cast(fd, C.POINTER(C.c_uint8)) if fd is not None else None), ZkeyContributeReport()
     nm = name.encode() if isinstance(name, str) else bytes(name)
-    if isinstance(zkey, (str, os.PathLike)):
-        if out is None:
-            raise TypeError("zkey_contribute: a zkey path needs the path to write the new key to")
+    if _path_or_image("zkey_contribute", zkey, out):
         _pcheck(lib().groth16_zkey_contribute_file(os.fsencode(zkey), os.fsencode(out), sd, nm, device.encode(), C.byref(opt), C.byref(rep)), "zkey_contribute_file")
         return None, rep
-    if out is not None:
-        raise TypeError("zkey_contribute: `out` goes with a zkey path")
-    # sized by the library itself: a first call with no room reports the bytes it needs, before any device work
-    rc = lib().groth16_zkey_contribute(_image(zkey), C.c_size_t(len(zkey)), sd, nm, None, C.c_size_t(0), device.encode(), C.byref(opt), C.byref(rep))
-    if rc != -3 or rep.zkey_bytes == 0:
-        _pcheck(rc, "zkey_contribute")
-    buf = C.create_string_buffer(rep.zkey_bytes)
-    _pcheck(lib().groth16_zkey_contribute(_image(zkey), C.c_size_t(len(zkey)), sd, nm, buf, C.c_size_t(rep.zkey_bytes), device.encode(), C.byref(opt), C.byref(rep)), "zkey_contribute")
+    buf = _sized_twice(lambda buf, room: lib().groth16_zkey_contribute(_image(zkey), C.c_size_t(len(zkey)), sd, nm, buf, room, device.encode(), C.byref(opt), C.byref(rep)),
+                       rep, "zkey_bytes", "zkey_contribute")
     return buf.raw, rep
 
 
@@ -1276,15 +1264,11 @@ def ptau_prepare(ptau, out=None, device: str = "HIP"):
     `out`, the path the prepared file is written to (None comes back).  Raises ProverError (−2 a malformed or already prepared
     file, or a faulty point: section, element and kind in the text)."""
     rep = PtauPrepareReport()
-    if isinstance(ptau, (str, os.PathLike)):
-        if out is None:
-            raise TypeError("ptau_prepare: a ptau path needs the path to write the prepared file to")
+    if _path_or_image("ptau_prepare", ptau, out):
         rc = lib().groth16_ptau_prepare_file(os.fsencode(ptau), os.fsencode(out), device.encode(), C.byref(rep))
         if rc != 1:
             _pcheck(rc, "ptau_prepare_file")
         return None, rep
-    if out is not None:
-        raise TypeError("ptau_prepare: `out` goes with a ptau path")
     size = ptau_prepared_size(ptau)
     buf, got = C.create_string_buffer(size), C.c_uint64()
     rc = lib().groth16_ptau_prepare(_image(ptau), C.c_size_t(len(ptau)), buf, C.c_size_t(size), C.byref(got), device.encode(), C.byref(rep))
@@ -1343,26 +1327,16 @@ def ptau_contribute(ptau, secret=None, name="", out=None, device: str = "HIP", t
     new file is written to (None comes back).  secret: 32 bytes, None draws from the operating system.  name: str or bytes, at
     most 255 bytes.  tau, alpha, beta: the secrets themselves as integers in [1, r), for tests and reproducible runs.  Raises
     ProverError (−2 a faulty point, a prepared file, a malformed or stale section 7; −3 a name too long or a bad fixed secret)."""
-    if secret is not None and len(secret) != 32:
-        raise ValueError("ptau_contribute: the secret is 32 bytes")
-    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(secret)) if secret is not None else None
-    fixed = [(C.c_uint8 * 32).from_buffer_copy(int(v).to_bytes(32, "little")) if v is not None else None for v in (tau, alpha, beta)]
+    sd = _seed32(secret, "ptau_contribute", "secret")
+    fixed = [_seed32(_le32(v), "ptau_contribute") for v in (tau, alpha, beta)]
     opt = PtauContributeOptions(*[C.cast(f, C.POINTER(C.c_uint8)) if f is not None else None for f in fixed])
     rep = PtauContributeReport()
     nm = name.encode() if isinstance(name, str) else bytes(name)
-    if isinstance(ptau, (str, os.PathLike)):
-        if out is None:
-            raise TypeError("ptau_contribute: a ptau path needs the path to write the new file to")
+    if _path_or_image("ptau_contribute", ptau, out):
         _pcheck(lib().groth16_ptau_contribute_file(os.fsencode(ptau), os.fsencode(out), sd, nm, device.encode(), C.byref(opt), C.byref(rep)), "ptau_contribute_file")
         return None, rep
-    if out is not None:
-        raise TypeError("ptau_contribute: `out` goes with a ptau path")
-    # sized by the library itself: a first call with no room reports the bytes it needs, before any device work
-    rc = lib().groth16_ptau_contribute(_image(ptau), C.c_size_t(len(ptau)), sd, nm, None, C.c_size_t(0), device.encode(), C.byref(opt), C.byref(rep))
-    if rc != -3 or rep.ptau_bytes == 0:
-        _pcheck(rc, "ptau_contribute")
-    buf = C.create_string_buffer(rep.ptau_bytes)
-    _pcheck(lib().groth16_ptau_contribute(_image(ptau), C.c_size_t(len(ptau)), sd, nm, buf, C.c_size_t(rep.ptau_bytes), device.encode(), C.byref(opt), C.byref(rep)), "ptau_contribute")
+    buf = _sized_twice(lambda buf, room: lib().groth16_ptau_contribute(_image(ptau), C.c_size_t(len(ptau)), sd, nm, buf, room, device.encode(), C.byref(opt), C.byref(rep)),
+                       rep, "ptau_bytes", "ptau_contribute")
     return buf.raw, rep
 
 
@@ -1409,11 +1383,9 @@ def ptau_verify(ptau, seed=None, device: str = "HIP"):
     is mapped.  seed: 32 bytes for a reproducible run; None draws from the operating system, which is what soundness needs.  A
     faulty point or an identity in sections 2 to 6 is a verdict (ok False, kind POINT / IDENTITY), not an error.  It does NOT say who
     contributed: ptau_contributions does.  Raises ProverError (−2 a malformed container, −3 a power above 27)."""
-    if seed is not None and len(seed) != 32:
-        raise ValueError("ptau_verify: the seed is 32 bytes")
-    sd = (C.c_uint8 * 32).from_buffer_copy(bytes(seed)) if seed is not None else None
+    sd = _seed32(seed, "ptau_verify")
     rep = PtauVerifyReport()
-    if isinstance(ptau, (str, os.PathLike)):
+    if _is_path(ptau):
         rc, what = lib().groth16_ptau_verify_file(os.fsencode(ptau), sd, device.encode(), C.byref(rep)), "ptau_verify_file"
     else:
         rc, what = lib().groth16_ptau_verify(_image(ptau), C.c_size_t(len(ptau)), sd, device.encode(), C.byref(rep)), "ptau_verify"
@@ -1447,15 +1419,20 @@ class PointFault(ProverError):
     report = None
 
 
-def _pack_check(rc, what, rep):
+def _fault_check(fault_type, rc, what, rep):
+    """_pcheck, but a −2 whose report names a fault raises fault_type (a ProverError) carrying the report"""
     try:
         _pcheck(rc, what)
     except ProverError as e:
         if rc == -2 and rep.fault_kind:
-            fault = PointFault(str(e))
+            fault = fault_type(str(e))
             fault.report = rep
             raise fault from None
         raise
+
+
+def _pack_check(rc, what, rep):
+    _fault_check(PointFault, rc, what, rep)
 
 
 def _points_call(entry, what, buf, in_elem, out_elem, g2, device):
@@ -1498,18 +1475,10 @@ def ptau_unpacked_size(power: int, prepared: bool, packed_bytes: int) -> int:
 
 def _ptau_transcode(what, buffer_entry, file_entry, src, out, device):
     rep = PtauPackReport()
-    if isinstance(src, (str, os.PathLike)):
-        if out is None:
-            raise TypeError(f"{what}: an input path needs the path to write to")
+    if _path_or_image(what, src, out):
         _pack_check(file_entry(os.fsencode(src), os.fsencode(out), device.encode(), C.byref(rep)), what + "_file", rep)
         return None, rep
-    if out is not None:
-        raise TypeError(f"{what}: `out` goes with an input path")
-    rc = buffer_entry(_image(src), C.c_size_t(len(src)), None, C.c_size_t(0), device.encode(), C.byref(rep))
-    if rc != -3 or rep.out_bytes == 0:
-        _pack_check(rc, what, rep)
-    buf = C.create_string_buffer(rep.out_bytes)
-    _pack_check(buffer_entry(_image(src), C.c_size_t(len(src)), buf, C.c_size_t(rep.out_bytes), device.encode(), C.byref(rep)), what, rep)
+    buf = _sized_twice(lambda buf, room: buffer_entry(_image(src), C.c_size_t(len(src)), buf, room, device.encode(), C.byref(rep)), rep, "out_bytes", what, _pack_check)
     return buf.raw[:rep.out_bytes], rep
 
 
@@ -1552,13 +1521,9 @@ def ptau_truncate(ptau, power: int, out=None, device: str = "HIP"):
     input, or power equal to the file's, opens no GPU.  A faulty point of the block or of the one point of section 2 that is read
     raises PointFault (−2) with .report, and nothing is written; the copied prefixes are not tested (ptau_verify judges a file)."""
     rep = PtauTruncateReport()
-    if isinstance(ptau, (str, os.PathLike)):
-        if out is None:
-            raise TypeError("ptau_truncate: an input path needs the path to write to")
+    if _path_or_image("ptau_truncate", ptau, out):
         _pack_check(lib().groth16_ptau_truncate_file(os.fsencode(ptau), os.fsencode(out), C.c_uint32(power), device.encode(), C.byref(rep)), "ptau_truncate_file", rep)
         return None, rep
-    if out is not None:
-        raise TypeError("ptau_truncate: `out` goes with an input path")
     size = ptau_truncated_size(ptau, power)
     buf = C.create_string_buffer(size)
     _pack_check(lib().groth16_ptau_truncate(_image(ptau), C.c_size_t(len(ptau)), C.c_uint32(power), buf, C.c_size_t(size), device.encode(), C.byref(rep)), "ptau_truncate", rep)
@@ -1582,31 +1547,15 @@ class WitnessFault(ProverError):
 
 
 def _wtns_check(rc, what, rep):
-    try:
-        _pcheck(rc, what)
-    except ProverError as e:
-        if rc == -2 and rep.fault_kind:
-            fault = WitnessFault(str(e))
-            fault.report = rep
-            raise fault from None
-        raise
+    _fault_check(WitnessFault, rc, what, rep)
 
 
 def _wtns_transcode(what, buffer_call, file_call, src, out):
     rep = WtnsPackReport()
-    if isinstance(src, (str, os.PathLike)):
-        if out is None:
-            raise TypeError(f"{what}: an input path needs the path to write to")
+    if _path_or_image(what, src, out):
         _wtns_check(file_call(os.fsencode(src), os.fsencode(out), C.byref(rep)), what + "_file", rep)
         return None, rep
-    if out is not None:
-        raise TypeError(f"{what}: `out` goes with an input path")
-    # sized by the library itself: a first call with no room reports the bytes it needs
-    rc = buffer_call(_image(src), C.c_size_t(len(src)), None, C.c_size_t(0), C.byref(rep))
-    if rc != -3 or rep.out_bytes == 0:
-        _wtns_check(rc, what, rep)
-    buf = C.create_string_buffer(rep.out_bytes)
-    _wtns_check(buffer_call(_image(src), C.c_size_t(len(src)), buf, C.c_size_t(rep.out_bytes), C.byref(rep)), what, rep)
+    buf = _sized_twice(lambda buf, room: buffer_call(_image(src), C.c_size_t(len(src)), buf, room, C.byref(rep)), rep, "out_bytes", what, _wtns_check)
     return buf.raw[:rep.out_bytes], rep
 
 
@@ -1658,14 +1607,7 @@ class KeyFault(ProverError):
 
 
 def _key_check(rc, what, rep):
-    try:
-        _pcheck(rc, what)
-    except ProverError as e:
-        if rc == -2 and rep.fault_kind:
-            fault = KeyFault(str(e))
-            fault.report = rep
-            raise fault from None
-        raise
+    _fault_check(KeyFault, rc, what, rep)
 
 
 def zkey_unpacked_size(zkez) -> int:
@@ -1684,13 +1626,9 @@ def zkey_packed_bound(zkey) -> int:
 
 def _zkey_transcode(what, buffer_entry, file_entry, room, src, out, device):
     rep = ZkeyPackReport()
-    if isinstance(src, (str, os.PathLike)):
-        if out is None:
-            raise TypeError(f"{what}: an input path needs the path to write to")
+    if _path_or_image(what, src, out):
         _key_check(file_entry(os.fsencode(src), os.fsencode(out), device.encode(), C.byref(rep)), what + "_file", rep)
         return None, rep
-    if out is not None:
-        raise TypeError(f"{what}: `out` goes with an input path")
     buf = C.create_string_buffer(max(room(src), 1))      # (a refused container raises here, with the reader's message)
     _key_check(buffer_entry(_image(src), C.c_size_t(len(src)), buf, C.c_size_t(len(buf)), device.encode(), C.byref(rep)), what, rep)
     return buf.raw[:rep.out_bytes], rep
