@@ -291,4 +291,20 @@ inline eIcicleError check_launch(const char* what)
   return ICICLE_SUCCESS;
 }
 
+// Raise the dynamic-LDS cap of a launch site's kernels (a per-device function attribute) once per device, at the site's first use there.
+class LdsCapOnce
+{
+  std::atomic<uint32_t> done_{0}; // bit (device mod 32)
+public:
+  template <class... K>
+  eIcicleError raise(int dev, int bytes, K... kernels)
+  {
+    const uint32_t bit = 1u << (dev & 31);
+    if (done_.load(std::memory_order_acquire) & bit) return ICICLE_SUCCESS;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...}) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), ICICLE_UNKNOWN_ERROR);
+    done_.fetch_or(bit, std::memory_order_release);
+    return ICICLE_SUCCESS;
+  }
+};
+
 } // namespace isnark

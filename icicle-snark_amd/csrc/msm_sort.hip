@@ -14,12 +14,14 @@
 //              The order inside a bucket is arbitrary — addition is commutative, results are not affected.
 // HBM traffic: 2 × 32 B per scalar read, 4 B per digit written (the key is implicit in the position): the
 // reference moves 8-byte (key, value) pairs through three CUB radix sorts + RLE + scan (cuda_msm.cuh:401-485, :561-636).
+// The shape of a sort — threshold, path, partitions, LDS sizes, workspace layouts — is msm_sort_shape (msm_sort_plan.h, walked on the
+// host by tests/msm_sort_plan_check.cpp); msm_sort_run allocates what it says and enqueues one of enqueue_staged / _two_level / _global.
 #include <atomic>
 #include <mutex>
 #include <string.h>
 
 #include "msm_plan.h"
-#include "msm_recode.h"
+#include "msm_sort_plan.h"
 
 using namespace bn254;
 
@@ -171,8 +173,6 @@ __global__ __launch_bounds__(256) void msm_scatter_kernel(const fe* __restrict__
 }
 
 // ---- exclusive scan of m counters: 2048 per workgroup (256 threads × 8) --------------------------
-constexpr int SCAN_T = 256, SCAN_E = 8, SCAN_B = SCAN_T * SCAN_E;
-
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t* total)
 {
   const uint32_t tid = threadIdx.x;
@@ -276,7 +276,6 @@ __global__ __launch_bounds__(SCAN_T) void msm_scan_apply_kernel(const uint32_t* 
 // reference sorts bucket sizes with two more CUB radix sorts (cuda_msm.cuh:606-630); sizes are small
 // integers, so a counting sort is enough: per-workgroup LDS histograms, one scan, LDS ranks — no global
 // atomics (a first version with global atomics on ~100 hot counters cost 1.1 ms at 2^19 buckets).
-constexpr int ORDER_BINS = 256;
 __device__ __forceinline__ uint32_t order_key(uint32_t cnt) { return (uint32_t)ORDER_BINS - 1 - min(cnt, (uint32_t)ORDER_BINS - 1); } // ascending key = descending size
 __global__ __launch_bounds__(ORDER_BINS) void msm_order_hist_kernel(const uint32_t* __restrict__ counts, uint32_t m, uint32_t nblk, uint32_t* __restrict__ blockhist)
 {
@@ -513,21 +512,7 @@ __global__ __launch_bounds__(256) void msm_fine_place_kernel(const uint32_t* __r
 // workgroup.  Launches per sort: 14 → 9 (zeroing folded into the histogram, the column scan's middle kernel into its first,
 // the size order's histogram into the bucket scan, its three-kernel scan into one).
 // HBM bytes: scalars 2 × 32·L, entries 4·L·W written and read twice, 4·L·W written — each once, in full lines.
-constexpr int S2_TILE = 1024;    // scalars per tile (pass A): a row = (tile, all W ≤ 16 windows) stages ≤ 64 KiB of entries in LDS
-constexpr int S2_CHUNK = 12288;  // entries per chunk (pass B): 48 KiB of LDS
-constexpr int S2_LI_BITS = 10, S2_W_SHIFT = 10, S2_LOW_SHIFT = 14;
-// Workgroup size of the three big kernels (partition, chunk histogram, placement): 512 threads when the sort has the GPU to itself
-// or shares it with the transforms, 256 (`crowded`) when it runs beside the bucket accumulations — a 512-thread workgroup needs two
-// free wave slots with 64 registers each on ALL FOUR SIMDs of a CU at once, and beside three 136-register accumulation waves per
-// SIMD (104 registers left) that happens only when waves retire in step: H's sort took 9 ms beside the witness accumulations
-// (0.45 ms alone; its partition pass alone 4.9–5.3 ms) and had become what H's accumulation waits for.  One wave per SIMD fits the
-// gap: 2.9 ms (profiles/r05_ab_sort_wg256.txt).  The witness sort keeps 512: beside the transforms the smaller groups slow the
-// front end by 0.14 ms.
-constexpr int S2_THREADS_WIDE = 512, S2_THREADS_CROWDED = 256;
-constexpr int S2_RG = 32;        // row groups of the column scan
-constexpr int S2_GRP = 16;       // lanes that copy one run
-constexpr uint32_t S2_LONG = 192; // a run above this is copied by the whole workgroup
-constexpr size_t S2_LDS_MAX = 76 * 1024; // two workgroups per CU; ≤ 66 KiB at the benchmark sizes (room next to one NTT workgroup)
+// (tile, chunk and workgroup sizes: msm_sort_plan.h)
 
 // largest i < n with a[i] <= x (a non-decreasing, a[0] <= x)
 __device__ __forceinline__ uint32_t s2_upper(const uint32_t* a, uint32_t n, uint32_t x)
@@ -897,180 +882,142 @@ __global__ __launch_bounds__(1024) void sort2_order_scatter_kernel(const uint32_
 
 MsmGeom msm_geometry(uint32_t L, int c_cfg, int tab, int bits, int pf) { return msm_geometry_plan(L, c_cfg, tab, bits, pf); }
 
-eIcicleError msm_sort_run(const fe* d_scalars, uint32_t L, int c_cfg, int lbf, int mont_sc, hipStream_t s, SortPlan* pl, int tab, int bits, int pf, uint64_t entries_hint, bool crowded)
-{
-  pl->g = msm_geometry(L, c_cfg, tab, bits, pf);
-  const MsmGeom& g = pl->g;
-  pl->L = L;
-  pl->stream = s;
-  const uint32_t nb = g.NBb * (uint32_t)g.Wb;
-  pl->nbuckets = nb;
-  // Large-bucket threshold.  One thread sums one bucket, so the accumulation kernel lasts as long as its longest chain: buckets
-  // with more than `thr` entries go to the workgroup-per-chunk kernels instead.  The reference takes large_bucket_factor (10) ×
-  // the average (cuda_msm.cuh:205-220); here the default is 3 × the average with a floor of 64 — uniform scalars have no bucket
-  // beyond 2 × the average, while witnesses of real circuits (0/1 wires, bytes, small packed values) put hundreds of entries
-  // into the low buckets of the first window: with 10 × / floor 512 the synthetic stand-in circuits spent 2 ms (G1) / 6.5 ms (G2)
-  // in 500-addition chains of single threads (prove 11.2 → 6.3 ms at 1.0 M constraints, 14.1 → 8.3 ms at 1.4 M; 1.6 M uniform:
-  // unchanged).  The caller's large_bucket_factor (ConfigExtension) is honoured when given.
-  constexpr uint32_t large_floor = 64u;
-  const uint64_t avg = (entries_hint ? entries_hint : g.tab ? (uint64_t)L * g.W : (uint64_t)L * g.pf) / g.NB + 1;
-  uint32_t thr = (uint32_t)(avg * (uint64_t)(lbf > 0 ? lbf : 3));
-  if (thr < large_floor) thr = large_floor;
-  if (thr < 8) thr = 8;
-  pl->large_thr = thr;
-  const uint32_t nblocks = (nb + SCAN_B - 1) / SCAN_B;
-  const uint64_t nentries = (uint64_t)L * g.W;
-  // bucket index = partition | low bits (≤ 128 buckets per partition; ≤ 8192 partitions: two u32 per partition in LDS)
-  int low_bits = (g.c - 1) > 8 ? (g.c - 1) - 8 : 0;
-  if (g.tab) {
-    low_bits = tab_low_bits(g.c, g.IB, g.W);
-    if (low_bits < 0) low_bits = 7; // forced c that does not fit: the two_level test below fails and the global-histogram path runs
-  }
-  const uint32_t NP = g.NBb >> low_bits, nparts = nb >> low_bits;
-  const int idx_bits = g.tab ? g.IB + ilog2_ceil((uint64_t)g.W) : ilog2_ceil((L ? (uint64_t)L : 1) * g.pf);
-  if (idx_bits > 31) {
-    set_last_error("msm: %u scalars x precompute_factor %d exceed the 31-bit point index of a sort entry", L, g.pf);
-    return ICICLE_INVALID_ARGUMENT;
-  }
-  const bool two_level = idx_bits + low_bits <= 31 && low_bits <= 7 && (size_t)nparts * 8 <= 128 * 1024;
-  const uint32_t oblk = (nb + ORDER_BINS - 1) / ORDER_BINS;           // workgroups of the size-order pass
-  const uint32_t om = oblk * ORDER_BINS, oscan = (om + SCAN_B - 1) / SCAN_B;
-  // work items of large buckets: ≤ entries/CHUNK full chunks + one partial chunk per large bucket (≤ entries/thr of those)
-  pl->item_cap = (uint32_t)(nentries / MSM_LARGE_CHUNK + nentries / thr + 2);
-  // layout: counts | offsets | cursor | large_list | order | large_first | n_large[4] | tickets[TK] | bsum[nblocks] | part_count[nparts] | part_start[nparts+1] |
-  //         part_cursor[nparts] | blockhist[om] | obsum[oscan] | large_items[2·item_cap]
-  constexpr uint32_t TK = MSM_TICKET_SLOTS * 64;
-  constexpr uint32_t S2TK = 4; // tickets of the LDS-staged path's own last-workgroup steps (column scan, order scan)
-  const size_t head = (size_t)nb * 6 + 4 + TK + S2TK + nblocks + 3 * (size_t)nparts + 1 + om + oscan;
-  HIP_TRY(ws_alloc((void**)&pl->ws, (head + 2 * (size_t)pl->item_cap + 2) * 4, s), ICICLE_ALLOCATION_FAILED);
-  pl->counts = pl->ws;
-  pl->offsets = pl->counts + nb;
-  uint32_t* cursor = pl->offsets + nb;
-  pl->large_list = cursor + nb;
-  pl->order = pl->large_list + nb;
-  pl->large_first = pl->order + nb;
-  pl->n_large = pl->large_first + nb;
-  pl->tickets = pl->n_large + 4;
-  uint32_t* s2tickets = pl->tickets + TK;
-  uint32_t* bsum = s2tickets + S2TK;
-  uint32_t* part_count = bsum + nblocks;
-  uint32_t* part_start = part_count + nparts;
-  uint32_t* part_cursor = part_start + nparts + 1;
-  uint32_t* blockhist = part_cursor + nparts;
-  uint32_t* obsum = blockhist + om;
-  pl->large_items = reinterpret_cast<uint2*>(obsum + oscan + (head & 1)); // 8-byte aligned
-  HIP_TRY(ws_alloc((void**)&pl->sorted, (size_t)(nentries ? nentries : 1) * 4, s), ICICLE_ALLOCATION_FAILED);
-  uint32_t* tmp = nullptr;
-  WsScoped<uint32_t> tmp_block;
-  if (two_level) {
-    HIP_TRY(tmp_block.alloc((size_t)nentries, s), ICICLE_ALLOCATION_FAILED);
-    tmp = tmp_block;
-  }
+namespace {
+// what the enqueue stages share: the shape, the caller's plan with its pointers carved, and the workspace regions no caller sees
+struct SortCall {
+  const SortShape& sh;
+  SortPlan* pl;
+  const fe* d_scalars;
+  int mont_sc;
+  hipStream_t s;
+  uint32_t *cursor, *s2tickets, *bsum, *part_count, *part_start, *part_cursor, *blockhist, *obsum;
+};
 
-  // LDS-staged path (table mode, ≥ 2^17 entries): partitions of ≤ 28 K entries, ≤ 1024 buckets each
-  bool lds_sort = false;
-  int s2_pb = 0, s2_low = 0;
-  uint32_t s2_ntiles = 0, s2_maxchunks = 0;
-  size_t s2_lds_a = 0, s2_lds_b = 0;
-  if (g.tab && nentries >= (1u << 17) && g.W <= 16) { // (2^20 until round 5: with nine launches the staged path is no slower than the two-level one down to the witness heads and 8-way shards)
-    while ((nentries >> s2_pb) > 28000) s2_pb++;
-    s2_low = (g.c - 1) - s2_pb;
-    if (s2_low > 10) {
-      s2_pb += s2_low - 10;
-      s2_low = 10;
-    }
-    s2_ntiles = (L + S2_TILE - 1) / S2_TILE;
-    s2_maxchunks = (uint32_t)(nentries / S2_CHUNK) + (1u << s2_pb);
-    s2_lds_a = ((size_t)2 * (1u << s2_pb) + 1 + (size_t)S2_TILE * g.W) * 4;
-    s2_lds_b = ((size_t)2 * (1u << (s2_low > 0 ? s2_low : 0)) + 1 + s2_ntiles + 1 + S2_CHUNK) * 4;
-    lds_sort = s2_low >= 0 && s2_pb <= 12 && (1u << s2_pb) * (uint64_t)(1u << s2_low) == nb && s2_lds_a <= S2_LDS_MAX && s2_lds_b <= S2_LDS_MAX && S2_LOW_SHIFT + s2_low <= 31 &&
-               (size_t)(1u << s2_pb) * 4 <= 64 * 1024;
-  }
-  if (lds_sort) {
-    const uint32_t P = 1u << s2_pb, NL = 1u << s2_low, R = s2_ntiles;
-    // workspace: cnt[R][P] | off[R][P] | partial[S2_RG][P] | part_start[P + 1] | chunk_first[P + 1] | chunk_hist | chunk_off [maxchunks][NL] | order hist [256][P] | keytot[256]
-    WsScoped<uint32_t> s2ws;
-    const size_t n_cnt = (size_t)R * P, n_part = (size_t)S2_RG * P, n_ch = (size_t)s2_maxchunks * NL, n_bh = (size_t)ORDER_BINS * P;
-    HIP_TRY(s2ws.alloc(2 * n_cnt + n_part + 2 * (size_t)P + 2 + 2 * n_ch + n_bh + ORDER_BINS, s), ICICLE_ALLOCATION_FAILED);
-    uint32_t* cnt = s2ws.p;
-    uint32_t* off = cnt + n_cnt;      // first entry of every (row, partition) run inside its partition
-    uint32_t* partial = off + n_cnt;
-    uint32_t* pstart = partial + n_part;
-    uint32_t* cfirst = pstart + P + 1;
-    uint32_t* chist = cfirst + P + 1;
-    uint32_t* coff = chist + n_ch;
-    uint32_t* s2bh = coff + n_ch;
-    uint32_t* keytot = s2bh + n_bh;
-    WsScoped<uint32_t> s2tmp_own;
-    uint32_t* s2tmp = tmp; // the scatter buffer of the two-level path when that one was set up as well
-    if (!s2tmp) {
-      HIP_TRY(s2tmp_own.alloc((size_t)nentries, s), ICICLE_ALLOCATION_FAILED);
-      s2tmp = s2tmp_own.p;
-    }
-    static std::atomic<int> attr_dev_mask{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!(attr_dev_mask.load() & (1 << (dev & 31)))) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sort2_tile_partition_kernel<S2_THREADS_WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_MAX), ICICLE_UNKNOWN_ERROR);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sort2_chunk_place_kernel<S2_THREADS_WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_MAX), ICICLE_UNKNOWN_ERROR);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sort2_tile_partition_kernel<S2_THREADS_CROWDED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_MAX), ICICLE_UNKNOWN_ERROR);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sort2_chunk_place_kernel<S2_THREADS_CROWDED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S2_LDS_MAX), ICICLE_UNKNOWN_ERROR);
-      attr_dev_mask.fetch_or(1 << (dev & 31));
-    }
-    const dim3 cgrid((P + 255) / 256, S2_RG);
-    // nine launches: histogram (+ zeroing of n_large | tickets | this path's tickets), column scan (2), partition, chunk histogram,
-    // bucket scan (+ histogram of the bucket sizes), placement, size order (2)
-    hipLaunchKernelGGL(sort2_tile_hist_kernel, dim3(s2_ntiles), dim3(256), (size_t)P * 4, s, d_scalars, L, g, mont_sc, s2_low, P, cnt, pl->n_large, 4u + TK + S2TK);
-    hipLaunchKernelGGL(sort2_col_sum_kernel, cgrid, dim3(256), 0, s, cnt, R, P, partial, s2tickets, pstart, cfirst);
-    hipLaunchKernelGGL(sort2_col_apply_kernel, cgrid, dim3(256), 0, s, cnt, off, R, P, partial);
-#define ISNARK_S2_BIG(T)                                                                                                                                                                    \
-  hipLaunchKernelGGL(sort2_tile_partition_kernel<T>, dim3(R), dim3(T), s2_lds_a, s, d_scalars, L, g, mont_sc, s2_low, P, cnt, off, pstart, s2tmp);                                          \
-  hipLaunchKernelGGL(sort2_chunk_hist_kernel<T>, dim3(s2_maxchunks), dim3(T), 0, s, s2tmp, pstart, cfirst, P, s2_low, chist);                                                               \
-  hipLaunchKernelGGL(sort2_bucket_scan_kernel, dim3(P), dim3(NL), 0, s, chist, coff, pstart, cfirst, s2_low, thr, pl->counts, pl->offsets, pl->n_large, pl->large_list, pl->large_first,    \
-                     pl->large_items, pl->item_cap, s2bh);                                                                                                                                   \
-  hipLaunchKernelGGL(sort2_chunk_place_kernel<T>, dim3(s2_maxchunks), dim3(T), s2_lds_b, s, s2tmp, pstart, cfirst, P, s2_low, chist, coff, pl->offsets, off, R, g, pl->sorted)
-    if (crowded) {
-      ISNARK_S2_BIG(S2_THREADS_CROWDED);
-    } else {
-      ISNARK_S2_BIG(S2_THREADS_WIDE);
-    }
-#undef ISNARK_S2_BIG
-    hipLaunchKernelGGL(sort2_order_scan_kernel, dim3(ORDER_BINS), dim3(256), 0, s, s2bh, P, keytot, s2tickets + 1);
-    hipLaunchKernelGGL(sort2_order_scatter_kernel, dim3(P), dim3(NL), 0, s, pl->counts, s2_low, s2bh, keytot, pl->order);
-    return check_launch("msm_sort (LDS-staged)");
-  } else {
+// LDS-staged path, nine launches: histogram (+ zeroing of n_large | tickets | this path's tickets), column scan (2), partition, chunk
+// histogram, bucket scan (+ histogram of the bucket sizes), placement, size order (2).  `w`: its workspace (SortShape::s2), `tmp`: L·W entries
+LdsCapOnce g_s2_cap; // both widths of the two kernels with dynamic LDS, at the first staged sort of a device
+template <int THREADS>
+eIcicleError enqueue_staged(const SortCall& c, uint32_t* w, uint32_t* tmp)
+{
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  ICICLE_TRY(g_s2_cap.raise(dev, (int)S2_LDS_MAX, sort2_tile_partition_kernel<S2_THREADS_WIDE>, sort2_chunk_place_kernel<S2_THREADS_WIDE>, sort2_tile_partition_kernel<S2_THREADS_CROWDED>,
+                            sort2_chunk_place_kernel<S2_THREADS_CROWDED>));
+  const SortShape& sh = c.sh;
+  const MsmGeom& g = sh.g;
+  SortPlan* pl = c.pl;
+  hipStream_t s = c.s;
+  const uint32_t L = pl->L, P = 1u << sh.pb, NL = 1u << sh.low, R = sh.ntiles;
+  uint32_t *cnt = w + sh.s2.cnt, *off = w + sh.s2.off /* first entry of every (row, partition) run inside its partition */, *partial = w + sh.s2.partial;
+  uint32_t *pstart = w + sh.s2.pstart, *cfirst = w + sh.s2.cfirst, *chist = w + sh.s2.chist, *coff = w + sh.s2.coff, *bh = w + sh.s2.bh, *keytot = w + sh.s2.keytot;
+  const dim3 cgrid((P + 255) / 256, S2_RG);
+  hipLaunchKernelGGL(sort2_tile_hist_kernel, dim3(R), dim3(256), (size_t)P * 4, s, c.d_scalars, L, g, c.mont_sc, sh.low, P, cnt, pl->n_large, 4u + TK + S2TK);
+  hipLaunchKernelGGL(sort2_col_sum_kernel, cgrid, dim3(256), 0, s, cnt, R, P, partial, c.s2tickets, pstart, cfirst);
+  hipLaunchKernelGGL(sort2_col_apply_kernel, cgrid, dim3(256), 0, s, cnt, off, R, P, partial);
+  hipLaunchKernelGGL(sort2_tile_partition_kernel<THREADS>, dim3(R), dim3(THREADS), sh.lds_a, s, c.d_scalars, L, g, c.mont_sc, sh.low, P, cnt, off, pstart, tmp);
+  hipLaunchKernelGGL(sort2_chunk_hist_kernel<THREADS>, dim3(sh.maxchunks), dim3(THREADS), 0, s, tmp, pstart, cfirst, P, sh.low, chist);
+  hipLaunchKernelGGL(sort2_bucket_scan_kernel, dim3(P), dim3(NL), 0, s, chist, coff, pstart, cfirst, sh.low, sh.large_thr, pl->counts, pl->offsets, pl->n_large, pl->large_list, pl->large_first,
+                     pl->large_items, pl->item_cap, bh);
+  hipLaunchKernelGGL(sort2_chunk_place_kernel<THREADS>, dim3(sh.maxchunks), dim3(THREADS), sh.lds_b, s, tmp, pstart, cfirst, P, sh.low, chist, coff, pl->offsets, off, R, g, pl->sorted);
+  hipLaunchKernelGGL(sort2_order_scan_kernel, dim3(ORDER_BINS), dim3(256), 0, s, bh, P, keytot, c.s2tickets + 1);
+  hipLaunchKernelGGL(sort2_order_scatter_kernel, dim3(P), dim3(NL), 0, s, pl->counts, sh.low, bh, keytot, pl->order);
+  return check_launch("msm_sort (LDS-staged)");
+}
+
+// both other paths start from zeroed counters
+void enqueue_zero(const SortCall& c)
+{
+  const uint32_t nb = c.sh.nbuckets;
   unsigned zb = (3 * nb + 255) / 256;
   if (zb > 1024) zb = 1024;
-  hipLaunchKernelGGL(msm_zero_kernel, dim3(zb), dim3(256), 0, s, pl->counts, 3 * nb); // counts | offsets | cursor
-  hipLaunchKernelGGL(msm_zero_kernel, dim3(8), dim3(256), 0, s, pl->n_large, 4u + TK + S2TK + nblocks + nparts); // n_large | tickets | bsum | part_count
+  hipLaunchKernelGGL(msm_zero_kernel, dim3(zb), dim3(256), 0, c.s, c.pl->counts, 3 * nb); // counts | offsets | cursor
+  hipLaunchKernelGGL(msm_zero_kernel, dim3(8), dim3(256), 0, c.s, c.pl->n_large, 4u + TK + S2TK + c.sh.nblocks + c.sh.nparts); // n_large | tickets | bsum | part_count
+}
+// two-level path: counts and offsets come out of the partitions, no per-digit global atomics
+void enqueue_two_level(const SortCall& c, uint32_t* tmp)
+{
+  const SortShape& sh = c.sh;
+  SortPlan* pl = c.pl;
+  const uint32_t L = pl->L, nparts = sh.nparts;
+  enqueue_zero(c);
+  const unsigned pgrid = (L + PA_SCALARS - 1) / PA_SCALARS;
+  if (L) hipLaunchKernelGGL(msm_coarse_hist_kernel, dim3(pgrid), dim3(PA_THREADS), (size_t)nparts * 4, c.s, c.d_scalars, L, sh.g, c.mont_sc, sh.low_bits, nparts, c.part_count);
+  hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1), dim3(SCAN_T), 0, c.s, c.part_count, nparts, c.part_start, c.part_cursor);
+  if (L) {
+    if ((size_t)nparts * 8 > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msm_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)nparts * 8));
+    hipLaunchKernelGGL(msm_partition_kernel, dim3(pgrid), dim3(PA_THREADS), (size_t)nparts * 8, c.s, c.d_scalars, L, sh.g, c.mont_sc, sh.low_bits, sh.NP, nparts, c.part_cursor, tmp);
+    hipLaunchKernelGGL(msm_fine_count_kernel, dim3(nparts, PB_SPLIT), dim3(256), 0, c.s, tmp, c.part_start, sh.low_bits, pl->counts);
+  }
+  hipLaunchKernelGGL(msm_fine_place_kernel, dim3(nparts, PB_SPLIT), dim3(256), 0, c.s, tmp, c.part_start, pl->counts, c.cursor, sh.low_bits, sh.large_thr, pl->offsets, pl->n_large, pl->large_list,
+                     pl->large_first, pl->large_items, pl->item_cap, pl->sorted);
+}
+// global-histogram path: histogram, scan (+ list of large buckets), scatter
+void enqueue_global(const SortCall& c)
+{
+  const SortShape& sh = c.sh;
+  SortPlan* pl = c.pl;
+  const uint32_t L = pl->L, nb = sh.nbuckets;
+  enqueue_zero(c);
   const unsigned lgrid = (L + 255) / 256;
-  if (two_level) {
-    // counts and offsets come out of the partitions: no per-digit global atomics
-    const unsigned pgrid = (L + PA_SCALARS - 1) / PA_SCALARS;
-    if (L) hipLaunchKernelGGL(msm_coarse_hist_kernel, dim3(pgrid), dim3(PA_THREADS), (size_t)nparts * 4, s, d_scalars, L, g, mont_sc, low_bits, nparts, part_count);
-    hipLaunchKernelGGL(msm_part_scan_kernel, dim3(1), dim3(SCAN_T), 0, s, part_count, nparts, part_start, part_cursor);
-    if (L) {
-      if ((size_t)nparts * 8 > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(msm_partition_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)nparts * 8));
-      hipLaunchKernelGGL(msm_partition_kernel, dim3(pgrid), dim3(PA_THREADS), (size_t)nparts * 8, s, d_scalars, L, g, mont_sc, low_bits, NP, nparts, part_cursor, tmp);
-      hipLaunchKernelGGL(msm_fine_count_kernel, dim3(nparts, PB_SPLIT), dim3(256), 0, s, tmp, part_start, low_bits, pl->counts);
-    }
-    hipLaunchKernelGGL(msm_fine_place_kernel, dim3(nparts, PB_SPLIT), dim3(256), 0, s, tmp, part_start, pl->counts, cursor, low_bits, thr, pl->offsets, pl->n_large, pl->large_list,
-                       pl->large_first, pl->large_items, pl->item_cap, pl->sorted);
-  } else {
-    if (L) hipLaunchKernelGGL(msm_hist_kernel, dim3(lgrid), dim3(256), 0, s, d_scalars, L, g, mont_sc, pl->counts);
-    hipLaunchKernelGGL(msm_scan_sums_kernel, dim3(nblocks), dim3(SCAN_T), 0, s, pl->counts, nb, bsum);
-    hipLaunchKernelGGL(msm_scan_top_kernel, dim3(1), dim3(SCAN_T), 0, s, bsum, nblocks);
-    hipLaunchKernelGGL(msm_scan_finish_kernel, dim3(nblocks), dim3(SCAN_T), 0, s, pl->counts, nb, bsum, pl->offsets, cursor, thr, pl->n_large, pl->large_list, pl->large_first, pl->large_items, pl->item_cap);
-    if (L) hipLaunchKernelGGL(msm_scatter_kernel, dim3(lgrid), dim3(256), 0, s, d_scalars, L, g, mont_sc, cursor, pl->sorted);
-  }
-  }
-  // bucket ids by decreasing size
-  hipLaunchKernelGGL(msm_order_hist_kernel, dim3(oblk), dim3(ORDER_BINS), 0, s, pl->counts, nb, oblk, blockhist);
-  hipLaunchKernelGGL(msm_scan_sums_kernel, dim3(oscan), dim3(SCAN_T), 0, s, blockhist, om, obsum);
-  hipLaunchKernelGGL(msm_scan_top_kernel, dim3(1), dim3(SCAN_T), 0, s, obsum, oscan);
-  hipLaunchKernelGGL(msm_scan_apply_kernel, dim3(oscan), dim3(SCAN_T), 0, s, blockhist, om, obsum, blockhist);
-  hipLaunchKernelGGL(msm_order_scatter_kernel, dim3(oblk), dim3(ORDER_BINS), 0, s, pl->counts, nb, oblk, blockhist, pl->order);
+  if (L) hipLaunchKernelGGL(msm_hist_kernel, dim3(lgrid), dim3(256), 0, c.s, c.d_scalars, L, sh.g, c.mont_sc, pl->counts);
+  hipLaunchKernelGGL(msm_scan_sums_kernel, dim3(sh.nblocks), dim3(SCAN_T), 0, c.s, pl->counts, nb, c.bsum);
+  hipLaunchKernelGGL(msm_scan_top_kernel, dim3(1), dim3(SCAN_T), 0, c.s, c.bsum, sh.nblocks);
+  hipLaunchKernelGGL(msm_scan_finish_kernel, dim3(sh.nblocks), dim3(SCAN_T), 0, c.s, pl->counts, nb, c.bsum, pl->offsets, c.cursor, sh.large_thr, pl->n_large, pl->large_list, pl->large_first, pl->large_items, pl->item_cap);
+  if (L) hipLaunchKernelGGL(msm_scatter_kernel, dim3(lgrid), dim3(256), 0, c.s, c.d_scalars, L, sh.g, c.mont_sc, c.cursor, pl->sorted);
+}
+// bucket ids by decreasing size (the staged path orders them itself)
+eIcicleError enqueue_size_order(const SortCall& c)
+{
+  const SortShape& sh = c.sh;
+  hipLaunchKernelGGL(msm_order_hist_kernel, dim3(sh.oblk), dim3(ORDER_BINS), 0, c.s, c.pl->counts, sh.nbuckets, sh.oblk, c.blockhist);
+  hipLaunchKernelGGL(msm_scan_sums_kernel, dim3(sh.oscan), dim3(SCAN_T), 0, c.s, c.blockhist, sh.om, c.obsum);
+  hipLaunchKernelGGL(msm_scan_top_kernel, dim3(1), dim3(SCAN_T), 0, c.s, c.obsum, sh.oscan);
+  hipLaunchKernelGGL(msm_scan_apply_kernel, dim3(sh.oscan), dim3(SCAN_T), 0, c.s, c.blockhist, sh.om, c.obsum, c.blockhist);
+  hipLaunchKernelGGL(msm_order_scatter_kernel, dim3(sh.oblk), dim3(ORDER_BINS), 0, c.s, c.pl->counts, sh.nbuckets, sh.oblk, c.blockhist, c.pl->order);
   return check_launch("msm_sort");
+}
+} // namespace
+
+eIcicleError msm_sort_run(const fe* d_scalars, uint32_t L, int c_cfg, int lbf, int mont_sc, hipStream_t s, SortPlan* pl, int tab, int bits, int pf, uint64_t entries_hint, bool crowded)
+{
+  const SortShape sh = msm_sort_shape(L, c_cfg, lbf, tab, bits, pf, entries_hint);
+  pl->g = sh.g;
+  pl->L = L;
+  pl->stream = s;
+  pl->nbuckets = sh.nbuckets;
+  pl->large_thr = sh.large_thr;
+  if (sh.err != ICICLE_SUCCESS) {
+    set_last_error("%s", sh.msg);
+    return sh.err;
+  }
+  pl->item_cap = sh.item_cap;
+  // workspace, entries, and the scatter buffer of whichever path needs one
+  HIP_TRY(ws_alloc((void**)&pl->ws, sh.ws.total * 4, s), ICICLE_ALLOCATION_FAILED);
+  HIP_TRY(ws_alloc((void**)&pl->sorted, (size_t)(sh.nentries ? sh.nentries : 1) * 4, s), ICICLE_ALLOCATION_FAILED);
+  WsScoped<uint32_t> tmp, s2ws, s2tmp;
+  if (sh.two_level_ok) HIP_TRY(tmp.alloc((size_t)sh.nentries, s), ICICLE_ALLOCATION_FAILED);
+  if (sh.path == SORT_STAGED) {
+    HIP_TRY(s2ws.alloc(sh.s2.total, s), ICICLE_ALLOCATION_FAILED);
+    if (!tmp.p) HIP_TRY(s2tmp.alloc((size_t)sh.nentries, s), ICICLE_ALLOCATION_FAILED);
+  }
+  uint32_t* const w = pl->ws;
+  pl->counts = w + sh.ws.counts;
+  pl->offsets = w + sh.ws.offsets;
+  pl->large_list = w + sh.ws.large_list;
+  pl->order = w + sh.ws.order;
+  pl->large_first = w + sh.ws.large_first;
+  pl->n_large = w + sh.ws.n_large;
+  pl->tickets = w + sh.ws.tickets;
+  pl->large_items = reinterpret_cast<uint2*>(w + sh.ws.large_items);
+  const SortCall c = {sh, pl, d_scalars, mont_sc, s, w + sh.ws.cursor, w + sh.ws.s2tickets, w + sh.ws.bsum, w + sh.ws.part_count, w + sh.ws.part_start, w + sh.ws.part_cursor,
+                      w + sh.ws.blockhist, w + sh.ws.obsum};
+  if (sh.path == SORT_STAGED) {
+    uint32_t* const t = tmp.p ? tmp.p : s2tmp.p;
+    return crowded ? enqueue_staged<S2_THREADS_CROWDED>(c, s2ws.p, t) : enqueue_staged<S2_THREADS_WIDE>(c, s2ws.p, t);
+  }
+  if (sh.path == SORT_TWO_LEVEL) enqueue_two_level(c, tmp.p);
+  else enqueue_global(c);
+  return enqueue_size_order(c);
 }
 
 void msm_sort_release(SortPlan* pl)

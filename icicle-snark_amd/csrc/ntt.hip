@@ -24,6 +24,8 @@
 //  * transforms of 2^11 elements and more whose passes can all work on full tiles run the same plan on a LAZY
 //    RADIX-2^29 field (fr29.h, ntt_pass29_kernel below): nine-word tiles, no reduction after additions, value
 //    bounds planned on the host — ≈ 20 % faster; the 8×32-bit kernels keep the small and ragged sizes.
+// The host plan — pass split, tile geometry, bounds, LDS, grids — is ntt_plan (ntt_plan.h, walked on the host by
+// tests/ntt_plan_check.cpp); ntt_impl below stages the operands, asks for the plan and enqueues it (enqueue_passes).
 #include <atomic>
 #include <mutex>
 #include <string.h>
@@ -33,15 +35,14 @@
 #include "ff.h"
 #include "fr29.h"
 #include "ntt_fuse.h"
+#include "ntt_plan.h"
 
 using namespace bn254;
 using namespace isnark;
+using namespace isnark::ntt;
 
 namespace {
 
-constexpr int LOG_TILE = 11; // 2048 elements per workgroup
-constexpr int NT = 256;      // threads per workgroup
-constexpr int MAX_LOG_R = 9; // rows per tile ≤ 512 so that columns ≥ 4 (128-B runs)
 constexpr int OMEGAS_COUNT = 28;
 
 // fp_config::rou — primitive 2^28-th root of unity, standard form
@@ -86,27 +87,6 @@ __global__ void gen_twiddles_kernel(fe* tw, const fe* pw /* root^(2^j), Montgome
     if ((i >> j) & 1) acc = Fr::mul(acc, pw[j]);
   tw[i] = acc;
 }
-
-struct PassParams {
-  int log_r, log_c;
-  uint32_t tiles_per_group_log; // b -> b_hi = b >> log, b_lo = b & mask
-  uint64_t in_hi, in_lo, in_row, in_col;
-  uint64_t out_hi, out_lo, out_row, out_col;
-  uint32_t tw_mul;       // inter-pass twiddle exponent = k · (b_lo·C + c) · tw_mul ; 0 = none
-  uint32_t stage_stride; // ω_R^e = tw[e · stage_stride]
-  uint32_t n_mask;       // N − 1
-  int inverse;
-  int scale; // multiply by n^-1 (last pass of an inverse transform)
-  uint64_t batch_stride;
-  int load_rows_fastest; // global loads: consecutive threads walk rows (in_row == 1) instead of columns
-  // prover fusions (last pass only; full 2048-element tiles):
-  const fe* scale_tab;   // non-null: out[i] *= scale_tab[i·scale_stride] (i = natural output index) INSTEAD of the n⁻¹ constant —
-  uint32_t scale_stride; // the prover passes n⁻¹·g^i, which folds the coset keys of src/proof_helper.rs:121-141 into the inverse transform
-  int fuse_abc;          // batch of 3 rows [B | A | C'] handled by ONE workgroup per tile: writes A·B − C' (src/proof_helper.rs:154-167) to row 0 of `out`
-  // radix-2^29 passes: 1-D grid of tiles·batch workgroups with the rows of ONE tile on consecutive workgroups of the SAME XCD
-  // (workgroup b runs on XCD b mod 8): they gather the same inter-pass twiddles, and each XCD has its own L2
-  uint32_t xcd_batch;    // 0: grid (tiles, batch) as before; else the batch count of the 1-D grid (tiles is a multiple of 8)
-};
 
 __device__ __forceinline__ uint32_t tw_index(uint32_t e, uint32_t n_mask, int inverse)
 {
@@ -417,11 +397,6 @@ __global__ __launch_bounds__(NT, 2) void ntt_pass_kernel(const fe* __restrict__ 
 //    K_l·r of every level and says whether the tile needs one `shrink` before its last round;
 //  * everything that leaves a pass has gone through a product (inter-pass twiddle, 1/n, per-element scale) and is < 4·r, which
 //    fits the packed 32-byte form; the LAST pass of a transform stores canonical values.
-struct Plan29 {
-  uint32_t b0;       // bound of the tile's values at the load (multiples of r): level l of a round that is not the last sees b0·2^l
-  uint32_t bs;       // bound at the start of the last round (after the shrink, if any): its level t sees (bs + 1)·2^t − 1
-  int shrink_last;   // apply fr29::shrink to the operands of the last round
-};
 struct Lds29 {
   uint4 *lo, *hi;
   uint32_t* top;
@@ -722,13 +697,6 @@ __global__ void coset_mul_kernel(fe* data, uint64_t n, int batch, const fe* gpow
   }
 }
 
-int ilog2(uint64_t x)
-{
-  int l = 0;
-  while ((1ull << l) < x) l++;
-  return l;
-}
-
 } // namespace
 
 namespace isnark {
@@ -841,63 +809,90 @@ ISNARK_API eIcicleError bn254_get_root_of_unity_from_domain(uint64_t logn, bn254
 }
 
 namespace {
-// pass plan of the radix-2^29 kernel: 2 or 3 passes of 4 … 8 bits whose tiles are all full (2048 elements), fewest LDS rounds
-bool plan29(int logn, int& np, int (&lr)[3])
+// the caller's layout: the transform itself runs natural → natural; bit-reversed inputs / outputs and the columns_batch layout
+// (element i of batch b at b + i·batch) are handled by one re-layout pass on either side (relayout_kernel)
+struct Relayout {
+  bool rev_in, rev_out, cols;
+  WsScoped<fe> pre, post;
+};
+// stage 2: `d_in` / `d_out` become what the passes read and write
+eIcicleError stage_layout(Relayout& r, const fe*& d_in, fe*& d_out, uint64_t n, int batch, int logn, hipStream_t s)
 {
-  int best = 1 << 30;
-  auto full = [&](const int* l, int n) {
-    uint64_t rem = 1ull << logn;
-    for (int pi = 0; pi < n; pi++) {
-      const uint64_t C = 1ull << (LOG_TILE - l[pi]);
-      if (pi < n - 1) {
-        const uint64_t tail = rem >> l[pi];
-        if (C > tail) return false;
-        rem = tail;
-      } else if (C > (1ull << l[0])) return false;
-    }
-    return true;
-  };
-  for (int a = 8; a >= 4; a--)
-    for (int b = 8; b >= 4; b--) {
-      {
-        const int l2[2] = {a, b};
-        const int cost = (a + 2) / 3 + (b + 2) / 3;
-        if (a + b == logn && cost < best && full(l2, 2)) { best = cost; np = 2; lr[0] = a; lr[1] = b; lr[2] = 0; }
-      }
-      for (int c = 8; c >= 4; c--) {
-        const int l3[3] = {a, b, c};
-        const int cost = (a + 2) / 3 + (b + 2) / 3 + (c + 2) / 3 + 1; // a third pass costs more than a round
-        if (a + b + c == logn && cost < best && full(l3, 3)) { best = cost; np = 3; lr[0] = a; lr[1] = b; lr[2] = c; }
-      }
-    }
-  return best < (1 << 30);
+  const uint64_t total = n * batch;
+  if (r.rev_in || r.cols) {
+    HIP_TRY(r.pre.alloc(total, s), ICICLE_ALLOCATION_FAILED);
+    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_in, r.pre.p, n, batch, logn, r.rev_in ? 1 : 0, r.cols ? 1 : 0, 0);
+    ICICLE_TRY(check_launch("ntt_relayout_in"));
+    d_in = r.pre.p;
+  }
+  if (r.rev_out || r.cols) {
+    HIP_TRY(r.post.alloc(total, s), ICICLE_ALLOCATION_FAILED);
+    d_out = r.post.p;
+  }
+  return ICICLE_SUCCESS;
 }
-// value bounds of one pass (multiples of r): b_in at the load, ×2 per level (sums), 2B + 1 per level of the last round (its unit
-// twiddles leave differences unmultiplied); one shrink (B → B/4 + 1) in front of the last round when the end would pass `limit`
-bool bounds29(int log_r, uint32_t b_in, uint32_t limit, Plan29& pl)
+// stage 3: coset generator (NTTConfig.coset_gen): forward evaluates on g·H (x_j *= g^j first), inverse interpolates from g·H
+// (multiply by g^-j afterwards) — ntt.h:52-64, mixed_radix_ntt.cu:911-1017.  *d_gpow = g^(±2^j), Montgomery; nullptr: g = 1
+eIcicleError coset_powers(const NTTConfig* cfg, bool inverse, int logn, fe** d_gpow)
 {
-  memset(&pl, 0, sizeof pl);
-  const int q_last = log_r % 3 ? log_r % 3 : 3;
-  pl.b0 = b_in;
-  uint32_t B = b_in << (log_r - q_last); // at the start of the last round
-  uint32_t e = B;
-  for (int k = 0; k < q_last; k++) e = 2 * e + 1;
-  if (e > limit) {
-    pl.shrink_last = 1;
-    B = B / 4 + 2;
-  }
-  pl.bs = B;
-  for (int k = 0; k < q_last; k++) {
-    if (2 * B + 1 >= 1350) return false; // (K·r)_8 + a_8 must fit 32 bits
-    B = 2 * B + 1;
-  }
-  return B <= limit && (uint64_t)b_in << (log_r - q_last) < 650;
+  fe g;
+  memcpy(g.l, cfg->coset_gen.limbs, 32);
+  *d_gpow = nullptr;
+  if (Fr::eq(g, Fr::one_std())) return ICICLE_SUCCESS;
+  fe gm = Fr::to_mont(g);
+  if (inverse) gm = Fr::inv(gm);
+  std::vector<fe> gp(logn > 0 ? logn : 1);
+  fe cur = gm;
+  for (int j = 0; j < logn; j++) { gp[j] = cur; cur = Fr::sqr(cur); }
+  HIP_TRY(hipMalloc((void**)d_gpow, gp.size() * sizeof(fe)), ICICLE_ALLOCATION_FAILED);
+  HIP_TRY(hipMemcpy(*d_gpow, gp.data(), gp.size() * sizeof(fe), hipMemcpyHostToDevice), ICICLE_COPY_FAILED);
+  return ICICLE_SUCCESS;
 }
-} // namespace
+eIcicleError coset_mul(fe* data, uint64_t n, int batch, const fe* d_gpow, int logn, hipStream_t s)
+{
+  hipLaunchKernelGGL(coset_mul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, data, n, batch, d_gpow, logn);
+  return check_launch("coset_mul");
+}
 
-namespace {
+// stage 5: the plan's passes, one launch each, over buf[BUF_IN | BUF_SCRATCH | BUF_OUT]
+eIcicleError enqueue_passes(const Plan& plan, const Domain& dom, fe* const buf[3], uint64_t n, const isnark::NttFuse* fuse, hipStream_t s)
+{
+  static LdsCapOnce cap, cap29; // (the 8×32-bit kernels' cap is raised by every first transform of a device, as it always was)
+  const int devi = dom.device >= 0 && dom.device < MAX_DEVICES ? dom.device : 0;
+  ICICLE_TRY(cap.raise(devi, 160 * 1024, ntt_pass_kernel<false>, ntt_pass_kernel<true>));
+  if (plan.use29) ICICLE_TRY(cap29.raise(devi, 160 * 1024, ntt_pass29_kernel<false>, ntt_pass29_kernel<true>));
+  fe ninv = Fr::zero();
+  ninv.l[0] = 1;
+  if (plan.pass[0].p.inverse) {
+    fe nn = Fr::zero();
+    nn.l[0] = (uint32_t)n;
+    ninv = Fr::inv(Fr::to_mont(nn)); // n^-1 in Montgomery form
+  }
+  fe c32 = Fr::zero();
+  c32.l[0] = 32;
+  const fe ninv261 = Fr::mul(ninv, Fr::to_mont(c32)); // n⁻¹·2^256 → n⁻¹·2^261
+  for (int pi = 0; pi < plan.np; pi++) {
+    const Pass& ps = plan.pass[pi];
+    PassParams p = ps.p;
+    if (ps.scale_tab) {
+      p.scale_tab = fuse->scale_tab;
+      p.scale_stride = fuse->scale_stride;
+    }
+    const fe* src = buf[ps.src];
+    fe* dst = ps.fused ? fuse->fused_out : buf[ps.dst];
+    const dim3 grid(ps.grid_x, ps.grid_y);
+    if (plan.use29 && ps.fused) hipLaunchKernelGGL(ntt_pass29_kernel<true>, grid, dim3(NT), ps.lds, s, src, dst, dom.tw29, p, ps.pl29, ninv261);
+    else if (plan.use29) hipLaunchKernelGGL(ntt_pass29_kernel<false>, grid, dim3(NT), ps.lds, s, src, dst, dom.tw29, p, ps.pl29, ninv261);
+    else if (ps.fused) hipLaunchKernelGGL(ntt_pass_kernel<true>, grid, dim3(NT), ps.lds, s, src, dst, dom.tw, p, ninv);
+    else hipLaunchKernelGGL(ntt_pass_kernel<false>, grid, dim3(NT), ps.lds, s, src, dst, dom.tw, p, ninv);
+    ICICLE_TRY(check_launch("ntt_pass"));
+  }
+  return ICICLE_SUCCESS;
+}
+
 eIcicleError ntt_impl(const bn254_scalar_t* input, int size, NTTDir dir, const NTTConfig* cfg, bn254_scalar_t* output, const isnark::NttFuse* fuse)
 {
+  // 1. arguments and domain
   if (!cfg || !input || !output) return ICICLE_INVALID_POINTER;
   if (size <= 0 || (size & (size - 1))) {
     set_last_error("ntt: size %d is not a power of two", size);
@@ -907,12 +902,6 @@ eIcicleError ntt_impl(const bn254_scalar_t* input, int size, NTTDir dir, const N
     set_last_error("ntt: unknown ordering %d", (int)cfg->ordering);
     return ICICLE_INVALID_ARGUMENT;
   }
-  // Orderings (icicle/include/icicle/ntt.h:32-43): the transform itself runs natural → natural; bit-reversed inputs /
-  // outputs and the columns_batch layout (element i of batch b at b + i·batch) are handled by one re-layout pass on
-  // either side.  kNM / kMN ("mixed" digit order, defined by the CUDA backend's radix plan) are taken as kNR / kRN,
-  // exactly as the reference's radix-2 CPU backend does (ntt.h:32).
-  const bool rev_in = cfg->ordering == kRN || cfg->ordering == kRR || cfg->ordering == kMN;
-  const bool rev_out = cfg->ordering == kNR || cfg->ordering == kRR || cfg->ordering == kNM;
   ICICLE_TRY(require_device());
   const int logn = ilog2((uint64_t)size);
   Domain dom;
@@ -930,193 +919,54 @@ eIcicleError ntt_impl(const bn254_scalar_t* input, int size, NTTDir dir, const N
   hipStream_t s = (hipStream_t)cfg->stream;
   const bool inverse = dir == kInverse;
 
+  // 2. operands on the device, in the passes' layout.  Orderings (icicle/include/icicle/ntt.h:32-43): kNM / kMN ("mixed" digit order,
+  // defined by the CUDA backend's radix plan) are taken as kNR / kRN, exactly as the reference's radix-2 CPU backend does (ntt.h:32).
   Staged sin, sout;
   ICICLE_TRY(sin.in(input, total * sizeof(fe), cfg->are_inputs_on_device, s));
   ICICLE_TRY(sout.out(output, total * sizeof(fe), cfg->are_outputs_on_device, s));
+  Relayout lay;
+  lay.rev_in = cfg->ordering == kRN || cfg->ordering == kRR || cfg->ordering == kMN;
+  lay.rev_out = cfg->ordering == kNR || cfg->ordering == kRR || cfg->ordering == kNM;
+  lay.cols = cfg->columns_batch && batch > 1;
   const fe* d_in = sin.ptr<fe>();
-  fe* d_final = sout.ptr<fe>();
-  const bool cols = cfg->columns_batch && batch > 1;
-  WsScoped<fe> pre_block, post_block;
-  if (rev_in || cols) {
-    HIP_TRY(pre_block.alloc(total, s), ICICLE_ALLOCATION_FAILED);
-    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_in, pre_block.p, n, batch, logn, rev_in ? 1 : 0, cols ? 1 : 0, 0);
-    ICICLE_TRY(check_launch("ntt_relayout_in"));
-    d_in = pre_block.p;
-  }
+  fe* const d_final = sout.ptr<fe>();
   fe* d_out = d_final;
-  if (rev_out || cols) {
-    HIP_TRY(post_block.alloc(total, s), ICICLE_ALLOCATION_FAILED);
-    d_out = post_block.p;
-  }
+  ICICLE_TRY(stage_layout(lay, d_in, d_out, n, batch, logn, s));
 
-  // coset generator (NTTConfig.coset_gen): forward evaluates on g·H (x_j *= g^j first), inverse
-  // interpolates from g·H (multiply by g^-j afterwards) — ntt.h:52-64, mixed_radix_ntt.cu:911-1017.
-  fe g;
-  memcpy(g.l, cfg->coset_gen.limbs, 32);
-  const bool has_coset = !Fr::eq(g, Fr::one_std());
+  // 3. coset powers
   fe* d_gpow = nullptr;
-  if (has_coset) {
-    fe gm = Fr::to_mont(g);
-    if (inverse) gm = Fr::inv(gm);
-    std::vector<fe> gp(logn > 0 ? logn : 1);
-    fe cur = gm;
-    for (int j = 0; j < logn; j++) { gp[j] = cur; cur = Fr::sqr(cur); }
-    HIP_TRY(hipMalloc((void**)&d_gpow, gp.size() * sizeof(fe)), ICICLE_ALLOCATION_FAILED);
-    HIP_TRY(hipMemcpy(d_gpow, gp.data(), gp.size() * sizeof(fe), hipMemcpyHostToDevice), ICICLE_COPY_FAILED);
-  }
+  ICICLE_TRY(coset_powers(cfg, inverse, logn, &d_gpow));
 
-  // pass plan
-  int np, lr[3] = {0, 0, 0};
-  if (logn <= MAX_LOG_R) { np = 1; lr[0] = logn; }
-  else if (logn <= 2 * MAX_LOG_R) { np = 2; lr[0] = (logn + 1) / 2; lr[1] = logn / 2; }
-  else { np = 3; lr[0] = MAX_LOG_R; lr[1] = (logn - MAX_LOG_R + 1) / 2; lr[2] = (logn - MAX_LOG_R) / 2; } // 9 bits = three radix-8 rounds
-  // transforms whose passes can all work on full tiles of at most 8 bits run on the lazy radix-2^29 field (ntt_pass29_kernel)
+  // 4. plan
   static const bool allow29 = env_int("ICICLE_SNARK_NTT29", 1) != 0;
-  int np29 = 0, lr29[3] = {0, 0, 0};
-  const bool use29 = allow29 && dom.tw29 && plan29(logn, np29, lr29);
-  if (use29) {
-    np = np29;
-    for (int k = 0; k < 3; k++) lr[k] = lr29[k];
+  const FuseKind kind = fuse && fuse->fused_out ? FUSE_ABC : fuse && fuse->scale_tab ? FUSE_SCALE_TAB : FUSE_NONE;
+  const Plan plan = ntt_plan(logn, dom.log_n, batch, inverse, allow29, dom.tw29 != nullptr, kind, lay.rev_out, lay.cols);
+  if (plan.err != ICICLE_SUCCESS) {
+    set_last_error("%s", plan.msg);
+    return plan.err;
   }
 
-  fe* scratch = nullptr;
-  WsScoped<fe> scratch_block;
-  const bool need_pre_coset = has_coset && !inverse;
-  if (np > 1 || need_pre_coset) {
-    HIP_TRY(scratch_block.alloc(total, s), ICICLE_ALLOCATION_FAILED);
-    scratch = scratch_block;
+  // 5. passes (the forward coset multiplies x_j by g^j into scratch first, and the transform reads that)
+  WsScoped<fe> scratch;
+  const bool pre_coset = d_gpow && !inverse;
+  if (plan.need_scratch || pre_coset) HIP_TRY(scratch.alloc(total, s), ICICLE_ALLOCATION_FAILED);
+  if (pre_coset) {
+    HIP_TRY(hipMemcpyAsync(scratch.p, d_in, total * sizeof(fe), hipMemcpyDeviceToDevice, s), ICICLE_COPY_FAILED);
+    ICICLE_TRY(coset_mul(scratch.p, n, batch, d_gpow, logn, s));
+    d_in = scratch.p;
   }
-  if (need_pre_coset) {
-    // x_j *= g^j into scratch, then transform from scratch
-    HIP_TRY(hipMemcpyAsync(scratch, d_in, total * sizeof(fe), hipMemcpyDeviceToDevice, s), ICICLE_COPY_FAILED);
-    hipLaunchKernelGGL(coset_mul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, n, batch, d_gpow, logn);
-    ICICLE_TRY(check_launch("coset_mul"));
-    d_in = scratch;
-  }
+  fe* const buf[3] = {const_cast<fe*>(d_in), scratch.p, d_out};
+  ICICLE_TRY(enqueue_passes(plan, dom, buf, n, fuse, s));
 
-  fe ninv = Fr::zero();
-  ninv.l[0] = 1;
-  if (inverse) {
-    fe nn = Fr::zero();
-    nn.l[0] = (uint32_t)n;
-    ninv = Fr::inv(Fr::to_mont(nn)); // n^-1 in Montgomery form
-  }
-  const uint32_t N = 1u << dom.log_n;
-  const uint32_t dom_stride = N >> logn; // ω_n = ω_N^dom_stride
-
-  uint64_t rem = n; // n_p : size of the sub-transform still to do at pass p
-  for (int pi = 0; pi < np; pi++) {
-    PassParams p;
-    memset(&p, 0, sizeof p);
-    const bool last = pi == np - 1;
-    p.log_r = lr[pi];
-    const uint64_t R = 1ull << p.log_r;
-    const uint64_t tail = rem / R; // n_{p+1}
-    int log_c = LOG_TILE - p.log_r;
-    p.inverse = inverse;
-    p.scale = last && inverse;
-    p.n_mask = N - 1;
-    p.stage_stride = N >> p.log_r;
-    p.batch_stride = n;
-    const fe* src = pi == 0 ? d_in : scratch;
-    fe* dst = last ? d_out : scratch;
-    uint64_t tiles;
-    if (!last) {
-      // in-place positions: pos = head·rem + j·tail + t ; tile = C consecutive t
-      if ((uint64_t)(1 << log_c) > tail) log_c = ilog2(tail);
-      p.log_c = log_c;
-      const uint64_t C = 1ull << log_c;
-      const uint64_t tpg = tail / C; // tiles per head
-      p.tiles_per_group_log = ilog2(tpg);
-      p.in_hi = rem; p.in_lo = C; p.in_row = tail; p.in_col = 1;
-      p.out_hi = rem; p.out_lo = C; p.out_row = tail; p.out_col = 1;
-      p.tw_mul = (uint32_t)((uint64_t)dom_stride * (n / rem)); // ω_rem^(k·t) = ω_N^(dom_stride·(n/rem)·k·t)
-      p.load_rows_fastest = 0;
-      tiles = (n / rem) * tpg;
-    } else {
-      // last pass: rows contiguous (tail == 1); columns walk the leading output digit k1
-      const uint64_t R1 = np == 1 ? 1 : (1ull << lr[0]);
-      if ((uint64_t)(1 << log_c) > R1) log_c = ilog2(R1);
-      p.log_c = log_c;
-      const uint64_t C = 1ull << log_c;
-      const uint64_t mid = n / (R1 * R);   // product of the middle radices (R2 for 3 passes, else 1)
-      const uint64_t tpg = R1 / C;         // tiles per middle index
-      p.tiles_per_group_log = ilog2(tpg);
-      p.in_lo = C * (n / R1); p.in_hi = R; p.in_row = 1; p.in_col = n / R1;
-      p.out_lo = C; p.out_hi = R1; p.out_row = R1 * mid; p.out_col = 1;
-      p.tw_mul = 0;
-      p.load_rows_fastest = 1;
-      tiles = tpg * mid;
-    }
-    const size_t lds = ((size_t)2 << (p.log_r + p.log_c)) * 16 + (size_t)(R >> 1) * 32 + 32;
-    static std::atomic<bool> lds_attr_set[MAX_DEVICES]; // function attributes are per device
-    const int devi = dom.device >= 0 && dom.device < MAX_DEVICES ? dom.device : 0;
-    if (!lds_attr_set[devi].load(std::memory_order_acquire)) {
-      HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), ICICLE_UNKNOWN_ERROR);
-      HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), ICICLE_UNKNOWN_ERROR);
-      lds_attr_set[devi].store(true, std::memory_order_release);
-    }
-    const bool full_tile = ((size_t)1 << (p.log_r + p.log_c)) == (size_t)NT * 8;
-    if (last && fuse && fuse->scale_tab && inverse) {
-      p.scale_tab = fuse->scale_tab;
-      p.scale_stride = fuse->scale_stride;
-    }
-    Plan29 pl29;
-    size_t lds29 = 0;
-    fe ninv261 = ninv;
-    if (use29) {
-      // bounds: the first pass reads canonical values, later ones what a pass stored (< 4); a pass ends in a product (→ < 4) except
-      // the last pass of a plain forward transform and the fused epilogue (→ canon / sub<600>)
-      const bool ends_in_product = !last || (inverse && true);
-      if (!full_tile || !bounds29(p.log_r, pi == 0 ? 1u : 4u, ends_in_product ? 506u : 598u, pl29)) {
-        set_last_error("ntt: internal error — no radix-2^29 bound plan for a %d-bit pass", p.log_r);
-        return ICICLE_UNKNOWN_ERROR;
-      }
-      lds29 = (size_t)NT * 8 * 36 + (size_t)(R >> 1) * 36;
-      static std::atomic<bool> lds29_attr_set[MAX_DEVICES];
-      if (!lds29_attr_set[devi].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass29_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), ICICLE_UNKNOWN_ERROR);
-        HIP_TRY(hipFuncSetAttribute((const void*)ntt_pass29_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), ICICLE_UNKNOWN_ERROR);
-        lds29_attr_set[devi].store(true, std::memory_order_release);
-      }
-      fe c32 = Fr::zero();
-      c32.l[0] = 32;
-      ninv261 = Fr::mul(ninv, Fr::to_mont(c32)); // n⁻¹·2^256 → n⁻¹·2^261
-    }
-    if (last && fuse && fuse->fused_out) {
-      // A·B − C' epilogue: one workgroup per tile walks the three rows
-      if (!full_tile || batch != 3 || inverse || rev_out || cols) {
-        set_last_error("ntt: fused epilogue needs a forward batch-of-3 transform with full tiles");
-        return ICICLE_INVALID_ARGUMENT;
-      }
-      p.fuse_abc = 1;
-      if (use29) hipLaunchKernelGGL(ntt_pass29_kernel<true>, dim3((unsigned)tiles, 1), dim3(NT), lds29, s, src, fuse->fused_out, dom.tw29, p, pl29, ninv261);
-      else hipLaunchKernelGGL(ntt_pass_kernel<true>, dim3((unsigned)tiles, 1), dim3(NT), lds, s, src, fuse->fused_out, dom.tw, p, ninv);
-    } else if (use29) {
-      // (measured at 3 × 2^21: 0.75 / 0.85 → 0.74 / 0.83 ms per transform alone, −0.1 to −0.2 ms per prove at 1.6 M constraints)
-      if (batch > 1 && tiles % 8 == 0 && (uint64_t)tiles * (uint64_t)batch < (1ull << 31)) {
-        p.xcd_batch = (uint32_t)batch;
-        hipLaunchKernelGGL(ntt_pass29_kernel<false>, dim3((unsigned)(tiles * batch), 1), dim3(NT), lds29, s, src, dst, dom.tw29, p, pl29, ninv261);
-      } else
-        hipLaunchKernelGGL(ntt_pass29_kernel<false>, dim3((unsigned)tiles, (unsigned)batch), dim3(NT), lds29, s, src, dst, dom.tw29, p, pl29, ninv261);
-    } else {
-      hipLaunchKernelGGL(ntt_pass_kernel<false>, dim3((unsigned)tiles, (unsigned)batch), dim3(NT), lds, s, src, dst, dom.tw, p, ninv);
-    }
-    ICICLE_TRY(check_launch("ntt_pass"));
-    rem = tail;
-  }
-
-  if (has_coset && inverse) {
-    hipLaunchKernelGGL(coset_mul_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_out, n, batch, d_gpow, logn);
-    ICICLE_TRY(check_launch("coset_mul"));
-  }
-  if (rev_out || cols) {
-    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_out, d_final, n, batch, logn, rev_out ? 1 : 0, cols ? 1 : 0, 1);
+  // 6. inverse coset, the caller's layout, releases
+  if (d_gpow && inverse) ICICLE_TRY(coset_mul(d_out, n, batch, d_gpow, logn, s));
+  if (lay.rev_out || lay.cols) {
+    hipLaunchKernelGGL(relayout_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_out, d_final, n, batch, logn, lay.rev_out ? 1 : 0, lay.cols ? 1 : 0, 1);
     ICICLE_TRY(check_launch("ntt_relayout_out"));
   }
-  pre_block.release();
-  post_block.release();
-  scratch_block.release();
+  lay.pre.release();
+  lay.post.release();
+  scratch.release();
   if (d_gpow) {
     HIP_TRY(hipStreamSynchronize(s), ICICLE_SYNCHRONIZATION_FAILED);
     HIP_TRY(hipFree(d_gpow), ICICLE_DEALLOCATION_FAILED);

@@ -1,6 +1,6 @@
 """bn254_msm / bn254_g2_msm at every window geometry of their host plan (needs an MI355X), bit-exact against the CPU oracle.
 
-msm_geometry (csrc/msm_recode.h) and msm_sort_run (csrc/msm_sort.hip) switch on the length L: automatic c = ⌈log2 L⌉ − 4 in the
+msm_geometry (csrc/msm_recode.h) and msm_sort_shape (csrc/msm_sort_plan.h) switch on the length L: automatic c = ⌈log2 L⌉ − 4 in the
 classic layout, with the top windows narrowed by one bit at c = 5, 8, 15, 16; behind device-resident bases of 2^15 points and more
 the table mode with c = 15 (two-level sort: 17 windows), 16, 17, 19 (twelve of fourteen windows narrowed) and 20, whose table
 msm_table_refresh_kernel rebuilds from (c, W, wide) when the bases change behind the library's back.  DESIGN.md §6 has the table.

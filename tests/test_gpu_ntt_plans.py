@@ -1,6 +1,6 @@
 """bn254_ntt at every size and on every path of its host plan (needs an MI355X), bit-exact against the CPU oracle.
 
-csrc/ntt.hip switches on log2(n): one pass of the 8×32-bit kernel up to 2^9 (and two at 2^10), the lazy radix-2^29 passes from 2^11
+csrc/ntt_plan.h: ntt_plan (walked on the host by tests/test_ntt_plan_host.py) switches on log2(n): one pass of the 8×32-bit kernel up to 2^9 (and two at 2^10), the lazy radix-2^29 passes from 2^11
 to 2^24 (plan29: a pass plan of its own per size; bounds29: a value-bound plan per pass, with `shrink_last` where a sum would pass
 its limit; the `xcd_batch` launch once tiles % 8 == 0), and the 8×32-bit three-pass plan again from 2^25 on, which plan29 does not
 take.  Every log n from 0 to 24 runs here in a 2^24 domain (strides 2^24 … 1), six sizes again in a domain of their own size, one
