@@ -772,6 +772,8 @@ groth16_zkey_contribute groth16_zkey_contribute_file groth16_zkey_contributions
 groth16_ptau_prepared_size groth16_ptau_prepare groth16_ptau_prepare_file
 groth16_ptau_new_size groth16_ptau_new groth16_ptau_new_file
 groth16_ptau_contribute groth16_ptau_contribute_file groth16_ptau_contributions
+groth16_beacon_digest groth16_ptau_beacon groth16_ptau_beacon_file groth16_zkey_beacon groth16_zkey_beacon_file
+groth16_ptau_beacons groth16_zkey_beacons
 groth16_ptau_verify groth16_ptau_verify_file
 groth16_points_pack groth16_points_unpack groth16_ptau_packed_size groth16_ptau_unpacked_size
 groth16_ptau_pack groth16_ptau_pack_file groth16_ptau_unpack groth16_ptau_unpack_file
@@ -1197,14 +1199,67 @@ class ContributionsReport(C.Structure):
     (after1 bytes, name bytes) of the records whose bounds hold"""
     _fields_ = [("count", C.c_uint32), ("kind", C.c_int32), ("index", C.c_uint32)]
     records = ()
+    beacons = {}
 
 
 class ContributionInfo(C.Structure):
     _fields_ = [("after1", C.c_uint8 * 64), ("name", C.c_char * 256)]
 
 
-CONTRIB_SECTION, CONTRIB_POINT, CONTRIB_POK, CONTRIB_HEADER, CONTRIB_PAIR = range(1, 6)
-CONTRIB_KIND_NAMES = ["ok", "SECTION", "POINT", "POK", "HEADER", "PAIR"]
+CONTRIB_SECTION, CONTRIB_POINT, CONTRIB_POK, CONTRIB_HEADER, CONTRIB_PAIR, CONTRIB_BEACON = range(1, 7)
+CONTRIB_KIND_NAMES = ["ok", "SECTION", "POINT", "POK", "HEADER", "PAIR", "BEACON"]
+BEACON_ITER_EXP_MAX = 24
+
+
+class BeaconInfo(C.Structure):
+    """Groth16BeaconInfo: a beacon record's number (from 1), its beacon_hash and iter_exp as the record holds them"""
+    _fields_ = [("index", C.c_uint32), ("hash", C.c_uint8 * 32), ("iter_exp", C.c_uint32)]
+
+
+def _beacons(entry, image, cap):
+    """groth16_ptau_beacons / groth16_zkey_beacons → {record number: (beacon_hash, iter_exp)} of the flagged records among
+    those .records lists (the first `cap` of them): every key is the number of an entry of .records; host only"""
+    infos = (BeaconInfo * cap)()
+    n = getattr(lib(), entry)(_image(image), C.c_size_t(len(image)), infos, C.c_size_t(cap))
+    if n < 0:
+        _pcheck(n, entry)
+    return {int(infos[i].index): (bytes(infos[i].hash), int(infos[i].iter_exp)) for i in range(min(n, cap))}
+
+
+def beacon_digest(hash, iter_exp: int) -> bytes:
+    """groth16_beacon_digest: beacon_hash (32 bytes) hashed 2^iter_exp times in sequence with SHA-256 — the public "secret" of a
+    beacon; host only.  Raises ProverError −3 for iter_exp above 24."""
+    h = _seed32(hash, "beacon_digest", "hash")
+    if h is None:
+        raise ValueError("beacon_digest: hash must be 32 bytes")
+    out = (C.c_uint8 * 32)()
+    _pcheck(lib().groth16_beacon_digest(h, C.c_uint32(iter_exp), out), "beacon_digest")
+    return bytes(out)
+
+
+def _beacon(tool, report_type, size_field, image, beacon_hash, iter_exp, name, out, device):
+    """groth16_ptau_beacon / groth16_zkey_beacon and their _file entries: contribute's calling convention with the beacon's
+    parameters in the secret's place"""
+    h = _seed32(beacon_hash, tool, "beacon_hash")
+    if h is None:
+        raise ValueError(f"{tool}: beacon_hash must be 32 bytes")
+    rep = report_type()
+    nm = name.encode() if isinstance(name, str) else bytes(name)
+    if _path_or_image(tool, image, out):
+        _pcheck(getattr(lib(), f"groth16_{tool}_file")(os.fsencode(image), os.fsencode(out), h, C.c_uint32(iter_exp), nm, device.encode(), C.byref(rep)), f"{tool}_file")
+        return None, rep
+    entry = getattr(lib(), f"groth16_{tool}")
+    buf = _sized_twice(lambda buf, room: entry(_image(image), C.c_size_t(len(image)), h, C.c_uint32(iter_exp), nm, buf, room, device.encode(), C.byref(rep)),
+                       rep, size_field, tool)
+    return buf.raw, rep
+
+
+def zkey_beacon(zkey, beacon_hash, iter_exp: int, name="", out=None, device: str = "HIP"):
+    """groth16_zkey_beacon → (zkey bytes | None, ZkeyContributeReport): the random beacon of phase 2 — zkey_contribute with the
+    secret beacon_digest(beacon_hash, iter_exp), which anybody can recompute, and a record that says so (bit 31 of its name_len,
+    beacon_hash and iter_exp behind the name); zkey_contributions audits it (CONTRIB_BEACON) and lists it (.beacons).  zkey, out,
+    name, device as zkey_contribute's.  Raises ProverError (−3 iter_exp above 24; else as zkey_contribute)."""
+    return _beacon("zkey_beacon", ZkeyContributeReport, "zkey_bytes", zkey, beacon_hash, iter_exp, name, out, device)
 
 
 def zkey_contribute(zkey, secret=None, name="", out=None, device: str = "HIP", delta=None):
@@ -1238,6 +1293,7 @@ def zkey_contributions(zkey):
         _pcheck(rc, "zkey_contributions")
     held = rep.count if rep.kind != CONTRIB_SECTION else max(int(rep.index) - 1, 0)
     rep.records = [(bytes(infos[i].after1), infos[i].name) for i in range(min(held, cap))]
+    rep.beacons = _beacons("groth16_zkey_beacons", zkey, cap)
     return rc == 1, rep
 
 
@@ -1294,6 +1350,7 @@ class PtauContributionsReport(C.Structure):
     .records: (tau1, alpha1, beta1, tau2, beta2, name) bytes of the records whose bounds hold"""
     _fields_ = [("count", C.c_uint32), ("kind", C.c_int32), ("index", C.c_uint32)]
     records = ()
+    beacons = {}
 
 
 class PtauContributionInfo(C.Structure):
@@ -1340,6 +1397,14 @@ def ptau_contribute(ptau, secret=None, name="", out=None, device: str = "HIP", t
     return buf.raw, rep
 
 
+def ptau_beacon(ptau, beacon_hash, iter_exp: int, name="", out=None, device: str = "HIP"):
+    """groth16_ptau_beacon → (ptau bytes | None, PtauContributeReport): the random beacon of phase 1 — ptau_contribute with the
+    secret beacon_digest(beacon_hash, iter_exp), which anybody can recompute, and a record that says so (bit 31 of its name_len,
+    beacon_hash and iter_exp behind the name); ptau_contributions audits it (CONTRIB_BEACON) and lists it (.beacons).  ptau, out,
+    name, device as ptau_contribute's.  Raises ProverError (−3 iter_exp above 24; else as ptau_contribute)."""
+    return _beacon("ptau_beacon", PtauContributeReport, "ptau_bytes", ptau, beacon_hash, iter_exp, name, out, device)
+
+
 def ptau_contributions(ptau):
     """groth16_ptau_contributions → (ok, PtauContributionsReport with .records): is section 7 a chain of valid contributions from
     the generators to what sections 2 to 6 hold at their first elements, and do the G1 and G2 sides pair?  Host only: needs no
@@ -1353,6 +1418,7 @@ def ptau_contributions(ptau):
     held = rep.count if rep.kind != CONTRIB_SECTION else max(int(rep.index) - 1, 0)
     rep.records = [(bytes(infos[i].tau1), bytes(infos[i].alpha1), bytes(infos[i].beta1), bytes(infos[i].tau2), bytes(infos[i].beta2), infos[i].name)
                    for i in range(min(held, cap))]
+    rep.beacons = _beacons("groth16_ptau_beacons", ptau, cap)
     return rc == 1, rep
 
 

@@ -4,6 +4,7 @@
 // `prove` or `verify` with an unknown --system, print the help and no completion line.
 // The commands are the entries of `commands` below: name, usage line (the help is assembled from them) and function.  A new command
 // is one entry and one function; its options go through parse(), its failure line through report_failure().
+#include <algorithm>
 #include <fstream>
 #include <initializer_list>
 #include <iostream>
@@ -105,21 +106,30 @@ static int64_t write_vk(const std::string& image, const std::string& vk_path)
 }
 
 // One line per record that is listed, then CHAIN_OK or CHAIN_BAD <kind> <index>: for section 10 of a key and section 7 of a
-// powers-of-tau file, which differ in the point that is shown.  The verdict is over all records, listed or not.
+// powers-of-tau file, which differ in the point that is shown.  The verdict is over all records, listed or not.  A beacon record's
+// line ends in " beacon <the 64 hex digits of its hash> <iter_exp>" (beacons: groth16_*_beacons' list).
 template <class Report, class Info>
-static void print_chain(int rc, const Report& rep, const std::vector<Info>& infos, uint8_t (Info::*shown)[64], const char* label)
+static void print_chain(int rc, const Report& rep, const std::vector<Info>& infos, uint8_t (Info::*shown)[64], const char* label, const std::vector<Groth16BeaconInfo>& beacons)
 {
-  static const char* const kinds[6] = {"", "SECTION", "POINT", "POK", "HEADER", "PAIR"};
-  const uint32_t held = rep.kind == GROTH16_CONTRIB_SECTION ? (rep.index ? rep.index - 1 : 0) : rep.count;
-  for (uint32_t i = 0; i < held && i < infos.size(); i++) {
-    static const char hex[] = "0123456789abcdef";
-    const uint8_t* p = infos[i].*shown;
+  static const char* const kinds[7] = {"", "SECTION", "POINT", "POK", "HEADER", "PAIR", "BEACON"};
+  static const char hex[] = "0123456789abcdef";
+  auto hex_of = [](const uint8_t* p, int n) {
     std::string d;
-    for (int k = 0; k < 8; k++) d += {hex[p[k] >> 4], hex[p[k] & 15]};
-    std::cout << "contribution " << i + 1 << " name \"" << infos[i].name << "\" " << label << " " << d << "..." << std::endl;
+    for (int k = 0; k < n; k++) d += {hex[p[k] >> 4], hex[p[k] & 15]};
+    return d;
+  };
+  const uint32_t held = rep.kind == GROTH16_CONTRIB_SECTION ? (rep.index ? rep.index - 1 : 0) : rep.count;
+  size_t b = 0;
+  for (uint32_t i = 0; i < held && i < infos.size(); i++) {
+    std::cout << "contribution " << i + 1 << " name \"" << infos[i].name << "\" " << label << " " << hex_of(infos[i].*shown, 8) << "...";
+    if (b < beacons.size() && beacons[b].index == i + 1) {
+      std::cout << " beacon " << hex_of(beacons[b].hash, 32) << " " << beacons[b].iter_exp;
+      b++;
+    }
+    std::cout << std::endl;
   }
   if (rc == 1) std::cout << "CHAIN_OK" << std::endl;
-  else std::cout << "CHAIN_BAD " << kinds[rep.kind >= 1 && rep.kind <= 5 ? rep.kind : 0] << " " << rep.index << std::endl;
+  else std::cout << "CHAIN_BAD " << kinds[rep.kind >= 1 && rep.kind <= 6 ? rep.kind : 0] << " " << rep.index << std::endl;
 }
 
 // the end of the summary line of a tool that writes a file; device_detail, when given, stands between the device and download times
@@ -390,7 +400,10 @@ static void cmd_zkey_contributions(Call& c)
   std::vector<Groth16ContributionInfo> infos(4096); // the records that are listed
   const int rc = read ? groth16_zkey_contributions(image.data(), image.size(), &rep, infos.data(), infos.size()) : -1;
   if (rc < 0) return report_failure(c.cmd.name, rc, read ? groth16_last_error() : "cannot read the zkey");
-  print_chain(rc, rep, infos, &Groth16ContributionInfo::after1, "delta1");
+  std::vector<Groth16BeaconInfo> beacons(infos.size());
+  const int n_beacons = groth16_zkey_beacons(image.data(), image.size(), beacons.data(), beacons.size());
+  beacons.resize(std::min<size_t>(beacons.size(), (size_t)std::max(n_beacons, 0)));
+  print_chain(rc, rep, infos, &Groth16ContributionInfo::after1, "delta1", beacons);
 }
 
 // sections 12 to 15 of a powers-of-tau file made from its sections 2 to 5 (groth16_ptau_prepare_file)
@@ -441,7 +454,10 @@ static void cmd_ptau_contributions(Call& c)
   std::vector<Groth16PtauContributionInfo> infos(1024); // the records that are listed
   const int rc = read ? groth16_ptau_contributions(image.data(), image.size(), &rep, infos.data(), infos.size()) : -1;
   if (rc < 0) return report_failure(c.cmd.name, rc, read ? groth16_last_error() : "cannot read the ptau");
-  print_chain(rc, rep, infos, &Groth16PtauContributionInfo::tau1, "tau1");
+  std::vector<Groth16BeaconInfo> beacons(infos.size());
+  const int n_beacons = groth16_ptau_beacons(image.data(), image.size(), beacons.data(), beacons.size());
+  beacons.resize(std::min<size_t>(beacons.size(), (size_t)std::max(n_beacons, 0)));
+  print_chain(rc, rep, infos, &Groth16PtauContributionInfo::tau1, "tau1", beacons);
 }
 
 // the audit first, as zkey-verify runs r1cs-match: who contributed, then whether the points are what they should be

@@ -1,6 +1,7 @@
 // ptau_contribute.hip — groth16_ptau_new: the starting file of a powers-of-tau ceremony; groth16_ptau_contribute: one participant's
 // secrets (τ′, α′, β′) applied to every point of an unprepared file; groth16_ptau_contributions: the host's audit of the chain section
-// 7 records.  include/groth16_prover.h has the contract and section 7's layout; DESIGN.md §7h.
+// 7 records.  include/groth16_prover.h has the contract and section 7's layout; DESIGN.md §7h.  groth16_ptau_beacon is the same call
+// with the secret replaced by the beacon's public digest and the record's tail added (§7o): no stage of it is written twice.
 //
 //   host, first  the container (ptau_unprepared_layout), section 7's bounds and its last record against the file, the output's size
 //                against the room, section 6 through the lane test; τ′, α′, β′ and the three nonces (transcript.h has the hashes, the
@@ -72,15 +73,15 @@ void chain_start(const pv::PtauLayout& L, uint8_t h[32])
   if (L.power < L.ceremony_power) memcpy(m.data() + TAG_LEN + 36, &L.ceremony_power, 4); // (ptau_header: the payload has 44 bytes)
   isnark::sha256(m.data(), m.size(), h);
 }
-// e_i = SHA-256(h_{i−1} ‖ before ‖ the five after points ‖ R_tau ‖ R_alpha ‖ R_beta ‖ name_len ‖ name) → h (in place); c: its first
-// 16 bytes, little-endian, 0 → 1.  The responses are not hashed.
+// e_i = SHA-256(h_{i−1} ‖ before ‖ the five after points ‖ R_tau ‖ R_alpha ‖ R_beta ‖ name_len as stored ‖ name ‖ a beacon's trailer)
+// → h (in place); c: its first 16 bytes, little-endian, 0 → 1.  The responses are not hashed.
 void chain_step(uint8_t h[32], const uint8_t* before, const Record& r, fe* c)
 {
   std::vector<uint8_t> m;
   append(m, h, 32);
   append(m, before, BEFORE_BYTES);
   append(m, r.p, Z_TAU);
-  append(m, r.p + NAME_LEN, 4 + r.name_len);
+  append(m, r.p + NAME_LEN, hashed_tail(r));
   hash_step(m, h, c);
 }
 
@@ -117,6 +118,32 @@ void generators(uint8_t out[AFTER_BYTES])
   const G2::A g2 = vb::g2_generator_mont();
   for (size_t off : {TAU1, ALPHA1, BETA1}) memcpy(out + off, &g1, 64);
   for (size_t off : {TAU2, BETA2}) memcpy(out + off, &g2, 128);
+}
+
+// x′ = W(seed ‖ TAG ‖ label) → *x, standard form, for `which` = 0, 1, 2 (τ, α, β: labels 1, 2, 3); false when it is zero
+bool derive_secret(const uint8_t seed[32], int which, fe* x)
+{
+  const uint8_t label = (uint8_t)(which + 1);
+  std::vector<uint8_t> m;
+  append(m, seed, 32);
+  append(m, TAG, TAG_LEN);
+  append(m, &label, 1);
+  *x = wide_hash(m);
+  return !Fr::is_zero(*x);
+}
+// BEACON's last question (transcript.h's beacon_work_allowed has passed): with the digest and τ′, α′, β′ recomputed, is
+// after.x1 = x′·before.x1 in the file's canonical affine bytes for tau1, alpha1, beta1?
+bool record_is_the_beacons(const Record& r, const uint8_t* before)
+{
+  uint8_t digest[32];
+  beacon_digest(r.trailer, beacon_iter_exp(r), digest);
+  for (int x = 0; x < 3; x++) {
+    fe s;
+    if (!derive_secret(digest, x, &s)) return false;
+    const G1::A want = zc29::zc_mul_affine<G1, G1L>(point_at<G1::A>(before + 64 * x), s);
+    if (memcmp(&want, r.p + 64 * x, 64) != 0) return false;
+  }
+  return true;
 }
 
 // everything secret of one call; wiped on every way out (best effort: the compiler may have kept copies in registers or spills)
@@ -210,11 +237,14 @@ int scale_section(hipStream_t st, const Buffers& b, int k4, uint64_t n, const fe
   return pv::to_file_form<C>(st, d_p, n, d_a, (typename Group<C>::Fo::T*)b.scratch);
 }
 
+// beacon: null for a participant's contribution; else secret32 is not read — the secret is the beacon's digest — and opt is null
 int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, const char* name, const char* device, const Groth16PtauContributeOptions* opt,
-                    Groth16PtauContributeReport* rep, const Sink& sink)
+                    Groth16PtauContributeReport* rep, const Sink& sink, const Beacon* beacon = nullptr)
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
+  if (beacon && !beacon->hash) return pv::fail(pv::ERR_ARG, "null beacon hash");
+  if (beacon && beacon->iter_exp > BEACON_ITER_EXP_MAX) return pv::fail(pv::ERR_ARG, "beacon: iter_exp %u is above %u", beacon->iter_exp, BEACON_ITER_EXP_MAX);
   int dev;
   if (int rc = pv::parse_device(device, &dev)) return rc;
   if (!name) name = "";
@@ -235,7 +265,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   if (count && !header_holds(held, recs.back().p)) return pv::fail(pv::ERR_FORMAT, "ptau: section 7's last record is not what sections 2 to 6 hold");
 
   // the output's size, before anything else is done
-  const uint64_t rec_bytes = RECORD_FIXED + name_len, total = (uint64_t)len + rec_bytes;
+  const uint64_t rec_bytes = RECORD_FIXED + tail_bytes(name_len, beacon), total = (uint64_t)len + rec_bytes;
   rep->contribution = count + 1;
   rep->power = power;
   for (int k4 = 0; k4 < 4; k4++) rep->points[k4] = counts[k4];
@@ -265,21 +295,17 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
 
   // ---- τ′, α′, β′, the nonces
   Secrets S;
+  uint8_t digest[32];
+  if (beacon) beacon_digest(beacon->hash, beacon->iter_exp, digest), secret32 = digest; // (public: nothing of it needs wiping)
   if (int rc = pv::seed_or_random(secret32, S.seed)) return rc;
   static const char* const NAMES[3] = {"tau", "alpha", "beta"};
   const uint8_t* const fixed[3] = {opt ? opt->fixed_tau : nullptr, opt ? opt->fixed_alpha : nullptr, opt ? opt->fixed_beta : nullptr};
   for (int x = 0; x < 3; x++) {
-    const uint8_t label = (uint8_t)(x + 1);
     if (fixed[x]) {
       memcpy(S.x[x].l, fixed[x], 32);
       if (!Fr::is_canonical(S.x[x]) || Fr::is_zero(S.x[x])) return pv::fail(pv::ERR_ARG, "fixed_%s is not in [1, r)", NAMES[x]);
-    } else {
-      std::vector<uint8_t> m;
-      append(m, S.seed, 32);
-      append(m, TAG, TAG_LEN);
-      append(m, &label, 1);
-      S.x[x] = wide_hash(m);
-      if (Fr::is_zero(S.x[x])) return pv::fail(pv::ERR_ARG, "the secret gives %s' = 0", NAMES[x]);
+    } else if (!derive_secret(S.seed, x, &S.x[x])) {
+      return pv::fail(pv::ERR_ARG, "the secret gives %s' = 0", NAMES[x]);
     }
   }
   // h_{i−1} over the records there are, as groth16_ptau_contributions hashes them
@@ -364,10 +390,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
     beta2_out = zc29::zc_mul_affine<G2, G2L>(beta2_in, S.x[2]);
     memcpy(r + TAU2, &tau2, 128);
     memcpy(r + BETA2, &beta2_out, 128);
-    const uint32_t nl = (uint32_t)name_len;
-    memcpy(r + NAME_LEN, &nl, 4);
-    memcpy(r + RECORD_FIXED, name, name_len);
-    const Record rec = {r, nl};
+    const Record rec = put_tail(r, NAME_LEN, name, name_len, beacon);
     fe c;
     chain_step(h, before, rec, &c);
     for (int x = 0; x < 3; x++) {
@@ -479,6 +502,7 @@ ISNARK_API int groth16_ptau_contributions(const void* ptau, size_t len, Groth16P
     memcpy(infos[i].name, p + RECORD_FIXED, recs[i].name_len);
   }
   if (malformed) return fault(GROTH16_CONTRIB_SECTION, bad);
+  uint64_t beacon_work = 0;
 
   uint8_t gens[AFTER_BYTES], h[32];
   generators(gens);
@@ -505,10 +529,48 @@ ISNARK_API int groth16_ptau_contributions(const void* ptau, size_t len, Groth16P
       memcpy(z.l, r.p + Z_TAU + 32 * x, 32);
       if (!pok_holds(point_at<G1::A>(before + 64 * x), after[x], commitment[x], z, cd)) return fault(GROTH16_CONTRIB_POK, i + 1);
     }
+    // BEACON: a flagged record within the work bound, whose three G1 points are the recomputed beacon's
+    if (r.beacon && (!beacon_work_allowed(beacon_iter_exp(r), &beacon_work) || !record_is_the_beacons(r, before))) return fault(GROTH16_CONTRIB_BEACON, i + 1);
     // PAIR: e(tau1, G₂) = e(G₁, tau2) and e(beta1, G₂) = e(G₁, beta2)
     if (!vb::pairing_eq(std_affine(after[0]), g2, g1, std_affine(tau2)) || !vb::pairing_eq(std_affine(after[2]), g2, g1, std_affine(beta2))) return fault(GROTH16_CONTRIB_PAIR, i + 1);
     before = r.p;
   }
   if (!header_holds(held_points(L), before)) return fault(GROTH16_CONTRIB_HEADER, 0);
   return 1;
+}
+
+// ---- the random beacon
+ISNARK_API int groth16_beacon_digest(const uint8_t hash[32], uint32_t iter_exp, uint8_t out[32])
+{
+  if (!hash || !out) return pv::fail(pv::ERR_ARG, "null argument");
+  if (iter_exp > BEACON_ITER_EXP_MAX) return pv::fail(pv::ERR_ARG, "beacon: iter_exp %u is above %u", iter_exp, BEACON_ITER_EXP_MAX);
+  beacon_digest(hash, iter_exp, out);
+  return 0;
+}
+
+ISNARK_API int groth16_ptau_beacon(const void* ptau, size_t len, const uint8_t beacon_hash[32], uint32_t iter_exp, const char* name, void* out, size_t cap, const char* device,
+                                   Groth16PtauContributeReport* report)
+{
+  const Beacon b = {beacon_hash, iter_exp};
+  return contribute_impl((const uint8_t*)ptau, len, nullptr, name, device, nullptr, report, pv::buffer_sink("file", out, cap), &b);
+}
+
+ISNARK_API int groth16_ptau_beacon_file(const char* in_path, const char* out_path, const uint8_t beacon_hash[32], uint32_t iter_exp, const char* name, const char* device,
+                                        Groth16PtauContributeReport* report)
+{
+  const Beacon b = {beacon_hash, iter_exp};
+  return pv::rewrite_file(in_path, out_path, report ? &report->write_ms : nullptr, [&](const uint8_t* data, size_t len, const Sink& sink) {
+    return contribute_impl(data, len, nullptr, name, device, nullptr, report, sink, &b);
+  });
+}
+
+ISNARK_API int groth16_ptau_beacons(const void* ptau, size_t len, Groth16BeaconInfo* infos, size_t cap)
+{
+  std::vector<pv::Section> secs;
+  pv::PtauLayout L;
+  if (int rc = pv::ptau_unprepared_layout((const uint8_t*)ptau, len, secs, &L)) return rc;
+  std::vector<Record> recs;
+  uint32_t count, bad;
+  const int malformed = walk_records(L.sec[7], RECORD_FIXED, NAME_LEN, recs, &count, &bad);
+  return list_beacons(held_records(recs, malformed, bad), infos, cap);
 }

@@ -1,5 +1,6 @@
 // zkey_contribute.hip — groth16_zkey_contribute: one phase-2 contribution δ′ applied to a proving key, and groth16_zkey_contributions,
 // the host's audit of the chain section 10 records.  include/groth16_prover.h has the contract and section 10's layout; DESIGN.md §7f.
+// groth16_zkey_beacon is the same call with the secret replaced by the beacon's public digest and the record's tail added (§7o).
 //
 //   host, first  the container (zkey_layout), section 10's bounds and hash chain, the output's size against the room, the header's δ₁
 //                and δ₂ through the key check's lane tests; δ′, the nonce k and the record — three G1 and one G2 scalar
@@ -71,7 +72,8 @@ void chain_start(const pv::ZkeyLayout& L, uint8_t h[32])
   append(m, L.sec[3]->p, (size_t)L.sec[3]->size);
   isnark::sha256(m.data(), m.size(), h);
 }
-// e_i = SHA-256(h_{i−1} ‖ before1 ‖ after1 ‖ R ‖ name_len ‖ name) → h (in place); c: its first 16 bytes, little-endian, 0 → 1
+// e_i = SHA-256(h_{i−1} ‖ before1 ‖ after1 ‖ R ‖ name_len as stored ‖ name ‖ a beacon's trailer) → h (in place); c: its first 16
+// bytes, little-endian, 0 → 1
 void chain_step(uint8_t h[32], const uint8_t* before1, const Record& r, fe* c)
 {
   std::vector<uint8_t> m;
@@ -79,8 +81,29 @@ void chain_step(uint8_t h[32], const uint8_t* before1, const Record& r, fe* c)
   append(m, before1, 64);
   append(m, r.p + AFTER1, 64);
   append(m, r.p + COMMITMENT, 64);
-  append(m, r.p + NAME_LEN, 4 + r.name_len);
+  append(m, r.p + NAME_LEN, hashed_tail(r));
   hash_step(m, h, c);
+}
+
+// δ′ = W(seed ‖ TAG), standard form; false when it is zero
+bool derive_delta(const uint8_t seed[32], fe* delta)
+{
+  std::vector<uint8_t> m;
+  append(m, seed, 32);
+  append(m, TAG, TAG_LEN);
+  *delta = wide_hash(m);
+  return !Fr::is_zero(*delta);
+}
+// BEACON's last question (transcript.h's beacon_work_allowed has passed): with the digest and δ′ recomputed, is after1 = δ′·before1
+// in the file's canonical affine bytes?
+bool record_is_the_beacons(const Record& r, const G1::A& before)
+{
+  uint8_t digest[32];
+  beacon_digest(r.trailer, beacon_iter_exp(r), digest);
+  fe delta;
+  if (!derive_delta(digest, &delta)) return false;
+  const G1::A want = zc29::zc_mul_affine<G1, G1L>(before, delta);
+  return memcmp(&want, r.p + AFTER1, 64) == 0;
 }
 
 // everything secret of one call; wiped on every way out (best effort: the compiler may have kept copies in registers or spills)
@@ -93,11 +116,14 @@ struct Secrets {
 
 using pv::Sink;
 
+// beacon: null for a participant's contribution; else secret32 is not read — the secret is the beacon's digest — and opt is null
 int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, const char* name, const char* device, const Groth16ZkeyContributeOptions* opt,
-                    Groth16ZkeyContributeReport* rep, const Sink& sink)
+                    Groth16ZkeyContributeReport* rep, const Sink& sink, const Beacon* beacon = nullptr)
 {
   if (!rep) return pv::fail(pv::ERR_ARG, "null report");
   memset(rep, 0, sizeof *rep);
+  if (beacon && !beacon->hash) return pv::fail(pv::ERR_ARG, "null beacon hash");
+  if (beacon && beacon->iter_exp > BEACON_ITER_EXP_MAX) return pv::fail(pv::ERR_ARG, "beacon: iter_exp %u is above %u", beacon->iter_exp, BEACON_ITER_EXP_MAX);
   int dev;
   if (int rc = pv::parse_device(device, &dev)) return rc;
   if (!name) name = "";
@@ -116,7 +142,7 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
 
   // the output's size, before anything else is done
   const std::vector<pv::SectionEntry> order = pv::sections_in_order(data);
-  const uint64_t rec_bytes = RECORD_FIXED + name_len;
+  const uint64_t rec_bytes = RECORD_FIXED + tail_bytes(name_len, beacon);
   uint64_t total = 12 + rec_bytes + (s10 ? 0 : 12 + 4);
   for (const pv::SectionEntry& e : order) total += 12 + e.size;
   const uint64_t n8 = L.sec[8]->size / 64, n9 = L.sec[9]->size / 64, n = n8 + n9;
@@ -135,16 +161,14 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
 
   // ---- δ′, the nonce, the record
   Secrets S;
+  uint8_t digest[32];
+  if (beacon) beacon_digest(beacon->hash, beacon->iter_exp, digest), secret32 = digest; // (public: nothing of it needs wiping)
   if (int rc = pv::seed_or_random(secret32, S.seed)) return rc;
   if (opt && opt->fixed_delta) {
     memcpy(S.delta.l, opt->fixed_delta, 32);
     if (!Fr::is_canonical(S.delta) || Fr::is_zero(S.delta)) return pv::fail(pv::ERR_ARG, "fixed_delta is not in [1, r)");
-  } else {
-    std::vector<uint8_t> m;
-    append(m, S.seed, 32);
-    append(m, TAG, TAG_LEN);
-    S.delta = wide_hash(m);
-    if (Fr::is_zero(S.delta)) return pv::fail(pv::ERR_ARG, "the secret gives delta' = 0");
+  } else if (!derive_delta(S.seed, &S.delta)) {
+    return pv::fail(pv::ERR_ARG, "the secret gives delta' = 0");
   }
   S.delta_inv = fr_inv(S.delta);
   S.digits = zc29::zc_recode(S.delta_inv);
@@ -169,13 +193,10 @@ int contribute_impl(const uint8_t* data, size_t len, const uint8_t* secret32, co
   const G2::A after2 = zc29::zc_mul_affine<G2, G2L>(d2, S.delta);
   std::vector<uint8_t> record(rec_bytes);
   {
-    const uint32_t nl = (uint32_t)name_len;
     uint8_t* const b = record.data();
     memcpy(b + AFTER1, &after1, 64);
     memcpy(b + COMMITMENT, &commitment, 64);
-    memcpy(b + NAME_LEN, &nl, 4);
-    memcpy(b + RECORD_FIXED, name, name_len);
-    const Record r = {b, nl};
+    const Record r = put_tail(b, NAME_LEN, name, name_len, beacon);
     fe c;
     chain_step(h, hdr + DELTA1_OFF, r, &c);
     const fe z = schnorr_response(S.k, c, S.delta);
@@ -303,6 +324,7 @@ ISNARK_API int groth16_zkey_contributions(const void* zkey, size_t len, Groth16C
   uint8_t h[32];
   chain_start(L, h);
   G1::A before = g1;
+  uint64_t beacon_work = 0;
   for (uint32_t i = 0; i < report->count; i++) {
     const Record& r = recs[i];
     const G1::A after = point_at<G1::A>(r.p + AFTER1), commitment = point_at<G1::A>(r.p + COMMITMENT);
@@ -312,6 +334,8 @@ ISNARK_API int groth16_zkey_contributions(const void* zkey, size_t len, Groth16C
     fe c;
     chain_step(h, (const uint8_t*)&before, r, &c);
     if (!pok_holds(before, after, commitment, z, zc29::zc_recode(c))) return fault(GROTH16_CONTRIB_POK, i + 1);
+    // BEACON: a flagged record within the work bound, whose after1 is the recomputed beacon's
+    if (r.beacon && (!beacon_work_allowed(beacon_iter_exp(r), &beacon_work) || !record_is_the_beacons(r, before))) return fault(GROTH16_CONTRIB_BEACON, i + 1);
     before = after;
   }
   if (memcmp(&before, hdr + DELTA1_OFF, 64) != 0) return fault(GROTH16_CONTRIB_HEADER, 0);
@@ -320,4 +344,33 @@ ISNARK_API int groth16_zkey_contributions(const void* zkey, size_t len, Groth16C
   if (classify(d2) || G2::aff_is_zero(d2)) return fault(GROTH16_CONTRIB_PAIR, 0);
   if (!vb::pairing_eq(std_affine(before), vb::g2_generator_affine(), vb::g1_generator_affine(), std_affine(d2))) return fault(GROTH16_CONTRIB_PAIR, 0);
   return 1;
+}
+
+// ---- the random beacon (groth16_beacon_digest is ptau_contribute.hip's)
+ISNARK_API int groth16_zkey_beacon(const void* zkey, size_t len, const uint8_t beacon_hash[32], uint32_t iter_exp, const char* name, void* out, size_t cap, const char* device,
+                                   Groth16ZkeyContributeReport* report)
+{
+  const Beacon b = {beacon_hash, iter_exp};
+  return contribute_impl((const uint8_t*)zkey, len, nullptr, name, device, nullptr, report, pv::buffer_sink("key", out, cap), &b);
+}
+
+ISNARK_API int groth16_zkey_beacon_file(const char* zkey_path, const char* out_path, const uint8_t beacon_hash[32], uint32_t iter_exp, const char* name, const char* device,
+                                        Groth16ZkeyContributeReport* report)
+{
+  const Beacon b = {beacon_hash, iter_exp};
+  return pv::rewrite_file(zkey_path, out_path, report ? &report->write_ms : nullptr, [&](const uint8_t* data, size_t len, const Sink& sink) {
+    return contribute_impl(data, len, nullptr, name, device, nullptr, report, sink, &b);
+  });
+}
+
+ISNARK_API int groth16_zkey_beacons(const void* zkey, size_t len, Groth16BeaconInfo* infos, size_t cap)
+{
+  std::vector<pv::Section> secs;
+  pv::ZkeyLayout L;
+  if (int rc = pv::zkey_layout((const uint8_t*)zkey, len, secs, &L)) return rc;
+  if (secs[10].count > 1) return 0; // (the audit's SECTION fault of the count: no record's bounds hold)
+  std::vector<Record> recs;
+  uint32_t count, bad;
+  const int malformed = walk_records(secs[10].count ? &secs[10] : nullptr, RECORD_FIXED, NAME_LEN, recs, &count, &bad);
+  return list_beacons(held_records(recs, malformed, bad), infos, cap);
 }

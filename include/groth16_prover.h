@@ -608,7 +608,7 @@ int groth16_zkey_contributions(const void* zkey, size_t len, Groth16Contribution
  * input, T = +-P, w = 1) is exact.  One path for every level: there is no switch point between kernels, so no such argument.
  * groth16_ptau_prepared_size is the host half: the output's size from the input's container alone.  Never initialises a GPU.
  * What it does NOT do: check its source's powers against one another or its records (groth16_ptau_verify and
- * groth16_ptau_contributions do: run them first), apply phase-1 contributions or beacons, use more than one GPU.  No file written by snarkjs exists offline: reader and writer share the layout stated here.
+ * groth16_ptau_contributions do: run them first), apply phase-1 contributions (a beacon is one: groth16_ptau_beacon), use more than one GPU.  No file written by snarkjs exists offline: reader and writer share the layout stated here.
  * 1 prepared; -1 I/O; -2 format; -3 argument: cap too small (report->ptau_bytes says what is needed, nothing is written), power 28,
  * equal paths, a device string that does not name one HIP device; -5 device failure (groth16_last_error).  The _file variant maps
  * the input, writes a temporary beside out_path and renames it: a failed call leaves nothing.  The calling thread's device is what
@@ -678,7 +678,7 @@ int groth16_ptau_prepare_file(const char* in_path, const char* out_path, const c
  * ICICLE_SNARK_TRACE_PTAU_CONTRIBUTE=1 prints the stage times on stderr.
  * What none of this does: check that a file's powers are CONSISTENT WITH ONE ANOTHER — the audit ties the records to element 1 and
  * element 0 of the sections and to section 6, NOT the other 2N - 2 powers: that is groth16_ptau_verify's same-ratio test over all
- * points, below; apply a beacon; read or write snarkjs' record format; use more than one GPU; decompose the scalars (GLV). */
+ * points, below; read or write snarkjs' record format; use more than one GPU; decompose the scalars (GLV). */
 int groth16_ptau_new_size(uint32_t power, uint64_t* ptau_bytes);
 int groth16_ptau_new(uint32_t power, void* out, size_t cap, uint64_t* out_len);
 int groth16_ptau_new_file(uint32_t power, const char* out_path);
@@ -710,6 +710,7 @@ int groth16_ptau_contribute_file(const char* in_path, const char* out_path, cons
  *   POINT    one of a record's eight points has a coordinate >= q or is off the curve, tau2 or beta2 is outside the subgroup, or
  *            one of the five after points is the identity
  *   POK      a z >= r, or one of the three equations fails
+ *   BEACON   (a record that states a beacon only: the beacon block below) over the work bound, or not the recomputed beacon's
  *   PAIR     e(tau1, G2) != e(G1, tau2), or e(beta1, G2) != e(G1, beta2)
  *   and at the end
  *   HEADER   (index 0) the last record's alpha1, beta1, beta2 are not section 4 element 0, section 5 element 0 and section 6, or —
@@ -730,6 +731,57 @@ typedef struct {
 /* infos (may be NULL) receives the points and the name of the first min(count, infos_cap) records whose bounds hold. */
 int groth16_ptau_contributions(const void* ptau, size_t len, Groth16PtauContributionsReport* report,
                                Groth16PtauContributionInfo* infos, size_t infos_cap);
+
+/* groth16_ptau_beacon, groth16_zkey_beacon, groth16_beacon_digest, groth16_ptau_beacons, groth16_zkey_beacons — THE RANDOM BEACON:
+ * the last step of each ceremony phase, what `snarkjs powersoftau beacon` and `snarkjs zkey beacon` apply.  Opt-in.  DESIGN.md 7o.
+ * A beacon is a contribution whose secret is PUBLIC: beacon_hash, 32 bytes nobody could have known before the last participant
+ * finished (a block hash, a drand round), stretched by 2^iter_exp sequential hashes so that the last participant cannot choose
+ * their share after seeing the outcome: d_0 = beacon_hash, d_(j+1) = SHA-256(d_j), digest = d at j = 2^iter_exp (iter_exp = 0 is
+ * ONE hash).  groth16_beacon_digest computes it, on the host; iter_exp above GROTH16_BEACON_ITER_EXP_MAX is -3.
+ * THE SECRETS are groth16_ptau_contribute's / groth16_zkey_contribute's with secret := digest and nothing else changed: the same W,
+ * tags, labels and nonces.  So the points a beacon writes are, byte for byte, what the contribute call with secret32 = digest
+ * writes (sections 2 to 6 of a .ptau; the header and sections 8 and 9 of a .zkey) by the same kernels; only the record differs.
+ * THE RECORD is a record of its section (7 or 10) with two differences: BIT 31 of the stored name_len word is set (the name's
+ * length is the low bits, still <= 255), and 36 bytes follow the name: beacon_hash (32 B), iter_exp (u32 LE).  e_i hashes the
+ * name_len word AS STORED, the name, then those 36 bytes: the beacon's parameters are bound into the chain.  Any other bit above
+ * bit 8 of name_len, or a trailer cut short, is a SECTION fault.  A file without beacon records reads and audits as before; a build
+ * of this library from before beacons answers SECTION for a file with one (name_len > 255) — the right answer for a reader that
+ * cannot audit it.  Contributions may follow a beacon, as in snarkjs: groth16_*_contribute appends behind beacon records.
+ * THE AUDIT (groth16_ptau_contributions, groth16_zkey_contributions) tests a flagged record for the new kind BEACON right after its
+ * POK has passed (so: SECTION, then per record POINT, POK, BEACON, and for a .ptau PAIR; HEADER and the key's PAIR at the end):
+ *   iter_exp > GROTH16_BEACON_ITER_EXP_MAX; or the running total of 2^iter_exp over the file's beacon records, this one included,
+ *   exceeds 2^25 (the index is the record that crosses) — both BEFORE any hashing: a hostile file cannot buy more work; or
+ *   the record is not the beacon's: with the digest and the secrets recomputed, after.x1 != x' * before.x1 in canonical affine
+ *   bytes for one of tau1, alpha1, beta1 (.ptau) or for after1 (.zkey), or a recomputed secret is zero.  The G2 side stays PAIR's.
+ * A proof of knowledge of any OTHER x, however honest, is therefore BEACON.  groth16_*_beacons list the flagged records among
+ * those the audit lists (the records whose bounds hold; after a SECTION fault the ones BEFORE the record at fault, so an index
+ * here is always an entry of the audit's infos): the return value is their number, infos (may be NULL) receives the first
+ * min(that, cap).  Host only, bounds only: they verify nothing.  < 0: the container is malformed (-2).
+ * groth16_*_beacon[_file] are groth16_*_contribute[_file] in everything else: the lane tests before any arithmetic, cap tested first
+ * against a size known before any device work (the contribution's plus 36), the temporary file and the rename, nothing left by a
+ * failed call, -2 for a truncated or prepared .ptau or a stale chain, the reports.  There are no fixed_* options.  iter_exp above
+ * GROTH16_BEACON_ITER_EXP_MAX, or a null beacon_hash, is -3 before any work.
+ * What none of this does: read or write snarkjs' beacon record (its format needs BLAKE2b and hash-to-G2); take numIterationsExp
+ * above 24 (snarkjs allows up to 63); exist as a command of the `prove` worker (its -contributions and ptau-verify commands do
+ * audit and list beacon records); use more than one GPU. */
+#define GROTH16_CONTRIB_BEACON  6   /* a beacon record's iter_exp or the file's beacon work is over the bound, or the record is not the beacon's */
+#define GROTH16_BEACON_ITER_EXP_MAX 24
+typedef struct {
+  uint32_t index;            /* the record, 1 for the first */
+  uint8_t  hash[32];         /* beacon_hash as the record holds it */
+  uint32_t iter_exp;
+} Groth16BeaconInfo;
+int groth16_beacon_digest(const uint8_t hash[32], uint32_t iter_exp, uint8_t out[32]);
+int groth16_ptau_beacon(const void* ptau, size_t len, const uint8_t beacon_hash[32], uint32_t iter_exp, const char* name,
+                        void* out, size_t cap, const char* device, Groth16PtauContributeReport* report);
+int groth16_ptau_beacon_file(const char* in_path, const char* out_path, const uint8_t beacon_hash[32], uint32_t iter_exp,
+                             const char* name, const char* device, Groth16PtauContributeReport* report);
+int groth16_zkey_beacon(const void* zkey, size_t len, const uint8_t beacon_hash[32], uint32_t iter_exp, const char* name,
+                        void* out, size_t cap, const char* device, Groth16ZkeyContributeReport* report);
+int groth16_zkey_beacon_file(const char* zkey_path, const char* out_path, const uint8_t beacon_hash[32], uint32_t iter_exp,
+                             const char* name, const char* device, Groth16ZkeyContributeReport* report);
+int groth16_ptau_beacons(const void* ptau, size_t len, Groth16BeaconInfo* infos, size_t cap);
+int groth16_zkey_beacons(const void* zkey, size_t len, Groth16BeaconInfo* infos, size_t cap);
 
 /* groth16_ptau_verify — two questions about one .ptau, UNPREPARED OR PREPARED, answered on the GPU: are sections 2 to 6 the powers of
  * one (tau, alpha, beta), and — when sections 12 to 15 are present — are they the inverse transforms of 2 to 5 that
@@ -783,7 +835,7 @@ int groth16_ptau_contributions(const void* ptau, size_t len, Groth16PtauContribu
  * The file is worked through pair by pair — (2, 12), (3, 13), (4, 14), (5, 15): up, lane tests, sums, freed — so no more than one
  * pair is resident.  The _file entry maps the file.  No fixed-base table is built, the NTT domain is not touched, the calling thread's
  * device is what it was afterwards.  ICICLE_SNARK_TRACE_PTAU_VERIFY=1 prints the stage times on stderr.
- * What it does NOT show: WHO CONTRIBUTED (groth16_ptau_contributions' answer: run both); beacons; snarkjs' section-7 format; a file
+ * What it does NOT show: WHO CONTRIBUTED (groth16_ptau_contributions' answer, beacon records included: run both); snarkjs' section-7 format; a file
  * truncated by a prefix copy (other counts: -2, or LAGRANGE_12; groth16_ptau_truncate's files have this layout and are judged as
  * any other); more than one GPU; WHICH element of a failing equation is wrong.
  * 1 both questions hold; 0 not (report says what); -1 I/O; -2 a malformed container; -3 argument: power above 27, a device string
@@ -926,7 +978,7 @@ int groth16_ptau_unpack_file(const char* in_path, const char* out_path, const ch
  * device failure (groth16_last_error).  The _file entry maps the input, writes a temporary beside out_path and renames it: a failed
  * call leaves nothing.  The calling thread's device is what it was afterwards.  ICICLE_SNARK_TRACE_PTAU_TRUNCATE=1 prints the stage
  * times on stderr.
- * What it does NOT do: read a packed (ptaz) file; RAISE a power; apply or check beacons; read or write snarkjs' section-7 format; use
+ * What it does NOT do: read a packed (ptaz) file; RAISE a power; read or write snarkjs' section-7 format; use
  * more than one GPU; test the copied prefixes. */
 typedef struct {
   uint32_t power_in, power_out;
