@@ -102,7 +102,7 @@ bn254_pairing_target_field_add bn254_pairing_target_field_sub bn254_pairing_targ
 bn254_pairing_target_field_pow bn254_pairing_target_field_from_u32 bn254_pairing_target_field_generate_scalars
 icicle_snark_last_error icicle_snark_g1_generator_mul icicle_snark_g2_generator_mul icicle_snark_last_msm_timings
 icicle_snark_msm_profile icicle_snark_microbench icicle_snark_pmc_probes icicle_snark_access_probes
-icicle_snark_pairing_batch icicle_snark_pairing_product
+icicle_snark_pairing_batch icicle_snark_pairing_product icicle_snark_msm_segmented
 """.split()
 
 _lib = None
@@ -120,7 +120,7 @@ def lib():
         _lib.groth16_last_error.restype = _lib.groth16_verify_last_error.restype = C.c_char_p
         _lib.groth16_cache_manager_new.restype = C.c_void_p
         _lib.groth16_zkey_export_vk.restype = C.c_int64
-        _lib.groth16_verify_combined_coefficients.restype = None
+        _lib.groth16_verify_combined_coefficients.restype = _lib.groth16_vkset_free.restype = None
         for n in ("bn254_eq", "bn254_g2_eq", "bn254_is_on_curve", "bn254_g2_is_on_curve"):
             getattr(_lib, n).restype = C.c_bool
     return _lib
@@ -762,6 +762,7 @@ groth16_witness_ready groth16_cache_load_devices groth16_parse_device groth16_ca
 groth16_verify groth16_verify_json groth16_verify_last_error groth16_group_describe groth16_cache_tables_ready
 groth16_cache_manager_prewarm groth16_verify_batch groth16_verify_batch_last_timings
 groth16_verify_batch_combined groth16_verify_combined_coefficients
+groth16_vkset_new groth16_vkset_info groth16_vkset_free groth16_verify_batch_mixed
 groth16_zkey_check groth16_zkey_check_file
 groth16_r1cs_info groth16_r1cs_load groth16_r1cs_load_file groth16_r1cs_get_info groth16_r1cs_free
 groth16_witness_check groth16_witness_check_file groth16_r1cs_match_zkey
@@ -883,6 +884,80 @@ def groth16_verify_batch_combined(proofs, publics, vk: str, device: str = "HIP",
     return [int(out[i]) for i in range(n)], int(path.value)
 
 
+class MixedReport(C.Structure):
+    _fields_ = [("path", C.c_int32), ("keys_live", C.c_uint32), ("keys_fallback", C.c_uint32), ("parse_ms", C.c_double),
+                ("device_ms", C.c_double)]
+
+
+class VkSet:
+    """a set of verification keys (JSON texts) checked once and kept on one device (groth16_vkset_new), for verify(): proofs of
+    many keys, interleaved, in one call (groth16_verify_batch_mixed).  Raises ProverError for a refused key ("key <index>: …",
+    before any device is touched), a bad device string or a device failure.  A context manager; free() releases the device
+    memory, and a freed set refuses further calls."""
+
+    def __init__(self, vks, device: str = "HIP"):
+        self._h = None
+        n = len(vks)
+        arr = (C.c_char_p * max(n, 1))(*[v.encode() if isinstance(v, str) else v for v in vks])
+        h = C.c_void_p()
+        rc = lib().groth16_vkset_new(arr, C.c_int(n), device.encode(), C.byref(h))
+        if rc != 0:
+            _verify_fail(rc, "groth16_vkset_new")
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ProverError("VkSet: the set has been freed")
+        return self._h
+
+    @property
+    def n_keys(self) -> int:
+        return int(lib().groth16_vkset_info(self._handle(), C.c_int(-1), None))
+
+    def n_public(self, k: int) -> int:
+        out = C.c_uint32(0)
+        rc = lib().groth16_vkset_info(self._handle(), C.c_int(k), C.byref(out))
+        if rc != 0:
+            _verify_fail(rc, "groth16_vkset_info")
+        return int(out.value)
+
+    def verify(self, proofs, publics, key_of, seed=None):
+        """(verdicts, report): verdicts[i] is groth16_verify_batch's verdict for item i under key key_of[i] (−2 for a key index
+        outside the set); report.path is 1 when the one randomised equation accepted every live item, else 0 with
+        report.keys_fallback keys sent through the per-item stage.  `seed`: 32 secret bytes, or None for the operating
+        system's randomness — see groth16_verify_batch_combined."""
+        n = len(proofs)
+        if len(publics) != n or len(key_of) != n:
+            raise ValueError("VkSet.verify: proofs, publics and key_of differ in length")
+        sd = _seed32(seed, "VkSet.verify")
+        pa = (C.c_char_p * max(n, 1))(*[p.encode() if isinstance(p, str) else p for p in proofs])
+        qa = (C.c_char_p * max(n, 1))(*[q.encode() if isinstance(q, str) else q for q in publics])
+        ka = (C.c_int32 * max(n, 1))(*[int(k) for k in key_of])
+        out = (C.c_int32 * max(n, 1))()
+        rep = MixedReport()
+        rc = lib().groth16_verify_batch_mixed(self._handle(), pa, qa, ka, C.c_int(n), sd, out, C.byref(rep))
+        if rc != 0:
+            _verify_fail(rc, "groth16_verify_batch_mixed")
+        return [int(out[i]) for i in range(n)], rep
+
+    def free(self):
+        if self._h is not None:
+            lib().groth16_vkset_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def verify_combined_coefficients(seed: bytes, first: int, count: int) -> list:
     """the combined verifier's coefficients z_first … z_{first+count−1} for a 32-byte seed, as integers (no GPU)"""
     sd = _seed32(bytes(seed), "verify_combined_coefficients")   # not optional here
@@ -908,6 +983,32 @@ def pairing_product(P: np.ndarray, Q: np.ndarray) -> np.ndarray:
         check(lib().icicle_snark_pairing_product(ptr_of(bufs[1]) if n else None, ptr_of(bufs[2]) if n else None, C.c_uint64(n), None,
                                                  ptr_of(bufs[0])), "pairing_product")
         check(lib().icicle_device_synchronize(), "pairing_product")
+        out = bufs[0].to_host(out.shape)
+    finally:
+        for d in bufs:
+            d.free()
+    return out
+
+
+def msm_segmented(points: np.ndarray, scalars: np.ndarray, offsets, bits, cut: int = 0) -> np.ndarray:
+    """out[s] = Σ scalars[k]·points[k] over offsets[s] ≤ k < offsets[s+1] on the current device (icicle_snark_msm_segmented):
+    points (n,2,4) standard-form affine u64, (0,0) = identity; scalars (n,4); bits[s] ∈ {128, 254} = the bits walked in segment
+    s; cut = entries per workgroup (0 = the default).  Returns (segments,2,4) canonical affine, (0,0) = identity."""
+    points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 2, 4)
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    ns = len(bits)
+    if len(offsets) != ns + 1 or len(points) != len(scalars) or (ns and int(offsets[-1]) > len(points)):
+        raise ValueError("msm_segmented: offsets, bits, points and scalars do not fit together")
+    out = np.zeros((ns, 2, 4), dtype=np.uint64)
+    if ns == 0:
+        return out
+    bufs = [DeviceVec(out.nbytes), DeviceVec.from_host(points), DeviceVec.from_host(scalars)]
+    try:
+        check(lib().icicle_snark_msm_segmented(ptr_of(bufs[1]), ptr_of(bufs[2]), ptr_of(offsets), C.c_uint32(ns), ptr_of(bits),
+                                               C.c_uint32(cut), None, ptr_of(bufs[0])), "msm_segmented")
+        check(lib().icicle_device_synchronize(), "msm_segmented")
         out = bufs[0].to_host(out.shape)
     finally:
         for d in bufs:

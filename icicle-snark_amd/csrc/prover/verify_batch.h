@@ -38,6 +38,14 @@ int parse_stage(const char* const* proof_jsons, const char* const* public_jsons,
 // adds its device time to the thread's
 int per_item_stage(const Parsed& pz, PreparedKey& pk, int dev, int32_t* verdicts);
 void set_last_timings(double parse_ms, double device_ms);
+// the combined verifier's kernels (verify_combined.hip), enqueued on `st` for another caller — the mixed-key verifier:
+//   combined_lane_kernel     lane i < m: f[i] = the Miller value of ([zᵢ](−Aᵢ), Bᵢ), ok[i] = 0 for a pi_b outside the subgroup
+//   miller_strided_kernel    lane i < lanes: f[i] = Π of the Miller values of the pairs i, i + lanes, … below n; a pair with (0, 0) on
+//                            either side contributes 1
+//   the product passes       f[0] ← Π f[0 … n), n ≥ 1 (in place: the other slots are spent)
+hipError_t enqueue_combined_lanes(const VbItem* items, const uint32_t* z, uint32_t m, bn254::p29::F12* f, uint8_t* ok, hipStream_t st);
+hipError_t enqueue_miller_strided(const bn254::fe* p, const bn254::fe2* q, uint64_t n, uint32_t lanes, bn254::p29::F12* f, hipStream_t st);
+hipError_t enqueue_product(bn254::p29::F12* f, uint32_t n, hipStream_t st);
 
 // small helpers of the two device stages
 using isnark::ms_since; // common.h

@@ -245,6 +245,25 @@ int combined_stage(const isnark::vb::Parsed& pz, isnark::vb::PreparedKey& pk, in
 
 } // namespace
 
+// ---- the three kernels above as the mixed-key verifier (verify_mixed.hip) enqueues them: declared in verify_batch.h ------------------
+namespace isnark {
+namespace vb {
+
+hipError_t enqueue_combined_lanes(const VbItem* items, const uint32_t* z, uint32_t m, p29::F12* f, uint8_t* ok, hipStream_t st)
+{
+  hipLaunchKernelGGL(combined_lane_kernel, dim3((m + WG - 1) / WG), dim3(WG), 0, st, items, z, m, f, ok);
+  return hipGetLastError();
+}
+hipError_t enqueue_miller_strided(const fe* p, const fe2* q, uint64_t n, uint32_t lanes, p29::F12* f, hipStream_t st)
+{
+  hipLaunchKernelGGL(miller_strided_kernel, dim3((lanes + WG - 1) / WG), dim3(WG), 0, st, p, q, n, lanes, f);
+  return hipGetLastError();
+}
+hipError_t enqueue_product(p29::F12* f, uint32_t n, hipStream_t st) { return reduce_product(f, n, st); }
+
+} // namespace vb
+} // namespace isnark
+
 ISNARK_API eIcicleError icicle_snark_pairing_product(const bn254_affine_t* p, const bn254_g2_affine_t* q, uint64_t n, icicleStreamHandle stream,
                                                      bn254_fq12_t* out)
 {

@@ -1,8 +1,10 @@
 // verify_host.h — the host-only pieces of the Groth16 verifiers: what the parser leaves (VbKey, VbItem), the per-key
-// preparation every device stage and the combined tail read (PreparedKey), the combined verifier's host sums (CombinedSums), and the
-// host point helpers of the key tools (identity-aware affine forms, the generators, one pairing equation).
+// preparation every device stage and the combined tail read (PreparedKey), the combined verifier's host sums (CombinedSums), the
+// mixed-key verifier's grouping, per-key sums and segment layout (KeyGroups, MixedSums, MixedSegments), and the host point helpers
+// of the key tools (identity-aware affine forms, the generators, one pairing equation).
 // No HIP types: the product's .hip files and the F29_CHECK host builds (tests/pairing29_check.cpp,
-// tests/pairing29_combined_check.cpp) compile the same code, so a bound broken here fires in the checked build.
+// tests/pairing29_combined_check.cpp, tests/verify_mixed_check.cpp) compile the same code, so a bound broken here fires in the
+// checked build.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -100,6 +102,68 @@ struct CombinedSums {
   }
 };
 
+// ---- the mixed-key verifier's host part (verify_mixed.hip): live items grouped by key, one CombinedSums per key, and the layout of
+// the one segmented sum over 3·K segments.
+// pos[off[k] … off[k+1]) = the positions in `live` of key k's items, ascending; key_of[live[·]] is in range (the parse refused the rest)
+struct KeyGroups {
+  std::vector<uint32_t> off, pos;
+  size_t n_keys() const { return off.size() - 1; }
+  size_t count(size_t k) const { return off[k + 1] - off[k]; }
+};
+inline KeyGroups group_by_key(const int32_t* key_of, const std::vector<int>& live, size_t n_keys)
+{
+  KeyGroups g;
+  g.off.assign(n_keys + 1, 0);
+  g.pos.resize(live.size());
+  for (int i : live) g.off[(size_t)key_of[i] + 1]++;
+  for (size_t k = 0; k < n_keys; k++) g.off[k + 1] += g.off[k];
+  std::vector<uint32_t> cursor(g.off.begin(), g.off.end() - 1);
+  for (size_t p = 0; p < live.size(); p++) g.pos[cursor[(size_t)key_of[live[p]]]++] = (uint32_t)p;
+  return g;
+}
+// u₀,k = Σ_{i∈k} zᵢ, u_{j+1,k} = Σ_{i∈k} zᵢ·sᵢⱼ: the one-key sums, once per key
+struct MixedSums {
+  std::vector<CombinedSums> per_key;
+  explicit MixedSums(const std::vector<size_t>& n_public)
+  {
+    per_key.reserve(n_public.size());
+    for (size_t np : n_public) per_key.emplace_back(np);
+  }
+  void add_item(size_t key, const uint8_t seed[32], uint64_t index, const bn254::fe* s, uint32_t z4[4]) { per_key[key].add_item(seed, index, s, z4); }
+  void add(const MixedSums& o)
+  {
+    for (size_t k = 0; k < per_key.size(); k++) per_key[k].add(o.per_key[k]);
+  }
+};
+// The segmented sum's operands, region by region: [the live items' C, key-major as KeyGroups orders them | every key's IC | every
+// key's α₁], with the scalars [zᵢ | u₀,k … u_{np,k} | u₀,k] beside them.  Segment k < K is S_C,k (128 bits), K + k is S_pub,k and
+// 2K + k is u₀,k·α₁,k (254 bits): the pair partners are δ₂,k, γ₂,k and β₂,k in that order.
+struct MixedSegments {
+  std::vector<uint64_t> offsets; // 3K + 1
+  std::vector<uint8_t> bits;     // 3K
+  uint64_t ic_base = 0, alpha_base = 0, total = 0;
+};
+inline MixedSegments mixed_segments(const KeyGroups& g, const std::vector<size_t>& n_public)
+{
+  const size_t K = g.n_keys();
+  MixedSegments m;
+  m.offsets.resize(3 * K + 1);
+  m.bits.resize(3 * K);
+  uint64_t at = 0;
+  size_t s = 0;
+  const auto segment = [&](uint64_t len, uint8_t b) {
+    m.offsets[s] = at;
+    m.bits[s++] = b;
+    at += len;
+  };
+  for (size_t k = 0; k < K; k++) segment(g.count(k), 128);
+  m.ic_base = at;
+  for (size_t k = 0; k < K; k++) segment(n_public[k] + 1, 254);
+  m.alpha_base = at;
+  for (size_t k = 0; k < K; k++) segment(1, 254);
+  m.offsets[s] = m.total = at;
+  return m;
+}
 
 // ---- host point helpers: the C ABI's standard-form points, an affine (0, 0) or a projective z = 0 the identity
 inline bool words_zero(const void* p, size_t bytes)

@@ -211,6 +211,46 @@ int groth16_verify_batch_combined(const char* const* proof_jsons, const char* co
 /* out16[16·k …] = z_{first + k} (16 bytes, little endian) for k < count, as derived above.  Needs no GPU. */
 void groth16_verify_combined_coefficients(const uint8_t seed32[32], uint64_t first, uint64_t count, uint8_t* out16);
 
+/* A set of verification keys, prepared once and kept on one device, for groth16_verify_batch_mixed.
+ * groth16_vkset_new: every key goes through the key checks of groth16_verify_json (the host subgroup tests included), on the
+ * library's worker threads.  A refused key gives −2 with the text "key <index>: <the key's error>" for the lowest such index; a
+ * null argument (vk_jsons, one of its entries, device, out) gives −3.  Both are decided BEFORE any device is touched.  device:
+ * "HIP", "CUDA" or "HIP:k" — one device, to which the set is bound; > 0 (eIcicleError) for a bad device string or a device failure.
+ * On the device the set keeps, in standard form with (0, 0) the identity: every key's IC (concatenated) and α₁, and β₂, γ₂, δ₂ as
+ * affine points.  n_keys = 0 is accepted.  A mutex in the set serialises the calls made on it; groth16_vkset_free releases
+ * everything (the set must not be used afterwards).
+ * groth16_vkset_info: key = −1 returns the number of keys; otherwise 0 with *n_public = that key's nPublic, −3 for a null set or a
+ * key index outside the set. */
+typedef struct Groth16VkSet Groth16VkSet;
+int groth16_vkset_new(const char* const* vk_jsons, int n_keys, const char* device, Groth16VkSet** out);
+int groth16_vkset_info(const Groth16VkSet* set, int key, uint32_t* n_public);   /* key = -1: returns n_keys */
+void groth16_vkset_free(Groth16VkSet* set);
+
+/* groth16_verify_batch_mixed — n proofs of MANY keys, interleaved, in one call: item i is a proof under key key_of[i] of the set.
+ * verdicts[i] = what groth16_verify_batch returns for item i under that key (1 accepted, 0 rejected, negative = the item's format
+ * error), with the one exception of the combined call: an invalid item is accepted with probability ≤ 2^-127.  An item whose
+ * key_of is outside the set gets −2 (text in groth16_verify_last_error()) and disturbs nothing else.  n = 0 succeeds.
+ * With z_i = groth16_verify_batch_combined's coefficients (same rule, i = the index in the caller's arrays), the live items are
+ * checked together:
+ *     Π_i e(−z_i·A_i, B_i) · Π_k [ e((Σ_{i∈k} z_i)·α₁,k, β₂,k) · e(S_pub,k, γ₂,k) · e(Σ_{i∈k} z_i·C_i, δ₂,k) ] = 1
+ * S_pub,k = Σ_j u_j,k·IC_j,k, u_0,k = Σ_{i∈k} z_i, u_{j+1,k} = Σ_{i∈k} z_i·s_ij — with one key, groth16_verify_batch_combined's
+ * equation.  The lanes run over all live items at once whatever their keys, the 3·K sums are one segmented multi-scalar sum, the
+ * 3·K fixed-G2 Miller loops one launch.  If every pi_b passes the subgroup test and the equation holds, every live item gets 1
+ * and report->path = 1 (also when no item is live).  Otherwise path = 0 and the keys are decided one by one from the values
+ * already on the device: a key whose own equation (its items' factors and its three pairs) holds and whose items all passed the
+ * subgroup test has its items accepted; only the items of the other keys (report->keys_fallback of them, out of
+ * report->keys_live keys with a live item) go through groth16_verify_batch's per-item stage, one pass per such key.
+ * An invalid item is accepted with probability ≤ 2^-127 per call on the global equation, and per key on the per-key equations,
+ * over the seed.  THE SEED MUST BE SECRET AND FRESH, as for groth16_verify_batch_combined: pass NULL outside tests.
+ * Not done: bisection inside a failing key (its items all take the per-item stage), several lanes per proof, more than one GPU,
+ * proofs in any other form than the JSON texts; the command-line worker has no command for it.
+ * Returns 0 when every item was judged; −3 for a null argument (report may be NULL) or no randomness; > 0 for a device failure.
+ * report: parse_ms = the host parse, device_ms = the wall time from there to the verdicts. */
+typedef struct { int32_t path; uint32_t keys_live, keys_fallback; double parse_ms, device_ms; } Groth16MixedReport;
+int groth16_verify_batch_mixed(Groth16VkSet* set, const char* const* proof_jsons, const char* const* public_jsons,
+                               const int32_t* key_of, int n, const uint8_t* seed32 /* NULL = OS randomness */,
+                               int32_t* verdicts, Groth16MixedReport* report);
+
 /* groth16_zkey_check — is this proving key sound?  Opt-in: groth16_cache_load* and the proves trust the key they are given.
  * Every point of sections 3 (IC), 5 (A), 6 (B1), 7 (B2), 8 (C), 9 (H) and of the header is tested on one GPU, one lane per point,
  * in the file's Montgomery form; section 4 gets the loader's range check plus value < r; then three pair checks.

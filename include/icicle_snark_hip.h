@@ -264,6 +264,17 @@ eIcicleError icicle_snark_pairing_batch(const bn254_affine_t* p, const bn254_g2_
  * writes 1.  Enqueued on `stream`. */
 eIcicleError icicle_snark_pairing_product(const bn254_affine_t* p, const bn254_g2_affine_t* q, uint64_t n, icicleStreamHandle stream,
                                           bn254_fq12_t* out);
+/* Segmented G1 multi-scalar sum: out[s] = Σ scalars[k]·points[k] over k in [offsets[s], offsets[s+1]) for s < n_segments, as a
+ * canonical standard-form affine point, (0, 0) for the identity (an empty segment, a sum that cancels).  points, scalars and out
+ * are DEVICE pointers, standard form, (0, 0) an identity point; offsets (n_segments + 1 entries, non-decreasing) and bits (one
+ * byte per segment) are HOST arrays, read before the call returns.  bits[s] is 128 or 254: how many low bits of the segment's
+ * scalars are walked — a scalar of a 128-bit segment that is 2^128 or more is the caller's error, its high bits are ignored.
+ * One launch sums all segments, one workgroup each; a segment of more than `cut` entries (0 = the default, 1024) is cut into
+ * pieces of `cut`, one workgroup each, and a second launch adds the pieces.  The output bytes do not depend on `cut`.
+ * Enqueued on `stream`; nothing is synchronised.  ICICLE_INVALID_ARGUMENT for decreasing offsets or another bits value. */
+eIcicleError icicle_snark_msm_segmented(const bn254_affine_t* points, const bn254_scalar_t* scalars, const uint64_t* offsets,
+                                        uint32_t n_segments, const uint8_t* bits /* per segment: 128 or 254 */,
+                                        uint32_t cut /* 0 = default */, icicleStreamHandle stream, bn254_affine_t* out);
 /* per-phase device timings of the most recent MSM on this thread, milliseconds (HIP events):
  * [0] recode+sort, [1] bucket accumulation, [2] bucket reduction, [3] total.  Valid only when the
  * environment variable ICICLE_SNARK_PROFILE=1 is set (adds stream synchronisation). */
