@@ -1,5 +1,6 @@
 """Distributed QAP front end for a power-of-two number of GPUs — the index algebra of the HIP path (csrc/prover/qap.hip:
-qap_dist_*; csrc/prover/prover.cpp: shard_dist_stage1/2) restated on the CPU.  Test infrastructure (tests/test_dist_qap.py).
+qap_dist_*; csrc/prover/prover.cpp: shard_dist_stage1/2) restated on the CPU.  Test infrastructure (tests/test_dist_qap.py checks
+it against the oracle's transforms; tests/test_gpu_dist_shapes.py compares the device buffers of the HIP stages with it).
 
 n = G·m.  The inverse transform of construct_r1cs (src/proof_helper.rs:116), the coset multiplication (:121-141) and the
 forward transform (:145) are computed WITHOUT any rank holding a full row:
@@ -60,6 +61,83 @@ def stage2(recv_rows, b, G, n, omega_n, omega_2n):
                 z[i1][t] = s * pow(omega_n, (k2 * i1) % n, R_MOD) % R_MOD
         out.append(z)
     return out
+
+
+def power_table(w, count):
+    """[w^0, w^1, …, w^(count−1)] mod r"""
+    t = [1] * count
+    for i in range(1, count):
+        t[i] = t[i - 1] * w % R_MOD
+    return t
+
+
+def stage2_tab(recv_rows, b, G, n, pw2n):
+    """stage2 with every root read from pw2n = power_table(ω_2n, 2n): ω_n^e = pw2n[2e mod 2n], ω_G^e = pw2n[2·m·e mod 2n],
+    g^k = pw2n[k].  The same three formulas of the docstring, term by term — only the pow() calls are gone, so that
+    n = 2^15 with G = 8 is a few seconds of Python."""
+    m = n // G
+    mb = m // G
+    wn = lambda e: pw2n[2 * (e % n)]
+    wG = lambda e: pw2n[2 * m * (e % G)]
+    out = []
+    for rows in recv_rows:
+        z = [[0] * mb for _ in range(G)]
+        for t in range(mb):
+            k2 = b * mb + t
+            a = [sum(rows[j1][t] * wG(-j1 * k1) for j1 in range(G)) % R_MOD for k1 in range(G)]
+            ap = [a[k1] * pw2n[k1 * m + k2] % R_MOD for k1 in range(G)]
+            for i1 in range(G):
+                s = sum(ap[k1] * wG(k1 * i1) for k1 in range(G)) % R_MOD
+                z[i1][t] = s * wn(k2 * i1) % R_MOD
+        out.append(z)
+    return out
+
+
+def spmv_rows(coeffs, witness, n):
+    """The rows the spmv hands to the transforms, [B | A | A∘B] over the domain (three lists of n), from section-4 records
+    (matrix, row, wire, value) — matrix 0 = A, 1 = B, values and witness as plain integers — as a scatter-add: a record
+    given twice adds twice, a row without records is 0."""
+    a, b = [0] * n, [0] * n
+    for (mat, row, wire, value) in coeffs:
+        if mat == 0:
+            a[row] += value * witness[wire]
+        elif mat == 1:
+            b[row] += value * witness[wire]
+        else:
+            raise ValueError(f"section 4 holds matrix {mat}")
+    a = [v % R_MOD for v in a]
+    b = [v % R_MOD for v in b]
+    return [b, a, [x * y % R_MOD for x, y in zip(a, b)]]
+
+
+# ---- codecs: what the device buffers of the distributed stages hold ------------------------------------------------------
+_R2_INV = pow(1 << 512, -1, R_MOD)
+
+
+def fe_bytes_to_ints(raw):
+    """A stage buffer of the HIP path (d_dist_y = the send buffer of exchange 1, d_dist_send2 = that of exchange 2, and the
+    receive buffers d_dist_recv1 / d_fold they are copied into) → list of ints.  These buffers hold the DATA, and the data is
+    in STANDARD form throughout: the witness arrives in standard form, the cached coefficients are value·R so that
+    Fr::mul(coefficient, witness) = value·witness (qap_spmv_strided; A∘B gets its ·R² there), the fused inverse transform
+    multiplies by a Montgomery table (ntt.hip: `x = Fr::mul(x, scale_tab[…])`, the table of qap_dist_tw1) and qap_dist_mid
+    multiplies by Montgomery twiddles — standard × Montgomery = standard every time.  Only the TABLES (the domain's
+    twiddles, d_tw1, d_skeys) are Montgomery, and no stage hands those out.  One element = 32 bytes, little-endian, < r."""
+    raw = bytes(raw)
+    assert len(raw) % 32 == 0
+    return [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+
+
+def ints_to_fe_bytes(xs):
+    """the inverse of fe_bytes_to_ints (standard form, 32 bytes little-endian per element)"""
+    return b"".join(int(x).to_bytes(32, "little") for x in xs)
+
+
+def section4_records(m, c, s, coef):
+    """Section 4 of a .zkey as parsed (matrix, row and wire arrays; coef = the stored 32-byte values) → records
+    (matrix, row, wire, value) with plain-integer values.  The file stores value·R² mod r (R = 2^256: Montgomery form taken
+    twice, what snarkjs writes), so value = stored·R⁻² here."""
+    stored = fe_bytes_to_ints(coef.tobytes() if hasattr(coef, "tobytes") else coef)
+    return [(int(mm), int(cc), int(ss), v * _R2_INV % R_MOD) for mm, cc, ss, v in zip(m, c, s, stored)]
 
 
 def stage3(z_rows, ntt_forward):

@@ -8,20 +8,10 @@ import sys
 
 import pytest
 
+from dist_shapes import exchange as _exchange
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _exchange(K, bufs, rows, rb, cb):
-    """bufs[r] = (send ptr, recv ptr) of rank r: chunk (q, p) of r's send buffer → offset (q, r) of p's receive buffer"""
-    G = len(bufs)
-    sends = [K.raw_to_host(s, rows * rb) for s, _ in bufs]
-    for p in range(G):
-        recv = bytearray(rows * rb)
-        for q in range(rows):
-            for r in range(G):
-                recv[q * rb + r * cb:q * rb + (r + 1) * cb] = sends[r][q * rb + p * cb:q * rb + (p + 1) * cb]
-        K.raw_to_device(bufs[p][1], bytes(recv))
 
 
 @pytest.mark.parametrize("N,G", [(100_000, 2), (100_000, 4), (100_000, 8), (400_000, 8)])

@@ -45,8 +45,7 @@ def test_group_prove_equals_single_device_and_oracle(gpu, O, N, G):
     blk, _ = cm.commitments("grp", wtns)
     one, _ = cm.commitments("full", wtns)
     assert cm.assemble("full", wtns, blk, 5, 9)[0] == cm.assemble("full", wtns, one, 5, 9)[0] == want
-    # a different witness through the same group (the chain started at 5 instead of 3 does not satisfy the public
-    # output of the first, so only equality with the single-device prover is asserted)
+    # (a different witness through the same shard caches: tests/test_gpu_dist_shapes.py::test_stale_state_between_witnesses)
     cm.evict("grp")
     assert not cm.contains("grp")
     cm.close()
